@@ -209,6 +209,34 @@ def box_calibration():
     return out
 
 
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000            # --dump-outputs: 64 MB in all
+
+
+def dump_outputs(solver, out_dir, suffix="", budget=DUMP_BUDGET_BYTES):
+    """What a caller of the timed step receives, as float32 / float64 .npy files for an output-for-output comparison of two builds:
+    the six face fields ps_download_fields returns (velX..Z, validX..Z), dimData, and [result, error, iterations] of the solve
+    (solveData's timings are left out).  Face fields larger than their share of the budget are sampled at indices drawn once from a
+    fixed seed, so two runs at the same arguments sample the same entries."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    vel, valid = solver.download()
+    st = solver.stats
+    small = {"dimData": np.array(st.dimData, np.float64),
+             "solve": np.array([st.result, st.solveData[0], st.solveData[1]], np.float64)}
+    fields = {"vel" + "XYZ"[a]: vel[a].ravel() for a in range(3)}
+    fields.update({"valid" + "XYZ"[a]: valid[a].ravel() for a in range(3)})
+    # (4 KB per file covers its .npy header)
+    per_field = (budget - 4096 * (len(fields) + len(small)) - sum(v.nbytes for v in small.values())) // len(fields)
+    for name, v in fields.items():
+        k = per_field // v.itemsize
+        if v.size > k:
+            idx = np.sort(np.random.default_rng(20240607).choice(v.size, size=k, replace=False))
+            v = v[idx]
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), v)
+    for name, v in small.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), v)
+
+
 def _spawn(args):
     """`bench.py --gpus N` without a launcher: start N ranks with torch.distributed.run BEFORE this process touches the
     GPU (no exec of a process that has initialised HIP), wait, return their exit code."""
@@ -317,6 +345,9 @@ def main():
     ap.add_argument("--no-other-preconditioners", action="store_true", help="skip the identity / Chebyshev lines that follow the headline (SURVEY 8(d) config 3)")
     ap.add_argument("--strong-res", type=int, default=int(os.environ.get("PS_BENCH_STRONG_RES", "512")), help="resolution of the strong_512 block (tests use a small one)")
     ap.add_argument("--maxit", type=int, default=0, help="cap on solver iterations (profiling runs only; 0 = node default 5000)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last one computed (velocity and valid face fields, dimData, result / error / iterations) "
+                         "as DIR/<name>.npy, at most 64 MB in all: fields that do not fit are a fixed seeded sample of their entries")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -471,6 +502,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     ms_per_step = elapsed * 1e3 / max(args.steps, 1)
+    if args.dump_outputs:                # before the kernel micro-benchmarks below overwrite the solver's vectors
+        dump_outputs(solver, args.dump_outputs, "_rank%d" % rank if world > 1 else "", DUMP_BUDGET_BYTES // world)
 
     st = solver.stats
     iters = int(st.solveData[1])

@@ -269,13 +269,14 @@ def test_rccl_communicator_next_to_a_live_torch_context():
     assert " rc 1 " in after[0] and "closed" in pr.stdout
 
 
-def test_bench_single_gpu_line_keeps_the_contract():
+def test_bench_single_gpu_line_keeps_the_contract(tmp_path):
     """`python bench.py` (N = 1) on a small stand-in (64^3 cavity, 64^3 coil for the strong block, a 32^3 CPU sample): ONE JSON line with the
     driver's keys, the roofline and cpu_baseline objects, and r05's additions — the identity / Chebyshev lines beside the Jacobi headline
-     and the box calibration."""
+     and the box calibration; --dump-outputs writes the last timed step's fields whole (they fit the budget at 64^3)."""
     import json
+    dump = tmp_path / "out"
     pr = subprocess.run([sys.executable, os.path.join(os.path.dirname(HERE), "bench.py"), "--res", "64", "--steps", "2", "--warmup", "1", "--strong-res", "64",
-                         "--cpu-sample-res", "32"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+                         "--cpu-sample-res", "32", "--dump-outputs", str(dump)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert pr.returncode == 0, pr.stderr[-3000:]
     lines = [l for l in pr.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, pr.stdout[-2000:]
@@ -299,3 +300,39 @@ def test_bench_single_gpu_line_keeps_the_contract():
     assert o["chebyshev4"]["cg_iterations"] < d["cg_iterations"]      # the polynomial cuts the count
     assert d["box"]["d2d_copy_GBps"] > 500.0
     assert d["strong_512"]["n_gpus"] == 1 and d["strong_512"]["result"] == 1
+    files = {f: np.load(dump / f) for f in os.listdir(dump)}
+    shapes = abi.grid_shapes(64, 64, 64)
+    assert set(files) == {n + a + ".npy" for n in ("vel", "valid") for a in "XYZ"} | {"dimData.npy", "solve.npy"}
+    for a in "XYZ":
+        for n in ("vel", "valid"):
+            v = files[n + a + ".npy"]
+            assert v.dtype == np.float32 and v.size == int(np.prod(shapes["face" + a])) and np.isfinite(v).all()
+    assert files["dimData.npy"].dtype == np.float64 and files["dimData.npy"].size == 27
+    assert list(files["solve.npy"][[0, 2]]) == [d["result"], d["cg_iterations"]]
+    assert sum(os.path.getsize(dump / f) for f in files) <= 64 * 1000 * 1000
+
+
+def test_bench_dump_outputs_sample_within_the_budget(tmp_path):
+    """bench.dump_outputs on fields larger than the budget: every file within it, the same sampled entries on every call, and every sampled
+    entry one of the whole field's."""
+    import bench
+    import polystokes_amd
+    from polystokes_amd import scenes
+    sc, p = scenes.cavity(24, tile=12, pad=2)
+    s = polystokes_amd.Solver(0)
+    s.upload(sc, p)
+    assert s.step_device() == abi.SUCCESS
+    budget = 64 << 10
+    for tag, b in (("a", budget), ("b", budget), ("whole", bench.DUMP_BUDGET_BYTES)):
+        bench.dump_outputs(s, str(tmp_path / tag), budget=b)
+    s.close()
+    names = sorted(os.listdir(tmp_path / "whole"))
+    assert sorted(os.listdir(tmp_path / "a")) == names
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in names) <= budget
+    for f in names:
+        a, b, whole = (np.load(tmp_path / t / f) for t in ("a", "b", "whole"))
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b)
+        if f.startswith(("vel", "valid")):
+            assert a.size < whole.size and np.isin(a, whole).all()
+        else:
+            assert np.array_equal(a, whole)
