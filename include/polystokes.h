@@ -191,6 +191,26 @@ int32_t ps_set_interrupt(ps_context* ctx, ps_interrupt_fn cb, void* user);
 /* Device -> host copy of vel / valid. */
 int32_t ps_download_fields(ps_context* ctx, ps_fields_out* out);
 
+/* Warm start (extension; the reference builds a guess under useWarmStart and then solves from zero, HDK_PolyStokesSolver.cpp:768).
+ * PS_WARM_PREVIOUS_STEP: a single-domain PCG step whose velocity is written back (doSolve, not interrupted, SUCCESS or NOCONVERGE with
+ * keepNonConvergedResults) keeps its [p; tau] on the device as fp32 grids, and the next PCG solve on the same (nx, ny, nz, dx) starts from
+ * them (r0 = b - A x0, pcg.h:284): a DOF without a value in the previous step starts at 0.  The BiCGStab fallback still restarts from zero,
+ * the EIGEN path keeps its guessVector, decompositions start cold.  Every call drops the carried solution; a mode other than these two
+ * returns PS_INVALID.  Arrays "warmStartUsed" (int32) and "warmStartVector" (fp64, reference numbering: the x0 of the last PCG solve). */
+enum ps_warm_start { PS_WARM_NONE = 0, PS_WARM_PREVIOUS_STEP = 1 };
+int32_t ps_set_warm_start(ps_context* ctx, int32_t mode);
+
+/* The last solve's [p; tau] as dense x-fastest grids: pressure and the stress diagonal txx / tyy / tzz on the cell grid, the off-diagonal
+ * stresses tyz / txz / txy on the edgeYZ / edgeXZ / edgeXY grids (the layouts at the top of this file).  Each value is the solution vector's
+ * entry rounded to fp32; a sample without that DOF reads 0.  Any pointer may be NULL.  Single domain only; an error before the first solve
+ * after a setup.  (The reference fetches its `pressure` field, exec/HDK_PolyStokes.C:238, but never writes it.) */
+typedef struct ps_solution_out {
+    float* pressure;
+    float* tauDiag[3];                  /* txx, tyy, tzz */
+    float* tauEdge[3];                  /* tyz, txz, txy */
+} ps_solution_out;
+int32_t ps_download_solution_fields(ps_context* ctx, const ps_solution_out* out);
+
 /* solveGasSubclass equivalent on host buffers: upload + step + download (HDK_PolyStokes.C:222-609). */
 int32_t polystokes_step(ps_context* ctx, const ps_params* p, const ps_fields_in* in,
                         ps_fields_out* out, ps_stats* stats);

@@ -25,6 +25,7 @@ EXPORTED_SYMBOLS = [
     "ps_export_component_matrices", "ps_export_matrices", "ps_export_stats", "ps_bench_kernel", "ps_memory_stats", "ps_set_interrupt", "ps_solve_exported_system",
     "ps_set_slab", "ps_set_brick", "ps_comm_unique_id", "ps_comm_init_rccl", "ps_comm_selftest", "ps_comm_init_tcp", "ps_dist_stats",
     "ps_group_create", "ps_group_destroy", "ps_group_rank", "ps_group_step",
+    "ps_set_warm_start", "ps_download_solution_fields",
 ]
 
 
@@ -106,6 +107,10 @@ def lib():
         L.ps_group_rank.restype = C.c_void_p
         L.ps_group_step.argtypes = [C.c_void_p, C.POINTER(Stats)]
         L.ps_group_step.restype = C.c_int32
+        L.ps_set_warm_start.argtypes = [C.c_void_p, C.c_int32]
+        L.ps_set_warm_start.restype = C.c_int32
+        L.ps_download_solution_fields.argtypes = [C.c_void_p, C.POINTER(_abi.SolutionOut)]
+        L.ps_download_solution_fields.restype = C.c_int32
         _lib = L
     return _lib
 
@@ -116,7 +121,7 @@ _DT = {(1, "i"): np.int8, (4, "i"): np.int32, (4, "f"): np.float32, (8, "f"): np
 def _kind(name):
     if name.endswith(("Labels", "Indices", ".col", ".ptr", "Region", "Perm", ".chunkInfo", ".chunkRep", ".code")) or name.startswith("faceRow"):
         return "i"
-    if name in ("valuesCoded", "columns16", "diagonalsCoded", "fusedStep", "streamRuns", "rowPerLane", "chebInner32"):
+    if name in ("valuesCoded", "columns16", "diagonalsCoded", "fusedStep", "streamRuns", "rowPerLane", "chebInner32", "warmStartUsed"):
         return "i"
     if name in ("ownedX", "ownedY", "ownedZ"):
         return "f"
@@ -166,6 +171,25 @@ class Solver:
             return
         self._cb = C.CFUNCTYPE(C.c_int32, C.c_void_p)(lambda user: 1 if fn() else 0)
         self._check(self.L.ps_set_interrupt(self.h, C.cast(self._cb, C.c_void_p), None))
+
+    def set_warm_start(self, mode):
+        """ps_set_warm_start: 0 (WARM_NONE) solves from zero; 1 (WARM_PREVIOUS_STEP) starts the next PCG solve from the solution this
+        context carried over from its last kept step.  Every call drops the carried solution."""
+        self._check(self.L.ps_set_warm_start(self.h, int(mode)))
+
+    def solution_fields(self):
+        """ps_download_solution_fields: the last solve's [p; tau] as dense fp32 grids (x fastest), keyed pressure, txx, tyy, tzz, tyz, txz, txy;
+        0 where a sample has no such DOF."""
+        sh = _abi.grid_shapes(self.scene.nx, self.scene.ny, self.scene.nz)
+        out = {name: np.empty(sh[grid], np.float32) for name, grid in _abi.SOLUTION_FIELDS}
+        so = _abi.SolutionOut()
+        so.pressure = out["pressure"].ctypes.data
+        for a, name in enumerate(("txx", "tyy", "tzz")):
+            so.tauDiag[a] = out[name].ctypes.data
+        for a, name in enumerate(("tyz", "txz", "txy")):
+            so.tauEdge[a] = out[name].ctypes.data
+        self._check(self.L.ps_download_solution_fields(self.h, C.byref(so)))
+        return out
 
     def set_slab(self, slab):
         st = _abi.SlabStruct(slab.rank, slab.world, slab.zLoOwned, slab.zHiOwned, slab.hasLower, slab.hasUpper, slab.z0)

@@ -56,6 +56,18 @@ class FieldsOut(C.Structure):
     _fields_ = [("vel", C.c_void_p * 3), ("valid", C.c_void_p * 3)]
 
 
+class SolutionOut(C.Structure):
+    """ps_solution_out: destinations of ps_download_solution_fields (any may be NULL)"""
+    _fields_ = [("pressure", C.c_void_p), ("tauDiag", C.c_void_p * 3), ("tauEdge", C.c_void_p * 3)]
+
+
+# ps_warm_start
+WARM_NONE, WARM_PREVIOUS_STEP = 0, 1
+# the grids of ps_download_solution_fields: name -> sample grid (SAMPLE_NAMES / grid_shapes), in ps_solution_out order
+SOLUTION_FIELDS = [("pressure", "center"), ("txx", "center"), ("tyy", "center"), ("tzz", "center"),
+                   ("tyz", "edgeYZ"), ("txz", "edgeXZ"), ("txy", "edgeXY")]
+
+
 class Stats(C.Structure):
     _fields_ = [
         ("dimData", C.c_double * 27), ("solveData", C.c_double * 6),

@@ -162,6 +162,7 @@ void ps_context::setupPhase(int phase) {
         if (!uploaded) throw Error("ps_upload_fields has not been called");
         isSetup = false; isSolved = false;   // a setup that throws must not leave the previous step's system looking valid
         setupPhaseDone = -1;
+        warmUsedHost = 0; warmX0Valid = false;
         arrays.clear();
         HIP_CHECK(hipSetDevice(device));
         setupState = std::make_shared<SetupState>(stream);
@@ -276,6 +277,8 @@ int ps_context::solveStage(ps_stats* stats) {
         recoverVelocityFromPressureStress();
         T.mark(2);
         applySolutionToVelocity();
+        // warm start: a kept PCG step (SUCCESS, or NOCONVERGE with keepNonConvergedResults; after the BiCGStab fallback too) carries its x
+        if (warmMode == PS_WARM_PREVIOUS_STEP && P.doSolve && P.solverType == PS_PCG_MATRIX_VECTOR_PRODUCTS && !slabEnabled) carryWarmStart();
     } else {
         T.mark(2);
         for (int a = 0; a < 3; ++a)
@@ -332,6 +335,11 @@ void ps_context::registerArrays() {
     regp("b", b.p, nSystem, permSys.p, 0);
     regp("solutionVector", x.p, nSystem, permSys.p, 0);
     regp("guessVector", guess.p, nSystem, permSys.p, 0);
+    if (warmX0Valid) regp("warmStartVector", warmX0.p, nSystem, permSys.p, 0);   // (mode PS_WARM_PREVIOUS_STEP, after a PCG solve)
+    // 1: the last PCG solve started from the solution carried over from an earlier step (ps_set_warm_start); read from host memory, so that
+    // the default path does not gain a copy per step
+    reg("warmStartUsed", &warmUsedHost, 1, 4);
+    arrays["warmStartUsed"].host = true;
     if (P.preconditioner == PS_PRE_DIAGONAL) regp("dinv", dinv.p, nSystem, permSys.p, 0);
     if (isSolved) {
         regp("recoveredActiveVelocity", recovered.p, nActiveVs, permRow.p, 0);
@@ -636,6 +644,44 @@ int32_t ps_download_fields(ps_context* c, ps_fields_out* out) {
         return PS_SUCCESS;
     })
 }
+int32_t ps_set_warm_start(ps_context* c, int32_t mode) {
+    if (!c) return PS_FAILED;
+    PS_TRY(c, {
+        if (mode != PS_WARM_NONE && mode != PS_WARM_PREVIOUS_STEP) {
+            c->err = "ps_set_warm_start: unknown mode " + std::to_string(mode) + " (0: none, 1: previous step)";
+            return PS_INVALID;
+        }
+        HIP_CHECK(hipSetDevice(c->device));
+        c->warmMode = mode;
+        c->dropWarmStart();                                 // every call drops the carried solution
+        HIP_CHECK(hipStreamSynchronize(c->stream));
+        c->drainDeferred(true);
+        return PS_SUCCESS;
+    })
+}
+// [p; tau] of the last solve as dense grids (ps_solution_out), one grid at a time through a scratch buffer
+int32_t ps_download_solution_fields(ps_context* c, const ps_solution_out* out) {
+    if (!c || !out) return PS_FAILED;
+    PS_TRY(c, {
+        if (c->slabEnabled) throw Error("ps_download_solution_fields is a single-domain call");
+        if (!c->isSetup || !c->isSolved) throw Error("ps_download_solution_fields: no solve since the last setup");
+        HIP_CHECK(hipSetDevice(c->device));
+        float* dst[7] = {out->pressure, out->tauDiag[0], out->tauDiag[1], out->tauDiag[2], out->tauEdge[0], out->tauEdge[1], out->tauEdge[2]};
+        int64_t most = 1;
+        for (int q = 0; q < 7; ++q) if (dst[q]) most = std::max(most, c->solutionGridCount(q));
+        DevBuf<float> scratch;
+        scratch.alloc((size_t)most);
+        for (int q = 0; q < 7; ++q) {
+            if (!dst[q]) continue;
+            c->scatterSolution(scratch.p, q, 1);
+            HIP_CHECK(hipMemcpyAsync(dst[q], scratch.p, (size_t)c->solutionGridCount(q) * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+            HIP_CHECK(hipStreamSynchronize(c->stream));
+        }
+        scratch.free();
+        c->drainDeferred(true);
+        return PS_SUCCESS;
+    })
+}
 int32_t polystokes_step(ps_context* c, const ps_params* p, const ps_fields_in* in, ps_fields_out* out, ps_stats* st) {
     if (!c) return PS_FAILED;
     PS_TRY(c, {
@@ -710,7 +756,9 @@ int32_t ps_read_array(ps_context* c, const char* name, void* dst, int64_t dst_by
         if (it == c->arrays.end()) throw Error(std::string("unknown array ") + name);
         const int64_t need = it->second.count * it->second.elem;
         if (dst_bytes < need) throw Error("destination too small");
-        if (need > 0) {
+        if (need > 0 && it->second.host) {
+            std::memcpy(dst, it->second.dptr, (size_t)need);
+        } else if (need > 0) {
             HIP_CHECK(hipSetDevice(c->device));
             const void* src = it->second.dptr;
             if (it->second.perm) {

@@ -71,6 +71,7 @@ struct ArrayInfo {
     int elem;
     const int32_t* perm = nullptr;   // optional: out[i] = src[perm[permOffset + i]] (reference order view)
     int64_t permOffset = 0;
+    bool host = false;               // dptr is host memory of the context (no device copy behind it)
 };
 
 }  // namespace ps
@@ -191,6 +192,22 @@ struct ps_context {
     bool chebInner32 = false;                         // ... and this system runs it: the polynomial's z_j and face-row vector are stored as fp32 (ps_solve.hip: chebyshevApply)
     int32_t chebInner32Host = 0;
     ps::DevBuf<double> guess;   // [pressureGuess; stressGuess] of constructGuessVectors (Solver.cpp:512-531), internal numbering
+    // Warm start (ps_set_warm_start, extension): in mode PS_WARM_PREVIOUS_STEP a kept single-domain PCG step leaves its [p; tau] in warmStore — seven
+    // dense x-fastest fp32 grids (p, txx, tyy, tzz on the cell grid, then the YZ / XZ / XY edge stresses; 0 where a sample had no DOF), tagged with
+    // the grid it was solved on — and the next PCG solve on the same (nx, ny, nz, dx) starts from it, gathered through that step's index maps.
+    int32_t warmMode = 0;
+    ps::DevBuf<float> warmStore;
+    bool warmHave = false;
+    int warmTag[3] = {0, 0, 0};
+    double warmTagDx = 0;
+    ps::DevBuf<double> warmX0;               // the x0 the last PCG solve of a mode-1 context used (array "warmStartVector"), internal numbering
+    bool warmX0Valid = false;
+    int32_t warmUsedHost = 0;                // 1: the last PCG solve started from the carried solution (array "warmStartUsed")
+    int64_t solutionGridCount(int q) const { return g.count(q < 4 ? 0 : q); }   // grid q of the store: 0..3 cell grid, 4..6 edge grids
+    void scatterSolution(float* dst, int q0, int nq);   // ps_solve.hip: grids q0 .. q0+nq-1 of x, back to back in dst
+    void carryWarmStart();                              // ps_solve.hip: x -> warmStore (after a kept step)
+    bool gatherWarmStart();                             // ps_solve.hip: warmStore -> x, warmX0 (false: no matching store, x untouched)
+    void dropWarmStart();
     // dotPartials: p.Ap partials of the St kernel; dotPartials2: their first-stage sums (one-shot St kernel only);
     // dotPartialsR: r.r / r.z partials of k_cg_update_r; dotPartials3: x.x partials of k_cg_update_xp.  Separate buffers:
     // every block of a step kernel sums its predecessor's partials while other blocks already write this kernel's.

@@ -84,6 +84,46 @@ __global__ void __launch_bounds__(BS) k_cg_init_f(const double* __restrict__ b, 
     const double s = blockReduceSum(acc);
     if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
+// ---- warm start (ps_set_warm_start) ----------------------------------------------------------------
+// r = b - A x0 (Ax = A x0 from applyOperator); z = pre(r); p = z; partial rsold = r.z — k_cg_init_f on a carried x0, which stays in x
+__global__ void __launch_bounds__(BS) k_cg_init_warm(const double* __restrict__ b, const double* __restrict__ Ax, const diag_t* __restrict__ dinv,
+                                                     double* __restrict__ r, double* __restrict__ p, int64_t n, double* __restrict__ partial) {
+    double acc = 0.;
+    for (int64_t i = (int64_t)blockIdx.x * BS + threadIdx.x; i < n; i += (int64_t)gridDim.x * BS) {
+        const double rv = b[i] - Ax[i];
+        const double z = dinv ? diagValue(dinv[i]) * rv : rv;
+        r[i] = rv; p[i] = z;
+        acc += rv * z;
+    }
+    const double s = blockReduceSum(acc);
+    if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+// The solution as seven dense x-fastest grids (ps_context::warmStore): blockIdx.y = grid, its samples grid-stride; map = the grid's index
+// map (sample -> internal DOF, -1: none).  Every index is checked against -1 and the system size.
+struct SolutionGrids { const int32_t* map[7]; int64_t off[7]; int64_t cnt[7]; };
+// store[sample] = fp32(x[map[sample]]), 0 where the sample has no DOF
+__global__ void __launch_bounds__(BS) k_solution_scatter(SolutionGrids G, const double* __restrict__ x, int64_t n, float* __restrict__ store) {
+    const int32_t* __restrict__ map = G.map[blockIdx.y];
+    float* __restrict__ out = store + G.off[blockIdx.y];
+    const int64_t cnt = G.cnt[blockIdx.y];
+    for (int64_t c = (int64_t)blockIdx.x * BS + threadIdx.x; c < cnt; c += (int64_t)gridDim.x * BS) {
+        const int32_t i = map[c];
+        out[c] = (i >= 0 && i < n) ? (float)x[i] : 0.f;
+    }
+}
+// x[map[sample]] = x0[map[sample]] = store[sample] widened to fp64: every DOF has exactly one sample, so x is written whole
+__global__ void __launch_bounds__(BS) k_warm_gather(SolutionGrids G, const float* __restrict__ store, int64_t n, double* __restrict__ x,
+                                                    double* __restrict__ x0) {
+    const int32_t* __restrict__ map = G.map[blockIdx.y];
+    const float* __restrict__ in = store + G.off[blockIdx.y];
+    const int64_t cnt = G.cnt[blockIdx.y];
+    for (int64_t c = (int64_t)blockIdx.x * BS + threadIdx.x; c < cnt; c += (int64_t)gridDim.x * BS) {
+        const int32_t i = map[c];
+        if (i < 0 || i >= n) continue;
+        const double v = (double)in[c];
+        x[i] = v; x0[i] = v;
+    }
+}
 __global__ void k_to_diag(const double* __restrict__ a, diag_t* __restrict__ out, int64_t n) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) out[i] = diagStore(a[i]);
 }

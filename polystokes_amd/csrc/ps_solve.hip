@@ -645,6 +645,13 @@ int ps_context::solve() {
     }
 
     HIP_CHECK(hipMemsetAsync(dotPartials3.p, 0, VGRID * sizeof(double), stream));
+    // warm start (ps_set_warm_start): x0 = the carried solution, r0 = b - A x0 (pcg.h:284); from here on the PCG is the same
+    const bool warm = warmMode == PS_WARM_PREVIOUS_STEP && gatherWarmStart();
+    warmUsedHost = warm ? 1 : 0;
+    if (warm) {
+        applyOperator(x.p, Ap.p, dotPartials.p);
+        hipLaunchKernelGGL(k_cg_init_warm, dim3(vb), dim3(BS), 0, stream, (const double*)b.p, (const double*)Ap.p, dv, r.p, pvec.p, n, dotPartials.p);
+    } else
     hipLaunchKernelGGL(k_cg_init_f, dim3(vb), dim3(BS), 0, stream, b.p, dv, x.p, r.p, pvec.p, n, dotPartials.p);
     if (cheb) {   // z = M^-1 r, p = z, rsold = r.z
         HIP_CHECK(hipMemsetAsync(sc, 0, sizeof(CGScalars), stream));   // `done` must read 0 inside the polynomial's kernels
@@ -772,6 +779,66 @@ int ps_context::solve() {
         solveError = rre;
     }
     return solveIterations == maxit ? PS_NOCONVERGE : PS_SUCCESS;
+}
+
+// ---- warm start (ps_set_warm_start; DESIGN.md "Warm start") ----
+namespace {
+SolutionGrids solutionGrids(const ps_context* c, int q0, int nq, int64_t* most) {
+    SolutionGrids G{};
+    const int32_t* maps[7] = {c->sysIdx[0].p, c->sysIdxT[0].p, c->sysIdxT[1].p, c->sysIdxT[2].p, c->sysIdx[4].p, c->sysIdx[5].p, c->sysIdx[6].p};
+    int64_t off = 0;
+    *most = 1;
+    for (int k = 0; k < nq; ++k) {
+        G.map[k] = maps[q0 + k]; G.off[k] = off; G.cnt[k] = c->solutionGridCount(q0 + k);
+        off += G.cnt[k];
+        *most = std::max(*most, G.cnt[k]);
+    }
+    return G;
+}
+}  // namespace
+
+void ps_context::scatterSolution(float* dst, int q0, int nq) {
+    if (q0 < 0 || nq < 1 || q0 + nq > 7) throw Error("scatterSolution: bad grid range");
+    int64_t most;
+    const SolutionGrids G = solutionGrids(this, q0, nq, &most);
+    hipLaunchKernelGGL(k_solution_scatter, dim3((unsigned)std::min<int64_t>(4096, gridFor(most, BS)), (unsigned)nq), dim3(BS), 0, stream, G,
+                       (const double*)x.p, nSystem, dst);
+}
+
+// after a kept single-domain PCG step: x -> the store, tagged with the grid
+void ps_context::carryWarmStart() {
+    int64_t total = 0;
+    for (int q = 0; q < 7; ++q) total += solutionGridCount(q);
+    warmStore.alloc((size_t)total);
+    scatterSolution(warmStore.p, 0, 7);
+    warmHave = true;
+    warmTag[0] = g.nx; warmTag[1] = g.ny; warmTag[2] = g.nz; warmTagDx = dx;
+}
+
+// before a PCG solve of a mode-1 context: x0 through this step's maps when the store was written on the same grid; warmX0 keeps it for
+// the array "warmStartVector" (zeros when the solve starts cold).  Decompositions always start cold.
+bool ps_context::gatherWarmStart() {
+    const int64_t n = nSystem;
+    warmX0.alloc((size_t)std::max<int64_t>(n, 1));
+    warmX0Valid = true;
+    const bool match = warmHave && !slabEnabled && warmTag[0] == g.nx && warmTag[1] == g.ny && warmTag[2] == g.nz && warmTagDx == dx;
+    if (!match) {
+        HIP_CHECK(hipMemsetAsync(warmX0.p, 0, (size_t)std::max<int64_t>(n, 1) * sizeof(double), stream));
+        return false;
+    }
+    int64_t most;
+    const SolutionGrids G = solutionGrids(this, 0, 7, &most);
+    hipLaunchKernelGGL(k_warm_gather, dim3((unsigned)std::min<int64_t>(4096, gridFor(most, BS)), 7u), dim3(BS), 0, stream, G,
+                       (const float*)warmStore.p, n, x.p, warmX0.p);
+    return true;
+}
+
+void ps_context::dropWarmStart() {
+    warmStore.free();
+    warmX0.free();
+    warmHave = false;
+    warmX0Valid = false;
+    arrays.erase("warmStartVector");
 }
 
 // initializeGuessVectors + constructGuessVectors (Solver.cpp:512-531) and the guessVector of the assemble functions

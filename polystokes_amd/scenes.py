@@ -70,9 +70,10 @@ def cavity(n=64, tile=16, pad=2, precond=1):
     return sc, default_params(tileSize=tile, tilePadding=pad, preconditioner=precond)
 
 
-def spheres(n=64, tile=16, pad=2, nspheres=8, seed=12345, zrange=None):
+def spheres(n=64, tile=16, pad=2, nspheres=8, seed=12345, zrange=None, t=0.0):
     """Config 5 stand-in: half-filled pool with moving solid spheres, mixed uniform/reduced regions.
-    zrange = (k0, nz): only the layers k0 .. k0 + nz - 1 of the n^3 scene (a rank's slab + halo, see scene_slab)."""
+    zrange = (k0, nz): only the layers k0 .. k0 + nz - 1 of the n^3 scene (a rank's slab + halo, see scene_slab).
+    t: the scene at time t — every sphere's centre advanced by its collision velocity * t (a moving-geometry sequence: t = step * dt)."""
     dx, dt = 1.0 / n, 1.0 / 48.0
     rng = np.random.RandomState(seed)
     k0, nzl = zrange if zrange is not None else (0, n)
@@ -87,6 +88,8 @@ def spheres(n=64, tile=16, pad=2, nspheres=8, seed=12345, zrange=None):
         c[1] = rng.uniform(0.25, 0.55)
         rad = rng.uniform(0.06, 0.11)
         v = rng.uniform(-1.0, 1.0, 3)
+        if t:
+            c = c + v * t
         collision = np.minimum(collision, np.sqrt((x - c[0]) ** 2 + (y - c[1]) ** 2 + (z - c[2]) ** 2) - rad)
         for a in range(3):
             zz, yy, xx = np.meshgrid(fz[0] if a == 2 else fz[1], fx[0] if a == 1 else fx[1],

@@ -25,7 +25,7 @@ void initializeSIM(void*)
     IMPLEMENT_DATAFACTORY(HDK_PolyStokes);
 }
 
-HDK_PolyStokes::HDK_PolyStokes(const SIM_DataFactory* factory) : BaseClass(factory), myCtx(nullptr), myCtxDevice(-1) {}
+HDK_PolyStokes::HDK_PolyStokes(const SIM_DataFactory* factory) : BaseClass(factory), myCtx(nullptr), myCtxDevice(-1), myWarmMode(PS_WARM_NONE) {}
 
 HDK_PolyStokes::~HDK_PolyStokes()
 {
@@ -72,6 +72,8 @@ const ParmRow theRows[] = {
     {'I', "gpuDevice",                  "GPU Device",                       nullptr,            0},
     {'T', "hdkSampledWeights",          "Sample Weights With HDK",          nullptr,            1},
     {'T', "debugGeometry",              "Publish Debug Geometry",           nullptr,            0},
+    {'T', "warmStartPreviousStep",      "Warm Start From Previous Step",    nullptr,            0},
+    {'T', "writePressureField",         "Write Pressure Field",             nullptr,            0},
 };
 constexpr int theRowCount = (int)(sizeof(theRows) / sizeof(theRows[0]));
 }  // namespace
@@ -145,6 +147,7 @@ bool HDK_PolyStokes::ensureContext(SIM_Object* obj)
     if (myCtx) { ps_context_destroy(myCtx); myCtx = nullptr; }
     myCtx = ps_context_create(dev);
     myCtxDevice = dev;
+    myWarmMode = PS_WARM_NONE;          // a new context solves from zero until told otherwise
     if (!myCtx) { addError(obj, SIM_MESSAGE, ps_last_error(nullptr), UT_ERROR_ABORT); return false; }
     return true;
 }
@@ -155,7 +158,7 @@ bool HDK_PolyStokes::solveGasSubclass(SIM_Engine& engine, SIM_Object* obj, SIM_T
     SIM_VectorField*       velocityField = getVectorField(obj, GAS_NAME_VELOCITY);
     SIM_VectorField*       validField = getVectorField(obj, "valid");
     const SIM_ScalarField* viscosityField = getScalarField(obj, "viscosity");
-    const SIM_ScalarField* pressureField = getScalarField(obj, "pressure");
+    SIM_ScalarField*       pressureField = getScalarField(obj, "pressure");
     const SIM_ScalarField* densityField = getScalarField(obj, "density");
     const SIM_ScalarField* surfaceField = getConstScalarField(obj, GAS_NAME_SURFACE);
     const SIM_VectorField* surfaceWeights = getVectorField(obj, "surfaceweights");
@@ -182,6 +185,13 @@ bool HDK_PolyStokes::solveGasSubclass(SIM_Engine& engine, SIM_Object* obj, SIM_T
         return fail("User requested to use input collision weights but that field is missing.", UT_ERROR_ABORT);
     if (!collisionVelocityField) return fail("Collision velocity field is missing.", UT_ERROR_ABORT);   // the reference dereferences it unchecked
     if (!ensureContext(obj)) return false;
+    // shim-only: start each solve from the previous step's pressure and stress, kept on the device by the context (ps_set_warm_start drops
+    // what it carries, so it is called only when the toggle changes).  useWarmStart keeps the reference's meaning.
+    const int32_t warmMode = getWarmStartPreviousStep() ? PS_WARM_PREVIOUS_STEP : PS_WARM_NONE;
+    if (warmMode != myWarmMode) {
+        if (ps_set_warm_start(myCtx, warmMode) != PS_SUCCESS) return fail(ps_last_error(myCtx), UT_ERROR_ABORT);
+        myWarmMode = warmMode;
+    }
 
     const fpreal dt = timestep;
     const fpreal dx = velocityField->getVoxelSize(0).maxComponent();
@@ -268,6 +278,21 @@ bool HDK_PolyStokes::solveGasSubclass(SIM_Engine& engine, SIM_Object* obj, SIM_T
     for (int a = 0; a < 3; ++a) fromDense(*validField->getField(a), valid[a]);
     const bool keep = result == PS_SUCCESS || getKeepNonConvergedResults();
     if (keep) for (int a = 0; a < 3; ++a) fromDense(*velocityField->getField(a), vel[a]);
+    if (getDoSolve() && keep && getWritePressureField()) {
+        // shim-only: the solved pressure into the node's pressure field (the reference fetches it, HDK_PolyStokes.C:238, but never writes it)
+        int rx, ry, rz;
+        pressureField->getField()->getVoxelRes(rx, ry, rz);
+        if (rx != in.nx || ry != in.ny || rz != in.nz) {
+            addError(obj, SIM_MESSAGE, "Pressure field must have the surface field's resolution to receive the solved pressure.", UT_ERROR_WARNING);
+        } else {
+            std::vector<float> pressure((size_t)in.nx * in.ny * in.nz);
+            ps_solution_out sol = {};
+            sol.pressure = pressure.data();
+            if (ps_download_solution_fields(myCtx, &sol) != PS_SUCCESS) return fail(ps_last_error(myCtx), UT_ERROR_ABORT);
+            fromDense(*pressureField->getField(), pressure);
+            pressureField->pubHandleModification();
+        }
+    }
     if (getDoSolve()) {
         if (keep) { velocityField->pubHandleModification(); validField->pubHandleModification(); }
         else if (result == PS_NOCONVERGE) addError(obj, SIM_MESSAGE, "Solver did not converge, exiting...", UT_ERROR_ABORT);

@@ -43,6 +43,8 @@ public:
     GET_DATA_FUNC_I("gpuDevice",                        GpuDevice);               // HIP device index, default 0
     GET_DATA_FUNC_B("hdkSampledWeights",                HdkSampledWeights);       // sample the 14 weight fields with HDK itself (1)
     GET_DATA_FUNC_B("debugGeometry",                    DebugGeometry);           // rebuild the reference's 36 debug point clouds (0)
+    GET_DATA_FUNC_B("warmStartPreviousStep",            WarmStartPreviousStep);   // ps_set_warm_start(PS_WARM_PREVIOUS_STEP) (0)
+    GET_DATA_FUNC_B("writePressureField",               WritePressureField);      // solved pressure into the pressure field (0)
 
 protected:
     explicit HDK_PolyStokes(const SIM_DataFactory* factory);
@@ -53,6 +55,7 @@ protected:
 private:
     ps_context* myCtx;          // owns the device buffers; reused across substeps
     int         myCtxDevice;
+    int32_t     myWarmMode;     // the mode last set on myCtx (ps_set_warm_start)
 
     bool ensureContext(SIM_Object* obj);
     void publishDebugGeometry(SIM_Object* obj, const SIM_VectorField* velocity, fpreal dx);
