@@ -84,7 +84,7 @@ enum ps_index_order { PS_ORDER_VOXEL_TILES = 0, PS_ORDER_LINEAR = 1 };
  * Field-name string parms stay in the Houdini shim; they have no meaning below it.
  */
 typedef struct ps_params {
-    double mindensity;                  /* 1      (unused by the live path, kept for the surface) */
+    double mindensity;                  /* 1      clamp of a density field's face samples (ps_upload_density_field); the scalar density is not clamped */
     double maxdensity;                  /* 100000 */
     int32_t matrixSetup;                /* ps_matrix_scheme, 0 */
     int32_t solverType;                 /* ps_solver_type,   0 */
@@ -121,7 +121,7 @@ typedef struct ps_fields_in {
     double dx;                          /* max voxel size, HDK_PolyStokes.C:320 */
     double dt;                          /* timestep,       HDK_PolyStokes.C:319 */
     double orig[3];                     /* grid origin (debug output only, Solver.cpp:1134) */
-    float density;                      /* constant liquid density, HDK_PolyStokes.C:298-304 */
+    float density;                      /* constant liquid density, HDK_PolyStokes.C:298-304 (a field: ps_upload_density_field) */
     int32_t reserved;
     const float* vel[3];                /* face sampled velocity (in) */
     const float* surface;               /* cell, liquid SDF (<0 inside liquid) */
@@ -171,6 +171,22 @@ void ps_params_default(ps_params* p);             /* defaults of HDK_PolyStokes.
 
 /* Host -> device copy of the SIM fields (no reference equivalent: Houdini fields are host memory). */
 int32_t ps_upload_fields(ps_context* ctx, const ps_params* p, const ps_fields_in* in);
+
+/* Variable density (extension; the reference's getLocalDensity hook, HDK_PolyStokesSolver.cpp:1915, HDK_PolyStokes.C:298-304).
+ * density: cell field, nx*ny*nz, x-fastest, the grid of the last ps_upload_fields.  NULL drops it.
+ * Call it after ps_upload_fields and before ps_setup_device / ps_step_device (on a slab / brick rank: after that rank's ps_upload_fields).
+ * Every ps_upload_fields drops the field, so each step starts from the scalar ps_fields_in.density unless the field is passed again; a call
+ * before any ps_upload_fields returns PS_INVALID.
+ * The density of a face is the field sampled at the face centre with the viscosity's sampler (trilinear, clamped to the grid: an interior
+ * x-face (i,j,k) gets rho[i-1,j,k] + (rho[i,j,k] - rho[i-1,j,k]) * 0.5f in fp32, a face on the grid boundary its one cell), then clamped to
+ * [mindensity, maxdensity] of the ps_params of that upload (the scalar density is never clamped).  It replaces the scalar face by face in
+ * McInv = 1 / (volume rho_f), the rhs u volume rho_f and Mc, and in each tile's Mr = sum_f rho_f C_f^T C_f (hence rhs_r = Mr c_fit); the fit,
+ * K, uInv, recovery and export follow from these.  A field whose values all equal v runs the scalar path with density clamp(v), bit for bit.
+ * Values <= 0 are legal (FLIP density is 0 in air; the clamp lifts them to mindensity): a caller who wants the liquid's densities at the free
+ * surface extrapolates the field into the air first.  PS_INVALID (reason in ps_last_error): a NaN or infinite value, mindensity <= 0,
+ * maxdensity < mindensity, or either non-finite; the field is then dropped.  Array "densityField" (int32): 1 if the last setup sampled a
+ * non-constant field. */
+int32_t ps_upload_density_field(ps_context* ctx, const float* density);
 
 /* The whole hot path on device-resident inputs: buildIntegrationWeightsAlt ... solve ...
  * recoverVelocityFromPressureStress, applySolutionToVelocity (HDK_PolyStokes.C:344-583).

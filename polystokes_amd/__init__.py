@@ -25,7 +25,7 @@ EXPORTED_SYMBOLS = [
     "ps_export_component_matrices", "ps_export_matrices", "ps_export_stats", "ps_bench_kernel", "ps_memory_stats", "ps_set_interrupt", "ps_solve_exported_system",
     "ps_set_slab", "ps_set_brick", "ps_comm_unique_id", "ps_comm_init_rccl", "ps_comm_selftest", "ps_comm_init_tcp", "ps_dist_stats",
     "ps_group_create", "ps_group_destroy", "ps_group_rank", "ps_group_step",
-    "ps_set_warm_start", "ps_download_solution_fields",
+    "ps_set_warm_start", "ps_download_solution_fields", "ps_upload_density_field",
 ]
 
 
@@ -111,6 +111,8 @@ def lib():
         L.ps_set_warm_start.restype = C.c_int32
         L.ps_download_solution_fields.argtypes = [C.c_void_p, C.POINTER(_abi.SolutionOut)]
         L.ps_download_solution_fields.restype = C.c_int32
+        L.ps_upload_density_field.argtypes = [C.c_void_p, C.c_void_p]
+        L.ps_upload_density_field.restype = C.c_int32
         _lib = L
     return _lib
 
@@ -121,7 +123,7 @@ _DT = {(1, "i"): np.int8, (4, "i"): np.int32, (4, "f"): np.float32, (8, "f"): np
 def _kind(name):
     if name.endswith(("Labels", "Indices", ".col", ".ptr", "Region", "Perm", ".chunkInfo", ".chunkRep", ".code")) or name.startswith("faceRow"):
         return "i"
-    if name in ("valuesCoded", "columns16", "diagonalsCoded", "fusedStep", "streamRuns", "rowPerLane", "chebInner32", "warmStartUsed"):
+    if name in ("valuesCoded", "columns16", "diagonalsCoded", "fusedStep", "streamRuns", "rowPerLane", "chebInner32", "warmStartUsed", "densityField"):
         return "i"
     if name in ("ownedX", "ownedY", "ownedZ"):
         return "f"
@@ -243,6 +245,23 @@ class Solver:
         self.scene, self.params = scene, params
         fi = scene.fields_in()
         self._check(self.L.ps_upload_fields(self.h, C.byref(params), C.byref(fi)))
+        if getattr(scene, "density_field", None) is not None:
+            self._check(self.upload_density_field(scene.density_field))
+
+    def upload_density_field(self, field):
+        """ps_upload_density_field: a cell density field for the grid of the last upload (None drops it).  Returns the ps_result
+        (INVALID for a refused field, the reason in last_error()); FAILED raises."""
+        if field is None:
+            return self._check(self.L.ps_upload_density_field(self.h, None), allow=(1, -2))
+        sh = _abi.grid_shapes(self.scene.nx, self.scene.ny, self.scene.nz)["center"] if self.scene is not None else None
+        f = np.ascontiguousarray(field, dtype=np.float32)
+        if sh is not None and f.shape != sh:
+            f = f.reshape(sh)
+        self._density_keep = f
+        return self._check(self.L.ps_upload_density_field(self.h, f.ctypes.data), allow=(1, -2))
+
+    def last_error(self):
+        return self.L.ps_last_error(self.h).decode()
 
     def setup(self):
         return self._check(self.L.ps_setup_device(self.h, C.byref(self.stats)))
@@ -255,6 +274,11 @@ class Solver:
 
     def step(self, scene, params):
         """solveGasSubclass equivalent on host buffers (HDK_PolyStokes.C:222-609)."""
+        if getattr(scene, "density_field", None) is not None:          # upload, density field, step, download: polystokes_step has no field
+            self.upload(scene, params)
+            rc = self.step_device()
+            self.download()
+            return rc
         self.scene, self.params = scene, params
         fi = scene.fields_in()
         out, keep = self._fields_out()
@@ -401,7 +425,7 @@ class Group:
             return self._solve_scene_bricks(scene, params)
         slabs = [partition.make_slab(scene.nz, self.world, r, params.tileSize) for r in range(self.world)]
         for r, sl in enumerate(slabs):
-            self.ranks[r].upload(partition.local_scene(scene, sl), params)
+            self.ranks[r].upload(partition.local_scene(scene, sl), params)   # (with the scene's density field cut to the slab)
             self.ranks[r].set_slab(sl)
         rc = self.step()
         sh = _abi.grid_shapes(scene.nx, scene.ny, scene.nz)

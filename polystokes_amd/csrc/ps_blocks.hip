@@ -32,6 +32,8 @@ struct BlockArgs {
     const float* cvel[3];
     const float* visc;
     int viscUniform; float viscValue;   // a constant field: its samples without loads (ps_context::upload)
+    const float* dens;                  // cell density field (ps_upload_density_field); null: the scalar rho everywhere
+    double densMin, densMax;
     int64_t nCenter, nEdge0, nEdge1, nP, nA, faceOff[3];
     Own own;
     const int32_t* regionOwned;   // null: all owned
@@ -272,6 +274,39 @@ __global__ void __launch_bounds__(BS) k_skin(BlockArgs A, const int32_t* __restr
     }
 }
 
+// Density of the face (axis, i, j, k): the cell field sampled at the face centre with the viscosity's sampler (trilinear, clamped to the
+// grid — an interior face gets the mean of its two cells as a + (b - a) * 0.5f, a face on the grid boundary its one cell), clamped to
+// [mindensity, maxdensity].  Without a field: the scalar rho, unclamped (ps_upload_density_field).  ps_tiles.hip has the same helper.
+__device__ inline float densSample(const float* f, const Grid& g, float px, float py, float pz) {
+    const int n[3] = {g.nx, g.ny, g.nz};
+    const float p[3] = {px, py, pz};
+    int i0[3], i1[3];
+    float t[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        float u = p[a] - 0.5f;
+        if (u < 0.f) u = 0.f;
+        if (u > (float)(n[a] - 1)) u = (float)(n[a] - 1);
+        int b = (int)u;
+        if (b >= n[a] - 1) { b = n[a] - 1; i0[a] = b; i1[a] = b; t[a] = 0.f; }
+        else { i0[a] = b; i1[a] = b + 1; t[a] = u - (float)b; }
+    }
+    const int64_t sy = g.nx, sz = (int64_t)g.nx * g.ny;
+    auto at = [&](int i, int j, int k) { return f[i + j * sy + k * sz]; };
+    auto L = [](float a, float b, float tt) { return a + (b - a) * tt; };
+    const float c00 = L(at(i0[0], i0[1], i0[2]), at(i1[0], i0[1], i0[2]), t[0]);
+    const float c10 = L(at(i0[0], i1[1], i0[2]), at(i1[0], i1[1], i0[2]), t[0]);
+    const float c01 = L(at(i0[0], i0[1], i1[2]), at(i1[0], i0[1], i1[2]), t[0]);
+    const float c11 = L(at(i0[0], i1[1], i1[2]), at(i1[0], i1[1], i1[2]), t[0]);
+    return L(L(c00, c10, t[1]), L(c01, c11, t[1]), t[2]);
+}
+__device__ inline double densityAt(const BlockArgs& A, int axis, int i, int j, int k) {
+    if (!A.dens) return A.rho;
+    const float px = (float)i + (axis == 0 ? 0.f : 0.5f), py = (float)j + (axis == 1 ? 0.f : 0.5f), pz = (float)k + (axis == 2 ? 0.f : 0.5f);
+    const double v = (double)densSample(A.dens, A.g, px, py, pz);
+    return v < A.densMin ? A.densMin : (v > A.densMax ? A.densMax : v);
+}
+
 __global__ void k_S_count(BlockArgs A, int axis, int32_t* __restrict__ rowCount) {
     const int3 d = A.g.dims(1 + axis);
     const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -303,9 +338,11 @@ __global__ void k_S_fill(BlockArgs A, int axis, const int32_t* __restrict__ ptr,
         const double lo = 0.1 * 0.1;   // MINWEIGHT * MINWEIGHT, :365
         volume = volume < lo ? lo : (volume > 1.0 ? 1.0 : volume);
         const double u = (double)A.vel[axis][c];
-        McInv[row] = 1. / (volume * A.rho);
-        rhsA[row] = u * volume * A.rho;
-        if (Mc) Mc[row] = volume * A.rho;
+        const int3 q = unlin3(d, c);
+        const double rho = densityAt(A, axis, q.x, q.y, q.z);
+        McInv[row] = 1. / (volume * rho);
+        rhsA[row] = u * volume * rho;
+        if (Mc) Mc[row] = volume * rho;
         if (oldVs) oldVs[row] = u;
     }
 }
@@ -511,6 +548,7 @@ BlockArgs makeArgs(ps_context* c) {
     for (int a = 0; a < 3; ++a) { A.faceRow[a] = c->faceRow[a].p; A.vel[a] = c->vel[a].p; A.cvel[a] = c->cvel[a].p; A.sysT[a] = c->sysIdxT[a].p; }
     A.visc = c->viscosity.p;
     A.viscUniform = c->viscUniform ? 1 : 0; A.viscValue = c->viscUniformValue;
+    A.dens = c->densField ? c->density.p : nullptr; A.densMin = c->densMin; A.densMax = c->densMax;
     A.nCenter = c->nCenter; A.nEdge0 = c->nEdge[0]; A.nEdge1 = c->nEdge[1];
     A.nP = c->nPressures; A.nA = c->nActiveVs;
     A.faceOff[0] = 0; A.faceOff[1] = c->nFace[0]; A.faceOff[2] = c->nFace[0] + c->nFace[1];

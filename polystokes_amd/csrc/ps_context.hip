@@ -83,6 +83,7 @@ void ps_context::upload(const ps_params* p, const ps_fields_in* in) {
     chebInner32 = false;
     g.nx = in->nx; g.ny = in->ny; g.nz = in->nz; g.order = p->indexOrder;
     dx = in->dx; invDx = 1. / dx; dt = in->dt; invDt = 1. / dt; rho = (double)in->density;
+    rhoScalar = rho; densField = false;   // every upload drops a density field (ps_upload_density_field): it described the previous grid
     HIP_CHECK(hipSetDevice(device));
     const int64_t nc = g.count(0);
     uploadField(surface, in->surface, nc, stream);
@@ -123,6 +124,32 @@ void ps_context::upload(const ps_params* p, const ps_fields_in* in) {
     deviceShareRows = 0; nXseg[0] = nXseg[1] = 0;
     blockMapOwned = -1;
     gOff[0] = gOff[1] = gOff[2] = 0;
+}
+
+// ps_upload_density_field.  A constant field (all values equal) runs the scalar path at its clamped value, as a constant viscosity skips
+// the sampling (viscUniform); any other field is uploaded and sampled per face by the setup kernels (ps_blocks.hip / ps_tiles.hip: densityAt).
+// Returns the reason an input is refused (the field is then dropped), or an empty string.
+std::string ps_context::uploadDensity(const float* field) {
+    densField = false;
+    densFieldHost = 0;
+    rho = rhoScalar;
+    if (!field) return {};
+    const double lo = P.mindensity, hi = P.maxdensity;
+    if (!std::isfinite(lo) || !std::isfinite(hi) || !(lo > 0.) || hi < lo)
+        return "ps_upload_density_field: mindensity must be positive and maxdensity at least mindensity, both finite";
+    const int64_t nc = g.count(0);
+    for (int64_t i = 0; i < nc; ++i)
+        if (!std::isfinite(field[i])) return "ps_upload_density_field: non-finite value at cell " + std::to_string(i);
+    const float v0 = field[0];
+    bool same = true;
+    for (int64_t i = 1; i < nc && same; ++i) same = field[i] == v0;
+    densMin = lo; densMax = hi;
+    if (same) { const double v = (double)v0; rho = v < lo ? lo : (v > hi ? hi : v); return {}; }
+    HIP_CHECK(hipSetDevice(device));
+    uploadField(density, field, nc, stream);
+    HIP_CHECK(hipStreamSynchronize(stream));
+    densField = true;
+    return {};
 }
 
 void ps_context::fillDimData(ps_stats* st) const {   // Solver.cpp:578-593
@@ -340,6 +367,9 @@ void ps_context::registerArrays() {
     // the default path does not gain a copy per step
     reg("warmStartUsed", &warmUsedHost, 1, 4);
     arrays["warmStartUsed"].host = true;
+    densFieldHost = densField ? 1 : 0;   // 1: the last setup sampled a non-constant density field (ps_upload_density_field)
+    reg("densityField", &densFieldHost, 1, 4);
+    arrays["densityField"].host = true;
     if (P.preconditioner == PS_PRE_DIAGONAL) regp("dinv", dinv.p, nSystem, permSys.p, 0);
     if (isSolved) {
         regp("recoveredActiveVelocity", recovered.p, nActiveVs, permRow.p, 0);
@@ -641,6 +671,15 @@ int32_t ps_download_fields(ps_context* c, ps_fields_out* out) {
             if (out->valid[a]) HIP_CHECK(hipMemcpyAsync(out->valid[a], c->valid[a].p, nb, hipMemcpyDeviceToHost, c->stream));
         }
         HIP_CHECK(hipStreamSynchronize(c->stream));
+        return PS_SUCCESS;
+    })
+}
+int32_t ps_upload_density_field(ps_context* c, const float* density) {
+    if (!c) return PS_FAILED;
+    PS_TRY(c, {
+        if (!c->uploaded) { c->err = "ps_upload_density_field: call ps_upload_fields first"; return PS_INVALID; }
+        const std::string why = c->uploadDensity(density);
+        if (!why.empty()) { c->err = why; return PS_INVALID; }
         return PS_SUCCESS;
     })
 }

@@ -108,10 +108,17 @@ struct ps_context {
     bool haveInputWeights = false;
     bool viscUniform = false;       // the viscosity field is one value everywhere (checked at upload): samplers return it without loads
     float viscUniformValue = 0.f;
+    // Variable density (ps_upload_density_field): densField = a non-constant cell field in `density`, sampled per face and clamped to
+    // [densMin, densMax]; a constant one only sets rho to its clamped value.  rhoScalar: ps_fields_in.density of the last upload.
+    double rhoScalar = 0, densMin = 0, densMax = 0;
+    bool densField = false;
+    int32_t densFieldHost = 0;      // array "densityField": the last setup used a non-constant field
     bool uploaded = false, isSetup = false, isSolved = false;
+    std::string uploadDensity(const float* field);
 
     // ---- inputs (fp32 Houdini voxel arrays, HDK_PolyStokes.C:235-246) ----
-    ps::DevBuf<float> surface, collision, viscosity, vel[3], cvel[3];
+    ps::DevBuf<float> surface, collision, viscosity, density, vel[3], cvel[3];
+    ps::DevBuf<double> densFace[3];          // a density field's clamped face samples, per face grid (the tile mass sums read them)
     ps::DevBuf<float> velOut[3], valid[3];
 
     // ---- weights, labels, indices (Solver.h:316-335) ----

@@ -940,19 +940,23 @@ __global__ void __launch_bounds__(BS) k_spmv_St_ell(const uint16_t* __restrict__
 // second; a wave owns units 2 (w & 1) and 2 (w & 1) + 1 of its chunk and has the streams, the gathers and the epilogue loads of both in
 // flight before it sums either.  Same products, same order per row: bit-identical t; the per-workgroup partials of sum s.t group differently.
 // TV: element type of x and of the output (double; float = the inner applies of the single-precision Chebyshev polynomial, VecIO)
-template <int POL, bool LIST, class TV = double>
-__global__ void __launch_bounds__(BS) k_spmv_S_ell2(const uint16_t* __restrict__ ecol, const int8_t* __restrict__ ecode, unsigned colBytes, unsigned codeBytes,
-                                                    const int32_t* __restrict__ winBase, const int4* __restrict__ echunk, double scale,
-                                                    const TV* __restrict__ x, int cols, int rows, int nA, double dt, TV* __restrict__ out,
-                                                    const int* __restrict__ done, int nChunks, const uint8_t* __restrict__ mcCode, const double* __restrict__ mcDict,
-                                                    double* __restrict__ stPart, const int32_t* __restrict__ list) {   // LIST: as k_spmv_S_ell (nChunks = entries of the list)
+// MC: the face mass McInv comes as one-byte codes into a 256-entry table (true) or, when it takes more than 256 values — a density FIELD
+// (ps_upload_density_field) —, as the fp64 array itself, passed in mcCode's place and read through the same buffer policy (false: 7 more
+// bytes per active row; the St kernels' UC = false for the stress diagonal)
+// The coded form launches as k_spmv_S_ell2, the uncoded one as k_spmv_S_ell2u (one body, spmvSEll2).
+template <int POL, bool LIST, class TV, bool MC>
+__device__ __forceinline__ void spmvSEll2(const uint16_t* __restrict__ ecol, const int8_t* __restrict__ ecode, unsigned colBytes, unsigned codeBytes,
+                                          const int32_t* __restrict__ winBase, const int4* __restrict__ echunk, double scale,
+                                          const TV* __restrict__ x, int cols, int rows, int nA, double dt, TV* __restrict__ out,
+                                          const int* __restrict__ done, int nChunks, const uint8_t* __restrict__ mcCode, const double* __restrict__ mcDict,
+                                          double* __restrict__ stPart, const int32_t* __restrict__ list) {   // LIST: as k_spmv_S_ell (nChunks = entries of the list)
     if (done && *done) return;
     constexpr bool NT = (POL & 1) != 0, SNT = (POL & 2) != 0;
-    __shared__ double dict[256];
-    dict[threadIdx.x] = mcDict[threadIdx.x];
+    __shared__ double dict[MC ? 256 : 1];
+    if (MC) dict[threadIdx.x] = mcDict[threadIdx.x];
     __syncthreads();
     const __amdgpu_buffer_rsrc_t rCol = bufRsrc(ecol, colBytes), rCode = bufRsrc(ecode, codeBytes), rX = bufRsrc(x, (size_t)cols * sizeof(TV)),
-                                 rMcc = bufRsrc(mcCode, (size_t)nA), rOut = bufRsrc(out, (size_t)rows * sizeof(TV));
+                                 rMcc = bufRsrc(mcCode, MC ? (size_t)nA : (size_t)nA * 8), rOut = bufRsrc(out, (size_t)rows * sizeof(TV));
     const unsigned lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int half = wv >> 1, u0 = 2 * (wv & 1);
@@ -982,12 +986,16 @@ __global__ void __launch_bounds__(BS) k_spmv_S_ell2(const uint16_t* __restrict__
             const EllRegs sa = ellLoad<SNT>(rCol, rCode, ua, lane), sb = ellLoad<SNT>(rCol, rCode, ub, lane);
             if (nchunk >= 0) { nci = echunk[nchunk]; nBase = winBase[nchunk * 16 + (lane & 15)]; }     // the next step's record, behind this step's streams
             const unsigned rowA = (int)lane < ua.rows ? (unsigned)ua.row0 + lane : ROW_NONE, rowB = (int)lane < ub.rows ? (unsigned)ub.row0 + lane : ROW_NONE;
-            const int mA = (int)__builtin_amdgcn_raw_buffer_load_b8(rMcc, (int)rowA, 0, NT ? PS_EPI_AUX : 0);
-            const int mB = (int)__builtin_amdgcn_raw_buffer_load_b8(rMcc, (int)rowB, 0, NT ? PS_EPI_AUX : 0);
+            int mA = 0, mB = 0;
+            double mvA = 0., mvB = 0.;      // (rows past nA read 0 through the buffer's range; their scale is 1 below)
+            if (MC) {
+                mA = (int)__builtin_amdgcn_raw_buffer_load_b8(rMcc, (int)rowA, 0, NT ? PS_EPI_AUX : 0);
+                mB = (int)__builtin_amdgcn_raw_buffer_load_b8(rMcc, (int)rowB, 0, NT ? PS_EPI_AUX : 0);
+            } else { mvA = bufLoadF64epi<NT>(rMcc, rowA * 8u); mvB = bufLoadF64epi<NT>(rMcc, rowB * 8u); }
             const EllX XA = ellGatherW<TV>(ua.W, sa, myBase, rX);
             const EllX XB = ellGatherW<TV>(ub.W, sb, myBase, rX);
             const double a = ellSumW(ua.W, sa, XA, scale), b = ellSumW(ub.W, sb, XB, scale);
-            const double scA = (int)rowA < nA ? dt * dict[mA] : 1., scB = (int)rowB < nA ? dt * dict[mB] : 1.;
+            const double scA = (int)rowA < nA ? dt * (MC ? dict[mA] : mvA) : 1., scB = (int)rowB < nA ? dt * (MC ? dict[mB] : mvB) : 1.;
             stAcc += (int)rowA < nA ? a * (a * scA) : 0.;
             stAcc += (int)rowB < nA ? b * (b * scB) : 0.;
             VecIO<TV>::template store<NT>(rOut, rowA, a * scA);
@@ -1000,6 +1008,17 @@ __global__ void __launch_bounds__(BS) k_spmv_S_ell2(const uint16_t* __restrict__
         if (threadIdx.x == 0) stPart[blockIdx.x] = bs;
     }
 }
+#define PS_S_ELL2_PARAMS const uint16_t* __restrict__ ecol, const int8_t* __restrict__ ecode, unsigned colBytes, unsigned codeBytes, \
+                         const int32_t* __restrict__ winBase, const int4* __restrict__ echunk, double scale, const TV* __restrict__ x, int cols, int rows, \
+                         int nA, double dt, TV* __restrict__ out, const int* __restrict__ done, int nChunks, const uint8_t* __restrict__ mcCode, \
+                         const double* __restrict__ mcDict, double* __restrict__ stPart, const int32_t* __restrict__ list
+#define PS_S_ELL2_ARGS ecol, ecode, colBytes, codeBytes, winBase, echunk, scale, x, cols, rows, nA, dt, out, done, nChunks, mcCode, mcDict, stPart, list
+template <int POL, bool LIST, class TV = double>
+__global__ void __launch_bounds__(BS) k_spmv_S_ell2(PS_S_ELL2_PARAMS) { spmvSEll2<POL, LIST, TV, true>(PS_S_ELL2_ARGS); }
+template <int POL, bool LIST, class TV = double>       // mcCode = the fp64 McInv array
+__global__ void __launch_bounds__(BS) k_spmv_S_ell2u(PS_S_ELL2_PARAMS) { spmvSEll2<POL, LIST, TV, false>(PS_S_ELL2_ARGS); }
+#undef PS_S_ELL2_ARGS
+#undef PS_S_ELL2_PARAMS
 
 // The same for the St kernel of the plain single-domain step (k_spmv_St_ell<3, POL, 3>: coded uInv, residual update in the epilogue): two
 // units in flight per wave, two chunks per workgroup and step (r04; default, PS_ST_DUAL=0 switches back).  Compiled for six waves per SIMD

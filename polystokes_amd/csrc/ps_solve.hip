@@ -78,13 +78,17 @@ struct Launch {
             // two units in flight per wave (k_spmv_S_ell2; r04): 256^3, same box, two interleaved rounds: S 0.2809 / 0.2816 -> 0.2672 / 0.2609 ms in
             // sequence, step 1128.6 / 1130.2 -> 1117.3 / 1118.5 ms (profiles/r04_s_dual.txt).  PS_S_DUAL=0: the one-unit kernel.
             static const bool dual = !(PS_ENV("PS_S_DUAL") && atoi(PS_ENV("PS_S_DUAL")) == 0);
-            if (dual && mode == 0 && c->mcCoded && (gr.x & 7) == 0) {
+            // The face mass McInv as 1-byte codes (k_spmv_S_ell2) or, past 256 distinct values (a density field), as the fp64 array (k_spmv_S_ell2u).
+            if (dual && mode == 0 && (gr.x & 7) == 0) {
                 const int pol = policy(M);
-#define PS_LAUNCH_S2L(POL_, LIST_) hipLaunchKernelGGL((k_spmv_S_ell2<POL_, LIST_>), gr, bl, 0, c->stream, M.ecol.p, M.ecode.p, (unsigned)(M.ellCols * 2), (unsigned)M.ellCodes, M.winBase.p, \
-                                              M.echunk.p, c->valScale, x, (int)M.cols, rowsS, nA, c->dt, out, done, nChunks, (const uint8_t*)c->mcCode.p, c->mcDict.p, sPart, sList)
-#define PS_LAUNCH_S2(POL_) do { if (sList) PS_LAUNCH_S2L(POL_, true); else PS_LAUNCH_S2L(POL_, false); } while (0)
+                const uint8_t* mcArg = c->mcCoded ? (const uint8_t*)c->mcCode.p : (const uint8_t*)c->McInv.p;
+#define PS_LAUNCH_S2L(POL_, LIST_, K_) hipLaunchKernelGGL((K_<POL_, LIST_>), gr, bl, 0, c->stream, M.ecol.p, M.ecode.p, (unsigned)(M.ellCols * 2), (unsigned)M.ellCodes, M.winBase.p, \
+                                              M.echunk.p, c->valScale, x, (int)M.cols, rowsS, nA, c->dt, out, done, nChunks, mcArg, c->mcDict.p, sPart, sList)
+#define PS_LAUNCH_S2M(POL_, K_) do { if (sList) PS_LAUNCH_S2L(POL_, true, K_); else PS_LAUNCH_S2L(POL_, false, K_); } while (0)
+#define PS_LAUNCH_S2(POL_) do { if (c->mcCoded) PS_LAUNCH_S2M(POL_, k_spmv_S_ell2); else PS_LAUNCH_S2M(POL_, k_spmv_S_ell2u); } while (0)
                 if (pol == 3) PS_LAUNCH_S2(3); else if (pol == 1) PS_LAUNCH_S2(1); else PS_LAUNCH_S2(0);
 #undef PS_LAUNCH_S2
+#undef PS_LAUNCH_S2M
 #undef PS_LAUNCH_S2L
                 return;
             }
@@ -158,7 +162,7 @@ struct Launch {
     bool cheb32Ok() const {
         static const bool dualS = !(PS_ENV("PS_S_DUAL") && atoi(PS_ENV("PS_S_DUAL")) == 0), dualT = !(PS_ENV("PS_ST_DUAL") && atoi(PS_ENV("PS_ST_DUAL")) == 0);
         static const bool noFuse = PS_ENV("PS_TILE_SPLIT") && atoi(PS_ENV("PS_TILE_SPLIT")) != 0;
-        return dualS && dualT && listsOk() && c->mcCoded && !c->slabEnabled && !sList && !stList && xcdAware > 0 && c->S.nChunks >= 8 && c->St.nChunks >= 8 &&
+        return dualS && dualT && listsOk() && !c->slabEnabled && !sList && !stList && xcdAware > 0 && c->S.nChunks >= 8 && c->St.nChunks >= 8 &&
                rowsS > 0 && rowsSt > 0 && (c->regionCount == 0 || (c->maxRegionRows <= TILE_FUSED_MAX_ROWS && !noFuse));
     }
     void spmvS32(const float* x, float* out) const {
@@ -166,9 +170,12 @@ struct Launch {
         int xcd = xcdAware;
         const dim3 gr(pipeBlocks(M.nChunks, xcd, true, sCap())), bl(BS);
         const int pol = policy(M);
-#define PS_LAUNCH_S2F(POL_) hipLaunchKernelGGL((k_spmv_S_ell2<POL_, false, float>), gr, bl, 0, c->stream, M.ecol.p, M.ecode.p, (unsigned)(M.ellCols * 2), (unsigned)M.ellCodes, M.winBase.p, \
-                                               M.echunk.p, c->valScale, x, (int)M.cols, rowsS, nA, c->dt, out, done, M.nChunks, (const uint8_t*)c->mcCode.p, c->mcDict.p, (double*)nullptr, (const int32_t*)nullptr)
-        if (pol == 3) PS_LAUNCH_S2F(3); else if (pol == 1) PS_LAUNCH_S2F(1); else PS_LAUNCH_S2F(0);
+        const uint8_t* mcArg = c->mcCoded ? (const uint8_t*)c->mcCode.p : (const uint8_t*)c->McInv.p;
+#define PS_LAUNCH_S2F(POL_, K_) hipLaunchKernelGGL((K_<POL_, false, float>), gr, bl, 0, c->stream, M.ecol.p, M.ecode.p, (unsigned)(M.ellCols * 2), (unsigned)M.ellCodes, M.winBase.p, \
+                                               M.echunk.p, c->valScale, x, (int)M.cols, rowsS, nA, c->dt, out, done, M.nChunks, mcArg, c->mcDict.p, (double*)nullptr, (const int32_t*)nullptr)
+#define PS_LAUNCH_S2F2(POL_) do { if (c->mcCoded) PS_LAUNCH_S2F(POL_, k_spmv_S_ell2); else PS_LAUNCH_S2F(POL_, k_spmv_S_ell2u); } while (0)
+        if (pol == 3) PS_LAUNCH_S2F2(3); else if (pol == 1) PS_LAUNCH_S2F2(1); else PS_LAUNCH_S2F2(0);
+#undef PS_LAUNCH_S2F2
 #undef PS_LAUNCH_S2F
     }
     void tiles32(float* ts) const {

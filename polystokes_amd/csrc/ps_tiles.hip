@@ -19,7 +19,8 @@ constexpr int BS = 256;
 constexpr int FBATCH = 128;
 constexpr int OUTW = PS_RD * PS_RD + PS_RD;   // 676 block entries + 26 rhs entries
 
-enum { MODE_MASS = 0, MODE_LSQ = 1, MODE_VISC = 2 };
+// MODE_MASS_FIELD: MODE_MASS with a density field — each face's row scaled by its own density (densityAt) instead of the scalar rho
+enum { MODE_MASS = 0, MODE_LSQ = 1, MODE_VISC = 2, MODE_MASS_FIELD = 3 };
 
 struct TileArgs {
     Grid g;
@@ -29,6 +30,9 @@ struct TileArgs {
     const float* vel[3];
     const float* visc;
     int viscUniform; float viscValue;   // a constant field: its samples without loads (bit-identical: ps_context::upload)
+    const float* dens;                  // cell density field (ps_upload_density_field); null: the scalar rho everywhere
+    double densMin, densMax;
+    const double* densFace[3];          // its clamped face samples (k_face_density), read by the MODE_MASS_FIELD sums
     const double* COM;
     int3 off;                       // global index of the local cell (0, 0, 0) (ps_kernels_tiles.hpp: rowOffset)
     const int32_t* bbox;
@@ -68,6 +72,33 @@ __device__ inline float viscSample(const TileArgs& A, float px, float py, float 
     const float c01 = L(at(i0[0], i0[1], i1[2]), at(i1[0], i0[1], i1[2]), t[0]);
     const float c11 = L(at(i0[0], i1[1], i1[2]), at(i1[0], i1[1], i1[2]), t[0]);
     return L(L(c00, c10, t[1]), L(c01, c11, t[1]), t[2]);
+}
+
+// Density of the face (axis, i, j, k), as ps_blocks.hip:densityAt (the face rows' McInv / Mc): the cell field sampled at the face centre
+// with the viscosity's sampler, clamped to [mindensity, maxdensity] (a field is present: k_face_density samples every face once)
+__device__ inline double densityAt(const TileArgs& A, int axis, int i, int j, int k) {
+    const int n[3] = {A.g.nx, A.g.ny, A.g.nz};
+    const float p[3] = {(float)i + (axis == 0 ? 0.f : 0.5f), (float)j + (axis == 1 ? 0.f : 0.5f), (float)k + (axis == 2 ? 0.f : 0.5f)};
+    int i0[3], i1[3];
+    float t[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        float u = p[a] - 0.5f;
+        if (u < 0.f) u = 0.f;
+        if (u > (float)(n[a] - 1)) u = (float)(n[a] - 1);
+        int b = (int)u;
+        if (b >= n[a] - 1) { b = n[a] - 1; i0[a] = b; i1[a] = b; t[a] = 0.f; }
+        else { i0[a] = b; i1[a] = b + 1; t[a] = u - (float)b; }
+    }
+    const int64_t sy = A.g.nx, sz = (int64_t)A.g.nx * A.g.ny;
+    auto at = [&](int ii, int jj, int kk) { return A.dens[ii + jj * sy + kk * sz]; };
+    auto L = [](float a, float b, float tt) { return a + (b - a) * tt; };
+    const float c00 = L(at(i0[0], i0[1], i0[2]), at(i1[0], i0[1], i0[2]), t[0]);
+    const float c10 = L(at(i0[0], i1[1], i0[2]), at(i1[0], i1[1], i0[2]), t[0]);
+    const float c01 = L(at(i0[0], i0[1], i1[2]), at(i1[0], i0[1], i1[2]), t[0]);
+    const float c11 = L(at(i0[0], i1[1], i1[2]), at(i1[0], i1[1], i1[2]), t[0]);
+    const double v = (double)L(L(c00, c10, t[1]), L(c01, c11, t[1]), t[2]);
+    return v < A.densMin ? A.densMin : (v > A.densMax ? A.densMax : v);
 }
 
 __device__ inline void faceOffset(const TileArgs& A, int axis, int i, int j, int k, int region, double* o) {
@@ -165,9 +196,11 @@ __device__ void viscosityRow(const TileArgs& A, int faceAxis, int i, int j, int 
 
 template <int MODE>
 __global__ void __launch_bounds__(BS) k_region_outer(TileArgs A, double* __restrict__ partial) {
+    constexpr bool DENS = MODE == MODE_MASS_FIELD, MASS = MODE == MODE_MASS || DENS;
     __shared__ double sa[FBATCH][PS_RD];
     __shared__ double sb[MODE == MODE_VISC ? FBATCH : 1][PS_RD];
     __shared__ double su[FBATCH];
+    __shared__ double sr[DENS ? FBATCH : 1];   // the density of each staged face
     const int item = blockIdx.x;
     const int r = A.itemRegion[item], axis = A.itemAxis[item], start = A.itemStart[item];
     const int bx0 = A.bbox[r * 6 + 0], by0 = A.bbox[r * 6 + 1], bz0 = A.bbox[r * 6 + 2];
@@ -189,7 +222,7 @@ __global__ void __launch_bounds__(BS) k_region_outer(TileArgs A, double* __restr
             const int pos = base + t;
             bool use = false;
             double a[PS_RD];
-            double uval = 0.;
+            double uval = 0., rf = 0.;
             if (pos < end) {
                 const int li = pos % ex, lj = (pos / ex) % ey, lk = pos / (ex * ey);
                 const int i = bx0 + li, j = by0 + lj, k = bz0 + lk;
@@ -197,7 +230,7 @@ __global__ void __launch_bounds__(BS) k_region_outer(TileArgs A, double* __restr
                     int3 hi = make_int3(i, j, k), lo = hi;
                     addc(lo, axis, -1);
                     const int lhi = labAt(A, 0, cd, hi.x, hi.y, hi.z), llo = labAt(A, 0, cd, lo.x, lo.y, lo.z);
-                    if (MODE == MODE_MASS) use = (lhi == PS_REDUCED) || (llo == PS_REDUCED && isActiveL(lhi));
+                    if (MASS) use = (lhi == PS_REDUCED) || (llo == PS_REDUCED && isActiveL(lhi));
                     else if (MODE == MODE_LSQ) use = (lhi == PS_REDUCED && isActiveL(llo)) || (llo == PS_REDUCED && isActiveL(lhi));
                     else use = true;
                     if (use) {
@@ -205,6 +238,7 @@ __global__ void __launch_bounds__(BS) k_region_outer(TileArgs A, double* __restr
                         faceOffset(A, axis, i, j, k, r, o);
                         basisRow(o[0], o[1], o[2], axis, a);
                         if (MODE == MODE_LSQ) uval = (double)A.vel[axis][lin3(fd, i, j, k)];
+                        if (DENS) rf = A.densFace[axis][lin3(fd, i, j, k)];
                         if (MODE == MODE_VISC) {
                             double gv[PS_RD];
                             viscosityRow(A, axis, i, j, k, gv);
@@ -225,6 +259,7 @@ __global__ void __launch_bounds__(BS) k_region_outer(TileArgs A, double* __restr
 #pragma unroll
             for (int n = 0; n < PS_RD; ++n) sa[t][n] = a[n];
             su[t] = uval;
+            if (DENS) sr[t] = rf;
         }
         __syncthreads();
 #pragma unroll
@@ -233,8 +268,9 @@ __global__ void __launch_bounds__(BS) k_region_outer(TileArgs A, double* __restr
                 double s = acc[q];
                 if (MODE == MODE_VISC) {
                     for (int f = 0; f < FBATCH; ++f) s += sa[f][em[q]] * sb[f][en[q]];
-                } else if (MODE == MODE_MASS) {
-                    for (int f = 0; f < FBATCH; ++f) s += (A.rho * sa[f][em[q]]) * sa[f][en[q]];
+                } else if (MASS) {
+                    if (DENS) { for (int f = 0; f < FBATCH; ++f) s += (sr[f] * sa[f][em[q]]) * sa[f][en[q]]; }
+                    else { for (int f = 0; f < FBATCH; ++f) s += (A.rho * sa[f][em[q]]) * sa[f][en[q]]; }
                 } else {
                     for (int f = 0; f < FBATCH; ++f) s += sa[f][em[q]] * sa[f][en[q]];
                 }
@@ -267,6 +303,7 @@ constexpr int MPAD = 32;
 
 template <int MODE>
 __global__ void __launch_bounds__(BS) k_region_outer_mfma(TileArgs A, double* __restrict__ partial) {
+    constexpr bool DENS = MODE == MODE_MASS_FIELD, MASS = MODE == MODE_MASS || DENS;
     // rows padded to 33 doubles: with 32 every lane of a wave stores its row's entry n into the SAME bank pair (row stride 256 B =
     // all 64 banks) — a 32-way conflict on each of the 32 stores per face, which was most of this kernel's time
     __shared__ double sa[FBATCH][MPAD + 1];
@@ -317,7 +354,7 @@ __global__ void __launch_bounds__(BS) k_region_outer_mfma(TileArgs A, double* __
                 int3 hi = make_int3(i, j, k), lo = hi;
                 addc(lo, axis, -1);
                 const int lhi = labAt(A, 0, cd, hi.x, hi.y, hi.z), llo = labAt(A, 0, cd, lo.x, lo.y, lo.z);
-                if (MODE == MODE_MASS) use = (lhi == PS_REDUCED) || (llo == PS_REDUCED && isActiveL(lhi));
+                if (MASS) use = (lhi == PS_REDUCED) || (llo == PS_REDUCED && isActiveL(lhi));
                 else if (MODE == MODE_LSQ) use = (lhi == PS_REDUCED && isActiveL(llo)) || (llo == PS_REDUCED && isActiveL(lhi));
                 else use = true;
             }
@@ -331,9 +368,10 @@ __global__ void __launch_bounds__(BS) k_region_outer_mfma(TileArgs A, double* __
                 double o[3];
                 faceOffset(A, axis, i, j, k, r, o);
                 basisRow(o[0], o[1], o[2], axis, vec);
-                if (MODE == MODE_MASS && !doB) {
+                if (MASS && !doB) {
+                    const double rf = DENS ? A.densFace[axis][lin3(fd, i, j, k)] : A.rho;
 #pragma unroll
-                    for (int n = 0; n < PS_RD; ++n) vec[n] *= A.rho;
+                    for (int n = 0; n < PS_RD; ++n) vec[n] *= rf;
                 }
                 if (MODE == MODE_LSQ && doB) vec[PS_RD] = (double)A.vel[axis][lin3(fd, i, j, k)];   // rhs column: sum_f C_f u_f
                 if (MODE == MODE_VISC) viscosityRow(A, axis, i, j, k, gv1, 1);
@@ -393,6 +431,15 @@ __global__ void __launch_bounds__(BS) k_region_outer_mfma(TileArgs A, double* __
             else if (n == PS_RD) out[PS_RD * PS_RD + m] = acc[q];   // LSQ right-hand side (zero in the other modes)
         }
     }
+}
+
+// the density of every face of one axis (densityAt), sampled once for the tile mass sums
+__global__ void k_face_density(TileArgs A, int axis, double* __restrict__ out) {
+    const int3 fd = A.g.dims(1 + axis);
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= (int64_t)fd.x * fd.y * fd.z) return;
+    const int3 q = unlin3(fd, c);
+    out[c] = densityAt(A, axis, q.x, q.y, q.z);
 }
 
 // out[r] = sum of the region's item partials, in item order
@@ -696,6 +743,8 @@ TileArgs makeArgs(ps_context* c) {
     for (int a = 0; a < 3; ++a) A.vel[a] = c->vel[a].p;
     A.visc = c->viscosity.p;
     A.viscUniform = c->viscUniform ? 1 : 0; A.viscValue = c->viscUniformValue;
+    A.dens = c->densField ? c->density.p : nullptr; A.densMin = c->densMin; A.densMax = c->densMax;
+    for (int a = 0; a < 3; ++a) A.densFace[a] = c->densFace[a].p;
     A.COM = c->COM.p;
     A.off = make_int3(c->gOff[0], c->gOff[1], c->gOff[2]);
     A.bbox = c->bbox.p;
@@ -716,7 +765,9 @@ void runOuter(ps_context* c, double* out676, double* out26) {
     // shared (scripts/ladder_tile_classes.py): Mr carries the tile's rigid modes, which the large pressure-stress terms cancel against.
     // So Mr (2.3 of the 7.8 ms at 256^3) stays per tile and the tolerance ladder of tests/test_gpu_parity.py keeps its bounds.
     static const int clsMask = PS_ENV("PS_TILE_CLASS_MASK") ? atoi(PS_ENV("PS_TILE_CLASS_MASK")) : 2;
-    if (MODE != MODE_LSQ && ((MODE == MODE_MASS ? 1 : 2) & clsMask) && c->tileReps > 0 && c->tileReps < c->regionCount) {   // one sum per class of identical tiles, copied to the others
+    // (a density field makes Mr a function of the tile's densities, which the class signature does not see: Mr then stays per tile)
+    const bool shareable = MODE == MODE_VISC || (MODE == MODE_MASS && !c->densField);
+    if (shareable && ((MODE == MODE_MASS ? 1 : 2) & clsMask) && c->tileReps > 0 && c->tileReps < c->regionCount) {   // one sum per class of identical tiles, copied to the others
         A.itemRegion = c->repItemRegion.p; A.itemAxis = c->repItemAxis.p; A.itemStart = c->repItemStart.p;
         if (useMfma) hipLaunchKernelGGL(k_region_outer_mfma<MODE>, dim3((unsigned)c->repItems), dim3(BS), 0, c->stream, A, c->partials.p);
         else hipLaunchKernelGGL(k_region_outer<MODE>, dim3((unsigned)c->repItems), dim3(BS), 0, c->stream, A, c->partials.p);
@@ -724,7 +775,16 @@ void runOuter(ps_context* c, double* out676, double* out26) {
         hipLaunchKernelGGL(k_tile_replicate, dim3((unsigned)c->regionCount), dim3(BS), 0, c->stream, (const int32_t*)c->tileRep.p, out676);
         return;
     }
-    if (useMfma) hipLaunchKernelGGL(k_region_outer_mfma<MODE>, dim3((unsigned)c->fbItems), dim3(BS), 0, c->stream, A, c->partials.p);
+    if (MODE == MODE_MASS && c->densField) {   // (the scalar form below is the code without a field)
+        for (int a = 0; a < 3; ++a) {
+            const int64_t n = c->g.count(1 + a);
+            c->densFace[a].alloc((size_t)n);
+            A.densFace[a] = c->densFace[a].p;
+            hipLaunchKernelGGL(k_face_density, dim3(gridFor(n, BS)), dim3(BS), 0, c->stream, A, a, c->densFace[a].p);
+        }
+        if (useMfma) hipLaunchKernelGGL(k_region_outer_mfma<MODE_MASS_FIELD>, dim3((unsigned)c->fbItems), dim3(BS), 0, c->stream, A, c->partials.p);
+        else hipLaunchKernelGGL(k_region_outer<MODE_MASS_FIELD>, dim3((unsigned)c->fbItems), dim3(BS), 0, c->stream, A, c->partials.p);
+    } else if (useMfma) hipLaunchKernelGGL(k_region_outer_mfma<MODE>, dim3((unsigned)c->fbItems), dim3(BS), 0, c->stream, A, c->partials.p);
     else hipLaunchKernelGGL(k_region_outer<MODE>, dim3((unsigned)c->fbItems), dim3(BS), 0, c->stream, A, c->partials.p);
     hipLaunchKernelGGL(k_region_sum, dim3((unsigned)c->regionCount), dim3(BS), 0, c->stream, c->partials.p, c->fbRegionItemPtr.p, out676, out26);
 }

@@ -191,3 +191,25 @@ def scene_brick(name, n, dims, rank, tile=16, pad=2, precond=1, weak=False):
     zb.origin = [b.origin[0], b.origin[1], 0]
     return partition.local_scene_brick(full, zb), p, b
 
+
+
+def with_density_field(sc, kind, rho0=None, contrast=10.0, split=None):
+    """Attach a cell density field (Scene.density_field, ps_upload_density_field) to `sc` and return it.
+    kind "layers": rho0 * contrast below the z-plane k = split (default nz // 2 + 3: through the middle of a tile), rho0 above — two
+    liquids in one container; "smooth": rho0 * (1 + 0.5 sin(..) cos(..)) with a z term, thousands of distinct values (McInv is then
+    not value-set coded).  rho0 defaults to the scene's scalar density.  The values stay finite and positive; the solver clamps the
+    face samples to [mindensity, maxdensity] of its params (default [1, 1e5]), so pick rho0 inside that range."""
+    rho0 = float(sc.density if rho0 is None else rho0)
+    nx, ny, nz = sc.nx, sc.ny, sc.nz
+    x, y, z = _centers(nx, ny, nz, sc.dx)
+    L = np.float64(max(nx, ny, nz) * sc.dx)
+    if kind == "layers":
+        k = nz // 2 + 3 if split is None else int(split)
+        kk = np.arange(nz).reshape(nz, 1, 1)
+        f = np.where(kk < k, rho0 * contrast, rho0) + 0.0 * x + 0.0 * y
+    elif kind == "smooth":
+        f = rho0 * (1.0 + 0.5 * np.sin(2 * np.pi * x / L + 0.3) * np.cos(2 * np.pi * y / L - 0.7) + 0.1 * np.sin(3 * np.pi * z / L))
+    else:
+        raise ValueError(f"unknown density field kind {kind!r} (layers | smooth)")
+    sc.density_field = np.ascontiguousarray(np.broadcast_to(f, (nz, ny, nx)), dtype=np.float32)
+    return sc

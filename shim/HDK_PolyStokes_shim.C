@@ -74,6 +74,7 @@ const ParmRow theRows[] = {
     {'T', "debugGeometry",              "Publish Debug Geometry",           nullptr,            0},
     {'T', "warmStartPreviousStep",      "Warm Start From Previous Step",    nullptr,            0},
     {'T', "writePressureField",         "Write Pressure Field",             nullptr,            0},
+    {'T', "variableDensity",            "Variable Density",                 nullptr,            0},
 };
 constexpr int theRowCount = (int)(sizeof(theRows) / sizeof(theRows[0]));
 }  // namespace
@@ -177,8 +178,13 @@ bool HDK_PolyStokes::solveGasSubclass(SIM_Engine& engine, SIM_Object* obj, SIM_T
     if (!pressureField) return fail("Pressure field is missing.", UT_ERROR_ABORT);
     if (!densityField) return fail("Density field is missing.", UT_ERROR_ABORT);
     fpreal32 constantLiquidDensity = 0.;
-    if (!densityField->getField()->field()->isConstant(&constantLiquidDensity))
+    // shim-only toggle variableDensity: a non-constant density field goes to ps_upload_density_field (face samples clamped to
+    // [mindensity, maxdensity]); off, the reference's refusal stands
+    const bool variableDensity = !densityField->getField()->field()->isConstant(&constantLiquidDensity);
+    if (variableDensity && !getVariableDensity())
         return fail("Variable density is not currently supported", UT_ERROR_WARNING);
+    if (variableDensity && !densityField->isAligned(surfaceField))
+        return fail("Density field must align with the surface field to be used as a variable density.", UT_ERROR_ABORT);
     if (!surfaceWeights && getUseInputSurfaceWeights())
         return fail("User requested to use input surface weights but that field is missing.", UT_ERROR_ABORT);
     if (!collisionWeights && getUseInputCollisionWeights())
@@ -232,6 +238,8 @@ bool HDK_PolyStokes::solveGasSubclass(SIM_Engine& engine, SIM_Object* obj, SIM_T
     toDense(*surfaceField->getField(), surf);
     toDense(*collisionField->getField(), coll);
     toDense(*viscosityField->getField(), visc);
+    std::vector<float> dens;
+    if (variableDensity) toDense(*densityField->getField(), dens);
 
     ps_fields_in in = {};
     {
@@ -240,6 +248,7 @@ bool HDK_PolyStokes::solveGasSubclass(SIM_Engine& engine, SIM_Object* obj, SIM_T
         in.nx = rx; in.ny = ry; in.nz = rz;
     }
     in.dx = dx; in.dt = dt; in.density = constantLiquidDensity;   // fpreal (double) like HDK_PolyStokes.C:319-320
+    if (variableDensity) in.density = 1.f;                         // (positive placeholder: the field replaces it on every face)
     const UT_Vector3 orig = velocityField->getOrig();
     in.orig[0] = orig.x(); in.orig[1] = orig.y(); in.orig[2] = orig.z();
     for (int a = 0; a < 3; ++a) { in.vel[a] = vel[a].data(); in.collisionvel[a] = cvel[a].data(); }
@@ -266,7 +275,20 @@ bool HDK_PolyStokes::solveGasSubclass(SIM_Engine& engine, SIM_Object* obj, SIM_T
     ps_set_interrupt(myCtx, &interruptTrampoline, boss);
 
     ps_stats st;
-    const int result = polystokes_step(myCtx, &p, &in, &out, &st);      // == HDK_PolyStokes::Solver::SolverResult (Solver.h:61-70)
+    int result;                                                         // == HDK_PolyStokes::Solver::SolverResult (Solver.h:61-70)
+    if (!variableDensity) result = polystokes_step(myCtx, &p, &in, &out, &st);
+    else {                                                              // polystokes_step's sequence with the density field after the upload
+        result = ps_upload_fields(myCtx, &p, &in);
+        if (result == PS_SUCCESS && ps_upload_density_field(myCtx, dens.data()) != PS_SUCCESS) result = PS_FAILED;   // (reason: ps_last_error)
+        if (result == PS_SUCCESS) result = ps_setup_device(myCtx, nullptr);
+        if (result == PS_SUCCESS) {
+            result = ps_solve_device(myCtx, &st);
+            if (result != PS_FAILED && ps_download_fields(myCtx, &out) != PS_SUCCESS) result = PS_FAILED;
+            if (result != PS_FAILED && p.exportMatrices && p.exportDataPrefix) ps_export_matrices(myCtx, p.exportDataPrefix);
+            if (result != PS_FAILED && p.exportComponentMatrices && p.exportDataPrefix) ps_export_component_matrices(myCtx, p.exportDataPrefix);
+            if (result != PS_FAILED && p.exportStats && p.exportDataPrefix) ps_export_stats(myCtx, &st, p.exportDataPrefix);
+        }
+    }
     ps_set_interrupt(myCtx, nullptr, nullptr);
 
     if (result == PS_FAILED) return fail(ps_last_error(myCtx), UT_ERROR_ABORT);
