@@ -227,6 +227,24 @@ typedef struct ps_solution_out {
 } ps_solution_out;
 int32_t ps_download_solution_fields(ps_context* ctx, const ps_solution_out* out);
 
+/* Surface tension (extension; neither the reference node nor its solver has one).  A context setting like ps_set_warm_start: it persists
+ * across ps_upload_fields and applies to every later setup, so a polystokes_step caller sets it once.  sigma = 0 (the default) is off and
+ * launches exactly the kernels of a context that never made the call.  sigma > 0 gives the non-liquid part of every cell next to a face
+ * of the system the pressure sigma * kappa_c instead of 0 (a ghost-fluid pressure jump): with the stencil coefficient
+ * gradSign * wF_f * liquidW_c / dx of face f and cell c, the ghost coefficient g(f,c) is gradSign * wF_f * (1 - liquidW_c) / dx for a cell with
+ * a pressure DOF or inside a reduced tile, gradSign * wF_f / dx for any other cell of the grid, and the step adds the impulse
+ * -dt * sum_c g(f,c) sigma kappa_c to the active rhs of f ("activeRHSVector"), or C_f^T times it to its tile's rhs ("reducedRHSVector").
+ * b, the recovered velocity, the exports, the EIGEN path and ps_solve_exported_system follow from these two vectors.
+ * kappa = div(grad phi / |grad phi|) of the uploaded `surface` SDF in fp64 (central differences, the mixed terms on the 4-point diagonal
+ * stencil, indices clamped at the grid border; 0 where |grad phi| < 1e-6 / dx), stored in fp32 and sampled trilinearly (clamped to the grid)
+ * at the closest interface point x_c - phi_c grad phi_c / |grad phi_c|^2, the step capped at 4 cells (a solid cell deep under the liquid
+ * reads the level set 4 cells toward the surface), then clamped to [-1/dx, 1/dx]: that is kappa_c.  Every read lies within 7 cells of a face.
+ * Orthogonal to the density field, warm start, the Chebyshev preconditioners and the BiCGStab fallback; slab and brick ranks compute it on
+ * their own grid (the halo blocks cover the stencil).  PS_INVALID (reason in ps_last_error, the previous setting kept): sigma negative or
+ * not finite.  Arrays: "surfaceTension" (fp64, 1: the sigma of the last setup), "surfaceCurvature" (fp32 cell grid: the kappa_c the last
+ * setup used; only with sigma > 0), "surfaceTensionReducedFaces" (int32: reduced faces that received an impulse; only with sigma > 0). */
+int32_t ps_set_surface_tension(ps_context* ctx, double sigma);
+
 /* solveGasSubclass equivalent on host buffers: upload + step + download (HDK_PolyStokes.C:222-609). */
 int32_t polystokes_step(ps_context* ctx, const ps_params* p, const ps_fields_in* in,
                         ps_fields_out* out, ps_stats* stats);

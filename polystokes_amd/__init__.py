@@ -25,7 +25,7 @@ EXPORTED_SYMBOLS = [
     "ps_export_component_matrices", "ps_export_matrices", "ps_export_stats", "ps_bench_kernel", "ps_memory_stats", "ps_set_interrupt", "ps_solve_exported_system",
     "ps_set_slab", "ps_set_brick", "ps_comm_unique_id", "ps_comm_init_rccl", "ps_comm_selftest", "ps_comm_init_tcp", "ps_dist_stats",
     "ps_group_create", "ps_group_destroy", "ps_group_rank", "ps_group_step",
-    "ps_set_warm_start", "ps_download_solution_fields", "ps_upload_density_field",
+    "ps_set_warm_start", "ps_download_solution_fields", "ps_upload_density_field", "ps_set_surface_tension",
 ]
 
 
@@ -113,6 +113,8 @@ def lib():
         L.ps_download_solution_fields.restype = C.c_int32
         L.ps_upload_density_field.argtypes = [C.c_void_p, C.c_void_p]
         L.ps_upload_density_field.restype = C.c_int32
+        L.ps_set_surface_tension.argtypes = [C.c_void_p, C.c_double]
+        L.ps_set_surface_tension.restype = C.c_int32
         _lib = L
     return _lib
 
@@ -123,7 +125,8 @@ _DT = {(1, "i"): np.int8, (4, "i"): np.int32, (4, "f"): np.float32, (8, "f"): np
 def _kind(name):
     if name.endswith(("Labels", "Indices", ".col", ".ptr", "Region", "Perm", ".chunkInfo", ".chunkRep", ".code")) or name.startswith("faceRow"):
         return "i"
-    if name in ("valuesCoded", "columns16", "diagonalsCoded", "fusedStep", "streamRuns", "rowPerLane", "chebInner32", "warmStartUsed", "densityField"):
+    if name in ("valuesCoded", "columns16", "diagonalsCoded", "fusedStep", "streamRuns", "rowPerLane", "chebInner32", "warmStartUsed", "densityField",
+                "surfaceTensionReducedFaces"):
         return "i"
     if name in ("ownedX", "ownedY", "ownedZ"):
         return "f"
@@ -178,6 +181,11 @@ class Solver:
         """ps_set_warm_start: 0 (WARM_NONE) solves from zero; 1 (WARM_PREVIOUS_STEP) starts the next PCG solve from the solution this
         context carried over from its last kept step.  Every call drops the carried solution."""
         self._check(self.L.ps_set_warm_start(self.h, int(mode)))
+
+    def set_surface_tension(self, sigma):
+        """ps_set_surface_tension: sigma (force per length; 0 = off) for every later setup of this context, across uploads.  Returns the
+        ps_result: INVALID for a negative or non-finite sigma (the reason in last_error(), the previous setting kept)."""
+        return self._check(self.L.ps_set_surface_tension(self.h, float(sigma)), allow=(1, -2))
 
     def solution_fields(self):
         """ps_download_solution_fields: the last solve's [p; tau] as dense fp32 grids (x fastest), keyed pressure, txx, tyy, tzz, tyz, txz, txy;
@@ -245,8 +253,15 @@ class Solver:
         self.scene, self.params = scene, params
         fi = scene.fields_in()
         self._check(self.L.ps_upload_fields(self.h, C.byref(params), C.byref(fi)))
+        self._scene_surface_tension(scene)
         if getattr(scene, "density_field", None) is not None:
             self._check(self.upload_density_field(scene.density_field))
+
+    def _scene_surface_tension(self, scene):
+        """Scene.surface_tension (None: the context keeps its setting) -> ps_set_surface_tension; a refused value raises."""
+        sigma = getattr(scene, "surface_tension", None)
+        if sigma is not None:
+            self._check(self.L.ps_set_surface_tension(self.h, float(sigma)))
 
     def upload_density_field(self, field):
         """ps_upload_density_field: a cell density field for the grid of the last upload (None drops it).  Returns the ps_result
@@ -280,6 +295,7 @@ class Solver:
             self.download()
             return rc
         self.scene, self.params = scene, params
+        self._scene_surface_tension(scene)
         fi = scene.fields_in()
         out, keep = self._fields_out()
         rc = self._check(self.L.polystokes_step(self.h, C.byref(params), C.byref(fi), C.byref(out), C.byref(self.stats)),

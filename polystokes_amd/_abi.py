@@ -120,7 +120,7 @@ class Scene:
     """Host-side input bundle: numpy float32 arrays laid out as the C ABI expects."""
 
     def __init__(self, nx, ny, nz, dx, dt, density, vel, surface, collision, viscosity,
-                 collisionvel=None, weights=None, name="scene", density_field=None):
+                 collisionvel=None, weights=None, name="scene", density_field=None, surface_tension=None):
         self.nx, self.ny, self.nz, self.dx, self.dt, self.density = nx, ny, nz, float(dx), float(dt), float(density)
         sh = grid_shapes(nx, ny, nz)
         f32 = lambda a, s: np.array(np.broadcast_to(np.asarray(a, dtype=np.float32), s), dtype=np.float32, order="C", copy=True)
@@ -137,6 +137,8 @@ class Scene:
         self.name = name
         # optional cell density field (ps_upload_density_field); None: the scalar `density` everywhere
         self.density_field = None if density_field is None else f32(density_field, sh["center"])
+        # optional surface tension coefficient sigma (ps_set_surface_tension, applied at upload / step); None: leave the context's setting
+        self.surface_tension = None if surface_tension is None else float(surface_tension)
 
     def fields_in(self):
         fi = FieldsIn()

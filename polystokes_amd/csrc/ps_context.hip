@@ -370,6 +370,12 @@ void ps_context::registerArrays() {
     densFieldHost = densField ? 1 : 0;   // 1: the last setup sampled a non-constant density field (ps_upload_density_field)
     reg("densityField", &densFieldHost, 1, 4);
     arrays["densityField"].host = true;
+    reg("surfaceTension", &sigmaUsed, 1, 8);   // the sigma of the last setup (ps_set_surface_tension)
+    arrays["surfaceTension"].host = true;
+    if (sigmaUsed != 0.) {
+        reg("surfaceCurvature", kappaC.p, g.count(0), 4);
+        reg("surfaceTensionReducedFaces", stReduced.p, 1, 4);
+    }
     if (P.preconditioner == PS_PRE_DIAGONAL) regp("dinv", dinv.p, nSystem, permSys.p, 0);
     if (isSolved) {
         regp("recoveredActiveVelocity", recovered.p, nActiveVs, permRow.p, 0);
@@ -680,6 +686,17 @@ int32_t ps_upload_density_field(ps_context* c, const float* density) {
         if (!c->uploaded) { c->err = "ps_upload_density_field: call ps_upload_fields first"; return PS_INVALID; }
         const std::string why = c->uploadDensity(density);
         if (!why.empty()) { c->err = why; return PS_INVALID; }
+        return PS_SUCCESS;
+    })
+}
+int32_t ps_set_surface_tension(ps_context* c, double sigma) {
+    if (!c) return PS_FAILED;
+    PS_TRY(c, {
+        if (!std::isfinite(sigma) || sigma < 0.) {
+            c->err = "ps_set_surface_tension: sigma must be finite and not negative (0: off)";
+            return PS_INVALID;
+        }
+        c->sigmaSet = sigma;   // read by the next setup (applySurfaceTension)
         return PS_SUCCESS;
     })
 }

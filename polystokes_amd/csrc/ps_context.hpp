@@ -115,6 +115,12 @@ struct ps_context {
     int32_t densFieldHost = 0;      // array "densityField": the last setup used a non-constant field
     bool uploaded = false, isSetup = false, isSolved = false;
     std::string uploadDensity(const float* field);
+    // Surface tension (ps_set_surface_tension): sigmaSet is the context setting, sigmaUsed the value of the last setup (array "surfaceTension").
+    // With sigma > 0 the setup adds the ghost-pressure impulse to rhsA / rhsR (ps_surface.hip); the buffers exist only then.
+    double sigmaSet = 0, sigmaUsed = 0;
+    ps::DevBuf<float> kappaRaw, kappaC;      // cell grids: kappa of the SDF, and kappa_c (sampled at the interface point, clamped)
+    ps::DevBuf<int32_t> stReduced;           // reduced faces that received an impulse (array "surfaceTensionReducedFaces")
+    void applySurfaceTension();              // ps_surface.hip: after the blocks and tile rhs, before b
 
     // ---- inputs (fp32 Houdini voxel arrays, HDK_PolyStokes.C:235-246) ----
     ps::DevBuf<float> surface, collision, viscosity, density, vel[3], cvel[3];

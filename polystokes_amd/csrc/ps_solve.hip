@@ -422,6 +422,7 @@ void ps_context::applyOperator(const double* xdev, double* ydev, double* dotPart
 // AssembleSystem.cpp:432-470 (+ the reduced blocks of AssembleBlocks.cpp)
 void ps_context::assembleSystemPressureStressFactored() {
     assembleReducedBlocks();
+    applySurfaceTension();   // ps_surface.hip: the ghost-pressure impulse into rhsA / rhs_r (sigma = 0: nothing)
     const int64_t n = nSystem;
     ts.alloc((size_t)nRows + 1);
     vreg.alloc((size_t)std::max<int64_t>(1, regionCount) * PS_RD);

@@ -59,7 +59,8 @@ def local_scene(scene, slab):
                cut(scene.surface), cut(scene.collision), cut(scene.viscosity),
                collisionvel=[cut(scene.collisionvel[0]), cut(scene.collisionvel[1]), cut(scene.collisionvel[2], 1)],
                name=f"{scene.name}.r{slab.rank}",
-               density_field=None if getattr(scene, "density_field", None) is None else cut(scene.density_field))
+               density_field=None if getattr(scene, "density_field", None) is None else cut(scene.density_field),
+               surface_tension=getattr(scene, "surface_tension", None))
     return sc
 
 
@@ -112,7 +113,8 @@ def local_scene_brick(scene, b):
     faces = lambda v: [cut(v[0], ex=1), cut(v[1], ey=1), cut(v[2], ez=1)]
     return Scene(nx, ny, nz, scene.dx, scene.dt, scene.density, faces(scene.vel), cut(scene.surface), cut(scene.collision), cut(scene.viscosity),
                  collisionvel=faces(scene.collisionvel), name=f"{scene.name}.b{b.rank}",
-                 density_field=None if getattr(scene, "density_field", None) is None else cut(scene.density_field))
+                 density_field=None if getattr(scene, "density_field", None) is None else cut(scene.density_field),
+                 surface_tension=getattr(scene, "surface_tension", None))
 
 
 def merge_faces_brick(global_out, local_out, owned_mask, b, axis):

@@ -213,3 +213,18 @@ def with_density_field(sc, kind, rho0=None, contrast=10.0, split=None):
         raise ValueError(f"unknown density field kind {kind!r} (layers | smooth)")
     sc.density_field = np.ascontiguousarray(np.broadcast_to(f, (nz, ny, nx)), dtype=np.float32)
     return sc
+
+
+def ellipsoid_droplet(n=32, axes=(0.36, 0.26, 0.26), tile=8, pad=2, center=(0.5, 0.5, 0.5), sigma=None):
+    """A resting liquid ellipsoid with semi-axes `axes` (x, y, z) floating in air, no solids, no gravity: under surface tension
+    (Scene.surface_tension = sigma; None leaves it unset) it flows from the tips of its long axis toward its equator.
+    The SDF is the first-order distance estimate (|p / a| - 1) |p / a| / |p / a^2|: exact on the surface, with a unit gradient there."""
+    dx, dt = 1.0 / n, 1.0 / 24.0
+    x, y, z = _centers(n, n, n, dx)
+    a = [float(v) for v in axes]
+    p = (x - center[0], y - center[1], z - center[2])
+    k0 = np.sqrt(sum((p[i] / a[i]) ** 2 for i in range(3)))
+    k1 = np.sqrt(sum((p[i] / (a[i] * a[i])) ** 2 for i in range(3)))
+    surface = (k0 - 1.0) * k0 / np.maximum(k1, 1e-12)
+    sc = Scene(n, n, n, dx, dt, 1000.0, [0.0, 0.0, 0.0], surface, np.float32(10.0), 50.0, name=f"ellipsoid{n}", surface_tension=sigma)
+    return sc, default_params(tileSize=tile, tilePadding=pad)

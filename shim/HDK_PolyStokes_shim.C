@@ -75,6 +75,8 @@ const ParmRow theRows[] = {
     {'T', "warmStartPreviousStep",      "Warm Start From Previous Step",    nullptr,            0},
     {'T', "writePressureField",         "Write Pressure Field",             nullptr,            0},
     {'T', "variableDensity",            "Variable Density",                 nullptr,            0},
+    {'T', "enableSurfaceTension",       "Enable Surface Tension",           nullptr,            0},
+    {'F', "surfaceTension",             "Surface Tension",                  nullptr,            0},
 };
 constexpr int theRowCount = (int)(sizeof(theRows) / sizeof(theRows[0]));
 }  // namespace
@@ -198,6 +200,10 @@ bool HDK_PolyStokes::solveGasSubclass(SIM_Engine& engine, SIM_Object* obj, SIM_T
         if (ps_set_warm_start(myCtx, warmMode) != PS_SUCCESS) return fail(ps_last_error(myCtx), UT_ERROR_ABORT);
         myWarmMode = warmMode;
     }
+    // shim-only: surface tension as a curvature pressure jump in the solve (ps_set_surface_tension, a context setting: sigma = 0 is off and
+    // launches nothing extra).  A refused sigma (negative or not finite) aborts with the library's reason.
+    const double sigma = getEnableSurfaceTension() ? (double)getSurfaceTension() : 0.;
+    if (ps_set_surface_tension(myCtx, sigma) != PS_SUCCESS) return fail(ps_last_error(myCtx), UT_ERROR_ABORT);
 
     const fpreal dt = timestep;
     const fpreal dx = velocityField->getVoxelSize(0).maxComponent();

@@ -46,6 +46,8 @@ public:
     GET_DATA_FUNC_B("warmStartPreviousStep",            WarmStartPreviousStep);   // ps_set_warm_start(PS_WARM_PREVIOUS_STEP) (0)
     GET_DATA_FUNC_B("writePressureField",               WritePressureField);      // solved pressure into the pressure field (0)
     GET_DATA_FUNC_B("variableDensity",                  VariableDensity);         // a non-constant density field -> ps_upload_density_field (0)
+    GET_DATA_FUNC_B("enableSurfaceTension",             EnableSurfaceTension);    // ps_set_surface_tension(surfaceTension) (0)
+    GET_DATA_FUNC_F("surfaceTension",                   SurfaceTension);          // sigma of the curvature pressure jump (0)
 
 protected:
     explicit HDK_PolyStokes(const SIM_DataFactory* factory);
