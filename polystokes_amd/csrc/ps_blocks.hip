@@ -775,8 +775,8 @@ __global__ void __launch_bounds__(BS) k_ell_fill(const int4* __restrict__ chunkI
 // Row-per-lane form of M's compressed stream (needs the windowed stream of buildCol16 and coded values)
 void ps_context::buildEll(ps::DevCSR& M) {
     M.ellok = false;
-    static const bool off = (PS_ENV("PS_NO_ELL") && atoi(PS_ENV("PS_NO_ELL")) != 0) ||            // A/B: keep the 4-entries-per-lane kernels
-                            (PS_ENV("PS_PIPE_GRID") && atoi(PS_ENV("PS_PIPE_GRID")) == 0);       // (one-shot CSR kernels asked for)
+    static const bool off = envInt(PS_ENV("PS_NO_ELL"), 0) != 0 ||  // A/B: keep the 4-entries-per-lane kernels
+                            envInt(PS_ENV("PS_PIPE_GRID"), 1) == 0;   // (one-shot CSR kernels asked for)
     if (off || !M.col16ok || !M.packed || M.nChunks == 0 || (uint64_t)std::max(M.rows, M.cols) * 8 >= 0xffff8000ull) return;
     const int nChunks = M.nChunks;
     DevBuf<int32_t>& colBegin = scrEllCol; DevBuf<int32_t>& codeBegin = scrEllCode; DevBuf<int32_t>& wpack = scrEllW;
@@ -841,7 +841,7 @@ void ps_context::buildCol16(ps::DevCSR& M, int slot, const std::vector<int32_t>&
     std::vector<int2> rowsOf;
     {
         constexpr int CHUNK_ALIGN_MIN = 512;
-        static const bool plain = PS_ENV("PS_CHUNK_PLAIN") && atoi(PS_ENV("PS_CHUNK_PLAIN")) != 0;   // A/B: uniform 256-row chunks
+        static const bool plain = envInt(PS_ENV("PS_CHUNK_PLAIN"), 0) != 0;   // A/B: uniform 256-row chunks
         bool ok = !plain && cuts.size() >= 2 && cuts.front() == 0 && (int64_t)cuts.back() == M.rows;
         for (size_t i = 1; ok && i < cuts.size(); ++i) ok = cuts[i] >= cuts[i - 1];
         auto emit = [&](int64_t lo, int64_t hi) { for (int64_t r = lo; r < hi; r += BS) rowsOf.push_back(make_int2((int)r, (int)std::min<int64_t>(BS, hi - r))); };
@@ -880,8 +880,8 @@ void ps_context::buildCol16(ps::DevCSR& M, int slot, const std::vector<int32_t>&
                        M.code4.p, M.winBase.p, M.chunkInfo.p, M.len8.p, counters.p + slot, M.chunkRep.p, nChunks);
     M.col16ok = readCounter(slot) == 0;
     if (M.col16ok && !M.packed) buildVal4(M);
-    static const bool noShare = PS_ENV("PS_NO_SHARED_RUNS") && atoi(PS_ENV("PS_NO_SHARED_RUNS")) != 0;
-    static const bool weakHash = PS_ENV("PS_WEAK_CHUNK_HASH") && atoi(PS_ENV("PS_WEAK_CHUNK_HASH")) != 0;   // test: force hash collisions
+    static const bool noShare = envInt(PS_ENV("PS_NO_SHARED_RUNS"), 0) != 0;
+    static const bool weakHash = envInt(PS_ENV("PS_WEAK_CHUNK_HASH"), 0) != 0;   // test: force hash collisions
     if (M.col16ok && M.packed && shareRuns && !noShare && nChunks > 1) {          // coded values only: the fp64 values of equal codes need not be equal bits
         unsigned cap = 1024;
         while (cap < 4u * (unsigned)nChunks) cap <<= 1;

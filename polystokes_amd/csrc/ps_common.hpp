@@ -28,6 +28,8 @@
 #define PS_ENV(name) getenv(name)
 #endif
 #define PS_ENV_VERBOSE() getenv("PS_VERBOSE")
+// the integer value of a switch, given the result of PS_ENV("NAME") (never the name: the release build must not hold it); dflt when unset
+inline int envInt(const char* v, int dflt) { return v ? atoi(v) : dflt; }
 // the lab build names, once, every switch that changes RESULTS or loads code when it finds it set
 #ifdef PS_RELEASE
 #define PS_ENV_LOUD(name) (static_cast<const char*>(nullptr))

@@ -949,13 +949,13 @@ struct Dist {
     // while this rank's contributions to its neighbours travel.  Built from two flag kernels and a host pass per setup.
     void buildLists() {
         { int64_t all = 0; for (ps_context* c : R) all += c->nSystem; for (ps_context* c : R) c->deviceShareRows = inProcess() ? all : 0; }
-        static const bool mergedFix = !(PS_ENV("PS_DIST_FIXUP_MERGED") && atoi(PS_ENV("PS_DIST_FIXUP_MERGED")) == 0);   // A/B: 0 = one k_dist_fixup launch per link
+        static const bool mergedFix = envInt(PS_ENV("PS_DIST_FIXUP_MERGED"), 1) != 0;   // A/B: 0 = one k_dist_fixup launch per link
         for (ps_context* c : R) { c->nFix = 0; if (mergedFix) buildFixup(c); }
         for (ps_context* c : R) {
             c->distListsOk = false;
             for (int q = 0; q < 5; ++q) c->nDistList[q] = 0;
             Launch L = mk(c, nullptr);
-            static const bool off = PS_ENV("PS_DIST_OVERLAP") && atoi(PS_ENV("PS_DIST_OVERLAP")) == 0;   // A/B: the sequential exchange
+            static const bool off = envInt(PS_ENV("PS_DIST_OVERLAP"), 1) == 0;   // A/B: the sequential exchange
             if (off || !L.listsOk() || c->S.nChunks == 0 || c->St.nChunks == 0) continue;
             const int nS = c->S.nChunks, nT = c->St.nChunks;
             DevBuf<int32_t>& flags = c->scrVals;               // setup scratch
@@ -989,7 +989,7 @@ struct Dist {
     // if ANY rank finds one that is not (agreed through the scalar all-reduce), every rank rebuilds its lists with the forwarded copies and the
     // exchanges run axis after axis as in r03 / r04.  PS_DIST_FORWARD=1 (lab build) forces the forwarding rounds.
     void decideExchangeMode() {
-        static const bool force = PS_ENV("PS_DIST_FORWARD") && atoi(PS_ENV("PS_DIST_FORWARD")) != 0;
+        static const bool force = envInt(PS_ENV("PS_DIST_FORWARD"), 0) != 0;
         bool need = force;
         for (ps_context* c : R) {
             if (need || c->nSystem == 0 || c->S.nnz == 0) continue;
@@ -1097,7 +1097,7 @@ struct Dist {
         // neighbours, who subtract alpha times it (k_dist_fixup).  Same rule as the single-domain solve: coded streams on every
         // rank and >= FUSED_STEP_MIN_ROWS owned rows on the largest (PS_FUSED_R = 0 / 1 forces); decided from values every rank
         // knows or agrees on, so all ranks take the same branch.
-        static const int fusedEnv = PS_ENV("PS_FUSED_R") ? atoi(PS_ENV("PS_FUSED_R")) : -1;
+        static const int fusedEnv = envInt(PS_ENV("PS_FUSED_R"), -1);
         bool fused = !cheb && fusedEnv != 0;
         for (size_t q = 0; q < R.size(); ++q) fused = fused && loc[q].L.fusedOk() && loc[q].n > 0;
         {
@@ -1117,7 +1117,7 @@ struct Dist {
         // the exchanges overlap with the rows that do not need them when every rank has its chunk lists (row-per-lane kernels)
         // (the ranks of an in-process group share ONE stream: nothing runs beside anything, and splitting S and St into the chunks next to a cut and
         // the rest only doubles their launches — one launch each there; PS_DIST_OVERLAP=1 forces the split for the tests that walk that path on one GPU)
-        static const bool forceSplit = PS_ENV("PS_DIST_OVERLAP") && atoi(PS_ENV("PS_DIST_OVERLAP")) == 1;
+        static const bool forceSplit = envInt(PS_ENV("PS_DIST_OVERLAP"), 0) == 1;
         bool overlap = fused && (useRccl || useTcp || forceSplit);
         for (ps_context* c : R) overlap = overlap && c->distListsOk;
         if (useRccl || useTcp) {   // all ranks take the same branch (the kernels differ, not the messages — but keep the ranks alike)

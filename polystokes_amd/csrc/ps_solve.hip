@@ -15,7 +15,8 @@
 //                          with the scalar reductions and the stop rule folded in; scalars stay on the device), the legacy
 //                          k_cg_update_xr / _p / scal* used by the exported-system path, BiCGStab helpers, Jacobi diagonal,
 //                          velocity recovery / write-back.
-//   this file            : the launch dispatch (Launch), ps_context::applyOperator / assemble / solve / recover.
+//   this file            : the launch dispatch (Launch: planS / planSt choose the kernel and grid of a product, one launcher per kernel family runs it),
+//                          ps_context::applyOperator / assemble / solve / recover.
 //   ps_dist.hpp          : the z-slab distributed solve (RCCL or in-process ranks) and its C ABI.
 //   ps_import.hpp        : MatrixMarket import + general CSR PCG (ps_solve_exported_system).
 #include <chrono>
@@ -36,19 +37,40 @@ namespace {
 
 // ---------------------------------------------------------------------------------------------------
 namespace {
+// A runtime value as a template argument: f gets std::integral_constant<int, V> for the first V equal to v (withOneOf; the last V
+// otherwise) or not above v (withAtLeast).  Each launcher names the values its kernel is instantiated for, so no cross product is taken.
+// (They return auto, so each is instantiated where it is called, depth first: the kernels it names are instantiated in the order they are written.)
+template <class F> auto withBool(bool b, F&& f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
+template <int V0, int... V, class F> auto withOneOf(int v, F&& f) {
+    if constexpr (sizeof...(V) == 0) f(std::integral_constant<int, V0>{}); else if (v == V0) f(std::integral_constant<int, V0>{}); else withOneOf<V...>(v, f);
+}
+template <int V0, int... V, class F> auto withAtLeast(int v, F&& f) {
+    if constexpr (sizeof...(V) == 0) f(std::integral_constant<int, V0>{}); else if (v >= V0) f(std::integral_constant<int, V0>{}); else withAtLeast<V...>(v, f);
+}
+template <class F> auto withPolicy(int pol, F&& f) { withOneOf<3, 1, 0>(pol, f); }
+// the pipelined kernels: the fp64-value stream (F64) with POL 3 only
+template <class F> auto withPipe(bool packed, int pol, F&& f) {
+    if (!packed) f(std::true_type{}, std::integral_constant<int, 3>{}); else withPolicy(pol, [&](auto POL) { f(std::false_type{}, POL); });
+}
+template <class T> struct Type { using type = T; };
+
+// The kernel of one S or St product (ps_kernels_spmv.hpp).  CSR: k_spmv_S / k_spmv_St (one-shot); PIPE: k_spmv_S_pipe / k_spmv_St_pipe
+// (persistent, compressed or fp64-value stream); ELL: k_spmv_S_ell / k_spmv_St_ell (FX), row-per-lane on the coded stream; two units in flight
+// per wave: ELL2 = k_spmv_S_ell2 / _ell2u, or k_spmv_St_ell2 in its plain MODE 3 form, ELL2C = k_spmv_St_ell2c (a Chebyshev term), and
+// k_spmv_St_ell2 with the polynomial's first term (ELL2Z), over a rank's owned rows (ELL2_OWN) or over rows that include halo rows (ELL2_HALO).
+enum Kernel { CSR, PIPE, ELL, ELL2, ELL2C, ELL2Z, ELL2_OWN, ELL2_HALO };
+struct Plan {
+    Kernel kernel;
+    int grid = 0, xcd = 0, nChunks = 0;   // workgroups (one partial sum each), ChunkWalk parameter after pipeBlocks (0: plain walk)
+    int pol = 0, fx = 0;                  // Launch::policy, k_spmv_St_ell's FX
+    bool run = true;                      // false: nothing to launch (no rows, an empty chunk list)
+    const char* err = nullptr;            // a launch that must not happen
+};
+
 struct Launch {
     ps_context* c;
     const int* done;
     int rowsS, rowsSt, nA, nP;
-    void spmvS_(int mode, const double* x, double* out) const {
-        const dim3 gr(gridFor(rowsS, BS)), bl(BS);
-        const ps::DevCSR& M = c->S;
-#define PS_LAUNCH_S(MODE_, PK_) hipLaunchKernelGGL((k_spmv_S<MODE_, 8, PK_>), gr, bl, 0, c->stream, M.ptr.p, M.col.p, M.val.p, M.code.p, \
-                                                   c->valScale, x, rowsS, nA, c->dt, c->McInv.p, out, done)
-        if (mode == 0) { if (M.packed) PS_LAUNCH_S(0, true); else PS_LAUNCH_S(0, false); }
-        else { if (M.packed) PS_LAUNCH_S(1, true); else PS_LAUNCH_S(1, false); }
-#undef PS_LAUNCH_S
-    }
     // fused residual update (solve(): FusedR): where the S and tile kernels leave their shares of p.Ap (null: not asked for)
     double* sPart = nullptr;
     double* wvPart = nullptr;
@@ -56,273 +78,254 @@ struct Launch {
     const int32_t* sList = nullptr; int nSList = 0;
     const int32_t* stList = nullptr; int nStList = 0;
     bool stOwnedOnly = false;        // the St chunk list holds owned rows only (the decomposition's launch under the exchange): FX bit 2
-    bool listsOk() const { return pipeGrid > 0 && c->S.col16ok && c->S.packed && c->S.ellok && c->St.col16ok && c->St.packed && c->St.ellok; }
-    // workgroups of a launch over n chunks of S / St (the partial sums it writes)
-    int sBlocksFor(int n) const { int xcd = xcdAware; return n > 0 ? pipeBlocks(n, xcd, true, sCap()) : 0; }
-    int stBlocksFor(int n, int mode) const { int xcd = xcdAware; return n > 0 ? pipeBlocks(n, xcd, true, stGridFor(mode)) : 0; }
+    bool cz32 = false;   // MODE 3 with the polynomial's first term: fr.cz points at floats (k_spmv_St_ell2<.., float>)
     bool ntSpmv = true;   // cache policy of the pipelined kernels' streams (ps_context::ntLevel >= 1)
+    int pipeGrid;   // 0: one-shot kernels; >0: persistent software-pipelined kernels with this many blocks
+    int stGrid = 0; // > 0: the St kernel's own cap
+    int stGrid2 = 0; // > 0: the Chebyshev term's St launch alone (A/B)
+    int xcdAware;   // pipelined kernels: runs of this many chunks are dealt to the XCDs round robin (ChunkWalk); 0 = plain walk
+    bool dualS = true, dualT = true;   // the two-units-per-wave S / St kernels (PS_S_DUAL / PS_ST_DUAL = 0: the one-unit kernels)
+    bool tileSplit = false;            // the three-kernel tile apply (PS_TILE_SPLIT)
+    int tileTB = 0;                    // threads per region of the fused tile apply (PS_TILE_TB; 0: tileThreads())
+    // MODE 3 of the row-per-lane St kernel in its plain form (FX = 1: no Chebyshev first term, no halo rows, coded uInv) fits 7 workgroups per CU
+    bool plain3Hint = false;
+    bool plain3Hint2 = false;   // the same for the Chebyshev step: single domain, coded uInv
+
     // POL of the pipelined kernels (ps_kernels_spmv.hpp): 0 = default policy; 1 = non-temporal stores and epilogue streams, cached matrix
     // stream (most runs shared between chunks: read again and again); 3 = the matrix stream non-temporal too (every run read once)
     int policy(const ps::DevCSR& M) const { return !ntSpmv ? 0 : (2 * M.uniqueLen <= M.streamLen ? 1 : 3); }
-    int pipeGrid;   // 0: one-shot kernels; >0: persistent software-pipelined kernels with this many blocks
-    int stGrid = 0; // > 0: the St kernel's own cap
-    int xcdAware;   // pipelined kernels: runs of this many chunks are dealt to the XCDs round robin (ChunkWalk); 0 = plain walk
-    void spmvS(int mode, const double* x, double* out) const {
-        if (rowsS == 0) return;
+    static bool ellOk(const ps::DevCSR& M) { return M.col16ok && M.packed && M.ellok; }
+
+    // ---- the choice: which kernel runs a product, on how many workgroups.  The launchers below run it; the queries answer from it.
+    Plan planS(int mode, bool list, int nList) const {
         const ps::DevCSR& M = c->S;
-        if (pipeGrid > 0 && M.col16ok && M.packed && M.ellok) {   // row-per-lane kernels on the coded stream (ps_kernels_spmv.hpp: k_spmv_S_ell)
-            const int nChunks = sList ? nSList : c->S.nChunks;     // (a chunk list: the slab decomposition's interior / boundary launches)
-            if (nChunks == 0) return;
-            int xcdAware = this->xcdAware;
-            const dim3 gr(pipeBlocks(nChunks, xcdAware, true, sCap())), bl(BS);
+        Plan p{CSR};
+        p.run = rowsS > 0; p.pol = policy(M); p.xcd = xcdAware;
+        if (pipeGrid > 0 && ellOk(M)) {   // row-per-lane kernels on the coded stream (a chunk list: a decomposition's interior / boundary launches)
+            p.nChunks = list ? nList : M.nChunks;
+            p.grid = pipeBlocks(p.nChunks, p.xcd, true, sCap());
+            p.run = p.run && p.nChunks > 0;
             // two units in flight per wave (k_spmv_S_ell2; r04): 256^3, same box, two interleaved rounds: S 0.2809 / 0.2816 -> 0.2672 / 0.2609 ms in
             // sequence, step 1128.6 / 1130.2 -> 1117.3 / 1118.5 ms (profiles/r04_s_dual.txt).  PS_S_DUAL=0: the one-unit kernel.
-            static const bool dual = !(PS_ENV("PS_S_DUAL") && atoi(PS_ENV("PS_S_DUAL")) == 0);
-            // The face mass McInv as 1-byte codes (k_spmv_S_ell2) or, past 256 distinct values (a density field), as the fp64 array (k_spmv_S_ell2u).
-            if (dual && mode == 0 && (gr.x & 7) == 0) {
-                const int pol = policy(M);
-                const uint8_t* mcArg = c->mcCoded ? (const uint8_t*)c->mcCode.p : (const uint8_t*)c->McInv.p;
-#define PS_LAUNCH_S2L(POL_, LIST_, K_) hipLaunchKernelGGL((K_<POL_, LIST_>), gr, bl, 0, c->stream, M.ecol.p, M.ecode.p, (unsigned)(M.ellCols * 2), (unsigned)M.ellCodes, M.winBase.p, \
-                                              M.echunk.p, c->valScale, x, (int)M.cols, rowsS, nA, c->dt, out, done, nChunks, mcArg, c->mcDict.p, sPart, sList)
-#define PS_LAUNCH_S2M(POL_, K_) do { if (sList) PS_LAUNCH_S2L(POL_, true, K_); else PS_LAUNCH_S2L(POL_, false, K_); } while (0)
-#define PS_LAUNCH_S2(POL_) do { if (c->mcCoded) PS_LAUNCH_S2M(POL_, k_spmv_S_ell2); else PS_LAUNCH_S2M(POL_, k_spmv_S_ell2u); } while (0)
-                if (pol == 3) PS_LAUNCH_S2(3); else if (pol == 1) PS_LAUNCH_S2(1); else PS_LAUNCH_S2(0);
-#undef PS_LAUNCH_S2
-#undef PS_LAUNCH_S2M
-#undef PS_LAUNCH_S2L
-                return;
-            }
-#define PS_LAUNCH_SE(MODE_, POL_) do { if (sList) PS_LAUNCH_SEL(MODE_, POL_, true); else PS_LAUNCH_SEL(MODE_, POL_, false); } while (0)
-#define PS_LAUNCH_SEL(MODE_, POL_, LIST_) hipLaunchKernelGGL((k_spmv_S_ell<MODE_, POL_, LIST_>), gr, bl, 0, c->stream, M.ecol.p, M.ecode.p, (unsigned)(M.ellCols * 2), (unsigned)M.ellCodes, M.winBase.p, \
-                                                     M.echunk.p, c->valScale, x, (int)M.cols, rowsS, nA, c->dt, c->McInv.p, out, done, nChunks, xcdAware, c->mcCoded ? c->mcCode.p : (const uint8_t*)nullptr, c->mcDict.p, sPart, sList)
-#define PS_LAUNCH_SE2(MODE_) do { const int pol = policy(M); if (pol == 3) PS_LAUNCH_SE(MODE_, 3); else if (pol == 1) PS_LAUNCH_SE(MODE_, 1); else PS_LAUNCH_SE(MODE_, 0); } while (0)
-            if (mode == 0) PS_LAUNCH_SE2(0); else PS_LAUNCH_SE2(1);
-#undef PS_LAUNCH_SE2
-#undef PS_LAUNCH_SEL
-#undef PS_LAUNCH_SE
-            return;
+            p.kernel = (dualS && mode == 0 && (p.grid & 7) == 0) ? ELL2 : ELL;
+        } else if (pipeGrid > 0 && M.col16ok && (M.packed || M.val4.p)) {
+            p.kernel = PIPE; p.nChunks = M.nChunks;
+            p.grid = pipeBlocks(p.nChunks, p.xcd, M.packed);
+        } else
+            p.grid = gridFor(rowsS, BS);
+        return p;
+    }
+    // mode 2 (Chebyshev term fused into the epilogue, ChebArgs) exists on the pipelined kernels only: callers check stOnPipe()
+    // mode 3 (residual update fused into the epilogue, FusedR): pipelined kernels on the coded stream only — callers check fusedOk()
+    Plan planSt(int mode, bool list, int nList, bool ownedOnly, const FusedR& fr) const {
+        const ps::DevCSR& M = c->St;
+        Plan p{CSR};
+        p.run = rowsSt > 0; p.pol = policy(M); p.xcd = xcdAware;
+        if (pipeGrid > 0 && ellOk(M)) {   // row-per-lane kernels on the coded stream (k_spmv_St_ell)
+            p.nChunks = list ? nList : M.nChunks;
+            p.grid = pipeBlocks(p.nChunks, p.xcd, true, stGridFor(mode));
+            p.run = p.run && p.nChunks > 0;
+            p.kernel = ELL;
+            // Two units in flight per wave (k_spmv_St_ell2; r04): 256^3, one box, interleaved rounds: St with the residual update 0.4251 / 0.4242 ->
+            // 0.3923 / 0.3918 ms in sequence at 5 waves per SIMD on 1280 workgroups, step 1124.5 / 1122.6 -> 1098.3 / 1096.6 ms; compiled for 6 waves per
+            // SIMD on 1536 workgroups another 0.6 % (profiles/r04_st_dual.txt).  PS_ST_DUAL=0: the one-unit kernel on 1792 workgroups.
+            // The MODE 3 specialisations of k_spmv_St_ell (FX) take coded uInv only, without the Chebyshev term: in a single domain (3) or on a
+            // slab rank (1, 5); the two-unit kernels also take the stress diagonal as the fp64 array (UC = false, r06: a viscosity field with more
+            // than 256 values).
+            const bool g8 = (p.grid & 7) == 0, plainFr = !fr.yOut && !fr.red && fr.rStride == 0;
+            const bool coded3 = mode == 3 && c->uCoded && !fr.cz, single3 = mode == 3 && !fr.cz && plain3Hint && plainFr;
+            if (mode == 2 && dualT && !list && g8 && !c->slabEnabled) p.kernel = ELL2C;
+            else if (mode == 3 && dualT && plain3Hint2 && fr.cz && !fr.dinvF && plainFr && !list && g8) p.kernel = ELL2Z;
+            else if (cz32 && mode == 3 && fr.cz) p.err = "internal: single-precision Chebyshev vectors without the two-unit St kernel";
+            else if (single3 && stDual() && !list && g8) p.kernel = ELL2;
+            else if (single3 && c->uCoded) p.fx = 3;
+            else if (mode == 3 && !fr.cz && ownedOnly && list && dualT && fr.red && g8) p.kernel = ELL2_OWN;
+            else if (mode == 3 && !fr.cz && dualT && fr.red && fr.yOut && !ownedOnly && g8) p.kernel = ELL2_HALO;
+            else if (coded3 && ownedOnly && list) p.fx = 5;
+            else if (coded3) p.fx = 1;
+        } else if (pipeGrid > 0 && M.col16ok && (M.packed || M.val4.p)) {
+            p.kernel = PIPE; p.nChunks = M.nChunks;
+            p.grid = pipeBlocks(p.nChunks, p.xcd, M.packed, stGridFor(mode));
+            if (mode == 3 && !M.packed) p.err = "internal: fused residual update on the fp64 stream";
+        } else {
+            p.grid = gridFor(rowsSt, BS);
+            if (mode >= 2) p.err = "internal: fused St epilogue without the pipelined St kernel";
         }
-        if (pipeGrid > 0 && M.col16ok && (M.packed || M.val4.p)) {
-            const int nChunks = c->S.nChunks;
-            int xcdAware = this->xcdAware;
-            const dim3 gr(pipeBlocks(nChunks, xcdAware, M.packed)), bl(BS);
-#define PS_LAUNCH_SP(MODE_, NV_, F64_, POL_) hipLaunchKernelGGL((k_spmv_S_pipe<MODE_, NV_, F64_, POL_>), gr, bl, 0, c->stream, M.col16.p, M.code4.p, M.val4.p, (int)M.streamLen, M.winBase.p, \
-                                                    M.chunkInfo.p, M.len8.p, c->valScale, x, (int)M.cols, rowsS, nA, c->dt, c->McInv.p, out, done, nChunks, xcdAware, c->mcCoded ? c->mcCode.p : (const uint8_t*)nullptr, c->mcDict.p, sPart)
-#define PS_LAUNCH_SP2(MODE_, NV_) do { const int pol = policy(M); if (!M.packed) PS_LAUNCH_SP(MODE_, NV_, true, 3); else if (pol == 3) PS_LAUNCH_SP(MODE_, NV_, false, 3); \
-                                       else if (pol == 1) PS_LAUNCH_SP(MODE_, NV_, false, 1); else PS_LAUNCH_SP(MODE_, NV_, false, 0); } while (0)
-            if (M.nv == 1) { if (mode == 0) PS_LAUNCH_SP2(0, 1); else PS_LAUNCH_SP2(1, 1); }
-            else { if (mode == 0) PS_LAUNCH_SP2(0, 2); else PS_LAUNCH_SP2(1, 2); }
-#undef PS_LAUNCH_SP2
-#undef PS_LAUNCH_SP
+        return p;
+    }
+    bool listsOk() const { return planS(0, false, 0).kernel >= ELL && planSt(0, false, 0, false, FusedR{}).kernel >= ELL; }
+    bool stOnPipe() const { return planSt(0, false, 0, false, FusedR{}).kernel != CSR; }
+    // the fused step needs both products on the persistent coded-stream kernels (their per-workgroup partials)
+    bool fusedOk() const {
+        const Plan s = planS(0, false, 0), t = planSt(0, false, 0, false, FusedR{});
+        return rowsS > 0 && s.kernel != CSR && c->S.packed && t.kernel != CSR && c->St.packed;
+    }
+    // workgroups of a launch over every chunk / over a list of n chunks of S / St (the partial sums it writes)
+    int sBlocks() const { return planS(0, false, 0).grid; }
+    int sBlocksFor(int n) const { return planS(0, true, n).grid; }
+    int stBlocks(int mode = 0) const { return planSt(mode, false, 0, false, FusedR{}).grid; }
+    int stBlocksFor(int n, int mode) const { return planSt(mode, true, n, false, FusedR{}).grid; }
+    // ---- the inner operator applies of the single-precision Chebyshev polynomial (PS_PRE_CHEBYSHEV_F32): z_j and the face-row vector are stored
+    // as fp32 (ps_kernels_spmv.hpp: VecIO), on the pair-walking two-unit kernels only (their grid a multiple of 8 with the XCD walk on) and the
+    // fused tile apply; otherwise the fp64 form runs
+    bool cheb32Ok() const {
+        const Plan s = planS(0, false, 0), t = planSt(2, false, 0, false, FusedR{});
+        return s.run && s.kernel == ELL2 && s.xcd > 0 && t.run && t.kernel == ELL2C && t.xcd > 0 && (c->regionCount == 0 || tileFused());
+    }
+
+    // ---- launchers, one per kernel family.  (Each names its kernels in the order the dispatch has always instantiated them: the code
+    // object lays the kernels out in that order.)
+    // the row-per-lane kernels: the coded ELL stream of M leads every argument list
+    template <class K, class... A> auto ellLaunch(K k, const Plan& p, const ps::DevCSR& M, A... a) const {
+        hipLaunchKernelGGL(k, dim3(p.grid), dim3(BS), 0, c->stream, M.ecol.p, M.ecode.p, (unsigned)(M.ellCols * 2), (unsigned)M.ellCodes, M.winBase.p, M.echunk.p, c->valScale, a...);
+    }
+    // k_spmv_S_ell2 (the face mass McInv as 1-byte codes) / k_spmv_S_ell2u (past 256 distinct values, a density field: the fp64 array);
+    // TV = float (the Chebyshev polynomial's inner applies) over every chunk only
+    template <class TV> auto sEll2(const Plan& p, const TV* x, TV* out, double* part, const int32_t* list) const {
+        const ps::DevCSR& M = c->S;
+        const uint8_t* mc = c->mcCoded ? (const uint8_t*)c->mcCode.p : (const uint8_t*)c->McInv.p;
+        withPolicy(p.pol, [&](auto POL) { withBool(c->mcCoded, [&](auto MC) {
+            auto go = [&](auto LIST) {
+                constexpr int pol = decltype(POL)::value; constexpr bool lst = decltype(LIST)::value;
+                auto k = [] { if constexpr (decltype(MC)::value) return k_spmv_S_ell2<pol, lst, TV>; else return k_spmv_S_ell2u<pol, lst, TV>; }();
+                ellLaunch(k, p, M, x, (int)M.cols, rowsS, nA, c->dt, out, done, p.nChunks, mc, c->mcDict.p, part, list);
+            };
+            if constexpr (std::is_same<TV, double>::value) withBool(list, go); else go(std::false_type{});
+        }); });
+    }
+    template <class TV> auto stEll2c(const Plan& p, const TV* t, const TV* xin, TV* out, double* partial, const ChebArgs& ca) const {
+        const ps::DevCSR& M = c->St;
+        const uint8_t* uArg = c->uCoded ? (const uint8_t*)c->uCode.p : (const uint8_t*)c->uInv.p;
+        withBool(c->uCoded, [&](auto UC) { withPolicy(p.pol, [&](auto POL) {
+            ellLaunch(k_spmv_St_ell2c<POL, TV, UC>, p, M, t, (int)M.cols, rowsSt, xin, out, partial, done, p.nChunks, ca, uArg, c->uDict.p);
+        }); });
+    }
+    void spmvS(int mode, const double* x, double* out) const {
+        const Plan p = planS(mode, sList, nSList);
+        if (!p.run) return;
+        const ps::DevCSR& M = c->S;
+        const uint8_t* mc = c->mcCoded ? c->mcCode.p : (const uint8_t*)nullptr;
+        switch (p.kernel) {
+        case CSR:
+            withOneOf<0, 1>(mode, [&](auto MODE) { withBool(M.packed, [&](auto PK) {
+                hipLaunchKernelGGL((k_spmv_S<MODE, 8, PK>), dim3(p.grid), dim3(BS), 0, c->stream, M.ptr.p, M.col.p, M.val.p, M.code.p, c->valScale, x, rowsS, nA, c->dt, c->McInv.p, out, done);
+            }); });
             return;
+        case ELL2: sEll2(p, x, out, sPart, sList); return;
+        case ELL:
+            withOneOf<0, 1>(mode, [&](auto MODE) { withPolicy(p.pol, [&](auto POL) { withBool(sList, [&](auto LIST) {
+                ellLaunch(k_spmv_S_ell<MODE, POL, LIST>, p, M, x, (int)M.cols, rowsS, nA, c->dt, c->McInv.p, out, done, p.nChunks, p.xcd, mc, c->mcDict.p, sPart, sList);
+            }); }); });
+            return;
+        default:   // PIPE
+            withOneOf<1, 2>(M.nv, [&](auto NV) { withOneOf<0, 1>(mode, [&](auto MODE) { withPipe(M.packed, p.pol, [&](auto F64, auto POL) {
+                hipLaunchKernelGGL((k_spmv_S_pipe<MODE, NV, F64, POL>), dim3(p.grid), dim3(BS), 0, c->stream, M.col16.p, M.code4.p, M.val4.p, (int)M.streamLen, M.winBase.p,
+                                   M.chunkInfo.p, M.len8.p, c->valScale, x, (int)M.cols, rowsS, nA, c->dt, c->McInv.p, out, done, p.nChunks, p.xcd, mc, c->mcDict.p, sPart);
+            }); }); });
         }
-        spmvS_(mode, x, out);
+    }
+    // ---- tiles
+    bool tileFused() const { return c->maxRegionRows <= TILE_FUSED_MAX_ROWS && !tileSplit; }
+    // threads per region of the fused apply: enough threads in flight chip-wide (~256 K) without starving a region of work.  Measured
+    // at 256^3 (4096 tiles of 3204 rows): 0.080 ms with 64 threads, 0.087 / 0.106 / 0.166 with 128 / 256 / 512; at 32^3
+    // (8 tiles) one wavefront per tile serialises 50 rows per lane behind memory latency (60 us per CG iteration
+    // against 43 with 256 threads per tile; 1024 threads: 50, the block reduction over 16 waves costs more than it hides).
+    int tileThreads() const {
+        int tb = 64;
+        while (tb < 256 && (int64_t)tb * c->regionCount < 262144 && (int64_t)tb * 2 < c->maxRegionRows) tb *= 2;
+        return tb;
+    }
+    template <int MODE, class TS, class TB> auto tileApply(TB, TS* sred, double* part) const {
+        hipLaunchKernelGGL((k_tile_apply<MODE, TB::value, TS>), dim3((unsigned)c->regionCount), dim3(TB::value), 0, c->stream, c->regionRowPtr.p, c->rrowFace.p, c->COM.p,
+                           c->dx, make_int3(c->gOff[0], c->gOff[1], c->gOff[2]), c->Binv.p, c->rhsR.p, c->invDt, sred, c->vreg.p, done, part);
     }
     void tiles(int mode, double* ts) const {   // ts: face-row vector; reduced part rewritten in place
         if (c->regionCount == 0) return;
         double* sred = ts + nA;
-        const dim3 gr((unsigned)c->regionCount);
-        static const bool noFuse = PS_ENV("PS_TILE_SPLIT") && atoi(PS_ENV("PS_TILE_SPLIT")) != 0;   // A/B: force the three-kernel form
-        if (c->maxRegionRows <= TILE_FUSED_MAX_ROWS && !noFuse) {   // one workgroup per region: gather, 26x26 block, expand
-#define PS_TILE_APPLY(MODE_, TB_) hipLaunchKernelGGL((k_tile_apply<MODE_, TB_>), gr, dim3(TB_), 0, c->stream, c->regionRowPtr.p, c->rrowFace.p, c->COM.p, c->dx, make_int3(c->gOff[0], c->gOff[1], c->gOff[2]), c->Binv.p, \
-                                                c->rhsR.p, c->invDt, sred, c->vreg.p, done, wvPart)
-            // threads per region: enough threads in flight chip-wide (~256 K) without starving a region of work.  Measured
-            // at 256^3 (4096 tiles of 3204 rows): 0.080 ms with 64 threads, 0.087 / 0.106 / 0.166 with 128 / 256 / 512; at 32^3
-            // (8 tiles) one wavefront per tile serialises 50 rows per lane behind memory latency (60 us per CG iteration
-            // against 43 with 256 threads per tile; 1024 threads: 50, the block reduction over 16 waves costs more than it hides).
-            static const int tbEnv = PS_ENV("PS_TILE_TB") ? atoi(PS_ENV("PS_TILE_TB")) : 0;
-            int tb = tbEnv;
-            if (!tb) {
-                tb = 64;
-                while (tb < 256 && (int64_t)tb * c->regionCount < 262144 && (int64_t)tb * 2 < c->maxRegionRows) tb *= 2;
-            }
-#define PS_TILE_APPLY_TB(MODE_) do { if (tb >= 1024) PS_TILE_APPLY(MODE_, 1024); else if (tb >= 512) PS_TILE_APPLY(MODE_, 512); else if (tb >= 256) PS_TILE_APPLY(MODE_, 256); \
-                                     else if (tb >= 128) PS_TILE_APPLY(MODE_, 128); else PS_TILE_APPLY(MODE_, 64); } while (0)
-            if (mode == 0) PS_TILE_APPLY_TB(0); else if (mode == 1) PS_TILE_APPLY_TB(1); else PS_TILE_APPLY_TB(2);
-#undef PS_TILE_APPLY_TB
-#undef PS_TILE_APPLY
+        if (tileFused()) {   // one workgroup per region: gather, 26x26 block, expand
+            withOneOf<0, 1, 2>(mode, [&](auto MODE) { withAtLeast<1024, 512, 256, 128, 64>(tileTB ? tileTB : tileThreads(), [&](auto TB) {
+                tileApply<MODE, double>(TB, sred, wvPart);
+            }); });
             return;
         }
         if (mode != 2 && c->nRChunks > 0)
-            hipLaunchKernelGGL(k_tile_gather, dim3((unsigned)c->nRChunks), dim3(64), 0, c->stream, c->rchunkRegion.p, c->rchunkStart.p,
-                               c->rchunkEnd.p, c->rrowFace.p, c->COM.p, c->dx, make_int3(c->gOff[0], c->gOff[1], c->gOff[2]), sred, c->wreg.p, done);
-        const dim3 bl(64);
-        if (mode == 0)
-            hipLaunchKernelGGL(k_tile_solve<0>, gr, bl, 0, c->stream, c->regionChunkPtr.p, c->wreg.p, c->Binv.p, c->rhsR.p, c->invDt, c->vreg.p, done, wvPart);
-        else if (mode == 1)
-            hipLaunchKernelGGL(k_tile_solve<1>, gr, bl, 0, c->stream, c->regionChunkPtr.p, c->wreg.p, c->Binv.p, c->rhsR.p, c->invDt, c->vreg.p, done, (double*)nullptr);
-        else
-            hipLaunchKernelGGL(k_tile_solve<2>, gr, bl, 0, c->stream, c->regionChunkPtr.p, c->wreg.p, c->Binv.p, c->rhsR.p, c->invDt, c->vreg.p, done, (double*)nullptr);
+            hipLaunchKernelGGL(k_tile_gather, dim3((unsigned)c->nRChunks), dim3(64), 0, c->stream, c->rchunkRegion.p, c->rchunkStart.p, c->rchunkEnd.p,
+                               c->rrowFace.p, c->COM.p, c->dx, make_int3(c->gOff[0], c->gOff[1], c->gOff[2]), sred, c->wreg.p, done);
+        withOneOf<0, 1, 2>(mode, [&](auto MODE) {
+            hipLaunchKernelGGL(k_tile_solve<MODE>, dim3((unsigned)c->regionCount), dim3(64), 0, c->stream, c->regionChunkPtr.p, c->wreg.p, c->Binv.p, c->rhsR.p,
+                               c->invDt, c->vreg.p, done, MODE == 0 ? wvPart : (double*)nullptr);
+        });
         if (mode != 1 && c->nRChunks > 0)
-            hipLaunchKernelGGL(k_tile_expand, dim3((unsigned)c->nRChunks), dim3(BS), 0, c->stream, c->rchunkRegion.p, c->rchunkStart.p,
-                               c->rchunkEnd.p, c->rrowFace.p, c->COM.p, c->dx, make_int3(c->gOff[0], c->gOff[1], c->gOff[2]), c->vreg.p, sred, done);
+            hipLaunchKernelGGL(k_tile_expand, dim3((unsigned)c->nRChunks), dim3(BS), 0, c->stream, c->rchunkRegion.p, c->rchunkStart.p, c->rchunkEnd.p,
+                               c->rrowFace.p, c->COM.p, c->dx, make_int3(c->gOff[0], c->gOff[1], c->gOff[2]), c->vreg.p, sred, done);
     }
-    // ---- the inner operator applies of the single-precision Chebyshev polynomial (PS_PRE_CHEBYSHEV_F32): z_j and the face-row vector are stored
-    // as fp32 (ps_kernels_spmv.hpp: VecIO), on the two-units-per-wave kernels only — cheb32Ok() says whether this system runs them
-    bool cheb32Ok() const {
-        static const bool dualS = !(PS_ENV("PS_S_DUAL") && atoi(PS_ENV("PS_S_DUAL")) == 0), dualT = !(PS_ENV("PS_ST_DUAL") && atoi(PS_ENV("PS_ST_DUAL")) == 0);
-        static const bool noFuse = PS_ENV("PS_TILE_SPLIT") && atoi(PS_ENV("PS_TILE_SPLIT")) != 0;
-        return dualS && dualT && listsOk() && !c->slabEnabled && !sList && !stList && xcdAware > 0 && c->S.nChunks >= 8 && c->St.nChunks >= 8 &&
-               rowsS > 0 && rowsSt > 0 && (c->regionCount == 0 || (c->maxRegionRows <= TILE_FUSED_MAX_ROWS && !noFuse));
-    }
+    // ---- the fp32 inner applies of the Chebyshev polynomial (cheb32Ok)
     void spmvS32(const float* x, float* out) const {
-        const ps::DevCSR& M = c->S;
-        int xcd = xcdAware;
-        const dim3 gr(pipeBlocks(M.nChunks, xcd, true, sCap())), bl(BS);
-        const int pol = policy(M);
-        const uint8_t* mcArg = c->mcCoded ? (const uint8_t*)c->mcCode.p : (const uint8_t*)c->McInv.p;
-#define PS_LAUNCH_S2F(POL_, K_) hipLaunchKernelGGL((K_<POL_, false, float>), gr, bl, 0, c->stream, M.ecol.p, M.ecode.p, (unsigned)(M.ellCols * 2), (unsigned)M.ellCodes, M.winBase.p, \
-                                               M.echunk.p, c->valScale, x, (int)M.cols, rowsS, nA, c->dt, out, done, M.nChunks, mcArg, c->mcDict.p, (double*)nullptr, (const int32_t*)nullptr)
-#define PS_LAUNCH_S2F2(POL_) do { if (c->mcCoded) PS_LAUNCH_S2F(POL_, k_spmv_S_ell2); else PS_LAUNCH_S2F(POL_, k_spmv_S_ell2u); } while (0)
-        if (pol == 3) PS_LAUNCH_S2F2(3); else if (pol == 1) PS_LAUNCH_S2F2(1); else PS_LAUNCH_S2F2(0);
-#undef PS_LAUNCH_S2F2
-#undef PS_LAUNCH_S2F
+        const Plan p = planS(0, false, 0);
+        if (p.kernel != ELL2) throw Error("internal: single-precision S apply without the two-unit kernel");
+        sEll2(p, x, out, (double*)nullptr, (const int32_t*)nullptr);
     }
-    void tiles32(float* ts) const {
+    void tiles32(float* ts) const {   // the fused apply only, at the default threads per region
         if (c->regionCount == 0) return;
-        float* sred = ts + nA;
-        const dim3 gr((unsigned)c->regionCount);
-        int tb = 64;
-        while (tb < 256 && (int64_t)tb * c->regionCount < 262144 && (int64_t)tb * 2 < c->maxRegionRows) tb *= 2;
-#define PS_TILE_APPLY_F(TB_) hipLaunchKernelGGL((k_tile_apply<0, TB_, float>), gr, dim3(TB_), 0, c->stream, c->regionRowPtr.p, c->rrowFace.p, c->COM.p, c->dx, make_int3(c->gOff[0], c->gOff[1], c->gOff[2]), c->Binv.p, \
-                                                c->rhsR.p, c->invDt, sred, c->vreg.p, done, (double*)nullptr)
-        if (tb >= 256) PS_TILE_APPLY_F(256); else if (tb >= 128) PS_TILE_APPLY_F(128); else PS_TILE_APPLY_F(64);
-#undef PS_TILE_APPLY_F
+        withAtLeast<256, 128, 64>(tileThreads(), [&](auto TB) { tileApply<0, float>(TB, ts + nA, (double*)nullptr); });
     }
     int spmvSt2c32(const float* t, const float* xin, float* out, double* partial, const ChebArgs& ca) const {   // returns the number of partials written
-        const ps::DevCSR& M = c->St;
-        int xcd = xcdAware;
-        const dim3 gr(pipeBlocks(M.nChunks, xcd, true, stGridFor(2))), bl(BS);
-        const int pol = policy(M);
-        const uint8_t* uArg = c->uCoded ? (const uint8_t*)c->uCode.p : (const uint8_t*)c->uInv.p;
-#define PS_LAUNCH_T2CF(POL_, UC_) hipLaunchKernelGGL((k_spmv_St_ell2c<POL_, float, UC_>), gr, bl, 0, c->stream, M.ecol.p, M.ecode.p, (unsigned)(M.ellCols * 2), (unsigned)M.ellCodes, M.winBase.p, \
-                                                M.echunk.p, c->valScale, t, (int)M.cols, rowsSt, xin, out, partial, done, M.nChunks, ca, uArg, c->uDict.p)
-        if (c->uCoded) { if (pol == 3) PS_LAUNCH_T2CF(3, true); else if (pol == 1) PS_LAUNCH_T2CF(1, true); else PS_LAUNCH_T2CF(0, true); }
-        else { if (pol == 3) PS_LAUNCH_T2CF(3, false); else if (pol == 1) PS_LAUNCH_T2CF(1, false); else PS_LAUNCH_T2CF(0, false); }
-#undef PS_LAUNCH_T2CF
-        return (int)gr.x;
+        const Plan p = planSt(2, false, 0, false, FusedR{});
+        if (p.kernel != ELL2C) throw Error("internal: single-precision Chebyshev term without the two-unit St kernel");
+        stEll2c(p, t, xin, out, partial, ca);
+        return p.grid;
     }
-    bool cz32 = false;   // MODE 3 with the polynomial's first term: fr.cz points at floats (k_spmv_St_ell2<.., float>)
-    void spmvSt_(int mode, const double* t, const double* xin, const double* add, double* out, double* partial) const {
-        const dim3 gr(gridFor(rowsSt, BS)), bl(BS);
-        const ps::DevCSR& M = c->St;
-#define PS_LAUNCH_T(MODE_, PK_) hipLaunchKernelGGL((k_spmv_St<MODE_, 6, PK_>), gr, bl, 0, c->stream, M.ptr.p, M.col.p, M.val.p, M.code.p, \
-                                                   c->valScale, t, rowsSt, nP, c->uInv.p, xin, add, out, partial, done)
-        if (mode == 0) { if (M.packed) PS_LAUNCH_T(0, true); else PS_LAUNCH_T(0, false); }
-        else { if (M.packed) PS_LAUNCH_T(1, true); else PS_LAUNCH_T(1, false); }
-#undef PS_LAUNCH_T
-    }
-    bool stOnPipe() const { return pipeGrid > 0 && c->St.col16ok && (c->St.packed || c->St.val4.p); }
-    // mode 2 (Chebyshev term fused into the epilogue, ChebArgs) exists on the pipelined kernels only: callers check stOnPipe()
-    // mode 3 (residual update fused into the epilogue, FusedR): pipelined kernels on the coded stream only — callers check fusedOk()
-    void spmvSt(int mode, const double* t, const double* xin, const double* add, double* out, double* partial, const ChebArgs* cheb = nullptr,
-                const FusedR* fused = nullptr) const {
-        if (rowsSt == 0) return;
-        const ps::DevCSR& M = c->St;
+    void spmvSt(int mode, const double* t, const double* xin, const double* add, double* out, double* partial, const ChebArgs* cheb = nullptr, const FusedR* fused = nullptr) const {
         ChebArgs ca{nullptr, nullptr, nullptr, 0., 0.};
         if (cheb) ca = *cheb;
         FusedR fr{};
         if (fused) fr = *fused;
-        if (pipeGrid > 0 && M.col16ok && M.packed && M.ellok) {   // row-per-lane kernels on the coded stream (k_spmv_St_ell)
-            const int nChunks = stList ? nStList : c->St.nChunks;
-            if (nChunks == 0) return;
-            int xcdAware = this->xcdAware;
-            const dim3 gr(pipeBlocks(nChunks, xcdAware, true, stGridFor(mode))), bl(BS);
-#define PS_LAUNCH_TE(MODE_, POL_) PS_LAUNCH_TEX(MODE_, POL_, 0)
-#define PS_LAUNCH_TEX(MODE_, POL_, FX_) do { if (stList) PS_LAUNCH_TEL(MODE_, POL_, FX_, true); else PS_LAUNCH_TEL(MODE_, POL_, FX_, false); } while (0)
-#define PS_LAUNCH_TEL(MODE_, POL_, FX_, LIST_) hipLaunchKernelGGL((k_spmv_St_ell<MODE_, POL_, FX_, LIST_>), gr, bl, 0, c->stream, M.ecol.p, M.ecode.p, (unsigned)(M.ellCols * 2), (unsigned)M.ellCodes, M.winBase.p, \
-                                                     M.echunk.p, c->valScale, t, (int)M.cols, rowsSt, c->uInv.p, xin, add, out, partial, done, nChunks, xcdAware, ca, c->uCoded ? c->uCode.p : (const uint8_t*)nullptr, c->uDict.p, fr, stList)
-#define PS_LAUNCH_TE2(MODE_) do { const int pol = policy(M); if (pol == 3) PS_LAUNCH_TE(MODE_, 3); else if (pol == 1) PS_LAUNCH_TE(MODE_, 1); else PS_LAUNCH_TE(MODE_, 0); } while (0)
-            // MODE 3 specialisations (k_spmv_St_ell: FX): coded uInv without the Chebyshev term, in a single domain (3) or on a slab rank (1)
-            // (r06: the two-unit kernels also take the stress diagonal as the fp64 array — UC = false, a viscosity field with more than 256 values —; the one-unit
-            // FX forms stay coded-only)
-            const bool codedU = c->uCoded;
-            const uint8_t* uArg = codedU ? (const uint8_t*)c->uCode.p : (const uint8_t*)c->uInv.p;
-            const bool coded3 = mode == 3 && codedU && !fr.cz, single3 = mode == 3 && !fr.cz && plain3Hint && !fr.yOut && !fr.red && fr.rStride == 0;
-            // two units in flight per wave (k_spmv_St_ell2; r04): 256^3, one box, interleaved rounds: St with the residual update 0.4251 / 0.4242 ->
-            // 0.3923 / 0.3918 ms in sequence at 5 waves per SIMD on 1280 workgroups, step 1124.5 / 1122.6 -> 1098.3 / 1096.6 ms; compiled for 6 waves per
-            // SIMD on 1536 workgroups another 0.6 % (profiles/r04_st_dual.txt).  PS_ST_DUAL=0: the one-unit kernel on 1792 workgroups.
-            static const bool dualC = !(PS_ENV("PS_ST_DUAL") && atoi(PS_ENV("PS_ST_DUAL")) == 0);
-            if (mode == 2 && dualC && !stList && (gr.x & 7) == 0 && !c->slabEnabled) {   // a Chebyshev term, two units in flight per wave
-                const int pol = policy(M);
-#define PS_LAUNCH_T2C(POL_, UC_) hipLaunchKernelGGL((k_spmv_St_ell2c<POL_, double, UC_>), gr, bl, 0, c->stream, M.ecol.p, M.ecode.p, (unsigned)(M.ellCols * 2), (unsigned)M.ellCodes, M.winBase.p, \
-                                               M.echunk.p, c->valScale, t, (int)M.cols, rowsSt, xin, out, partial, done, nChunks, ca, uArg, c->uDict.p)
-                if (codedU) { if (pol == 3) PS_LAUNCH_T2C(3, true); else if (pol == 1) PS_LAUNCH_T2C(1, true); else PS_LAUNCH_T2C(0, true); }
-                else { if (pol == 3) PS_LAUNCH_T2C(3, false); else if (pol == 1) PS_LAUNCH_T2C(1, false); else PS_LAUNCH_T2C(0, false); }
-#undef PS_LAUNCH_T2C
-                return;
-            }
-            if (mode == 3 && dualC && plain3Hint2 && fr.cz && !fr.dinvF && !fr.yOut && !fr.red && fr.rStride == 0 && !stList && (gr.x & 7) == 0) {
-                const int pol = policy(M);   // the Chebyshev step's St launch (first term of the polynomial in the epilogue), two units in flight per wave
-#define PS_LAUNCH_T2Z(POL_, TZ_, UC_) hipLaunchKernelGGL((k_spmv_St_ell2<POL_, true, false, false, TZ_, false, UC_>), gr, bl, 0, c->stream, M.ecol.p, M.ecode.p, (unsigned)(M.ellCols * 2), (unsigned)M.ellCodes, M.winBase.p, \
-                                               M.echunk.p, c->valScale, t, (int)M.cols, rowsSt, xin, done, nChunks, uArg, c->uDict.p, fr, (const int32_t*)nullptr)
-#define PS_LAUNCH_T2Z2(POL_, TZ_) do { if (codedU) PS_LAUNCH_T2Z(POL_, TZ_, true); else PS_LAUNCH_T2Z(POL_, TZ_, false); } while (0)
-                if (cz32) { if (pol == 3) PS_LAUNCH_T2Z2(3, float); else if (pol == 1) PS_LAUNCH_T2Z2(1, float); else PS_LAUNCH_T2Z2(0, float); }
-                else { if (pol == 3) PS_LAUNCH_T2Z2(3, double); else if (pol == 1) PS_LAUNCH_T2Z2(1, double); else PS_LAUNCH_T2Z2(0, double); }
-#undef PS_LAUNCH_T2Z2
-#undef PS_LAUNCH_T2Z
-                return;
-            }
-            if (cz32 && mode == 3 && fr.cz) throw Error("internal: single-precision Chebyshev vectors without the two-unit St kernel");
-            if (single3 && stDual() && !stList && (gr.x & 7) == 0) {
-                const int pol = policy(M);
-#define PS_LAUNCH_T2(POL_, UC_) hipLaunchKernelGGL((k_spmv_St_ell2<POL_, false, false, false, double, false, UC_>), gr, bl, 0, c->stream, M.ecol.p, M.ecode.p, (unsigned)(M.ellCols * 2), (unsigned)M.ellCodes, M.winBase.p, \
-                                              M.echunk.p, c->valScale, t, (int)M.cols, rowsSt, xin, done, nChunks, uArg, c->uDict.p, fr, (const int32_t*)nullptr)
-                if (codedU) { if (pol == 3) PS_LAUNCH_T2(3, true); else if (pol == 1) PS_LAUNCH_T2(1, true); else PS_LAUNCH_T2(0, true); }
-                else { if (pol == 3) PS_LAUNCH_T2(3, false); else if (pol == 1) PS_LAUNCH_T2(1, false); else PS_LAUNCH_T2(0, false); }
-#undef PS_LAUNCH_T2
-                return;
-            }
-            if (single3 && codedU) { const int pol = policy(M); if (pol == 3) PS_LAUNCH_TEX(3, 3, 3); else if (pol == 1) PS_LAUNCH_TEX(3, 1, 3); else PS_LAUNCH_TEX(3, 0, 3); }
-            else if (mode == 3 && !fr.cz && stOwnedOnly && stList && dualC && fr.red && (gr.x & 7) == 0) {   // a rank's launch over owned rows only, two units in flight per wave
-                const int pol = policy(M);
-#define PS_LAUNCH_T2D(POL_, UC_) hipLaunchKernelGGL((k_spmv_St_ell2<POL_, false, true, true, double, false, UC_>), gr, bl, 0, c->stream, M.ecol.p, M.ecode.p, (unsigned)(M.ellCols * 2), (unsigned)M.ellCodes, M.winBase.p, \
-                                               M.echunk.p, c->valScale, t, (int)M.cols, rowsSt, xin, done, nChunks, uArg, c->uDict.p, fr, stList)
-                if (codedU) { if (pol == 3) PS_LAUNCH_T2D(3, true); else if (pol == 1) PS_LAUNCH_T2D(1, true); else PS_LAUNCH_T2D(0, true); }
-                else { if (pol == 3) PS_LAUNCH_T2D(3, false); else if (pol == 1) PS_LAUNCH_T2D(1, false); else PS_LAUNCH_T2D(0, false); }
-#undef PS_LAUNCH_T2D
-            }
-            else if (mode == 3 && !fr.cz && dualC && fr.red && fr.yOut && !stOwnedOnly && (gr.x & 7) == 0) {   // a rank's launch that holds halo rows (the chunks next to a cut, or the whole rank), two units in flight per wave
-                const int pol = policy(M);
-#define PS_LAUNCH_T2H(POL_, LIST_, UC_) hipLaunchKernelGGL((k_spmv_St_ell2<POL_, false, true, LIST_, double, true, UC_>), gr, bl, 0, c->stream, M.ecol.p, M.ecode.p, (unsigned)(M.ellCols * 2), (unsigned)M.ellCodes, M.winBase.p, \
-                                               M.echunk.p, c->valScale, t, (int)M.cols, rowsSt, xin, done, nChunks, uArg, c->uDict.p, fr, stList)
-#define PS_LAUNCH_T2H2(POL_, UC_) do { if (stList) PS_LAUNCH_T2H(POL_, true, UC_); else PS_LAUNCH_T2H(POL_, false, UC_); } while (0)
-                if (codedU) { if (pol == 3) PS_LAUNCH_T2H2(3, true); else if (pol == 1) PS_LAUNCH_T2H2(1, true); else PS_LAUNCH_T2H2(0, true); }
-                else { if (pol == 3) PS_LAUNCH_T2H2(3, false); else if (pol == 1) PS_LAUNCH_T2H2(1, false); else PS_LAUNCH_T2H2(0, false); }
-#undef PS_LAUNCH_T2H2
-#undef PS_LAUNCH_T2H
-            }
-            else if (coded3 && stOwnedOnly && stList) { const int pol = policy(M); if (pol == 3) PS_LAUNCH_TEL(3, 3, 5, true); else if (pol == 1) PS_LAUNCH_TEL(3, 1, 5, true); else PS_LAUNCH_TEL(3, 0, 5, true); }
-            else if (coded3) { const int pol = policy(M); if (pol == 3) PS_LAUNCH_TEX(3, 3, 1); else if (pol == 1) PS_LAUNCH_TEX(3, 1, 1); else PS_LAUNCH_TEX(3, 0, 1); }
-            else if (mode == 0) PS_LAUNCH_TE2(0); else if (mode == 1) PS_LAUNCH_TE2(1); else if (mode == 2) PS_LAUNCH_TE2(2); else PS_LAUNCH_TE2(3);
-#undef PS_LAUNCH_TE2
-#undef PS_LAUNCH_TEL
-#undef PS_LAUNCH_TEX
-#undef PS_LAUNCH_TE
-            return;
+        const Plan p = planSt(mode, stList, nStList, stOwnedOnly, fr);
+        if (!p.run) return;
+        if (p.err) throw Error(p.err);
+        const ps::DevCSR& M = c->St;
+        const uint8_t* uc = c->uCoded ? c->uCode.p : (const uint8_t*)nullptr;
+        const uint8_t* uArg = c->uCoded ? (const uint8_t*)c->uCode.p : (const uint8_t*)c->uInv.p;
+        using T = std::true_type; using F = std::false_type;
+        using M3 = std::integral_constant<int, 3>;
+        auto ell = [&](auto MODE, auto POL, auto FX, auto LIST) {
+            ellLaunch(k_spmv_St_ell<MODE, POL, FX, LIST>, p, M, t, (int)M.cols, rowsSt, c->uInv.p, xin, add, out, partial, done, p.nChunks, p.xcd, ca, uc, c->uDict.p, fr, stList);
+        };
+        auto ell2 = [&](auto POL, auto CZ, auto DIST, auto LIST, auto TZ, auto HALO, auto UC) {
+            ellLaunch(k_spmv_St_ell2<POL, CZ, DIST, LIST, typename decltype(TZ)::type, HALO, UC>, p, M, t, (int)M.cols, rowsSt, xin, done, p.nChunks, uArg, c->uDict.p, fr, stList);
+        };
+        auto pipe = [&](auto MODE, auto NV) { withPipe(M.packed, p.pol, [&](auto F64, auto POL) {
+            hipLaunchKernelGGL((k_spmv_St_pipe<MODE, NV, F64, POL>), dim3(p.grid), dim3(BS), 0, c->stream, M.col16.p, M.code4.p, M.val4.p, (int)M.streamLen, M.winBase.p,
+                               M.chunkInfo.p, M.len8.p, c->valScale, t, (int)M.cols, rowsSt, c->uInv.p, xin, add, out, partial, done, p.nChunks, p.xcd, ca, uc, c->uDict.p, fr);
+        }); };
+        if (p.kernel == CSR)
+            withOneOf<0, 1>(mode, [&](auto MODE) { withBool(M.packed, [&](auto PK) {
+                hipLaunchKernelGGL((k_spmv_St<MODE, 6, PK>), dim3(p.grid), dim3(BS), 0, c->stream, M.ptr.p, M.col.p, M.val.p, M.code.p, c->valScale, t, rowsSt, nP, c->uInv.p, xin, add, out, partial, done);
+            }); });
+        else if (p.kernel == ELL2C) stEll2c(p, t, xin, out, partial, ca);
+        else if (p.kernel == ELL2Z) {
+            auto z = [&](auto TZ) { withPolicy(p.pol, [&](auto POL) { withBool(c->uCoded, [&](auto UC) { ell2(POL, T{}, F{}, F{}, TZ, F{}, UC); }); }); };
+            if (cz32) z(Type<float>{}); else z(Type<double>{});
         }
-        if (pipeGrid > 0 && M.col16ok && (M.packed || M.val4.p)) {
-            const int nChunks = c->St.nChunks;
-            int xcdAware = this->xcdAware;
-            const dim3 gr(pipeBlocks(nChunks, xcdAware, M.packed, stGridFor(mode))), bl(BS);
-#define PS_LAUNCH_TP(MODE_, NV_, F64_, POL_) hipLaunchKernelGGL((k_spmv_St_pipe<MODE_, NV_, F64_, POL_>), gr, bl, 0, c->stream, M.col16.p, M.code4.p, M.val4.p, (int)M.streamLen, M.winBase.p, \
-                                                    M.chunkInfo.p, M.len8.p, c->valScale, t, (int)M.cols, rowsSt, c->uInv.p, xin, add, out, partial, done, nChunks, xcdAware, ca, c->uCoded ? c->uCode.p : (const uint8_t*)nullptr, c->uDict.p, fr)
-#define PS_LAUNCH_TP2(MODE_, NV_) do { const int pol = policy(M); if (!M.packed) PS_LAUNCH_TP(MODE_, NV_, true, 3); else if (pol == 3) PS_LAUNCH_TP(MODE_, NV_, false, 3); \
-                                       else if (pol == 1) PS_LAUNCH_TP(MODE_, NV_, false, 1); else PS_LAUNCH_TP(MODE_, NV_, false, 0); } while (0)
-            if (mode == 3) {
-                if (!M.packed) throw Error("internal: fused residual update on the fp64 stream");
-                if (M.nv == 1) PS_LAUNCH_TP2(3, 1); else PS_LAUNCH_TP2(3, 2);
-                return;
-            }
-            if (M.nv == 1) { if (mode == 0) PS_LAUNCH_TP2(0, 1); else if (mode == 1) PS_LAUNCH_TP2(1, 1); else PS_LAUNCH_TP2(2, 1); }
-            else { if (mode == 0) PS_LAUNCH_TP2(0, 2); else if (mode == 1) PS_LAUNCH_TP2(1, 2); else PS_LAUNCH_TP2(2, 2); }
-#undef PS_LAUNCH_TP2
-#undef PS_LAUNCH_TP
-            return;
-        }
-        if (mode >= 2) throw Error("internal: fused St epilogue without the pipelined St kernel");
-        spmvSt_(mode, t, xin, add, out, partial);
+        else if (p.kernel == ELL2) withBool(c->uCoded, [&](auto UC) { withPolicy(p.pol, [&](auto POL) { ell2(POL, F{}, F{}, F{}, Type<double>{}, F{}, UC); }); });
+        else if (p.kernel == ELL && p.fx == 3) withPolicy(p.pol, [&](auto POL) { withBool(stList, [&](auto LIST) { ell(M3{}, POL, M3{}, LIST); }); });
+        else if (p.kernel == ELL2_OWN) withBool(c->uCoded, [&](auto UC) { withPolicy(p.pol, [&](auto POL) { ell2(POL, F{}, T{}, T{}, Type<double>{}, F{}, UC); }); });
+        else if (p.kernel == ELL2_HALO)
+            withBool(c->uCoded, [&](auto UC) { withPolicy(p.pol, [&](auto POL) { withBool(stList, [&](auto LIST) {
+                ell2(POL, F{}, T{}, LIST, Type<double>{}, T{}, UC);
+            }); }); });
+        else if (p.kernel == ELL && p.fx == 5) withPolicy(p.pol, [&](auto POL) { ell(M3{}, POL, std::integral_constant<int, 5>{}, T{}); });
+        else if (p.kernel == ELL && p.fx == 1)
+            withPolicy(p.pol, [&](auto POL) { withBool(stList, [&](auto LIST) { ell(M3{}, POL, std::integral_constant<int, 1>{}, LIST); }); });
+        else if (p.kernel == ELL)
+            withOneOf<0, 1, 2, 3>(mode, [&](auto MODE) { withPolicy(p.pol, [&](auto POL) { withBool(stList, [&](auto LIST) {
+                ell(MODE, POL, std::integral_constant<int, 0>{}, LIST);
+            }); }); });
+        else if (mode == 3) withOneOf<1, 2>(M.nv, [&](auto NV) { pipe(M3{}, NV); });   // PIPE
+        else withOneOf<1, 2>(M.nv, [&](auto NV) { withOneOf<0, 1, 2>(mode, [&](auto MODE) { pipe(MODE, NV); }); });
     }
+
+    // ---- grids
     // grid of a persistent kernel; the XCD-grouped walk needs a multiple of 8 blocks (workgroup b runs on XCD b & 7)
     // The fp64-value stream (10 B per entry) runs one chunk per workgroup: measured at 256^3 St 0.54 ms against 0.64 ms
     // persistent (the persistent walk pays when the stream is short and the loop is issue-bound, not when it is 3x heavier).
@@ -341,64 +344,52 @@ struct Launch {
         }
         return g;
     }
-    // the fused step needs both products on the persistent coded-stream kernels (their per-workgroup partials)
-    bool fusedOk() const {
-        return stOnPipe() && c->St.packed && pipeGrid > 0 && c->S.col16ok && c->S.packed && rowsS > 0;
-    }
-    int sBlocks() const {
-        const int nChunks = c->S.nChunks;
-        int xcd = xcdAware;
-        return pipeBlocks(nChunks, xcd, true, sCap());
-    }
     // The row-per-lane S kernel has no per-workgroup prologue and balances better on more, shorter workgroups — 256^3, same box:
     // 4096 workgroups 0.265 ms, 5120 0.260, 6144 0.257, 8192 0.258, 12288 0.250 (each is one more partial sum for every St workgroup to read)
-    int sCap() const { return (c->S.ellok && c->S.packed && c->S.col16ok && pipeGrid == 4096) ? 6144 : 0; }
-    // MODE 3 of the row-per-lane St kernel in its plain form (FX = 1: no Chebyshev first term, no halo rows, coded uInv) fits 7 workgroups per CU
-    bool plain3Hint = false;
-    bool plain3Hint2 = false;   // the same for the Chebyshev step: single domain, coded uInv
+    int sCap() const { return (ellOk(c->S) && pipeGrid == 4096) ? 6144 : 0; }
     // Workgroups of the St kernel.  With the residual update in its epilogue (mode 3) it runs best on 6 per CU — measured at 256^3,
     // rocprof average in a solve: 1280 / 1536 workgroups 415 us, 1792 489, 2048 445, 2560 / 3072 425, 4096 430 (and every workgroup
     // less is 10 K partial sums less to read in the prologue); S and the other St modes keep 16 per CU (S: 300 us at 4096, 324 at
     // 1536, 339 at 1024).  PS_PIPE_GRID_ST overrides.
     // Row-per-lane kernel, plain MODE 3: 7 per CU — 1536 workgroups 0.418 ms, 1792 0.403, 2048 0.515 (the eighth does not fit: a second round),
     // 3584 / 5376 as 1792.
-    bool stDual() const {
-        static const bool on = !(PS_ENV("PS_ST_DUAL") && atoi(PS_ENV("PS_ST_DUAL")) == 0);
-        return on && plain3Hint && c->St.ellok && c->St.packed && c->St.col16ok && pipeGrid >= 1536;
-    }
+    bool stDual() const { return dualT && plain3Hint && ellOk(c->St) && pipeGrid >= 1536; }
     int stGridFor(int mode) const {
         if (stGrid > 0) return stGrid;
-        static const int g2 = PS_ENV("PS_PIPE_GRID_ST2") ? atoi(PS_ENV("PS_PIPE_GRID_ST2")) : 0;   // A/B: the Chebyshev term's launch alone
-        if (mode == 2 && g2 > 0) return g2;
+        if (mode == 2 && stGrid2 > 0) return stGrid2;
         if (mode != 3 || pipeGrid < 1536) return 0;
         if (stDual()) return 1536;   // k_spmv_St_ell2: 80 VGPRs, six workgroups per CU
         return (plain3Hint && c->uCoded && c->St.ellok && c->St.packed && pipeGrid >= 1792) ? 1792 : 1536;
     }
-    int stBlocks(int mode = 0) const {   // number of partials the St kernel writes: one per block
-        int xcd = xcdAware;
-        return stOnPipe() ? pipeBlocks(c->St.nChunks, xcd, c->St.packed, stGridFor(mode)) : gridFor(rowsSt, BS);
-    }
+};
+// The lab switches of this layer, read once per process
+struct LaunchSwitches {
+    int pipeGrid = envInt(PS_ENV("PS_PIPE_GRID"), 4096);     // persistent pipelined kernels, 16 blocks per CU, by default; 0 = one-shot kernels
+    int stGrid = envInt(PS_ENV("PS_PIPE_GRID_ST"), 0);
+    int stGrid2 = envInt(PS_ENV("PS_PIPE_GRID_ST2"), 0);     // A/B: the Chebyshev term's launch alone
+    // chunks per XCD run (rounded down to a power of two); 0: plain walk.  64: same kernel times as 4 / 16 / 256 on the row-per-lane kernels, a
+    // fifth less HBM-side traffic than 16 (FETCH_SIZE of S 0.64 / 0.54 / 0.44 / 0.42 M KiB at 4 / 16 / 64 / 256)
+    int xcd = envInt(PS_ENV("PS_XCD"), 64);
+    // log2 of the consecutive chunks a workgroup takes in a row (ChunkWalk): 2 chunks on the row-per-lane kernels (256^3, same box: S 0.264 ->
+    // 0.257 ms, St with the residual update 0.431 -> 0.408; 4 / 8 / 16 chunks: S 0.282 / 0.274 / 0.273, St 0.412 / 0.412 / 0.428)
+    int wgRun = envInt(PS_ENV("PS_WG_RUN"), -1);
+    bool dualS = envInt(PS_ENV("PS_S_DUAL"), 1) != 0;
+    bool dualT = envInt(PS_ENV("PS_ST_DUAL"), 1) != 0;
+    bool tileSplit = envInt(PS_ENV("PS_TILE_SPLIT"), 0) != 0;   // A/B: force the three-kernel form
+    int tileTB = envInt(PS_ENV("PS_TILE_TB"), 0);
 };
 Launch mk(ps_context* c, const int* done) {
+    static const LaunchSwitches sw;
     Launch L;
     L.c = c; L.done = done;
     L.rowsS = (int)c->nRows; L.rowsSt = (int)c->nSystem; L.nA = (int)c->nActiveVs; L.nP = (int)c->nPressures;
-    static int pg = -1;
-    if (pg < 0) {
-        const char* g = PS_ENV("PS_PIPE_GRID");   // A/B switch: 0 = one-shot kernels
-        pg = g ? atoi(g) : 4096;                   // persistent pipelined kernels, 16 blocks per CU, by default
-    }
-    L.pipeGrid = pg;
-    static const int sg = PS_ENV("PS_PIPE_GRID_ST") ? atoi(PS_ENV("PS_PIPE_GRID_ST")) : 0;
-    L.stGrid = pg > 0 ? sg : 0;
-    static int xa = -1;
-    if (xa < 0) { const char* e = PS_ENV("PS_XCD"); xa = e ? atoi(e) : 64; }   // chunks per XCD run (rounded down to a power of two); 0: plain walk.  64: same kernel times as 4 / 16 / 256 on the row-per-lane kernels, a fifth less HBM-side traffic than 16 (FETCH_SIZE of S 0.64 / 0.54 / 0.44 / 0.42 M KiB at 4 / 16 / 64 / 256)
-    L.xcdAware = xa > 0 ? xa : 0;
-    // log2 of the consecutive chunks a workgroup takes in a row (ChunkWalk): 2 chunks on the row-per-lane kernels (256^3, same box: S 0.264 ->
-    // 0.257 ms, St with the residual update 0.431 -> 0.408; 4 / 8 / 16 chunks: S 0.282 / 0.274 / 0.273, St 0.412 / 0.412 / 0.428)
-    static const int wr = PS_ENV("PS_WG_RUN") ? atoi(PS_ENV("PS_WG_RUN")) : -1;
-    const int run = wr >= 0 ? wr : ((c->S.ellok && c->St.ellok) ? 1 : 0);
+    L.pipeGrid = sw.pipeGrid;
+    L.stGrid = sw.pipeGrid > 0 ? sw.stGrid : 0;
+    L.stGrid2 = sw.stGrid2;
+    L.xcdAware = sw.xcd > 0 ? sw.xcd : 0;
+    const int run = sw.wgRun >= 0 ? sw.wgRun : ((c->S.ellok && c->St.ellok) ? 1 : 0);
     if (L.xcdAware > 0) L.xcdAware |= (run & 7) << 16;
+    L.dualS = sw.dualS; L.dualT = sw.dualT; L.tileSplit = sw.tileSplit; L.tileTB = sw.tileTB;
     L.ntSpmv = c->ntLevel() >= 1;
     L.plain3Hint = c->P.preconditioner != PS_PRE_CHEBYSHEV && !c->slabEnabled;     // (the stress diagonal coded or not: the two-unit kernels take both, r06)
     L.plain3Hint2 = c->P.preconditioner == PS_PRE_CHEBYSHEV && !c->slabEnabled;
@@ -473,7 +464,7 @@ void ps_context::constructPreconditioner() {
 // iteration at level 0 / 1 / 2 (cavity): 64^3 (0.8 M rows) 58.6 / 60.6 / 61.2; 96^3 (2.6 M) 97.9 / 104.8 / 103.4; 128^3 (5.9 M) 194.0 /
 // 187.4 / 191.8; 160^3 (11.4 M) 341.7 / 337.7 / 336.0; 192^3 (19.4 M) 558 / 535 / 530; 224^3 (30.6 M) 858 / 838 / 810.
 int ps_context::ntLevel() const {
-    static const int env = PS_ENV("PS_NT_LEVEL") ? atoi(PS_ENV("PS_NT_LEVEL")) : -1;
+    static const int env = envInt(PS_ENV("PS_NT_LEVEL"), -1);
     if (env >= 0) return env;
     const int64_t rows = std::max(nSystem, deviceShareRows);   // (ranks of an in-process group share the device's caches: ps_context::deviceShareRows)
     return rows < NT_LEVEL1_MIN_ROWS ? 0 : (rows < NT_LEVEL2_MIN_ROWS ? 1 : 2);
@@ -556,7 +547,7 @@ int ps_context::chebyshevApply(const double* rvec, double* zA, double* zB, doubl
         if (L.stOnPipe()) {
             const ChebArgs ca{rvec, dinvF.p, zprev, c1, c2};
             L.spmvSt(2, ts.p, cur, nullptr, other, rzPartial, &ca);
-            count = L.stBlocks();
+            count = L.stBlocks(2);   // the partials of the MODE 2 launch
         } else {
             tmp5.alloc((size_t)n);
             L.spmvSt(0, ts.p, cur, nullptr, tmp5.p, dotPartials2.p);
@@ -640,7 +631,7 @@ int ps_context::solve() {
     // partials 64 to 1 in the producers with a ticket per group costs more than it saves: one device-scope atomic per workgroup,
     // +30 us per iteration with write-through stores and no fence, +650 us with __threadfence(), which flushes the XCD's L2.)
     // PS_FUSED_R = 0 / 1 forces it off / on (on only where the kernels exist).
-    static const int fusedEnv = PS_ENV("PS_FUSED_R") ? atoi(PS_ENV("PS_FUSED_R")) : -1;
+    static const int fusedEnv = envInt(PS_ENV("PS_FUSED_R"), -1);
     const bool fused = fusedEnv != 0 && (fusedEnv > 0 || n >= FUSED_STEP_MIN_ROWS) && L.fusedOk();
     fusedStepHost = fused ? 1 : 0;
     const int sBlocks = fused ? L.sBlocks() : 0;

@@ -757,14 +757,14 @@ void runOuter(ps_context* c, double* out676, double* out26) {
     if (c->regionCount == 0 || c->fbItems == 0) return;
     c->partials.alloc((size_t)c->fbItems * OUTW);
     TileArgs A = makeArgs(c);
-    static const bool useMfma = !(PS_ENV("PS_TILE_VALU") && atoi(PS_ENV("PS_TILE_VALU")) != 0);
+    static const bool useMfma = envInt(PS_ENV("PS_TILE_VALU"), 0) == 0;
     // Which blocks are shared (PS_TILE_CLASS_MASK; bit 0: Mr, bit 1: K).  Default: K only.  A copied block differs from the tile's own sums
     // by the rounding of `index * dx - COM` at the representative's position (Mr 3e-16, K 4e-14 relative to the oracle's either way).  On
     // the stiff 48^3 spheres at tol 1e-8 — where a 1e-15 change of B moves the velocities by 1e-5..1e-4, the AMP sensitivity of
     // DESIGN.md section 4 — the distance to the oracle's velocities is 6.8e-5 with own sums, 7.3e-5 with K shared and 1.04e-4 with Mr
     // shared (scripts/ladder_tile_classes.py): Mr carries the tile's rigid modes, which the large pressure-stress terms cancel against.
     // So Mr (2.3 of the 7.8 ms at 256^3) stays per tile and the tolerance ladder of tests/test_gpu_parity.py keeps its bounds.
-    static const int clsMask = PS_ENV("PS_TILE_CLASS_MASK") ? atoi(PS_ENV("PS_TILE_CLASS_MASK")) : 2;
+    static const int clsMask = envInt(PS_ENV("PS_TILE_CLASS_MASK"), 2);
     // (a density field makes Mr a function of the tile's densities, which the class signature does not see: Mr then stays per tile)
     const bool shareable = MODE == MODE_VISC || (MODE == MODE_MASS && !c->densField);
     if (shareable && ((MODE == MODE_MASS ? 1 : 2) & clsMask) && c->tileReps > 0 && c->tileReps < c->regionCount) {   // one sum per class of identical tiles, copied to the others
@@ -862,7 +862,7 @@ void ps_context::computeCenterOfMasses() {
 void ps_context::buildTileClasses() {
     tileReps = 0; repItems = 0;
     const int64_t R = regionCount;
-    static const bool off = PS_ENV("PS_NO_TILE_CLASSES") && atoi(PS_ENV("PS_NO_TILE_CLASSES")) != 0;   // A/B: every tile sums its own blocks
+    static const bool off = envInt(PS_ENV("PS_NO_TILE_CLASSES"), 0) != 0;   // A/B: every tile sums its own blocks
     if (off || R < 2) return;
     TileArgs A = makeArgs(this);
     unsigned cap = 1024;

@@ -673,7 +673,8 @@ def test_exported_system_import_errors(gpu, tmp_path):
                                  {"PS_NT_LEVEL": "1"}, {"PS_NT_LEVEL": "2"}, {"PS_FUSED_R": "1", "PS_NT_LEVEL": "2"},
                                  {"PS_NO_SHARED_RUNS": "1"}, {"PS_CHUNK_PLAIN": "1"}, {"PS_WEAK_CHUNK_HASH": "1"}, {"PS_CHUNK_PLAIN": "1", "PS_FUSED_R": "1", "PS_NT_LEVEL": "2"},
                                  {"PS_NO_ELL": "1"}, {"PS_IL": "0"}, {"PS_IL": "3", "PS_NO_ELL": "1"}, {"PS_WG_RUN": "0"}, {"PS_WG_RUN": "2", "PS_FUSED_R": "1"},
-                                 {"PS_NO_ELL": "1", "PS_FUSED_R": "1"}, {"PS_NO_SHARED_RUNS": "1", "PS_FUSED_R": "1"}])
+                                 {"PS_NO_ELL": "1", "PS_FUSED_R": "1"}, {"PS_NO_SHARED_RUNS": "1", "PS_FUSED_R": "1"},
+                                 {"PS_S_DUAL": "0"}, {"PS_ST_DUAL": "0"}, {"PS_ST_DUAL": "0", "PS_FUSED_R": "1"}, {"PS_TILE_TB": "512"}])
 def test_fallback_kernel_paths_agree(gpu, tmp_path, env):
     """The SpMV has four storage formats chosen at setup — compressed stream with int8 value codes (3 B/nnz) or with fp64
     values (10 B/nnz: values that are not code * scale), both on the pipelined kernels; int8-coded CSR and fp64 CSR on the
@@ -712,6 +713,37 @@ def test_fallback_kernel_paths_agree(gpu, tmp_path, env):
         assert int(alt["c16"][0]) == 0
     if "PS_FORCE_FP64_VALUES" in env:
         assert int(alt["coded"][0]) == 0 and int(alt["c16"][0]) == (0 if "PS_COL32" in env else 3)
+    assert abs(float(alt["it"]) - gpu.stats.solveData[1]) <= 1
+    for a, k in enumerate(("vx", "vy", "vz")):
+        scale = max(np.abs(gpu.vel[a]).max(), 1e-30)
+        assert np.abs(alt[k] - gpu.vel[a]).max() <= 1e-6 * scale
+
+
+def test_chebyshev_f32_needs_the_pair_walk_grid(gpu, tmp_path):
+    """The fp32 inner applies run on the pair-walking two-unit kernels only, whose grid must be a multiple of 8 with the XCD walk on.
+    PS_PIPE_GRID_ST2=4 caps the Chebyshev term's St launch below that: PS_PRE_CHEBYSHEV_F32 then runs the fp64 polynomial (array
+    chebInner32 reads 0) and solves as the fp64 Chebyshev form does (run in a child process: the switch is read once per process)."""
+    import os
+    import subprocess
+    import sys
+    sc, p = scenes.cavity(32)
+    p.tolerance = 1e-8
+    p.preconditioner = abi.PRE_CHEBYSHEV
+    assert gpu.step(sc, p) == abi.SUCCESS
+    assert int(gpu.array("chebInner32")[0]) == 0
+    out = str(tmp_path / "alt.npz")
+    code = (
+        "import sys, numpy as np\n"
+        f"sys.path.insert(0, {os.path.dirname(os.path.dirname(os.path.abspath(__file__)))!r})\n"
+        "import polystokes_amd\nfrom polystokes_amd import _abi as abi, scenes\n"
+        "sc, p = scenes.cavity(32)\np.tolerance = 1e-8\np.preconditioner = abi.PRE_CHEBYSHEV_F32\n"
+        "s = polystokes_amd.Solver(0)\nrc = s.step(sc, p)\n"
+        f"np.savez({out!r}, rc=rc, it=s.stats.solveData[1], c32=s.array('chebInner32'), vx=s.vel[0], vy=s.vel[1], vz=s.vel[2])\n"
+    )
+    subprocess.run([sys.executable, "-c", code], check=True, env=dict(os.environ, PS_PIPE_GRID_ST2="4"), timeout=300)
+    alt = np.load(out)
+    assert int(alt["rc"]) == abi.SUCCESS
+    assert int(alt["c32"][0]) == 0
     assert abs(float(alt["it"]) - gpu.stats.solveData[1]) <= 1
     for a, k in enumerate(("vx", "vy", "vz")):
         scale = max(np.abs(gpu.vel[a]).max(), 1e-30)
