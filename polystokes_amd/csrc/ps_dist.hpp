@@ -695,15 +695,21 @@ struct Dist {
     }
     void syncAll() { for (ps_context* c : R) HIP_CHECK(hipStreamSynchronize(c->stream)); }
 
+    // host values summed over the ranks of the other processes (RCCL / TCP), in place: every rank takes the same branch.  False for
+    // in-process ranks, which see each other's values already (nothing exchanged).
+    bool agree(double* v, int count) {
+        if (!useRccl && !useTcp) return false;
+        for (ps_context* c : R) HIP_CHECK(hipMemcpyAsync(c->redbuf.p, v, (size_t)count * 8, hipMemcpyHostToDevice, c->stream));
+        allreduce(count);
+        HIP_CHECK(hipMemcpyAsync(v, R[0]->redbuf.p, (size_t)count * 8, hipMemcpyDeviceToHost, R[0]->stream));
+        syncAll();
+        return true;
+    }
     // a flag summed over all ranks (setup failures, interrupts): every rank learns that some rank wants to stop
     double sumFlag(double mine) {
-        for (ps_context* c : R) HIP_CHECK(hipMemcpyAsync(c->redbuf.p, &mine, 8, hipMemcpyHostToDevice, c->stream));
-        if (!useRccl && !useTcp) return mine * (double)R.size();   // in-process ranks: the caller already knows
-        allreduce(1);
-        double out = 0.;
-        HIP_CHECK(hipMemcpyAsync(&out, R[0]->redbuf.p, 8, hipMemcpyDeviceToHost, R[0]->stream));
-        HIP_CHECK(hipStreamSynchronize(R[0]->stream));
-        return out;
+        if (agree(&mine, 1)) return mine;
+        for (ps_context* c : R) HIP_CHECK(hipMemcpyAsync(c->redbuf.p, &mine, 8, hipMemcpyHostToDevice, c->stream));   // (in-process: the flag in redbuf all the same)
+        return mine * (double)R.size();   // in-process ranks: the caller already knows
     }
     // The cell labels of every rank's halo blocks := the owners' labels.  The reference's classification is not local: the boundary layers
     // reach up to three cells, fixReducedRegionBoundaries (Classifier.cpp:1073-1172) one cell beyond a region's tile — beyond the halo
@@ -891,7 +897,7 @@ struct Dist {
             hipLaunchKernelGGL(k_fill_f64, dim3(dotBlocks((int64_t)nl)), dim3(BS), 0, c->stream, c->tmp1.p, 1., (int64_t)nl);
             HIP_CHECK(hipMemsetAsync(c->tmp2.p, 0, nl * 8, c->stream));
         }
-        for (int it = 0; it < 10; ++it) {
+        const double lmax = powerLambdaMax([&] {
             applyDist(V, AV);
             for (ps_context* c : R) {
                 const int64_t n = c->ownHi - c->ownLo, lo = c->ownLo;
@@ -900,17 +906,16 @@ struct Dist {
                                    (const double*)c->dinv.p + lo, (c->*W).p + lo, n, c->chebPartials.p);
             }
             std::swap(V, W);
-        }
-        for (ps_context* c : R) {
-            const int vb = dotBlocks(std::max<int64_t>(c->ownHi - c->ownLo, 1));
-            hipLaunchKernelGGL(k_sumq, dim3(1), dim3(BS), 0, c->stream, (const CGScalars*)nullptr, (const double*)c->chebPartials.p, vb, vb, 2, c->redbuf.p);
-        }
-        allreduce(2);
-        double h[2] = {0., 0.};
-        HIP_CHECK(hipMemcpyAsync(h, R[0]->redbuf.p, sizeof(h), hipMemcpyDeviceToHost, R[0]->stream));
-        syncAll();
-        const double lam = (h[0] > 0. && std::isfinite(h[1] / h[0])) ? h[1] / h[0] : 0.;
-        for (ps_context* c : R) c->chebLmax = std::max(8.4, 1.25 * lam);
+        }, [&](double* h) {
+            for (ps_context* c : R) {
+                const int vb = dotBlocks(std::max<int64_t>(c->ownHi - c->ownLo, 1));
+                hipLaunchKernelGGL(k_sumq, dim3(1), dim3(BS), 0, c->stream, (const CGScalars*)nullptr, (const double*)c->chebPartials.p, vb, vb, 2, c->redbuf.p);
+            }
+            allreduce(2);
+            HIP_CHECK(hipMemcpyAsync(h, R[0]->redbuf.p, 2 * sizeof(double), hipMemcpyDeviceToHost, R[0]->stream));
+            syncAll();
+        });
+        for (ps_context* c : R) c->chebLmax = lmax;
     }
     // z = q(D^-1 A) D^-1 r on the owned DOFs (ps_context::chebyshevApply with the distributed operator; the update of a term is
     // its own kernel here: A z is complete only after the halo contributions have come back).  Returns the vector holding z;
@@ -918,19 +923,17 @@ struct Dist {
     Vec chebyshevDist(Vec Rv) {
         ps_context* c0 = R[0];
         const int k = c0->P.preconditionerDegree > 0 ? c0->P.preconditionerDegree : 4;
-        const double lmax = c0->chebLmax, lmin = lmax / PS_CHEB_INTERVAL_RATIO;
-        const double theta = 0.5 * (lmax + lmin), delta = 0.5 * (lmax - lmin), sigma = theta / delta;
-        double rho = 1. / sigma;
+        ChebRecurrence cr(c0->chebLmax);
         Vec cur = &ps_context::tmp1, other = &ps_context::tmp2;
         const Vec AZ = &ps_context::tmp5;
         for (ps_context* c : R) {
             const int64_t n = c->ownHi - c->ownLo, lo = c->ownLo;
             hipLaunchKernelGGL(k_cheb_first<double>, dim3(dotBlocks(std::max<int64_t>(n, 1))), dim3(BS), 0, c->stream, (const CGScalars*)c->scal.p, (const double*)(c->*Rv).p + lo,
-                               (const diag_t*)c->dinvF.p + lo, 1. / theta, c->tmp1.p + lo, n, c->chebPartials.p);
+                               (const diag_t*)c->dinvF.p + lo, 1. / cr.theta, c->tmp1.p + lo, n, c->chebPartials.p);
         }
         for (int j = 1; j < k; ++j) {
-            const double rhoN = 1. / (2. * sigma - rho);
-            const double c1 = rhoN * rho, c2 = 2. * rhoN / delta;
+            double c1, c2;
+            cr.next(c1, c2);
             applyDist(cur, AZ);
             for (ps_context* c : R) {
                 const int64_t n = c->ownHi - c->ownLo, lo = c->ownLo;
@@ -939,7 +942,6 @@ struct Dist {
                                    j == 1 ? (const double*)nullptr : (const double*)(c->*other).p + lo, (c->*other).p + lo, n, c->chebPartials.p);
             }
             std::swap(cur, other);
-            rho = rhoN;
         }
         return cur;
     }
@@ -1034,17 +1036,27 @@ struct Dist {
         if (cheb) estimateLambdaMaxDist();
     }
 
-    int solve() {
-        ps_context* c0 = R[0];
-        const int maxit = c0->P.maxSolverIterations;
-        const double tol = c0->P.tolerance;
-        const bool jac = c0->P.preconditioner == PS_PRE_DIAGONAL, cheb = c0->P.preconditioner == PS_PRE_CHEBYSHEV;
-        if (c0->P.solverType != PS_PCG_MATRIX_VECTOR_PRODUCTS) { c0->err = "Unsupported Solver."; return PS_UNSUPPORTED_SOLVER; }
-        struct Loc { int64_t n, lo; int vb, stBlocks; const diag_t* dv; CGScalars* sc; Launch L; };
-        std::vector<Loc> loc(R.size());
+    // ---- the solve: PCG across the ranks, then the BiCGStab fallback.  Per-rank state of one solve (solveStart):
+    struct RankSolve {
+        int64_t n, lo;                    // the owned DOF range
+        int vb, stBlocks;
+        const diag_t* dv;                 // Jacobi: the owned diagonal
+        CGScalars* sc;
+        Launch L;
+        // the four-kernel step (fusedStart): its partials in fusedPart; sI / tB: workgroups of the first of the two S / St launches
+        double *fS, *fT, *fU, *fR, *fX;
+        int sBlocks, stBF, gFix, sI, tB;
+    };
+    std::vector<RankSolve> rs;
+    bool jac = false, cheb = false, fused = false, overlap = false;
+    bool timed() const { return R[0]->commStream && R[0]->commStream != R[0]->stream; }   // transports on a stream of their own
+
+    // r = b, x = 0, p = z on the owned range; rsold = sum over ranks of r.z
+    void solveStart(double tol, int maxit) {
+        rs.assign(R.size(), RankSolve{});
         for (size_t q = 0; q < R.size(); ++q) {
             ps_context* c = R[q];
-            Loc& l = loc[q];
+            RankSolve& l = rs[q];
             l.lo = c->ownLo; l.n = c->ownHi - c->ownLo;
             l.vb = dotBlocks(std::max<int64_t>(l.n, 1));
             l.dv = jac ? c->dinvF.p + l.lo : nullptr;
@@ -1052,11 +1064,7 @@ struct Dist {
             l.L = mk(c, &l.sc->done);
             l.stBlocks = l.L.stBlocks();
             c->usedBiCGStab = 0;
-        }
-        // r = b, x = 0, p = z on the owned range; rsold = sum over ranks of r.z
-        for (size_t q = 0; q < R.size(); ++q) {
-            ps_context* c = R[q];
-            Loc& l = loc[q];
+            c->chebInner32 = false;      // the polynomial of a decomposition is fp64 (an earlier single-domain solve may have set it)
             HIP_CHECK(hipMemsetAsync(c->pvec.p, 0, (size_t)std::max<int64_t>(c->nSystem, 1) * 8, c->stream));
             HIP_CHECK(hipMemsetAsync(c->dotPartials3.p, 0, VGRID * sizeof(double), c->stream));
             // halo rows: A p there is this rank's share of a neighbour's row (or nothing: rows no launch of the overlapped step
@@ -1084,357 +1092,286 @@ struct Dist {
             const Vec z0 = chebyshevDist(&ps_context::r);
             for (size_t q = 0; q < R.size(); ++q) {
                 ps_context* c = R[q];
-                Loc& l = loc[q];
+                const RankSolve& l = rs[q];
                 if (l.n > 0) HIP_CHECK(hipMemcpyAsync(c->pvec.p + l.lo, (c->*z0).p + l.lo, (size_t)l.n * 8, hipMemcpyDeviceToDevice, c->stream));
                 hipLaunchKernelGGL(k_sumq, dim3(1), dim3(BS), 0, c->stream, (const CGScalars*)nullptr, (const double*)c->chebPartials.p, l.vb, 0, 1, c->redbuf.p);
             }
         }
         allreduce(1);
         for (size_t q = 0; q < R.size(); ++q)
-            hipLaunchKernelGGL(k_dscal0, dim3(1), dim3(1), 0, R[q]->stream, loc[q].sc, R[q]->redbuf.p, tol, maxit, R[q]->ntLevel() >= 2 ? 1 : 0);
-        // Four-kernel step across slabs (ps_solve.hip: solve, FusedR): every rank's share of p.Ap in its factored form is known after
-        // the tile kernel — one all-reduce, then the St kernel updates r on the owned DOFs and hands the halo rows' (A p) to the
-        // neighbours, who subtract alpha times it (k_dist_fixup).  Same rule as the single-domain solve: coded streams on every
-        // rank and >= FUSED_STEP_MIN_ROWS owned rows on the largest (PS_FUSED_R = 0 / 1 forces); decided from values every rank
-        // knows or agrees on, so all ranks take the same branch.
+            hipLaunchKernelGGL(k_dscal0, dim3(1), dim3(1), 0, R[q]->stream, rs[q].sc, R[q]->redbuf.p, tol, maxit, R[q]->ntLevel() >= 2 ? 1 : 0);
+    }
+
+    // Four-kernel step across slabs (ps_solve.hip: solve, FusedR): every rank's share of p.Ap in its factored form is known after
+    // the tile kernel — one all-reduce, then the St kernel updates r on the owned DOFs and hands the halo rows' (A p) to the
+    // neighbours, who subtract alpha times it (k_dist_fixup).  Same rule as the single-domain solve: coded streams on every
+    // rank and >= FUSED_STEP_MIN_ROWS owned rows on the largest (PS_FUSED_R = 0 / 1 forces); decided from values every rank
+    // knows or agrees on, so all ranks take the same branch.
+    // The exchanges overlap with the rows that do not need them when every rank has its chunk lists (row-per-lane kernels)
+    // (the ranks of an in-process group share ONE stream: nothing runs beside anything, and splitting S and St into the chunks next to a cut and
+    // the rest only doubles their launches — one launch each there; PS_DIST_OVERLAP=1 forces the split for the tests that walk that path on one GPU)
+    void chooseStepForm() {
         static const int fusedEnv = envInt(PS_ENV("PS_FUSED_R"), -1);
-        bool fused = !cheb && fusedEnv != 0;
-        for (size_t q = 0; q < R.size(); ++q) fused = fused && loc[q].L.fusedOk() && loc[q].n > 0;
-        {
-            double mine[2] = {fused ? 0. : 1., 0.};
-            for (size_t q = 0; q < R.size(); ++q) mine[1] = std::max(mine[1], (double)loc[q].n);
-            if (useRccl || useTcp) {   // a rank without the coded stream vetoes; the size rule looks at the SUM of the owned rows (identical everywhere)
-                for (ps_context* c : R) HIP_CHECK(hipMemcpyAsync(c->redbuf.p, mine, 16, hipMemcpyHostToDevice, c->stream));
-                allreduce(2);
-                HIP_CHECK(hipMemcpyAsync(mine, R[0]->redbuf.p, 16, hipMemcpyDeviceToHost, R[0]->stream));
-                syncAll();
-                mine[1] /= std::max(1, R[0]->slab.world);   // mean owned rows per rank
-            }
-            fused = fused && mine[0] == 0. && (fusedEnv > 0 || mine[1] >= (double)FUSED_STEP_MIN_ROWS);
-        }
-        struct FBuf { double *fS, *fT, *fU, *fR, *fX; int sBlocks, stBF, gFix, sI, tB; };   // sI / tB: workgroups of the first of the two S / St launches
-        std::vector<FBuf> fb(R.size());
-        // the exchanges overlap with the rows that do not need them when every rank has its chunk lists (row-per-lane kernels)
-        // (the ranks of an in-process group share ONE stream: nothing runs beside anything, and splitting S and St into the chunks next to a cut and
-        // the rest only doubles their launches — one launch each there; PS_DIST_OVERLAP=1 forces the split for the tests that walk that path on one GPU)
+        fused = !cheb && fusedEnv != 0;
+        for (const RankSolve& l : rs) fused = fused && l.L.fusedOk() && l.n > 0;
+        // a rank without the coded stream vetoes; the size rule looks at the SUM of the owned rows (identical everywhere)
+        double mine[2] = {fused ? 0. : 1., 0.};
+        for (const RankSolve& l : rs) mine[1] = std::max(mine[1], (double)l.n);
+        if (agree(mine, 2)) mine[1] /= std::max(1, R[0]->slab.world);   // mean owned rows per rank
+        fused = fused && mine[0] == 0. && (fusedEnv > 0 || mine[1] >= (double)FUSED_STEP_MIN_ROWS);
         static const bool forceSplit = envInt(PS_ENV("PS_DIST_OVERLAP"), 0) == 1;
-        bool overlap = fused && (useRccl || useTcp || forceSplit);
+        overlap = fused && (useRccl || useTcp || forceSplit);
         for (ps_context* c : R) overlap = overlap && c->distListsOk;
-        if (useRccl || useTcp) {   // all ranks take the same branch (the kernels differ, not the messages — but keep the ranks alike)
-            double mine = overlap ? 0. : 1.;
-            for (ps_context* c : R) HIP_CHECK(hipMemcpyAsync(c->redbuf.p, &mine, 8, hipMemcpyHostToDevice, c->stream));
-            allreduce(1);
-            HIP_CHECK(hipMemcpyAsync(&mine, R[0]->redbuf.p, 8, hipMemcpyDeviceToHost, R[0]->stream));
-            syncAll();
-            overlap = overlap && mine == 0.;
-        }
-        const bool timed = c0->commStream && c0->commStream != c0->stream;
+        double veto = overlap ? 0. : 1.;   // all ranks take the same branch (the kernels differ, not the messages — but keep the ranks alike)
+        agree(&veto, 1);
+        overlap = overlap && veto == 0.;
         for (ps_context* c : R) {
             for (int q = 0; q < 8; ++q) c->distStats[q] = 0.;
             c->distStats[0] = 8. * (double)c->exchangeEntries();   // bytes this rank sends per iteration (x layers + A p contributions)
             c->distStats[1] = (double)(c->ownHi - c->ownLo);                                        // owned DOFs
             c->distStats[2] = overlap ? 1. : 0.;
             c->distStats[7] = (double)c->haloLabelChanges;
+            c->fusedStepHost = fused ? 1 : 0;
         }
-        if (fused) {
+    }
+    // the partials of the four-kernel step and the first direction's share of p.Ap on the diagonal
+    void fusedStart() {
+        for (size_t q = 0; q < R.size(); ++q) {
+            ps_context* c = R[q];
+            RankSolve& f = rs[q];
+            f.sBlocks = f.L.sBlocks(); f.stBF = (c->distListsOk && !overlap) ? f.L.stBlocksFor(c->nDistList[4], 3) : f.L.stBlocks(3); f.sI = 0; f.tB = 0;
+            if (overlap) {
+                f.sI = f.L.sBlocksFor(c->nDistList[0]); f.sBlocks = f.sI + f.L.sBlocksFor(c->nDistList[1]);
+                f.tB = f.L.stBlocksFor(c->nDistList[2], 3); f.stBF = f.tB + f.L.stBlocksFor(c->nDistList[3], 3);
+            }
+            int64_t mostOwn = 1;
+            for (int a = 0; a < ps_context::NLINK; ++a) mostOwn = std::max(mostOwn, c->nLowOwn[a] + c->nUpOwn[a]);
+            if (c->nFix > 0) mostOwn = std::max<int64_t>(mostOwn, c->nFix);             // the merged fix-up: one thread per receiving DOF, up to 1024 workgroups
+            f.gFix = (int)std::min<int64_t>(c->nFix > 0 ? 1024 : 256, (mostOwn + BS - 1) / BS);   // workgroups of one axis's k_dist_fixup; its partials: [axis][2][gFix]
+            c->fusedPart.alloc((size_t)f.sBlocks + (size_t)c->regionCount + VGRID + 2 * (size_t)f.stBF + 2 * ps_context::NLINK * (size_t)f.gFix + 16);
+            f.fS = c->fusedPart.p; f.fT = f.fS + f.sBlocks; f.fU = f.fT + c->regionCount; f.fR = f.fU + VGRID; f.fX = f.fR + 2 * f.stBF;
+            HIP_CHECK(hipMemsetAsync(f.fX, 0, 2 * ps_context::NLINK * (size_t)f.gFix * sizeof(double), c->stream));
+            f.L.sPart = f.fS; f.L.wvPart = f.fT;
+            const uint8_t* ucode = c->uCoded ? c->uCode.p + f.lo : nullptr;
+            hipLaunchKernelGGL(k_uinv_pp, dim3(f.vb), dim3(BS), 0, c->stream, (const double*)c->pvec.p + f.lo, ucode, (const double*)c->uDict.p,
+                               (const double*)c->uInv.p + f.lo, f.n, f.fU);
+        }
+    }
+    // One iteration of the four-kernel step.  split (the overlapped form): S and St run in two launches each, the chunks that need no halo
+    // value / hold no halo row beside the transports on the comm stream; otherwise exchangeX, then one launch each.  sample: time the
+    // x transport (the batch's last iteration: the host synchronises there anyway).
+    void fusedStep(int it, bool split, bool sample) {
+        ps_context* c0 = R[0];
+        sample = sample && split && timed();
+        if (split) {   // (1) p on the cut layers -> the neighbours [comm stream]; meanwhile the S chunks that gather no halo value
             for (size_t q = 0; q < R.size(); ++q) {
                 ps_context* c = R[q];
-                Loc& l = loc[q];
-                FBuf& f = fb[q];
-                f.sBlocks = l.L.sBlocks(); f.stBF = (c->distListsOk && !overlap) ? l.L.stBlocksFor(c->nDistList[4], 3) : l.L.stBlocks(3); f.sI = 0; f.tB = 0;
-                if (overlap) {
-                    f.sI = l.L.sBlocksFor(c->nDistList[0]); f.sBlocks = f.sI + l.L.sBlocksFor(c->nDistList[1]);
-                    f.tB = l.L.stBlocksFor(c->nDistList[2], 3); f.stBF = f.tB + l.L.stBlocksFor(c->nDistList[3], 3);
-                }
-                int64_t mostOwn = 1;
-                for (int a = 0; a < ps_context::NLINK; ++a) mostOwn = std::max(mostOwn, c->nLowOwn[a] + c->nUpOwn[a]);
-                if (c->nFix > 0) mostOwn = std::max<int64_t>(mostOwn, c->nFix);             // the merged fix-up: one thread per receiving DOF, up to 1024 workgroups
-                f.gFix = (int)std::min<int64_t>(c->nFix > 0 ? 1024 : 256, (mostOwn + BS - 1) / BS);   // workgroups of one axis's k_dist_fixup; its partials: [axis][2][gFix]
-                c->fusedPart.alloc((size_t)f.sBlocks + (size_t)c->regionCount + VGRID + 2 * (size_t)f.stBF + 2 * ps_context::NLINK * (size_t)f.gFix + 16);
-                f.fS = c->fusedPart.p; f.fT = f.fS + f.sBlocks; f.fU = f.fT + c->regionCount; f.fR = f.fU + VGRID; f.fX = f.fR + 2 * f.stBF;
-                HIP_CHECK(hipMemsetAsync(f.fX, 0, 2 * ps_context::NLINK * (size_t)f.gFix * sizeof(double), c->stream));
-                l.L.sPart = f.fS; l.L.wvPart = f.fT;
-                c->fusedStepHost = 1;
-                const uint8_t* ucode = c->uCoded ? c->uCode.p + l.lo : nullptr;
-                hipLaunchKernelGGL(k_uinv_pp, dim3(l.vb), dim3(BS), 0, c->stream, (const double*)c->pvec.p + l.lo, ucode, (const double*)c->uDict.p,
-                                   (const double*)c->uInv.p + l.lo, l.n, f.fU);
+                RankSolve& f = rs[q];
+                order(c, 0, true);
+                f.L.sList = c->distList[0].p; f.L.nSList = c->nDistList[0]; f.L.sPart = f.fS;
+                f.L.spmvS(0, c->pvec.p, c->ts.p);
             }
-        } else for (ps_context* c : R) c->fusedStepHost = 0;
-        CGScalars h{};
-        const int batch = 25;
-        int it = 0;
-        bool finished = false, interrupted = false;
-        for (ps_context* c : R) c->interrupted = false;
-        while (it < maxit && !finished) {
-            const int upto = std::min(maxit, it + batch);
-            for (; it < upto; ++it) {
-                if (fused && overlap) {
-                    // (1) p on the cut layers -> the neighbours [comm stream]; meanwhile the S chunks that gather no halo value
-                    const bool sample = it + 1 == upto;          // time the transports of the batch's last iteration (the host synchronises there anyway)
-                    for (size_t q = 0; q < R.size(); ++q) {
-                        ps_context* c = R[q];
-                        order(c, 0, true);
-                        Loc& l = loc[q];
-                        FBuf& f = fb[q];
-                        l.L.sList = c->distList[0].p; l.L.nSList = c->nDistList[0]; l.L.sPart = f.fS;
-                        l.L.spmvS(0, c->pvec.p, c->ts.p);
-                    }
-                    if (sample && timed) HIP_CHECK(hipEventRecord(c0->distEv[2], cs(c0, true)));
-                    valuesOut(&ps_context::pvec, true);          // pack, transport, unpack — axis after axis — on the comm stream
-                    if (sample && timed) HIP_CHECK(hipEventRecord(c0->distEv[3], cs(c0, true)));
-                    for (size_t q = 0; q < R.size(); ++q) {
-                        ps_context* c = R[q];
-                        order(c, 1, false);
-                        // (2) the S chunks next to a cut, the tiles, this rank's share of p.Ap
-                        Loc& l = loc[q];
-                        FBuf& f = fb[q];
-                        l.L.sList = c->distList[1].p; l.L.nSList = c->nDistList[1]; l.L.sPart = f.fS + f.sI;
-                        l.L.spmvS(0, c->pvec.p, c->ts.p);
-                        l.L.tiles(0, c->ts.p);
-                        hipLaunchKernelGGL(k_fused_local_sum, dim3(1), dim3(1024), 0, c->stream, (const CGScalars*)l.sc, (const double*)f.fS, f.sBlocks, (const double*)f.fT,
-                                           (int)c->regionCount, (const double*)f.fU, l.vb, (const double*)c->dotPartials3.p, l.vb, c->redbuf.p);
-                    }
-                    allreduce(2);
-                    // (3) St on the chunks that hold halo rows: their share of the neighbours' A p -> [comm stream]; meanwhile St on the rest
-                    for (size_t q = 0; q < R.size(); ++q) {
-                        ps_context* c = R[q];
-                        Loc& l = loc[q];
-                        FBuf& f = fb[q];
-                        FusedR fr{l.sc, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, it, c->r.p, jac ? c->dinvF.p : (const diag_t*)nullptr, f.fR, nullptr, 0., nullptr,
-                                  (const double*)c->redbuf.p, (int)c->ownLo, (int)c->ownHi, c->Ap.p, f.stBF};
-                        l.L.stList = c->distList[2].p; l.L.nStList = c->nDistList[2];
-                        l.L.spmvSt(3, c->ts.p, c->pvec.p, nullptr, nullptr, nullptr, nullptr, &fr);
-                        order(c, 4, true);
-                        fr.rPart = f.fR + f.tB;
-                        l.L.stList = c->distList[3].p; l.L.nStList = c->nDistList[3]; l.L.stOwnedOnly = true;
-                        l.L.spmvSt(3, c->ts.p, c->pvec.p, nullptr, nullptr, nullptr, nullptr, &fr);
-                        l.L.stOwnedOnly = false;
-                    }
-                    contributionsBack(&ps_context::Ap, true, false);   // [comm stream] the owners correct r from the receive buffers below
-                    for (size_t q = 0; q < R.size(); ++q) {
-                        ps_context* c = R[q];
-                        Loc& l = loc[q];
-                        FBuf& f = fb[q];
-                        order(c, 5, false);
-                        fixup(c, l.sc, jac, f.fX, f.gFix);
-                        hipLaunchKernelGGL(k_sum_rr, dim3(1), dim3(1024), 0, c->stream, (const CGScalars*)l.sc, (const double*)f.fR, f.stBF, (const double*)f.fX, f.gFix, c->nFix > 0 ? 1 : ps_context::NLINK, c->redbuf.p);   // (the merged fix-up writes ONE set of partials)
-                    }
-                    allreduce(2);
-                    for (size_t q = 0; q < R.size(); ++q) {
-                        ps_context* c = R[q];
-                        Loc& l = loc[q];
-                        FBuf& f = fb[q];
-                        const uint8_t* ucode = c->uCoded ? c->uCode.p + l.lo : nullptr;
-                        hipLaunchKernelGGL(k_cg_update_xp_u, dim3(l.vb), dim3(BS), 0, c->stream, l.sc, (const double*)c->redbuf.p, (const double*)nullptr, 0, jac ? 1 : 0, it,
-                                           (const double*)c->r.p + l.lo, l.dv, c->x.p + l.lo, c->pvec.p + l.lo, l.n, c->dotPartials3.p, ucode, (const double*)c->uDict.p,
-                                           (const double*)c->uInv.p + l.lo, f.fU);
-                    }
-                    continue;
-                }
-                exchangeX(&ps_context::pvec);
-                if (fused) {
-                    for (size_t q = 0; q < R.size(); ++q) {
-                        ps_context* c = R[q];
-                        Loc& l = loc[q];
-                        FBuf& f = fb[q];
-                        l.L.spmvS(0, c->pvec.p, c->ts.p);
-                        l.L.tiles(0, c->ts.p);
-                        hipLaunchKernelGGL(k_fused_local_sum, dim3(1), dim3(1024), 0, c->stream, (const CGScalars*)l.sc, (const double*)f.fS, f.sBlocks, (const double*)f.fT,
-                                           (int)c->regionCount, (const double*)f.fU, l.vb, (const double*)c->dotPartials3.p, l.vb, c->redbuf.p);
-                    }
-                    allreduce(2);
-                    for (size_t q = 0; q < R.size(); ++q) {
-                        ps_context* c = R[q];
-                        Loc& l = loc[q];
-                        FBuf& f = fb[q];
-                        const FusedR fr{l.sc, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, it, c->r.p, jac ? c->dinvF.p : (const diag_t*)nullptr, f.fR, nullptr, 0., nullptr,
-                                        (const double*)c->redbuf.p, (int)c->ownLo, (int)c->ownHi, c->Ap.p, f.stBF};
-                        // (the chunks that hold work: halo rows without entries — most of a halo block — are in no list; r and A p of those rows stay as the solve's start left them: zero)
-                        if (c->distListsOk) { l.L.stList = c->distList[4].p; l.L.nStList = c->nDistList[4]; }
-                        l.L.spmvSt(3, c->ts.p, c->pvec.p, nullptr, nullptr, nullptr, nullptr, &fr);
-                        l.L.stList = nullptr; l.L.nStList = 0;
-                    }
-                    // the halo rows' share of A p goes to its owners (the packing and transport of exchangeAddY; the owners correct r instead of adding into A p)
-                    contributionsBack(&ps_context::Ap, false, false);
-                    for (size_t q = 0; q < R.size(); ++q) {
-                        ps_context* c = R[q];
-                        Loc& l = loc[q];
-                        FBuf& f = fb[q];
-                        fixup(c, l.sc, jac, f.fX, f.gFix);
-                        hipLaunchKernelGGL(k_sum_rr, dim3(1), dim3(1024), 0, c->stream, (const CGScalars*)l.sc, (const double*)f.fR, f.stBF, (const double*)f.fX, f.gFix, c->nFix > 0 ? 1 : ps_context::NLINK, c->redbuf.p);   // (the merged fix-up writes ONE set of partials)
-                    }
-                    allreduce(2);
-                    for (size_t q = 0; q < R.size(); ++q) {
-                        ps_context* c = R[q];
-                        Loc& l = loc[q];
-                        FBuf& f = fb[q];
-                        const uint8_t* ucode = c->uCoded ? c->uCode.p + l.lo : nullptr;
-                        hipLaunchKernelGGL(k_cg_update_xp_u, dim3(l.vb), dim3(BS), 0, c->stream, l.sc, (const double*)c->redbuf.p, (const double*)nullptr, 0, jac ? 1 : 0, it,
-                                           (const double*)c->r.p + l.lo, l.dv, c->x.p + l.lo, c->pvec.p + l.lo, l.n, c->dotPartials3.p, ucode, (const double*)c->uDict.p,
-                                           (const double*)c->uInv.p + l.lo, f.fU);
-                    }
-                    continue;
-                }
-                for (size_t q = 0; q < R.size(); ++q) {
-                    ps_context* c = R[q];
-                    Loc& l = loc[q];
-                    l.L.spmvS(0, c->pvec.p, c->ts.p);
-                    l.L.tiles(0, c->ts.p);
-                    l.L.spmvSt(0, c->ts.p, c->pvec.p, nullptr, c->Ap.p, c->dotPartials.p);
-                    if (l.stBlocks <= 8192) {
-                        hipLaunchKernelGGL(k_sumq, dim3(1), dim3(BS), 0, c->stream, (const CGScalars*)l.sc, c->dotPartials.p, l.stBlocks, 0, 1, c->redbuf.p);
-                    } else {
-                        hipLaunchKernelGGL(k_reduce_partials, dim3(RED_BLOCKS), dim3(BS), 0, c->stream, l.sc, c->dotPartials.p, l.stBlocks, c->dotPartials2.p);
-                        hipLaunchKernelGGL(k_sumq, dim3(1), dim3(BS), 0, c->stream, (const CGScalars*)l.sc, c->dotPartials2.p, RED_BLOCKS, 0, 1, c->redbuf.p);
-                    }
-                    // ||x||^2 of the x updated last iteration rides along (stop test of the previous iteration, see k_cg_update_r)
-                    hipLaunchKernelGGL(k_sumq, dim3(1), dim3(BS), 0, c->stream, (const CGScalars*)l.sc, c->dotPartials3.p, l.vb, 0, 1, c->redbuf.p + 1);
-                }
-                exchangeAddY(&ps_context::Ap);
-                allreduce(2);
-                for (size_t q = 0; q < R.size(); ++q) {
-                    ps_context* c = R[q];
-                    Loc& l = loc[q];
-                    hipLaunchKernelGGL(k_cg_update_r, dim3(l.vb), dim3(BS), 0, c->stream, l.sc, (const double*)c->redbuf.p, (const double*)nullptr, 0,
-                                       (const double*)nullptr, 0, it, c->Ap.p + l.lo, l.dv, c->r.p + l.lo, l.n, c->dotPartialsR.p);
-                    hipLaunchKernelGGL(k_sumq, dim3(1), dim3(BS), 0, c->stream, (const CGScalars*)l.sc, c->dotPartialsR.p, l.vb, l.vb, 2, c->redbuf.p);
-                }
-                if (cheb) {   // z = M^-1 r (k-1 distributed applies), then {r.r, r.z} and x, p with the vector z
-                    const Vec zf = chebyshevDist(&ps_context::r);
-                    for (size_t q = 0; q < R.size(); ++q) {
-                        ps_context* c = R[q];
-                        Loc& l = loc[q];
-                        hipLaunchKernelGGL(k_sumq, dim3(1), dim3(BS), 0, c->stream, (const CGScalars*)l.sc, (const double*)c->chebPartials.p, l.vb, 0, 1, c->redbuf.p + 1);
-                    }
-                    allreduce(2);
-                    for (size_t q = 0; q < R.size(); ++q) {
-                        ps_context* c = R[q];
-                        Loc& l = loc[q];
-                        hipLaunchKernelGGL(k_cg_update_xp_z<double>, dim3(l.vb), dim3(BS), 0, c->stream, l.sc, (const double*)c->redbuf.p, 1, (const double*)c->redbuf.p + 1, 1, it,
-                                           (const double*)(c->*zf).p + l.lo, c->x.p + l.lo, c->pvec.p + l.lo, l.n, c->dotPartials3.p);
-                    }
-                    continue;
-                }
-                allreduce(2);
-                for (size_t q = 0; q < R.size(); ++q) {
-                    ps_context* c = R[q];
-                    Loc& l = loc[q];
-                    hipLaunchKernelGGL(k_cg_update_xp, dim3(l.vb), dim3(BS), 0, c->stream, l.sc, (const double*)c->redbuf.p, (const double*)nullptr, 0,
-                                       jac ? 1 : 0, it, c->r.p + l.lo, l.dv, c->x.p + l.lo, c->pvec.p + l.lo, l.n, c->dotPartials3.p);
-                }
+            if (sample) HIP_CHECK(hipEventRecord(c0->distEv[2], cs(c0, true)));
+            valuesOut(&ps_context::pvec, true);          // pack, transport, unpack — axis after axis — on the comm stream
+            if (sample) HIP_CHECK(hipEventRecord(c0->distEv[3], cs(c0, true)));
+        } else
+            exchangeX(&ps_context::pvec);
+        for (size_t q = 0; q < R.size(); ++q) {   // (2) the S chunks next to a cut (split) or all of S, the tiles, this rank's share of p.Ap
+            ps_context* c = R[q];
+            RankSolve& f = rs[q];
+            if (split) {
+                order(c, 1, false);
+                f.L.sList = c->distList[1].p; f.L.nSList = c->nDistList[1]; f.L.sPart = f.fS + f.sI;
             }
-            // the stop test of the batch's last iteration; the ranks' interrupt requests ride along in the same all-reduce,
-            // so that every rank leaves the loop at the same batch (a rank stopping alone would strand its neighbours in a receive)
-            double wantStop = 0.;
-            for (ps_context* c : R) if (c->interruptCb && c->interruptCb(c->interruptUser)) wantStop = 1.;
-            for (size_t q = 0; q < R.size(); ++q) {
-                hipLaunchKernelGGL(k_sumq, dim3(1), dim3(BS), 0, R[q]->stream, (const CGScalars*)loc[q].sc, R[q]->dotPartials3.p, loc[q].vb, 0, 1, R[q]->redbuf.p);
-                HIP_CHECK(hipMemcpyAsync(R[q]->redbuf.p + 1, &wantStop, 8, hipMemcpyHostToDevice, R[q]->stream));
+            f.L.spmvS(0, c->pvec.p, c->ts.p);
+            f.L.tiles(0, c->ts.p);
+            hipLaunchKernelGGL(k_fused_local_sum, dim3(1), dim3(1024), 0, c->stream, (const CGScalars*)f.sc, (const double*)f.fS, f.sBlocks, (const double*)f.fT,
+                               (int)c->regionCount, (const double*)f.fU, f.vb, (const double*)c->dotPartials3.p, f.vb, c->redbuf.p);
+        }
+        allreduce(2);
+        // (3) St: r on the owned rows, the halo rows' share of A p for their owners.  split: the chunks that hold halo rows first, their
+        // contributions -> [comm stream], St on the rest meanwhile
+        for (size_t q = 0; q < R.size(); ++q) {
+            ps_context* c = R[q];
+            RankSolve& f = rs[q];
+            FusedR fr{f.sc, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, it, c->r.p, jac ? c->dinvF.p : (const diag_t*)nullptr, f.fR, nullptr, 0., nullptr,
+                      (const double*)c->redbuf.p, (int)c->ownLo, (int)c->ownHi, c->Ap.p, f.stBF};
+            if (split) {
+                f.L.stList = c->distList[2].p; f.L.nStList = c->nDistList[2];
+                f.L.spmvSt(3, c->ts.p, c->pvec.p, nullptr, nullptr, nullptr, nullptr, &fr);
+                order(c, 4, true);
+                fr.rPart = f.fR + f.tB;
+                f.L.stList = c->distList[3].p; f.L.nStList = c->nDistList[3]; f.L.stOwnedOnly = true;
+                f.L.spmvSt(3, c->ts.p, c->pvec.p, nullptr, nullptr, nullptr, nullptr, &fr);
+                f.L.stOwnedOnly = false;
+                continue;
             }
-            const auto ar0 = std::chrono::high_resolution_clock::now();
-            if (useRccl || useTcp) syncAll();                    // (so that the clock below sees the collective alone)
-            const auto ar1 = std::chrono::high_resolution_clock::now();
-            allreduce(2);
-            if (useRccl || useTcp) {
-                syncAll();
-                c0->distStats[5] += std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - ar1).count();
-                c0->distStats[6] += 1.;
+            // (the chunks that hold work: halo rows without entries — most of a halo block — are in no list; r and A p of those rows stay as the solve's start left them: zero)
+            if (c->distListsOk) { f.L.stList = c->distList[4].p; f.L.nStList = c->nDistList[4]; }
+            f.L.spmvSt(3, c->ts.p, c->pvec.p, nullptr, nullptr, nullptr, nullptr, &fr);
+            f.L.stList = nullptr; f.L.nStList = 0;
+        }
+        // the halo rows' share of A p goes to its owners (the packing and transport of exchangeAddY; the owners correct r from the
+        // receive buffers instead of adding into A p)
+        contributionsBack(&ps_context::Ap, split, false);
+        for (size_t q = 0; q < R.size(); ++q) {
+            ps_context* c = R[q];
+            RankSolve& f = rs[q];
+            if (split) order(c, 5, false);
+            fixup(c, f.sc, jac, f.fX, f.gFix);
+            hipLaunchKernelGGL(k_sum_rr, dim3(1), dim3(1024), 0, c->stream, (const CGScalars*)f.sc, (const double*)f.fR, f.stBF, (const double*)f.fX, f.gFix, c->nFix > 0 ? 1 : ps_context::NLINK, c->redbuf.p);   // (the merged fix-up writes ONE set of partials)
+        }
+        allreduce(2);
+        for (size_t q = 0; q < R.size(); ++q) {   // (4) x, p
+            ps_context* c = R[q];
+            RankSolve& f = rs[q];
+            const uint8_t* ucode = c->uCoded ? c->uCode.p + f.lo : nullptr;
+            hipLaunchKernelGGL(k_cg_update_xp_u, dim3(f.vb), dim3(BS), 0, c->stream, f.sc, (const double*)c->redbuf.p, (const double*)nullptr, 0, jac ? 1 : 0, it,
+                               (const double*)c->r.p + f.lo, f.dv, c->x.p + f.lo, c->pvec.p + f.lo, f.n, c->dotPartials3.p, ucode, (const double*)c->uDict.p,
+                               (const double*)c->uInv.p + f.lo, f.fU);
+        }
+    }
+    // One iteration of the five-kernel step: A p (S, tiles, St), r; with the Chebyshev polynomial z = M^-1 r; then x, p
+    void fiveKernelStep(int it) {
+        exchangeX(&ps_context::pvec);
+        for (size_t q = 0; q < R.size(); ++q) {
+            ps_context* c = R[q];
+            RankSolve& l = rs[q];
+            l.L.spmvS(0, c->pvec.p, c->ts.p);
+            l.L.tiles(0, c->ts.p);
+            l.L.spmvSt(0, c->ts.p, c->pvec.p, nullptr, c->Ap.p, c->dotPartials.p);
+            if (l.stBlocks <= 8192) {
+                hipLaunchKernelGGL(k_sumq, dim3(1), dim3(BS), 0, c->stream, (const CGScalars*)l.sc, c->dotPartials.p, l.stBlocks, 0, 1, c->redbuf.p);
+            } else {
+                hipLaunchKernelGGL(k_reduce_partials, dim3(RED_BLOCKS), dim3(BS), 0, c->stream, l.sc, c->dotPartials.p, l.stBlocks, c->dotPartials2.p);
+                hipLaunchKernelGGL(k_sumq, dim3(1), dim3(BS), 0, c->stream, (const CGScalars*)l.sc, c->dotPartials2.p, RED_BLOCKS, 0, 1, c->redbuf.p);
             }
-            (void)ar0;
+            // ||x||^2 of the x updated last iteration rides along (stop test of the previous iteration, see k_cg_update_r)
+            hipLaunchKernelGGL(k_sumq, dim3(1), dim3(BS), 0, c->stream, (const CGScalars*)l.sc, c->dotPartials3.p, l.vb, 0, 1, c->redbuf.p + 1);
+        }
+        exchangeAddY(&ps_context::Ap);
+        allreduce(2);
+        for (size_t q = 0; q < R.size(); ++q) {
+            ps_context* c = R[q];
+            const RankSolve& l = rs[q];
+            hipLaunchKernelGGL(k_cg_update_r, dim3(l.vb), dim3(BS), 0, c->stream, l.sc, (const double*)c->redbuf.p, (const double*)nullptr, 0,
+                               (const double*)nullptr, 0, it, c->Ap.p + l.lo, l.dv, c->r.p + l.lo, l.n, c->dotPartialsR.p);
+            hipLaunchKernelGGL(k_sumq, dim3(1), dim3(BS), 0, c->stream, (const CGScalars*)l.sc, c->dotPartialsR.p, l.vb, l.vb, 2, c->redbuf.p);
+        }
+        if (cheb) {   // z = M^-1 r (k-1 distributed applies), then {r.r, r.z} and x, p with the vector z
+            const Vec zf = chebyshevDist(&ps_context::r);
             for (size_t q = 0; q < R.size(); ++q)
-                hipLaunchKernelGGL(k_cg_check, dim3(1), dim3(BS), 0, R[q]->stream, loc[q].sc, (const double*)R[q]->redbuf.p, (const double*)nullptr, 0, it - 1);
-            double stopSum = 0.;
-            HIP_CHECK(hipMemcpyAsync(&h, loc[0].sc, sizeof(h), hipMemcpyDeviceToHost, c0->stream));
-            HIP_CHECK(hipMemcpyAsync(&stopSum, c0->redbuf.p + 1, 8, hipMemcpyDeviceToHost, c0->stream));
+                hipLaunchKernelGGL(k_sumq, dim3(1), dim3(BS), 0, R[q]->stream, (const CGScalars*)rs[q].sc, (const double*)R[q]->chebPartials.p, rs[q].vb, 0, 1, R[q]->redbuf.p + 1);
+            allreduce(2);
+            for (size_t q = 0; q < R.size(); ++q) {
+                ps_context* c = R[q];
+                const RankSolve& l = rs[q];
+                hipLaunchKernelGGL(k_cg_update_xp_z<double>, dim3(l.vb), dim3(BS), 0, c->stream, l.sc, (const double*)c->redbuf.p, 1, (const double*)c->redbuf.p + 1, 1, it,
+                                   (const double*)(c->*zf).p + l.lo, c->x.p + l.lo, c->pvec.p + l.lo, l.n, c->dotPartials3.p);
+            }
+            return;
+        }
+        allreduce(2);
+        for (size_t q = 0; q < R.size(); ++q) {
+            ps_context* c = R[q];
+            const RankSolve& l = rs[q];
+            hipLaunchKernelGGL(k_cg_update_xp, dim3(l.vb), dim3(BS), 0, c->stream, l.sc, (const double*)c->redbuf.p, (const double*)nullptr, 0,
+                               jac ? 1 : 0, it, c->r.p + l.lo, l.dv, c->x.p + l.lo, c->pvec.p + l.lo, l.n, c->dotPartials3.p);
+        }
+    }
+    // The stop test of the batch's last iteration (it - 1), its scalars into h; the ranks' interrupt requests ride along in the same
+    // all-reduce, so that every rank leaves the loop at the same batch (a rank stopping alone would strand its neighbours in a receive).
+    // True: some rank asked to stop.
+    bool batchEnd(int it, CGScalars& h) {
+        ps_context* c0 = R[0];
+        double wantStop = 0.;
+        for (ps_context* c : R) if (c->interruptCb && c->interruptCb(c->interruptUser)) wantStop = 1.;
+        for (size_t q = 0; q < R.size(); ++q) {
+            hipLaunchKernelGGL(k_sumq, dim3(1), dim3(BS), 0, R[q]->stream, (const CGScalars*)rs[q].sc, R[q]->dotPartials3.p, rs[q].vb, 0, 1, R[q]->redbuf.p);
+            HIP_CHECK(hipMemcpyAsync(R[q]->redbuf.p + 1, &wantStop, 8, hipMemcpyHostToDevice, R[q]->stream));
+        }
+        if (useRccl || useTcp) syncAll();                    // (so that the clock below sees the collective alone)
+        const auto ar1 = std::chrono::high_resolution_clock::now();
+        allreduce(2);
+        if (useRccl || useTcp) {
             syncAll();
-            if (overlap && timed) {   // the transport of the batch's last x exchange, as the comm stream saw it
-                float ms = 0.f;
-                if (hipEventElapsedTime(&ms, c0->distEv[2], c0->distEv[3]) == hipSuccess) { c0->distStats[3] += (double)ms; c0->distStats[4] += 1.; }
-            }
-            if (h.done) finished = true;
-            else if (stopSum > 0. || (wantStop > 0. && !useRccl && !useTcp)) { interrupted = true; break; }
+            c0->distStats[5] += std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - ar1).count();
+            c0->distStats[6] += 1.;
         }
-        if (interrupted) {
-            for (ps_context* c : R) { c->solveIterations = it; c->solveError = std::sqrt(h.rre); c->interrupted = true; }
-            return PS_INCOMPLETE;
+        for (size_t q = 0; q < R.size(); ++q)
+            hipLaunchKernelGGL(k_cg_check, dim3(1), dim3(BS), 0, R[q]->stream, rs[q].sc, (const double*)R[q]->redbuf.p, (const double*)nullptr, 0, it - 1);
+        double stopSum = 0.;
+        HIP_CHECK(hipMemcpyAsync(&h, rs[0].sc, sizeof(h), hipMemcpyDeviceToHost, c0->stream));
+        HIP_CHECK(hipMemcpyAsync(&stopSum, c0->redbuf.p + 1, 8, hipMemcpyDeviceToHost, c0->stream));
+        syncAll();
+        if (overlap && timed()) {   // the transport of the batch's last x exchange, as the comm stream saw it
+            float ms = 0.f;
+            if (hipEventElapsedTime(&ms, c0->distEv[2], c0->distEv[3]) == hipSuccess) { c0->distStats[3] += (double)ms; c0->distStats[4] += 1.; }
         }
-        int iters = h.done ? h.iter : maxit;
-        double err = std::sqrt(h.rre);
-        if (iters == maxit) {
-            // bicgstab_external_matrix_A (pcg.h:134-200), restarted from zero (Solver.cpp:784-799): the host-driven loop
-            // of ps_context::solve() with distributed applies and dots.  Rare path.
-            for (ps_context* c : R) {
-                c->usedBiCGStab = 1;
-                const size_t nl = (size_t)std::max<int64_t>(c->nSystem, 1);
-                c->tmp1.alloc(nl); c->tmp2.alloc(nl); c->tmp3.alloc(nl); c->tmp4.alloc(nl); c->tmp5.alloc(nl);
-            }
-            using Vec = DevBuf<double> ps_context::*;
-            const Vec X = &ps_context::x, Rv = &ps_context::r, Pv = &ps_context::pvec, B = &ps_context::b, H = &ps_context::Ap,
-                      Rhat = &ps_context::tmp1, V = &ps_context::tmp2, S = &ps_context::tmp3, T = &ps_context::tmp4, E = &ps_context::tmp5;
-            auto apply = [&](Vec in, Vec out) {
-                exchangeX(in);
+        return !h.done && (stopSum > 0. || (wantStop > 0. && !useRccl && !useTcp));
+    }
+    // the BiCGStab fallback (ps_solve.hip: bicgstab) with distributed applies and dots, on the owned range of every rank
+    int bicgstabDist(int maxit, double tol, double& err) {
+        for (ps_context* c : R) {
+            c->usedBiCGStab = 1;
+            const size_t nl = (size_t)std::max<int64_t>(c->nSystem, 1);
+            c->tmp1.alloc(nl); c->tmp2.alloc(nl); c->tmp3.alloc(nl); c->tmp4.alloc(nl); c->tmp5.alloc(nl);
+        }
+        using P = ps_context;
+        return bicgstab(BiCGVecs<Vec>{&P::x, &P::r, &P::pvec, &P::b, &P::Ap, &P::tmp1, &P::tmp2, &P::tmp3, &P::tmp4, &P::tmp5}, maxit, tol, err,
+            [&](Vec in, Vec out) { applyDist(in, out); },
+            [&](Vec a, Vec bvec) {
                 for (size_t q = 0; q < R.size(); ++q) {
                     ps_context* c = R[q];
-                    Launch L = mk(c, nullptr);
-                    L.spmvS(0, (c->*in).p, c->ts.p);
-                    L.tiles(0, c->ts.p);
-                    L.spmvSt(0, c->ts.p, (c->*in).p, nullptr, (c->*out).p, c->dotPartials.p);
-                }
-                exchangeAddY(out);
-            };
-            auto dot = [&](Vec a, Vec bvec) {
-                for (size_t q = 0; q < R.size(); ++q) {
-                    ps_context* c = R[q];
-                    Loc& l = loc[q];
+                    const RankSolve& l = rs[q];
                     hipLaunchKernelGGL(k_dot, dim3(l.vb), dim3(BS), 0, c->stream, (c->*a).p + l.lo, (c->*bvec).p + l.lo, l.n, c->dotPartials.p);
                     hipLaunchKernelGGL(k_sum1, dim3(1), dim3(BS), 0, c->stream, c->dotPartials.p, l.vb, c->redbuf.p);
                 }
                 allreduce(1);
                 double out = 0.;
-                HIP_CHECK(hipMemcpyAsync(&out, c0->redbuf.p, sizeof(double), hipMemcpyDeviceToHost, c0->stream));
+                HIP_CHECK(hipMemcpyAsync(&out, R[0]->redbuf.p, sizeof(double), hipMemcpyDeviceToHost, R[0]->stream));
                 syncAll();
                 return out;
-            };
-            auto lin = [&](Vec out, double ca, Vec a, double cb, Vec bvec, double cc, Vec c3) {   // out = ca a + cb b + cc c on the owned range
+            },
+            [&](Vec out, double ca, Vec a, double cb, Vec bvec, double cc, Vec c3) {   // out = ca a + cb b + cc c on the owned range
                 for (size_t q = 0; q < R.size(); ++q) {
                     ps_context* c = R[q];
-                    Loc& l = loc[q];
+                    const RankSolve& l = rs[q];
                     if (l.n <= 0) continue;
                     hipLaunchKernelGGL(k_lin, dim3(l.vb), dim3(BS), 0, c->stream, (c->*out).p + l.lo, ca, (const double*)(c->*a).p + l.lo, cb,
                                        bvec ? (const double*)(c->*bvec).p + l.lo : (const double*)nullptr, cc,
                                        c3 ? (const double*)(c->*c3).p + l.lo : (const double*)nullptr, l.n);
                 }
-            };
-            auto zero = [&](Vec v) { for (ps_context* c : R) HIP_CHECK(hipMemsetAsync((c->*v).p, 0, (size_t)std::max<int64_t>(c->nSystem, 1) * 8, c->stream)); };
-            zero(X);
-            lin(Rv, 1., B, 0., nullptr, 0., nullptr);            // r = b - A*0
-            lin(Rhat, 1., Rv, 0., nullptr, 0., nullptr);
-            zero(Pv); zero(V);
-            double rhoCurr = 1., rhoOld = 1., alpha = 1., beta = 0., omega = 1., rre = 0.;
-            iters = maxit;
-            for (int i = 0; i < maxit; ++i) {
-                rhoOld = rhoCurr;
-                rhoCurr = dot(Rhat, Rv);
-                beta = (rhoCurr / rhoOld) * (alpha / omega);
-                lin(Pv, 1., Rv, beta, Pv, -beta * omega, V);      // p = r + beta (p - omega v)
-                apply(Pv, V);
-                alpha = rhoCurr / dot(Rhat, V);
-                lin(H, 1., X, alpha, Pv, 0., nullptr);             // h = x + alpha p
-                lin(S, 1., Rv, -alpha, V, 0., nullptr);            // s = r - alpha v
-                apply(S, T);
-                omega = dot(T, S) / dot(T, T);
-                lin(X, 1., H, omega, S, 0., nullptr);              // x = h + omega s
-                const double xmag = std::sqrt(dot(X, X));
-                apply(X, E);
-                lin(E, 1., B, -1., E, 0., nullptr);                // err = b - A x
-                const double rsnew = dot(E, E);
-                rre = rsnew;
-                if (std::sqrt(rsnew) / xmag < rre) rre = std::sqrt(rsnew) / xmag;
-                if (rre < tol) { iters = i; break; }
-                lin(Rv, 1., S, -omega, T, 0., nullptr);            // r = s - omega t
+            },
+            [&](Vec v) { for (ps_context* c : R) HIP_CHECK(hipMemsetAsync((c->*v).p, 0, (size_t)std::max<int64_t>(c->nSystem, 1) * 8, c->stream)); });
+    }
+
+    int solve() {
+        ps_context* c0 = R[0];
+        const int maxit = c0->P.maxSolverIterations;
+        const double tol = c0->P.tolerance;
+        jac = c0->P.preconditioner == PS_PRE_DIAGONAL; cheb = c0->P.preconditioner == PS_PRE_CHEBYSHEV;
+        if (c0->P.solverType != PS_PCG_MATRIX_VECTOR_PRODUCTS) { c0->err = "Unsupported Solver."; return PS_UNSUPPORTED_SOLVER; }
+        solveStart(tol, maxit);
+        chooseStepForm();
+        if (fused) fusedStart();
+        CGScalars h{};
+        int it = 0;
+        for (ps_context* c : R) c->interrupted = false;
+        while (it < maxit && !h.done) {
+            const int upto = std::min(maxit, it + CG_BATCH);
+            for (; it < upto; ++it) {
+                if (fused) fusedStep(it, overlap, it + 1 == upto);
+                else fiveKernelStep(it);
             }
-            err = rre;
+            if (batchEnd(it, h)) {
+                for (ps_context* c : R) { c->solveIterations = it; c->solveError = std::sqrt(h.rre); c->interrupted = true; }
+                return PS_INCOMPLETE;
+            }
         }
+        double err = std::sqrt(h.rre);
+        int iters = h.done ? h.iter : maxit;
+        if (iters == maxit) iters = bicgstabDist(maxit, tol, err);
         for (ps_context* c : R) { c->solveIterations = iters; c->solveError = err; }
         return iters == maxit ? PS_NOCONVERGE : PS_SUCCESS;
     }

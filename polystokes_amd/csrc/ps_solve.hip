@@ -399,6 +399,72 @@ constexpr int64_t FUSED_STEP_MIN_ROWS = 1200000;   // see solve() (r05: 2 M -> 1
                                                     // two rounds on one box; the 64^3 cavity, 0.8 M rows, stays faster in five: 57.3 against 58.8 us per iteration)
 constexpr int64_t NT_LEVEL1_MIN_ROWS = 4000000, NT_LEVEL2_MIN_ROWS = 10000000;   // see ps_context::ntLevel
 int dotBlocks(int64_t n) { return (int)std::min<int64_t>(VGRID, std::max<int64_t>(1, (n + BS - 1) / BS)); }
+constexpr int CG_BATCH = 25;   // PCG iterations between two stop tests on the host (ps_context::solve, Dist::solve)
+
+double chebRatio() { static const double r = PS_ENV("PS_CHEB_RATIO") ? atof(PS_ENV("PS_CHEB_RATIO")) : PS_CHEB_INTERVAL_RATIO; return r; }   // lmax / lmin (PS_CHEB_RATIO: experiments only — the oracle uses the constant)
+// The Chebyshev iteration on [lmax / chebRatio(), lmax] (ps_context::chebyshevApply, Dist::chebyshevDist): z_1 = D^-1 r / theta, then
+// next() gives c1, c2 of the terms 2..k in turn
+struct ChebRecurrence {
+    double theta, delta, sigma, rho;
+    explicit ChebRecurrence(double lmax) {
+        const double lmin = lmax / chebRatio();
+        theta = 0.5 * (lmax + lmin); delta = 0.5 * (lmax - lmin); sigma = theta / delta; rho = 1. / sigma;
+    }
+    void next(double& c1, double& c2) {
+        const double rhoN = 1. / (2. * sigma - rho);
+        c1 = rhoN * rho; c2 = 2. * rhoN / delta;
+        rho = rhoN;
+    }
+};
+
+// lambda_max(D^-1 A) for the Chebyshev polynomial: 10 power iterations from the all-ones vector (`step` runs one), the Rayleigh
+// quotient of the last iterate from the sums {v.v, v.w} (`sums` fills them on the host), then max(8.4, 1.25 * estimate) — same
+// procedure as the oracle (ps_oracle_solve.cpp:estimateLambdaMax).
+template <class Step, class Sums> double powerLambdaMax(Step step, Sums sums) {
+    for (int it = 0; it < 10; ++it) step();
+    double h[2] = {0., 0.};
+    sums(h);
+    const double lam = (h[0] > 0. && std::isfinite(h[1] / h[0])) ? h[1] / h[0] : 0.;   // A v = 0 on the way: the floor below
+    return std::max(8.4, 1.25 * lam);
+}
+
+// bicgstab_external_matrix_A (pcg.h:134-200), restarted from zero (Solver.cpp:784-799): the host-driven fallback of both solves (rare
+// path).  V names a vector: a device pointer, or a member of every rank's context (Dist::solve).  The caller supplies apply(in, out):
+// out = A in; dot(a, b) on the host; lin(out, ca, a, cb, b, cc, c): out = ca a + cb b + cc c (b, c may be null); zero(v).
+// Returns the iterations (maxit: not converged) and leaves the last relative error in `err`.
+template <class V> struct BiCGVecs { V x, r, p, b, h, rhat, v, s, t, e; };
+template <class V, class Apply, class Dot, class Lin, class Zero>
+int bicgstab(const BiCGVecs<V>& w, int maxit, double tol, double& err, Apply apply, Dot dot, Lin lin, Zero zero) {
+    zero(w.x);
+    lin(w.r, 1., w.b, 0., nullptr, 0., nullptr);           // r = b - A*0
+    lin(w.rhat, 1., w.r, 0., nullptr, 0., nullptr);
+    zero(w.p); zero(w.v);
+    double rhoCurr = 1., rhoOld = 1., alpha = 1., beta = 0., omega = 1., rre = 0.;
+    int iters = maxit;
+    for (int i = 0; i < maxit; ++i) {
+        rhoOld = rhoCurr;
+        rhoCurr = dot(w.rhat, w.r);
+        beta = (rhoCurr / rhoOld) * (alpha / omega);
+        lin(w.p, 1., w.r, beta, w.p, -beta * omega, w.v);  // p = r + beta (p - omega v)
+        apply(w.p, w.v);
+        alpha = rhoCurr / dot(w.rhat, w.v);
+        lin(w.h, 1., w.x, alpha, w.p, 0., nullptr);        // h = x + alpha p
+        lin(w.s, 1., w.r, -alpha, w.v, 0., nullptr);       // s = r - alpha v
+        apply(w.s, w.t);
+        omega = dot(w.t, w.s) / dot(w.t, w.t);
+        lin(w.x, 1., w.h, omega, w.s, 0., nullptr);        // x = h + omega s
+        const double xmag = std::sqrt(dot(w.x, w.x));
+        apply(w.x, w.e);
+        lin(w.e, 1., w.b, -1., w.e, 0., nullptr);          // err = b - A x
+        const double rsnew = dot(w.e, w.e);
+        rre = rsnew;
+        if (std::sqrt(rsnew) / xmag < rre) rre = std::sqrt(rsnew) / xmag;
+        if (rre < tol) { iters = i; break; }
+        lin(w.r, 1., w.s, -omega, w.t, 0., nullptr);       // r = s - omega t
+    }
+    err = rre;
+    return iters;
+}
 }  // namespace
 
 // y = A x on device vectors (ApplyPressureStressMatrix::apply).  dotPartialsOut receives the per-block
@@ -453,10 +519,6 @@ void ps_context::constructPreconditioner() {
     if (P.preconditioner == PS_PRE_CHEBYSHEV && !slabEnabled) estimateLambdaMax();   // with a slab: Dist::finishSetup, across the ranks
 }
 
-// lambda_max(D^-1 A) for the Chebyshev polynomial: 10 power iterations from the all-ones vector, Rayleigh quotient of the
-// last iterate, then max(8.4, 1.25 * estimate) — same procedure as the oracle (ps_oracle_solve.cpp:estimateLambdaMax).
-// The stencil part of A is a sum of rank-one face terms with <= 8 entries, so its lambda_max(D^-1 A) <= 8 by Cauchy-Schwarz;
-// the measurement covers the tile part.  10 applies at setup (~1 % of a 256^3 step).
 // Cache policy by system size (PS_NT_LEVEL = 0 / 1 / 2 forces): 2 = non-temporal streams in the SpMV kernels and the vector
 // kernels (a 45 M-row iteration moves 6.7 GB: nothing survives to the next kernel, and keeping the once-per-launch streams out of
 // the way of the gathers is worth 7 % of a step), 1 = in the SpMV kernels only, 0 = default policy everywhere (the working set of
@@ -470,13 +532,13 @@ int ps_context::ntLevel() const {
     return rows < NT_LEVEL1_MIN_ROWS ? 0 : (rows < NT_LEVEL2_MIN_ROWS ? 1 : 2);
 }
 
-static double chebRatio() { static const double r = PS_ENV("PS_CHEB_RATIO") ? atof(PS_ENV("PS_CHEB_RATIO")) : PS_CHEB_INTERVAL_RATIO; return r; }   // lmax / lmin (PS_CHEB_RATIO: experiments only — the oracle uses the constant)
-double ps_context::chebTheta() const { return 0.5 * (chebLmax + chebLmax / chebRatio()); }   // centre of the interval [lmax/250, lmax]
+double ps_context::chebTheta() const { return ChebRecurrence(chebLmax).theta; }   // centre of the interval [lmax/250, lmax]
 
+// lambda_max(D^-1 A) for the Chebyshev polynomial (powerLambdaMax).  The stencil part of A is a sum of rank-one face terms with <= 8
+// entries, so its lambda_max(D^-1 A) <= 8 by Cauchy-Schwarz; the measurement covers the tile part.  10 applies at setup (~1 % of a 256^3 step).
 void ps_context::estimateLambdaMax() {
-    // 10 steps of the power iteration on D^-1 A from the ones vector, Rayleigh quotient of the last step (oracle:
-    // estimateLambdaMax).  The iterate is not normalised between steps (the quotient does not depend on its length and the
-    // spectrum lies in (0, ~8]: ten steps grow it by < 1e10), so nothing comes back to the host until the end.
+    // The iterate is not normalised between steps (the quotient does not depend on its length and the spectrum lies in (0, ~8]: ten
+    // steps grow it by < 1e10), so nothing comes back to the host until the end.
     const int64_t n = nSystem;
     chebLmax = 8.4;
     if (n == 0) return;
@@ -485,18 +547,16 @@ void ps_context::estimateLambdaMax() {
     double* v = tmp1.p; double* w = tmp2.p; double* Av = tmp3.p;
     chebPartials.alloc((size_t)std::max<int64_t>(3 * VGRID, gridFor(n, BS)) + 16);
     hipLaunchKernelGGL(k_fill_f64, dim3(vb), dim3(BS), 0, stream, v, 1., n);
-    for (int it = 0; it < 10; ++it) {
+    chebLmax = powerLambdaMax([&] {
         applyOperator(v, Av, dotPartials.p);
         hipLaunchKernelGGL(k_power_step, dim3(vb), dim3(BS), 0, stream, (const double*)v, (const double*)Av, (const double*)dinv.p, w, n, chebPartials.p);
         std::swap(v, w);
-    }
-    hipLaunchKernelGGL(k_sum1, dim3(1), dim3(BS), 0, stream, chebPartials.p, vb, chebPartials.p + 2 * vb);
-    hipLaunchKernelGGL(k_sum1, dim3(1), dim3(BS), 0, stream, chebPartials.p + vb, vb, chebPartials.p + 2 * vb + 1);
-    double h[2];
-    HIP_CHECK(hipMemcpyAsync(h, chebPartials.p + 2 * vb, sizeof(h), hipMemcpyDeviceToHost, stream));
-    HIP_CHECK(hipStreamSynchronize(stream));
-    const double lam = (h[0] > 0. && std::isfinite(h[1] / h[0])) ? h[1] / h[0] : 0.;   // A v = 0 on the way: the floor below
-    chebLmax = std::max(8.4, 1.25 * lam);
+    }, [&](double* h) {
+        hipLaunchKernelGGL(k_sum1, dim3(1), dim3(BS), 0, stream, chebPartials.p, vb, chebPartials.p + 2 * vb);
+        hipLaunchKernelGGL(k_sum1, dim3(1), dim3(BS), 0, stream, chebPartials.p + vb, vb, chebPartials.p + 2 * vb + 1);
+        HIP_CHECK(hipMemcpyAsync(h, chebPartials.p + 2 * vb, 2 * sizeof(double), hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipStreamSynchronize(stream));
+    });
 }
 
 // z = q(D^-1 A) D^-1 r: k terms of the Chebyshev iteration on [lmax/250, lmax] (k-1 operator applies), see include/polystokes.h.
@@ -510,52 +570,42 @@ void ps_context::estimateLambdaMax() {
 int ps_context::chebyshevApply(const double* rvec, double* zA, double* zB, double* rzPartial, const ps::CGScalars* sc, bool firstDone, double** zOut) {
     const int64_t n = nSystem;
     const int k = P.preconditionerDegree > 0 ? P.preconditionerDegree : 4;
-    const double lmax = chebLmax, lmin = lmax / chebRatio();
-    const double theta = 0.5 * (lmax + lmin), delta = 0.5 * (lmax - lmin), sigma = theta / delta;
-    double rho = 1. / sigma;
+    ChebRecurrence cr(chebLmax);
     const int vb = dotBlocks(n);
     const int* done = sc ? &sc->done : nullptr;
     Launch L = mk(this, done);
-    if (chebInner32) {
-        // PS_PRE_CHEBYSHEV_F32: the same recurrence with z_j (zA / zB) and the face-row vector of the inner applies (the first half of ts) STORED as
-        // fp32; r, the diagonal, every product and sum fp64.  The two-units-per-wave kernels only (Launch::cheb32Ok decided chebInner32).
-        float* cur = (float*)zA; float* other = (float*)zB; float* tsF = (float*)ts.p;
-        if (!firstDone) hipLaunchKernelGGL(k_cheb_first<float>, dim3(vb), dim3(BS), 0, stream, sc, rvec, (const diag_t*)dinvF.p, 1. / theta, cur, n, rzPartial);
-        int count = firstDone ? 0 : vb;
-        for (int j = 1; j < k; ++j) {
-            const double rhoN = 1. / (2. * sigma - rho);
-            const double c1 = rhoN * rho, c2 = 2. * rhoN / delta;
-            const ChebArgs ca{rvec, dinvF.p, j == 1 ? (const double*)nullptr : (const double*)other, c1, c2};   // (zprev points at floats: k_spmv_St_ell2c<.., float>)
-            L.spmvS32(cur, tsF);
-            L.tiles32(tsF);
-            count = L.spmvSt2c32(tsF, cur, other, rzPartial, ca);
-            std::swap(cur, other);
-            rho = rhoN;
-        }
-        if (zOut) *zOut = (double*)cur;
-        return count;
+    // PS_PRE_CHEBYSHEV_F32 (chebInner32): the same recurrence with z_j (zA / zB) and the face-row vector of the inner applies (the first half
+    // of ts) STORED as fp32; r, the diagonal, every product and sum fp64.  The two-units-per-wave kernels only (Launch::cheb32Ok decided chebInner32).
+    if (!firstDone) {
+        if (chebInner32) hipLaunchKernelGGL(k_cheb_first<float>, dim3(vb), dim3(BS), 0, stream, sc, rvec, (const diag_t*)dinvF.p, 1. / cr.theta, (float*)zA, n, rzPartial);
+        else hipLaunchKernelGGL(k_cheb_first<double>, dim3(vb), dim3(BS), 0, stream, sc, rvec, (const diag_t*)dinvF.p, 1. / cr.theta, zA, n, rzPartial);
     }
-    if (!firstDone) hipLaunchKernelGGL(k_cheb_first<double>, dim3(vb), dim3(BS), 0, stream, sc, rvec, (const diag_t*)dinvF.p, 1. / theta, zA, n, rzPartial);
     int count = firstDone ? 0 : vb;
     double* cur = zA; double* other = zB;    // z_j, and the buffer of z_{j-1} that receives z_{j+1}
     for (int j = 1; j < k; ++j) {
-        const double rhoN = 1. / (2. * sigma - rho);
-        const double c1 = rhoN * rho, c2 = 2. * rhoN / delta;
+        double c1, c2;
+        cr.next(c1, c2);
         const double* zprev = j == 1 ? nullptr : other;            // z_0 = 0
-        L.spmvS(0, cur, ts.p);
-        L.tiles(0, ts.p);
-        if (L.stOnPipe()) {
-            const ChebArgs ca{rvec, dinvF.p, zprev, c1, c2};
-            L.spmvSt(2, ts.p, cur, nullptr, other, rzPartial, &ca);
-            count = L.stBlocks(2);   // the partials of the MODE 2 launch
+        const ChebArgs ca{rvec, dinvF.p, zprev, c1, c2};             // (fp32: zprev points at floats, k_spmv_St_ell2c<.., float>)
+        if (chebInner32) {
+            float* tsF = (float*)ts.p;
+            L.spmvS32((const float*)cur, tsF);
+            L.tiles32(tsF);
+            count = L.spmvSt2c32(tsF, (const float*)cur, (float*)other, rzPartial, ca);
         } else {
-            tmp5.alloc((size_t)n);
-            L.spmvSt(0, ts.p, cur, nullptr, tmp5.p, dotPartials2.p);
-            hipLaunchKernelGGL(k_cheb_step, dim3(vb), dim3(BS), 0, stream, sc, rvec, (const diag_t*)dinvF.p, (const double*)tmp5.p, c1, c2, (const double*)cur, zprev, other, n, rzPartial);
-            count = vb;
+            L.spmvS(0, cur, ts.p);
+            L.tiles(0, ts.p);
+            if (L.stOnPipe()) {
+                L.spmvSt(2, ts.p, cur, nullptr, other, rzPartial, &ca);
+                count = L.stBlocks(2);   // the partials of the MODE 2 launch
+            } else {
+                tmp5.alloc((size_t)n);
+                L.spmvSt(0, ts.p, cur, nullptr, tmp5.p, dotPartials2.p);
+                hipLaunchKernelGGL(k_cheb_step, dim3(vb), dim3(BS), 0, stream, sc, rvec, (const diag_t*)dinvF.p, (const double*)tmp5.p, c1, c2, (const double*)cur, zprev, other, n, rzPartial);
+                count = vb;
+            }
         }
         std::swap(cur, other);
-        rho = rhoN;
     }
     if (zOut) *zOut = cur;
     return count;
@@ -666,11 +716,10 @@ int ps_context::solve() {
     // the first direction's share of p.Ap on the diagonal
     if (fused) hipLaunchKernelGGL(k_uinv_pp, dim3(vb), dim3(BS), 0, stream, (const double*)pvec.p, ucode, (const double*)uDict.p, (const double*)uInv.p, n, fU);
     CGScalars h{};
-    const int batch = 25;
     int it = 0;
     bool finished = false;
     while (it < maxit && !finished) {
-        const int upto = std::min(maxit, it + batch);
+        const int upto = std::min(maxit, it + CG_BATCH);
         for (; it < upto; ++it) {
             L.spmvS(0, pvec.p, ts.p);
             L.tiles(0, ts.p);
@@ -730,52 +779,22 @@ int ps_context::solve() {
     solveError = std::sqrt(h.rre);
 
     if (solveIterations == maxit) {
-        // bicgstab_external_matrix_A (pcg.h:134-200), restarted from zero (Solver.cpp:784-799).  Rare path: host-driven.
-        usedBiCGStab = 1;
+        usedBiCGStab = 1;          // the BiCGStab fallback
         tmp1.alloc((size_t)n); tmp2.alloc((size_t)n); tmp3.alloc((size_t)n); tmp4.alloc((size_t)n); tmp5.alloc((size_t)n);
-        double* rhat = tmp1.p; double* v = tmp2.p; double* s = tmp3.p; double* t = tmp4.p; double* e = tmp5.p;
-        double* hvec = Ap.p;
-        auto dotH = [&](const double* a, const double* bb) {
-            hipLaunchKernelGGL(k_dot, dim3(vb), dim3(BS), 0, stream, a, bb, n, dotPartials.p);
-            hipLaunchKernelGGL(k_sum1, dim3(1), dim3(BS), 0, stream, dotPartials.p, vb, dotPartials.p + 3 * VGRID);
-            double out;
-            HIP_CHECK(hipMemcpyAsync(&out, dotPartials.p + 3 * VGRID, sizeof(double), hipMemcpyDeviceToHost, stream));
-            HIP_CHECK(hipStreamSynchronize(stream));
-            return out;
-        };
-        auto lin = [&](double* out, double ca, const double* a, double cb, const double* bb, double cc, const double* c3) {
-            hipLaunchKernelGGL(k_lin, dim3(vb), dim3(BS), 0, stream, out, ca, a, cb, bb, cc, c3, n);
-        };
-        HIP_CHECK(hipMemsetAsync(x.p, 0, (size_t)n * sizeof(double), stream));
-        lin(r.p, 1., b.p, 0., nullptr, 0., nullptr);           // r = b - A*0
-        lin(rhat, 1., r.p, 0., nullptr, 0., nullptr);
-        HIP_CHECK(hipMemsetAsync(pvec.p, 0, (size_t)n * sizeof(double), stream));
-        HIP_CHECK(hipMemsetAsync(v, 0, (size_t)n * sizeof(double), stream));
-        double rhoCurr = 1., rhoOld = 1., alpha = 1., beta = 0., omega = 1., rre = 0.;
-        int i = 0;
-        solveIterations = maxit;
-        for (; i < maxit; ++i) {
-            rhoOld = rhoCurr;
-            rhoCurr = dotH(rhat, r.p);
-            beta = (rhoCurr / rhoOld) * (alpha / omega);
-            lin(pvec.p, 1., r.p, beta, pvec.p, -beta * omega, v);      // p = r + beta (p - omega v)
-            applyOperator(pvec.p, v, dotPartials.p);
-            alpha = rhoCurr / dotH(rhat, v);
-            lin(hvec, 1., x.p, alpha, pvec.p, 0., nullptr);            // h = x + alpha p
-            lin(s, 1., r.p, -alpha, v, 0., nullptr);                   // s = r - alpha v
-            applyOperator(s, t, dotPartials.p);
-            omega = dotH(t, s) / dotH(t, t);
-            lin(x.p, 1., hvec, omega, s, 0., nullptr);                 // x = h + omega s
-            const double xmag = std::sqrt(dotH(x.p, x.p));
-            applyOperator(x.p, e, dotPartials.p);
-            lin(e, 1., b.p, -1., e, 0., nullptr);                      // err = b - A x
-            const double rsnew = dotH(e, e);
-            rre = rsnew;
-            if (std::sqrt(rsnew) / xmag < rre) rre = std::sqrt(rsnew) / xmag;
-            if (rre < tol) { solveIterations = i; break; }
-            lin(r.p, 1., s, -omega, t, 0., nullptr);                   // r = s - omega t
-        }
-        solveError = rre;
+        solveIterations = bicgstab(BiCGVecs<double*>{x.p, r.p, pvec.p, b.p, Ap.p, tmp1.p, tmp2.p, tmp3.p, tmp4.p, tmp5.p}, maxit, tol, solveError,
+            [&](double* in, double* out) { applyOperator(in, out, dotPartials.p); },
+            [&](const double* a, const double* bb) {
+                hipLaunchKernelGGL(k_dot, dim3(vb), dim3(BS), 0, stream, a, bb, n, dotPartials.p);
+                hipLaunchKernelGGL(k_sum1, dim3(1), dim3(BS), 0, stream, dotPartials.p, vb, dotPartials.p + 3 * VGRID);
+                double out;
+                HIP_CHECK(hipMemcpyAsync(&out, dotPartials.p + 3 * VGRID, sizeof(double), hipMemcpyDeviceToHost, stream));
+                HIP_CHECK(hipStreamSynchronize(stream));
+                return out;
+            },
+            [&](double* out, double ca, const double* a, double cb, const double* bb, double cc, const double* c3) {
+                hipLaunchKernelGGL(k_lin, dim3(vb), dim3(BS), 0, stream, out, ca, a, cb, bb, cc, c3, n);
+            },
+            [&](double* v) { HIP_CHECK(hipMemsetAsync(v, 0, (size_t)n * sizeof(double), stream)); });
     }
     return solveIterations == maxit ? PS_NOCONVERGE : PS_SUCCESS;
 }

@@ -24,8 +24,13 @@ def tall_coil(n, nz):
     return abi.Scene(n, n, nz, sc0.dx, sc0.dt, 1000.0, [0.0, 0.0, -1.0], surface, collision, 100.0, name=f"tallcoil{n}x{nz}"), p
 
 
+def base_case(case):
+    """the scene of a case without its variant suffix"""
+    return case.replace("_interrupt", "").replace("_failrank", "").replace("_f32first", "")
+
+
 def make(case):
-    base = case.replace("_interrupt", "").replace("_failrank", "")
+    base = base_case(case)
     if base == "cavity_w2":
         return tall_cavity(32, 64)
     if base == "cavity_w3_jacobi":

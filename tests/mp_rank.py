@@ -55,7 +55,7 @@ def run_rank(case, world, rank, port, out, device, done):
     from polystokes_amd import partition
     import mp_cases
     sc, p = mp_cases.make(case)
-    dims = mp_cases.DIMS.get(case.replace("_interrupt", "").replace("_failrank", ""))
+    dims = mp_cases.DIMS.get(mp_cases.base_case(case))
     s = polystokes_amd.Solver(device)
     if dims is not None:
         sl = partition.make_brick((sc.nx, sc.ny, sc.nz), dims, rank, p.tileSize)
@@ -67,7 +67,17 @@ def run_rank(case, world, rank, port, out, device, done):
         # this rank sees air in a patch of its own first layers: its labels on the cut differ from what rank 0 computes
         # from its halo copy: the owners' label exchange finds the two views of the same cells in disagreement
         loc.surface[sl.zLoOwned:sl.zLoOwned + 3, 5:12, 5:12] = 1.0
-    s.upload(loc, p)
+    res = {}
+    if case.endswith("_f32first"):
+        # the same context solved first on its own with the fp32 polynomial, then as a rank: the decomposition's fp64 polynomial
+        # must not report what the single-domain solve left (array chebInner32)
+        from polystokes_amd import _abi as abi
+        p.preconditioner = abi.PRE_CHEBYSHEV_F32
+        s.upload(loc, p)
+        res["single_rc"] = s.step_device()
+        res["single_c32"] = int(s.array("chebInner32")[0])
+    else:
+        s.upload(loc, p)
     if dims is not None:
         s.set_brick(sl)
     else:
@@ -98,7 +108,7 @@ def run_rank(case, world, rank, port, out, device, done):
         err = ""
     except polystokes_amd.PolyStokesError as e:
         rc, err = -1, str(e)
-    res = dict(rc=rc, err=err, iters=int(s.stats.solveData[1]), used_bicgstab=int(s.stats.usedBiCGStab), mem_after_upload=mem_after_upload,
+    res.update(rc=rc, err=err, iters=int(s.stats.solveData[1]), used_bicgstab=int(s.stats.usedBiCGStab), mem_after_upload=mem_after_upload,
                mem_peak=s.memory_stats()["peak_bytes"], mem_deferred=s.memory_stats()["deferred_bytes"])
     if rc in (0, 1):
         lv, lval = s.download()
@@ -108,6 +118,7 @@ def run_rank(case, world, rank, port, out, device, done):
         res["labels"] = s.array("centerLabels")
         res["fused"] = int(s.array("fusedStep")[0])
         res["overlap"] = int(bool(s.dist_stats()["overlap"]))
+        res["c32"] = int(s.array("chebInner32")[0])
     np.savez(out, **res)
     if done is not None:
         done.wait()

@@ -185,6 +185,16 @@ def test_multiprocess_interrupt_stops_every_rank(tmp_path):
     assert int(res[0]["iters"]) == int(res[1]["iters"]) == 25
 
 
+def test_decomposed_step_does_not_report_an_earlier_fp32_polynomial(tmp_path):
+    """Every rank's context first solves its local scene on its own with PS_PRE_CHEBYSHEV_F32 (the fp32 polynomial runs: array chebInner32
+    reads 1), then set_slab, comm_init_tcp and a decomposed step, whose polynomial is fp64: the array must read 0 on every rank, not the
+    value the single-domain solve left.  The decomposed result still matches the single domain."""
+    res = _run_ranks("cavity_w2_chebyshev_f32first", 2, tmp_path)
+    assert all(int(r["single_rc"]) in (abi.SUCCESS, abi.NOCONVERGE) and int(r["single_c32"]) == 1 for r in res)
+    assert [int(r["c32"]) for r in res] == [0, 0]
+    _compare_with_single_domain("cavity_w2_chebyshev", 2, res)
+
+
 def test_multiprocess_list_mismatch_fails_every_rank(tmp_path):
     """Ranks that were handed different fields for the same cells (here: rank 1 sees air in a patch of its own first layers, rank 0's
     halo copy does not): rank 0 finds the owner's labels differing from its copy deeper inside the halo block than the classification
