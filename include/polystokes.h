@@ -264,7 +264,10 @@ int32_t ps_apply_preconditioner(ps_context* ctx, const double* r, double* z);
  * Beside the reference's arrays there are a few int32 diagnostics of the device path: "valuesCoded" (1: stencil values are
  * int8 codes), "columns16" (bit 0 / 1: S / St have the compressed 16-bit-column stream), "diagonalsCoded" (bit 0 / 1: uInv /
  * McInv are 1-byte value-set codes), "fusedStep" (1: the last PCG solve ran the four-kernel step), "streamRuns" (4 values:
- * entries of the distinct runs / all entries of the compressed stream of S, then of St). */
+ * entries of the distinct runs / all entries of the compressed stream of S, then of St), "launchWalk" (5 records of 8 values for the
+ * S product, then the St products of modes 0..3, of the last single-domain PCG solve: launched, kernel, chunks, workgroups, walk
+ * parameter, 1 for the pair walk of the two-unit kernels, least and most steps with a chunk taken by one workgroup; zeros where that
+ * product did not run). */
 int64_t ps_query_array(ps_context* ctx, const char* name, int32_t* elem_bytes);
 int32_t ps_read_array(ps_context* ctx, const char* name, void* dst, int64_t dst_bytes);
 

@@ -389,6 +389,9 @@ void ps_context::registerArrays() {
     // 1: the last PCG solve ran the four-kernel step (residual update inside the St kernel, ps_solve.hip)
     HIP_CHECK(hipMemcpyAsync(counters.p + 28, &fusedStepHost, sizeof(int32_t), hipMemcpyHostToDevice, stream));
     reg("fusedStep", counters.p + 28, 1, 4);
+    // the walks of the persistent SpMV launches of the last single-domain PCG solve (5 records of 8: ps_context.hpp launchWalkHost)
+    reg("launchWalk", launchWalkHost, 5 * LAUNCH_WALK_FIELDS, 4);
+    arrays["launchWalk"].host = true;
     // 1: the last solve / preconditioner apply kept the Chebyshev polynomial's inner vectors in fp32 (PS_PRE_CHEBYSHEV_F32 where its kernels run)
     chebInner32Host = chebInner32 ? 1 : 0;
     HIP_CHECK(hipMemcpyAsync(counters.p + 36, &chebInner32Host, sizeof(int32_t), hipMemcpyHostToDevice, stream));

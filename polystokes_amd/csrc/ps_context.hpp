@@ -194,6 +194,11 @@ struct ps_context {
     bool uCoded = false, mcCoded = false;
     int32_t diagFlagsHost = 0;
     int32_t fusedStepHost = 0;
+    // The walks of the persistent SpMV launches of the last single-domain PCG solve (array "launchWalk", read from host memory): 5 records of
+    // LAUNCH_WALK_FIELDS int32 (S, then St modes 0..3; ps_solve.hip Launch::noteWalk), written from the launch plan on the host while walkRecord is set
+    static constexpr int LAUNCH_WALK_FIELDS = 8;
+    int32_t launchWalkHost[5 * LAUNCH_WALK_FIELDS] = {};
+    bool walkRecord = false;
     int32_t streamRunsHost[4] = {0, 0, 0, 0};
     int32_t rowPerLaneHost[2] = {0, 0};
     void buildDiagonalCodes();

@@ -19,7 +19,9 @@
 //                          ps_context::applyOperator / assemble / solve / recover.
 //   ps_dist.hpp          : the z-slab distributed solve (RCCL or in-process ranks) and its C ABI.
 //   ps_import.hpp        : MatrixMarket import + general CSR PCG (ps_solve_exported_system).
+#include <algorithm>
 #include <chrono>
+#include <iterator>
 #include <cstring>
 #include <cmath>
 #include <limits>
@@ -90,6 +92,7 @@ struct Launch {
     // MODE 3 of the row-per-lane St kernel in its plain form (FX = 1: no Chebyshev first term, no halo rows, coded uInv) fits 7 workgroups per CU
     bool plain3Hint = false;
     bool plain3Hint2 = false;   // the same for the Chebyshev step: single domain, coded uInv
+    int32_t* walk = nullptr;    // ps_context::launchWalkHost while a solve records its walks (noteWalk), null otherwise
 
     // POL of the pipelined kernels (ps_kernels_spmv.hpp): 0 = default policy; 1 = non-temporal stores and epilogue streams, cached matrix
     // stream (most runs shared between chunks: read again and again); 3 = the matrix stream non-temporal too (every run read once)
@@ -173,6 +176,41 @@ struct Launch {
         return s.run && s.kernel == ELL2 && s.xcd > 0 && t.run && t.kernel == ELL2C && t.xcd > 0 && (c->regionCount == 0 || tileFused());
     }
 
+    // ---- the walk of a launch (array "launchWalk"): the first launch of each slot (0: S, 1 + mode: St) in a recording solve writes
+    // {1, kernel, nChunks, grid, walk parameter, 1 if the pair walk, least / most steps with a chunk of one workgroup} — host arithmetic on the
+    // plan that restates the kernels' walks: the pair walk of the two-unit kernels (runs of 32 pairs per XCD, steps l, l + per, .. below qEnd)
+    // and ChunkWalk (ps_kernels_spmv.hpp) of the one-unit and pipelined kernels; the one-shot CSR kernels take one step
+    void noteWalk(int slot, const Plan& p) const {
+        if (!walk || !p.run) return;
+        int32_t* w = walk + slot * ps_context::LAUNCH_WALK_FIELDS;
+        if (w[0]) return;
+        const bool pair = p.kernel >= ELL2;
+        int lo = 1, hi = 1;
+        if (p.kernel != CSR) {
+            lo = INT32_MAX; hi = 0;
+            const int nPairs = (p.nChunks + 1) >> 1, qEnd = ((nPairs + 255) >> 8) << 5, per = p.grid >> 3;
+            const int g = p.xcd, sh = (g & 0xffff) > 0 ? 31 - __builtin_clz((unsigned)(g & 0xffff)) : -1, rs = (g >> 16) & 7, gridPer = p.grid >> 3;
+            for (int b = 0; b < p.grid; ++b) {
+                int steps = 0;
+                if (pair) {   // steps whose pair exists (chunkAt(q) >= 0 for the first half); the others run the loop without a chunk
+                    const int x = b & 7;
+                    for (int q = b >> 3; q < qEnd; q += per) steps += ((((q >> 5) << 3) + x) << 5) + (q & 31) < nPairs;
+                } else {
+                    for (int it = 0;; ++it) {   // ChunkWalk::at
+                        const int j = it >> rs, o = it & ((1 << rs) - 1);
+                        int64_t run;
+                        if (sh < 0) run = b + (int64_t)j * p.grid;
+                        else { const int64_t q = (b >> 3) + (int64_t)j * gridPer; run = ((((q >> sh) << 3) + (b & 7)) << sh) + (q & ((1 << sh) - 1)); }
+                        if ((run << rs) + o >= p.nChunks) break;
+                        ++steps;
+                    }
+                }
+                lo = std::min(lo, steps); hi = std::max(hi, steps);
+            }
+        }
+        const int32_t rec[ps_context::LAUNCH_WALK_FIELDS] = {1, (int32_t)p.kernel, p.nChunks, p.grid, p.xcd, pair ? 1 : 0, lo, hi};
+        std::memcpy(w, rec, sizeof(rec));
+    }
     // ---- launchers, one per kernel family.  (Each names its kernels in the order the dispatch has always instantiated them: the code
     // object lays the kernels out in that order.)
     // the row-per-lane kernels: the coded ELL stream of M leads every argument list
@@ -203,6 +241,7 @@ struct Launch {
     void spmvS(int mode, const double* x, double* out) const {
         const Plan p = planS(mode, sList, nSList);
         if (!p.run) return;
+        if (mode == 0 && !sList) noteWalk(0, p);
         const ps::DevCSR& M = c->S;
         const uint8_t* mc = c->mcCoded ? c->mcCode.p : (const uint8_t*)nullptr;
         switch (p.kernel) {
@@ -263,6 +302,7 @@ struct Launch {
     void spmvS32(const float* x, float* out) const {
         const Plan p = planS(0, false, 0);
         if (p.kernel != ELL2) throw Error("internal: single-precision S apply without the two-unit kernel");
+        noteWalk(0, p);
         sEll2(p, x, out, (double*)nullptr, (const int32_t*)nullptr);
     }
     void tiles32(float* ts) const {   // the fused apply only, at the default threads per region
@@ -272,6 +312,7 @@ struct Launch {
     int spmvSt2c32(const float* t, const float* xin, float* out, double* partial, const ChebArgs& ca) const {   // returns the number of partials written
         const Plan p = planSt(2, false, 0, false, FusedR{});
         if (p.kernel != ELL2C) throw Error("internal: single-precision Chebyshev term without the two-unit St kernel");
+        noteWalk(3, p);
         stEll2c(p, t, xin, out, partial, ca);
         return p.grid;
     }
@@ -283,6 +324,7 @@ struct Launch {
         const Plan p = planSt(mode, stList, nStList, stOwnedOnly, fr);
         if (!p.run) return;
         if (p.err) throw Error(p.err);
+        if (!stList) noteWalk(1 + mode, p);
         const ps::DevCSR& M = c->St;
         const uint8_t* uc = c->uCoded ? c->uCode.p : (const uint8_t*)nullptr;
         const uint8_t* uArg = c->uCoded ? (const uint8_t*)c->uCode.p : (const uint8_t*)c->uInv.p;
@@ -393,6 +435,7 @@ Launch mk(ps_context* c, const int* done) {
     L.ntSpmv = c->ntLevel() >= 1;
     L.plain3Hint = c->P.preconditioner != PS_PRE_CHEBYSHEV && !c->slabEnabled;     // (the stress diagonal coded or not: the two-unit kernels take both, r06)
     L.plain3Hint2 = c->P.preconditioner == PS_PRE_CHEBYSHEV && !c->slabEnabled;
+    L.walk = c->walkRecord ? c->launchWalkHost : nullptr;
     return L;
 }
 constexpr int64_t FUSED_STEP_MIN_ROWS = 1200000;   // see solve() (r05: 2 M -> 1.2 M: the coil 128^3 of BASELINE config 2, 1.49 M rows, solves 3 % faster in four kernels — 10.55 against 10.86 ms,
@@ -644,7 +687,9 @@ int ps_context::solve() {
     interrupted = false;
     if (P.solverType == PS_EIGEN) return solveEigenCG();
     if (P.solverType != PS_PCG_MATRIX_VECTOR_PRODUCTS) { err = "Unsupported Solver."; return PS_UNSUPPORTED_SOLVER; }
+    std::fill(std::begin(launchWalkHost), std::end(launchWalkHost), 0);
     if (n == 0) { solveIterations = 0; solveError = 0; return PS_SUCCESS; }
+    struct WalkRecord { bool& on; explicit WalkRecord(bool& f) : on(f) { on = true; } ~WalkRecord() { on = false; } } walkRecording(walkRecord);
     const bool cheb = P.preconditioner == PS_PRE_CHEBYSHEV;
     const diag_t* dv = (P.preconditioner == PS_PRE_DIAGONAL) ? dinvF.p : nullptr;
     const int vb = dotBlocks(n);

@@ -1,3 +1,5 @@
+import math
+
 import numpy as np
 import scipy.sparse as sp
 
@@ -157,3 +159,83 @@ def rigid_rotation_scene(n=24, w=(0.3, -0.2, 0.5)):
         sc.vel[a][:] = ua
         ref.append(ua.ravel())
     return sc, p, ref
+
+
+# ---- the PCG restated in fp64, and the library's iterate after a whole number of batches -------------------------------------------
+# Bounds on max |x_device - x_reference| / max |x_reference| after 25 and 50 iterations (tests/test_gpu_iterates.py): fp64 steps, and the
+# Chebyshev polynomial with fp32 inner vectors (its M taken from the device).  About 100x the largest drift measured on an MI355X: 1.3e-13
+# (fp64), 1.4e-8 (fp32: the solve's fused first term rounds its fp32 terms differently from the stand-alone apply).
+ITERATE_BOUND = 1e-11
+ITERATE_BOUND_F32 = 2e-6
+# Cases whose x_50 has converged so far that a 1e-6 error of beta at iteration 24 moves it by less than ITERATE_BOUND (the self-checks,
+# tests/test_iterate_tolerances_cpu.py: cavity32 / coil32 Chebyshev-10 1.7e-15 / 5.1e-13, blob6 Chebyshev-4 9.8e-13): x_25 only
+ITERATE_SHORT = {("cavity32", "cheb10"): (1,), ("coil32", "cheb10"): (1,), ("blob6", "cheb4"): (1,)}
+# cases no bound can check: blob6 Chebyshev-10 has converged by x_25 (the beta error moves it by 3.8e-15)
+ITERATE_DROPPED = {("blob6", "cheb10")}
+CG_BATCH = 25          # PCG iterations between two stop tests of the library (ps_solve.hip, ps_dist.hpp): an interrupt stops it there
+
+
+def fdot(a, b):
+    """a . b with a correctly rounded sum of the fp64 products (math.fsum): no summation order of a kernel is more accurate"""
+    return math.fsum(np.multiply(a, b))
+
+
+def numpy_pcg(A, M, b, x0, tol, maxit, iters=None, beta_scale=None, on_iterate=None):
+    """pcg_external_matrix_A (lib/include/pcg.h:268-340) restated: returns (0-based index of the converged iteration, x).
+    iters: stop after exactly that many iterations (x updates) without testing the stop rule, returning (iters, x).
+    beta_scale: (i, beta) -> beta, the beta formed at the end of iteration i as the next direction uses it (the tolerance self-checks).
+    on_iterate: (k, x) after the k-th x update."""
+    x = x0.copy()
+    r = b - A(x)
+    z = M(r)
+    p = z.copy()
+    rsold = fdot(r, z)
+    n_it = maxit if iters is None else iters
+    for i in range(n_it):
+        Ap = A(p)
+        alpha = rsold / fdot(p, Ap)
+        x = x + alpha * p
+        if on_iterate is not None:
+            on_iterate(i + 1, x)
+        r = r - alpha * Ap
+        rsnew = fdot(r, r)
+        xmag = fdot(x, x)
+        rre = rsnew
+        if rsnew / xmag < rre:
+            rre = rsnew / xmag
+        if iters is None and rre < tol * tol:
+            return i, x
+        z = M(r)
+        rsnew = fdot(r, z)
+        beta = rsnew / rsold
+        if beta_scale is not None:
+            beta = beta_scale(i, beta)
+        p = z + beta * p
+        rsold = rsnew
+    return n_it, x
+
+
+def trajectory_params(p):
+    """a copy of params whose stop rule cannot fire within a few hundred iterations: the solve runs until it is interrupted"""
+    q = type(p).from_buffer_copy(p)
+    q.tolerance = 1e-14
+    q.maxSolverIterations = 100000
+    return q
+
+
+def iterate_after(target, m, scene=None, params=None):
+    """x (reference numbering) after exactly CG_BATCH * m PCG iterations of a Solver: an interrupt fires at the m-th batch boundary
+    (ps_set_interrupt) and the solve returns PS_INCOMPLETE with solveData[1] == CG_BATCH * m.  With scene / params the solver uploads them
+    first, with the trajectory tolerance; otherwise it solves what it holds."""
+    calls = []
+    stop = lambda: calls.append(1) or len(calls) >= m
+    if scene is not None:
+        target.upload(scene, trajectory_params(params))
+    target.set_interrupt(stop)
+    try:
+        rc = target.step_device()
+    finally:
+        target.set_interrupt(None)
+    assert rc == abi.INCOMPLETE and len(calls) == m, (rc, len(calls))
+    assert int(target.stats.solveData[1]) == CG_BATCH * m, target.stats.solveData[1]
+    return target.array("solutionVector").copy()

@@ -13,6 +13,8 @@ import pytest
 from polystokes_amd import _abi as abi
 from polystokes_amd import scenes
 
+from helpers import numpy_pcg
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -73,32 +75,6 @@ def gather_ref(solver, fields):
         v[ea[em]] = fields[name][em]
         parts.append(v)
     return np.concatenate(parts)
-
-
-def numpy_pcg(A, M, b, x0, tol, maxit):
-    """pcg_external_matrix_A (lib/include/pcg.h:268-340) restated: returns (0-based index of the converged iteration, x)"""
-    x = x0.copy()
-    r = b - A(x)
-    z = M(r)
-    p = z.copy()
-    rsold = r @ z
-    for i in range(maxit):
-        Ap = A(p)
-        alpha = rsold / (p @ Ap)
-        x = x + alpha * p
-        r = r - alpha * Ap
-        rsnew = r @ r
-        xmag = x @ x
-        rre = rsnew
-        if rsnew / xmag < rre:
-            rre = rsnew / xmag
-        if rre < tol * tol:
-            return i, x
-        z = M(r)
-        rsnew = r @ z
-        p = z + (rsnew / rsold) * p
-        rsold = rsnew
-    return maxit, x
 
 
 def _close(x, ref, tol):
