@@ -245,6 +245,19 @@ int32_t ps_download_solution_fields(ps_context* ctx, const ps_solution_out* out)
  * setup used; only with sigma > 0), "surfaceTensionReducedFaces" (int32: reduced faces that received an impulse; only with sigma > 0). */
 int32_t ps_set_surface_tension(ps_context* ctx, double sigma);
 
+/* Solid boundary condition (extension; the reference node's colliders are all no-slip).  A context setting like ps_set_surface_tension: it
+ * persists across ps_upload_fields and is read by every later setup.  PS_SOLID_NO_SLIP (the default) launches exactly the kernels of a
+ * context that never made the call.  PS_SOLID_FREE_SLIP zeroes the shear stress tau_e of every active edge whose fluid weight is below 1
+ * (an edge cut by a solid): its entries in S and St (face rows, skin rows included) hold the value 0, its rhs is 0 and its uInv is kept,
+ * so the system row of tau_e reads uInv tau_e = 0.  The zeros keep no-slip's sparsity pattern (exports list them as explicit zeros).
+ * Pressure and centre-stress columns, their collisionvel rhs terms (the wall's normal constraint), labels, numbering and dimData are
+ * those of no-slip.  On axis-aligned walls that is free slip; on slanted walls the centre stresses still carry some tangential traction
+ * (the usual MAC approximation).  Slab and brick ranks apply the rule on their own grid.  PS_INVALID (reason in ps_last_error, the previous setting kept): another mode.
+ * Arrays: "solidBoundary" (int32, 1: the mode of the last setup), "solidSlipEdges" (int32, 1: the edges whose coupling the last setup
+ * dropped; only in free-slip mode). */
+enum ps_solid_boundary { PS_SOLID_NO_SLIP = 0, PS_SOLID_FREE_SLIP = 1 };
+int32_t ps_set_solid_boundary(ps_context* ctx, int32_t mode);
+
 /* solveGasSubclass equivalent on host buffers: upload + step + download (HDK_PolyStokes.C:222-609). */
 int32_t polystokes_step(ps_context* ctx, const ps_params* p, const ps_fields_in* in,
                         ps_fields_out* out, ps_stats* stats);

@@ -26,6 +26,7 @@ EXPORTED_SYMBOLS = [
     "ps_set_slab", "ps_set_brick", "ps_comm_unique_id", "ps_comm_init_rccl", "ps_comm_selftest", "ps_comm_init_tcp", "ps_dist_stats",
     "ps_group_create", "ps_group_destroy", "ps_group_rank", "ps_group_step",
     "ps_set_warm_start", "ps_download_solution_fields", "ps_upload_density_field", "ps_set_surface_tension",
+    "ps_set_solid_boundary",
 ]
 
 
@@ -115,6 +116,8 @@ def lib():
         L.ps_upload_density_field.restype = C.c_int32
         L.ps_set_surface_tension.argtypes = [C.c_void_p, C.c_double]
         L.ps_set_surface_tension.restype = C.c_int32
+        L.ps_set_solid_boundary.argtypes = [C.c_void_p, C.c_int32]
+        L.ps_set_solid_boundary.restype = C.c_int32
         _lib = L
     return _lib
 
@@ -126,7 +129,7 @@ def _kind(name):
     if name.endswith(("Labels", "Indices", ".col", ".ptr", "Region", "Perm", ".chunkInfo", ".chunkRep", ".code")) or name.startswith("faceRow"):
         return "i"
     if name in ("valuesCoded", "columns16", "diagonalsCoded", "fusedStep", "streamRuns", "rowPerLane", "chebInner32", "warmStartUsed", "densityField", "launchWalk",
-                "surfaceTensionReducedFaces"):
+                "surfaceTensionReducedFaces", "solidBoundary", "solidSlipEdges"):
         return "i"
     if name in ("ownedX", "ownedY", "ownedZ"):
         return "f"
@@ -186,6 +189,11 @@ class Solver:
         """ps_set_surface_tension: sigma (force per length; 0 = off) for every later setup of this context, across uploads.  Returns the
         ps_result: INVALID for a negative or non-finite sigma (the reason in last_error(), the previous setting kept)."""
         return self._check(self.L.ps_set_surface_tension(self.h, float(sigma)), allow=(1, -2))
+
+    def set_solid_boundary(self, mode):
+        """ps_set_solid_boundary: SOLID_NO_SLIP (0, the default) or SOLID_FREE_SLIP (1: no shear stress on the edges a solid cuts) for every
+        later setup of this context, across uploads.  Returns the ps_result: INVALID for another mode (the previous setting kept)."""
+        return self._check(self.L.ps_set_solid_boundary(self.h, int(mode)), allow=(1, -2))
 
     def solution_fields(self):
         """ps_download_solution_fields: the last solve's [p; tau] as dense fp32 grids (x fastest), keyed pressure, txx, tyy, tzz, tyz, txz, txy;
@@ -433,6 +441,11 @@ class Group:
         for r in self.ranks:
             r.stats = self.stats
         return rc
+
+    def set_solid_boundary(self, mode):
+        """ps_set_solid_boundary on every rank (a context setting: it holds for every later step of the group)."""
+        rc = [r.set_solid_boundary(mode) for r in self.ranks]
+        return rc[0]
 
     def solve_scene(self, scene, params):
         """Partition `scene` into slabs, run the distributed step, merge the owned faces into global arrays."""

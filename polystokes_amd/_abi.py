@@ -63,6 +63,8 @@ class SolutionOut(C.Structure):
 
 # ps_warm_start
 WARM_NONE, WARM_PREVIOUS_STEP = 0, 1
+# ps_solid_boundary
+SOLID_NO_SLIP, SOLID_FREE_SLIP = 0, 1
 # the grids of ps_download_solution_fields: name -> sample grid (SAMPLE_NAMES / grid_shapes), in ps_solution_out order
 SOLUTION_FIELDS = [("pressure", "center"), ("txx", "center"), ("tyy", "center"), ("tzz", "center"),
                    ("tyz", "edgeYZ"), ("txz", "edgeXZ"), ("txy", "edgeXY")]

@@ -39,7 +39,15 @@ struct BlockArgs {
     const int32_t* regionOwned;   // null: all owned
     double valScale;              // invDx / 64
     int32_t* codeFail;            // set to 1 if some value is not code * valScale
+    int freeSlip;                 // PS_SOLID_FREE_SLIP: an active edge with fluid weight < 1 has no stress (ps_set_solid_boundary)
+    int32_t* slipEdges;           // free slip: the count pass adds such edges here (array "solidSlipEdges")
 };
+
+// Free slip drops the coupling of the edge stress at `el` of edge grid `ea`: it is cut by a solid (the `edgeSolidish` test of
+// edgeColumnT).  Its entries in S and St are stored as explicit zeros and its rhs is 0; uInv keeps its value, so tau_e = 0 exactly.
+// The zeros keep the pattern of no-slip: a reduced face can touch such an edge (a tile two cells from a curved solid), and dropping
+// the entry would change the skin rows' length classes and hence their numbering (k_skin); no row or column becomes empty either.
+__device__ inline bool slipEdge(const BlockArgs& A, int ea, int64_t el) { return A.freeSlip && A.fw[4 + ea][el] < 1.f; }
 
 __device__ inline int8_t encodeVal(const BlockArgs& A, double v) {
     const double q = v / A.valScale;
@@ -101,7 +109,7 @@ __device__ inline int faceEntriesT(const BlockArgs& A, const int3 f, int32_t (&c
             if (!isActiveL(A.lab[4 + ea][el])) continue;
             const double coeff = wF * (double)A.lw[4 + ea][el] * A.invDx;
             if (coeff <= 0.) continue;
-            cols[4 + 2 * w + dir] = A.sys[4 + ea][el]; vals[4 + 2 * w + dir] = -1. * sign * coeff; ++n;
+            cols[4 + 2 * w + dir] = A.sys[4 + ea][el]; vals[4 + 2 * w + dir] = slipEdge(A, ea, el) ? 0. : -1. * sign * coeff; ++n;
         }
     }
     return n;
@@ -397,6 +405,7 @@ __device__ inline int edgeColumnT(const BlockArgs& A, const int3 e, int32_t (&ro
     for (int k = 0; k < 4; ++k) { rows[k] = NO_COL; vals[k] = 0.; }
     int n = 0;
     double rhs = 0.;
+    const bool slip = slipEdge(A, EA, el);   // free slip: zero values, rhs 0
     constexpr int FA0 = EA == 0 ? 1 : 0, FA1 = EA == 2 ? 1 : 2;
 #pragma unroll
     for (int w = 0; w < 2; ++w) {
@@ -415,8 +424,8 @@ __device__ inline int edgeColumnT(const BlockArgs& A, const int3 e, int32_t (&ro
             const float wFf = A.fw[1 + fa][fl];
             const double coeff = (double)wFf * wLe * A.invDx;
             if (coeff <= 0.) continue;
-            rows[2 * w + divDir] = row; vals[2 * w + divDir] = -1. * sign * coeff; ++n;
-            if (row < A.nA) {   // :582-599
+            rows[2 * w + divDir] = row; vals[2 * w + divDir] = slip ? 0. : -1. * sign * coeff; ++n;
+            if (row < A.nA && !slip) {   // :582-599
                 const double sc = sign * coeff;
                 const double svel = (double)A.cvel[fa][fl];
                 if (edgeSolidish) rhs += -1. * sc * svel;
@@ -523,7 +532,11 @@ __global__ void k_St_edges(BlockArgs A, int ea, int32_t* __restrict__ cnt, const
     const int n = edgeColumn(A, ea, q, rows, vals, &rhs);
     const int64_t j = A.sys[4 + ea][c];
     const int64_t t = j;
-    if (!FILL) { cnt[j] = n; return; }
+    if (!FILL) {
+        cnt[j] = n;
+        if (slipEdge(A, ea, c)) atomicAdd(A.slipEdges, 1);
+        return;
+    }
     sortRows4(rows, vals);
     const int p0 = ptr[j];
 #pragma unroll
@@ -556,6 +569,8 @@ BlockArgs makeArgs(ps_context* c) {
     A.valScale = c->valScale;
     A.codeFail = c->counters.p + 20;
     A.regionOwned = (c->slabEnabled && c->regionCount > 0) ? c->regionOwned.p : nullptr;
+    A.freeSlip = c->solidBoundaryUsed == PS_SOLID_FREE_SLIP ? 1 : 0;
+    A.slipEdges = A.freeSlip ? c->slipEdges.p : nullptr;
     return A;
 }
 
@@ -1015,6 +1030,11 @@ void ps_context::constructMatrixBlocks() {
 
     valScale = invDx / 64.;
     HIP_CHECK(hipMemsetAsync(counters.p + 20, 0, sizeof(int32_t), stream));
+    solidBoundaryUsed = solidBoundarySet;   // (ps_set_solid_boundary; read by makeArgs)
+    if (solidBoundaryUsed == PS_SOLID_FREE_SLIP) {
+        slipEdges.alloc(1);
+        HIP_CHECK(hipMemsetAsync(slipEdges.p, 0, sizeof(int32_t), stream));
+    }
     buildInternalNumbering();   // sysIdx[], faceRow[] (active rows), permSys, permRow
     haloForward = false;        // one exchange round unless Dist::decideExchangeMode finds a row that reaches a diagonal neighbour's sample
     buildHaloLists();

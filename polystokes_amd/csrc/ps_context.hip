@@ -376,6 +376,9 @@ void ps_context::registerArrays() {
         reg("surfaceCurvature", kappaC.p, g.count(0), 4);
         reg("surfaceTensionReducedFaces", stReduced.p, 1, 4);
     }
+    reg("solidBoundary", &solidBoundaryUsed, 1, 4);   // the mode of the last setup (ps_set_solid_boundary)
+    arrays["solidBoundary"].host = true;
+    if (solidBoundaryUsed == PS_SOLID_FREE_SLIP) reg("solidSlipEdges", slipEdges.p, 1, 4);
     if (P.preconditioner == PS_PRE_DIAGONAL) regp("dinv", dinv.p, nSystem, permSys.p, 0);
     if (isSolved) {
         regp("recoveredActiveVelocity", recovered.p, nActiveVs, permRow.p, 0);
@@ -700,6 +703,17 @@ int32_t ps_set_surface_tension(ps_context* c, double sigma) {
             return PS_INVALID;
         }
         c->sigmaSet = sigma;   // read by the next setup (applySurfaceTension)
+        return PS_SUCCESS;
+    })
+}
+int32_t ps_set_solid_boundary(ps_context* c, int32_t mode) {
+    if (!c) return PS_FAILED;
+    PS_TRY(c, {
+        if (mode != PS_SOLID_NO_SLIP && mode != PS_SOLID_FREE_SLIP) {
+            c->err = "ps_set_solid_boundary: unknown mode " + std::to_string(mode) + " (0: no slip, 1: free slip)";
+            return PS_INVALID;
+        }
+        c->solidBoundarySet = mode;   // read by the next setup (constructMatrixBlocks)
         return PS_SUCCESS;
     })
 }

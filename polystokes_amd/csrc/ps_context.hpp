@@ -121,6 +121,10 @@ struct ps_context {
     ps::DevBuf<float> kappaRaw, kappaC;      // cell grids: kappa of the SDF, and kappa_c (sampled at the interface point, clamped)
     ps::DevBuf<int32_t> stReduced;           // reduced faces that received an impulse (array "surfaceTensionReducedFaces")
     void applySurfaceTension();              // ps_surface.hip: after the blocks and tile rhs, before b
+    // Solid boundary (ps_set_solid_boundary): solidBoundarySet is the context setting, solidBoundaryUsed the mode of the last setup (array
+    // "solidBoundary"; constructMatrixBlocks copies it).  slipEdges: free-slip edges counted by the St count pass (array "solidSlipEdges").
+    int32_t solidBoundarySet = PS_SOLID_NO_SLIP, solidBoundaryUsed = PS_SOLID_NO_SLIP;
+    ps::DevBuf<int32_t> slipEdges;
 
     // ---- inputs (fp32 Houdini voxel arrays, HDK_PolyStokes.C:235-246) ----
     ps::DevBuf<float> surface, collision, viscosity, density, vel[3], cvel[3];

@@ -228,3 +228,27 @@ def ellipsoid_droplet(n=32, axes=(0.36, 0.26, 0.26), tile=8, pad=2, center=(0.5,
     surface = (k0 - 1.0) * k0 / np.maximum(k1, 1e-12)
     sc = Scene(n, n, n, dx, dt, 1000.0, [0.0, 0.0, 0.0], surface, np.float32(10.0), 50.0, name=f"ellipsoid{n}", surface_tension=sigma)
     return sc, default_params(tileSize=tile, tilePadding=pad)
+
+
+def _floor_box(n, floor, height, margin, velx, cvelx, viscosity, dt, name, tile, pad):
+    """A liquid box on a solid floor: the floor is solid below y = floor * dx (a face plane of the y faces), the liquid fills
+    margin <= x, z < n - margin cells and reaches y = height cells (its SDF continues into the floor).  No gravity."""
+    dx = 1.0 / n
+    x, y, z = _centers(n, n, n, dx)
+    surface = _box_sdf(x, y, z, (margin * dx, -1.0, margin * dx), ((n - margin) * dx, height * dx, (n - margin) * dx))
+    collision = y - floor * dx
+    sc = Scene(n, n, n, dx, dt, 1000.0, [velx, 0.0, 0.0], surface, collision, viscosity, collisionvel=[cvelx, 0.0, 0.0], name=name)
+    return sc, default_params(tileSize=tile, tilePadding=pad)
+
+
+def sliding_block(n=32, U=1.0, viscosity=100.0, dt=1.0 / 24.0, tile=8, pad=2, floor=2, height=26, margin=3):
+    """A liquid box resting on a solid floor, every face moving with u_x = U, the floor at rest.  Rigid sliding: under free-slip
+    solids (ps_set_solid_boundary) nothing changes it; a no-slip floor drags the liquid next to it (viscosity * dt / (density * dx^2) = 4.3
+    at the defaults)."""
+    return _floor_box(n, floor, height, margin, float(U), 0.0, viscosity, dt, f"sliding_block{n}", tile, pad)
+
+
+def moving_floor(n=32, V=1.0, viscosity=100.0, dt=1.0 / 24.0, tile=8, pad=2, floor=2, height=26, margin=3):
+    """Liquid at rest on a solid floor whose collision velocity is u_x = V.  A free-slip floor leaves the liquid at rest; a no-slip
+    one drags it along."""
+    return _floor_box(n, floor, height, margin, 0.0, float(V), viscosity, dt, f"moving_floor{n}", tile, pad)

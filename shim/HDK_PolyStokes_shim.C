@@ -25,7 +25,7 @@ void initializeSIM(void*)
     IMPLEMENT_DATAFACTORY(HDK_PolyStokes);
 }
 
-HDK_PolyStokes::HDK_PolyStokes(const SIM_DataFactory* factory) : BaseClass(factory), myCtx(nullptr), myCtxDevice(-1), myWarmMode(PS_WARM_NONE) {}
+HDK_PolyStokes::HDK_PolyStokes(const SIM_DataFactory* factory) : BaseClass(factory), myCtx(nullptr), myCtxDevice(-1), myWarmMode(PS_WARM_NONE), mySolidMode(PS_SOLID_NO_SLIP) {}
 
 HDK_PolyStokes::~HDK_PolyStokes()
 {
@@ -77,6 +77,7 @@ const ParmRow theRows[] = {
     {'T', "variableDensity",            "Variable Density",                 nullptr,            0},
     {'T', "enableSurfaceTension",       "Enable Surface Tension",           nullptr,            0},
     {'F', "surfaceTension",             "Surface Tension",                  nullptr,            0},
+    {'T', "solidFreeSlip",              "Free-Slip Solids",                 nullptr,            0},
 };
 constexpr int theRowCount = (int)(sizeof(theRows) / sizeof(theRows[0]));
 }  // namespace
@@ -151,6 +152,7 @@ bool HDK_PolyStokes::ensureContext(SIM_Object* obj)
     myCtx = ps_context_create(dev);
     myCtxDevice = dev;
     myWarmMode = PS_WARM_NONE;          // a new context solves from zero until told otherwise
+    mySolidMode = PS_SOLID_NO_SLIP;     // and has no-slip solids
     if (!myCtx) { addError(obj, SIM_MESSAGE, ps_last_error(nullptr), UT_ERROR_ABORT); return false; }
     return true;
 }
@@ -204,6 +206,13 @@ bool HDK_PolyStokes::solveGasSubclass(SIM_Engine& engine, SIM_Object* obj, SIM_T
     // launches nothing extra).  A refused sigma (negative or not finite) aborts with the library's reason.
     const double sigma = getEnableSurfaceTension() ? (double)getSurfaceTension() : 0.;
     if (ps_set_surface_tension(myCtx, sigma) != PS_SUCCESS) return fail(ps_last_error(myCtx), UT_ERROR_ABORT);
+    // shim-only: free-slip colliders (ps_set_solid_boundary, a context setting: no shear stress on the edges a solid cuts), set when the
+    // toggle changes.  Off keeps the reference's no-slip walls.
+    const int32_t solidMode = getSolidFreeSlip() ? PS_SOLID_FREE_SLIP : PS_SOLID_NO_SLIP;
+    if (solidMode != mySolidMode) {
+        if (ps_set_solid_boundary(myCtx, solidMode) != PS_SUCCESS) return fail(ps_last_error(myCtx), UT_ERROR_ABORT);
+        mySolidMode = solidMode;
+    }
 
     const fpreal dt = timestep;
     const fpreal dx = velocityField->getVoxelSize(0).maxComponent();

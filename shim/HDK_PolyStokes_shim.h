@@ -48,6 +48,7 @@ public:
     GET_DATA_FUNC_B("variableDensity",                  VariableDensity);         // a non-constant density field -> ps_upload_density_field (0)
     GET_DATA_FUNC_B("enableSurfaceTension",             EnableSurfaceTension);    // ps_set_surface_tension(surfaceTension) (0)
     GET_DATA_FUNC_F("surfaceTension",                   SurfaceTension);          // sigma of the curvature pressure jump (0)
+    GET_DATA_FUNC_B("solidFreeSlip",                    SolidFreeSlip);           // ps_set_solid_boundary(PS_SOLID_FREE_SLIP) (0)
 
 protected:
     explicit HDK_PolyStokes(const SIM_DataFactory* factory);
@@ -59,6 +60,7 @@ private:
     ps_context* myCtx;          // owns the device buffers; reused across substeps
     int         myCtxDevice;
     int32_t     myWarmMode;     // the mode last set on myCtx (ps_set_warm_start)
+    int32_t     mySolidMode;    // the mode last set on myCtx (ps_set_solid_boundary)
 
     bool ensureContext(SIM_Object* obj);
     void publishDebugGeometry(SIM_Object* obj, const SIM_VectorField* velocity, fpreal dx);
