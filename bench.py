@@ -4,6 +4,10 @@
 One "step" = ps_step_device(): the whole hot path (weights -> classification -> tile blocks -> CSR
 assembly -> PCG -> velocity recovery/write-back) on inputs already resident in HBM.
 Prints ONE JSON line (rank 0).  See DESIGN.md §measurement for the definitions used here.
+
+A plain run does what the headline needs and no more: set up, warm up, time the steps, write --dump-outputs, print the line.
+--full adds what takes runs of its own: the box calibration, the kernel roofline, the host-boundary step, the other
+preconditioners, the strong_512 block and the CPU baseline (the --no-* options still skip single parts of it).
 """
 import argparse
 import json
@@ -320,6 +324,74 @@ def strong_block(solver, world, rank, dist, pre, transport_used, res, barrier, s
     return blk
 
 
+def kernel_roofline(solver, with_traffic):
+    """Roofline of the dominant kernels, measured live with HIP events on the solver stream (--full: each kernel runs 20 launches of its
+    own, so it comes after the dump of the timed step's outputs).  with_traffic: the run is the 256^3 cavity on one GPU, which the
+    committed PMC summary measured."""
+    coded = bool(solver.array("valuesCoded")[0])
+    c16 = int(solver.array("columns16")[0]) == 3
+    kern = {}
+    # the PCG step as the solve ran it: four kernels (S, tiles, St with the residual update in its epilogue, x/p update) on
+    # the coded stream, five (S, tiles, St, r update, x/p update) otherwise — the five-kernel ones stay listed: they are what
+    # the distributed, Chebyshev and fallback-stream solves launch
+    fused = int(solver.array("fusedStep")[0]) == 1
+    rpl = solver.array("rowPerLane")
+    ell = int(rpl[0]) == 3                                  # both products on the row-per-lane kernels
+    names = (["spmv_St_r", "cg_update_xp_u"] if fused else []) + ["spmv_St", "spmv_S", "apply", "tiles", "cg_update_r", "cg_update_xp"]
+    if coded and c16:
+        names += ["spmv_St_fp64", "spmv_S_fp64"]     # the pipelined kernels on fp64 values (10 B/nnz): the non-dyadic-weights fallback
+    names += ["spmv_St_csr", "spmv_S_csr"]            # the one-shot kernels on the plain CSR (12 B/nnz): the last-resort fallback
+    # the five kernels of a CG iteration are timed IN SEQUENCE ("seq:": the loop's predecessor kernel runs, untimed, before
+    # every timed launch: what rocprof sees in a real solve); "replayed_ms" is the same kernel launched back to back
+    in_loop = ("spmv_St_r", "cg_update_xp_u", "spmv_St", "spmv_S", "tiles", "cg_update_r", "cg_update_xp")
+    for name in names:
+        ms, by = solver.bench_kernel(("seq:" + name) if name in in_loop else name, 20)
+        kern[name] = {"ms": ms, "algorithmic_bytes": by, "GBps": by / (ms * 1e-3) / 1e9 if ms > 0 else 0.0,
+                      "frac": by / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS if ms > 0 else 0.0}
+        if name in in_loop:
+            kern[name]["replayed_ms"] = solver.bench_kernel(name, 20)[0]
+    dom = "spmv_St_r" if fused else "spmv_St"
+    mode = 3 if fused else 0
+    traffic, traffic_source = _latest_traffic("k_spmv_St_r" if fused else "k_spmv_St") if with_traffic else (None, None)
+    # achieved = the bytes the production kernel has to move per launch (its stored matrix format + the vectors, each once)
+    # / its launch duration: the HBM utilisation of the kernel as it runs.  The production kernel streams a lossless 3 B/nnz
+    # encoding of the matrix, so this is FEWER bytes than SURVEY section 8(d)'s CSR figure (12 B/nnz + row pointers +
+    # vectors); that figure over the same launch duration is reported beside it ("csr_equivalent": it can exceed the
+    # HBM peak, which only says the kernel beats a CSR SpMV running at the roofline).  Every fraction in "other_kernels" is
+    # that kernel's OWN stored bytes over its OWN measured duration (the fallbacks are timed as themselves).
+    # must-move bytes (VERDICT r03): the stored bytes minus the part of the 3 B/nnz matrix stream that chunks sharing a run read from cache —
+    # the vectors (each once), the per-row streams, the chunk records and the DISTINCT stream entries: what has to cross the HBM interface
+    # per launch.  `traffic / must_move_bytes` is the re-fetch factor of the gathers (S 2.08x, St 1.34x at the end of r03).
+    runs = [int(v) for v in solver.array("streamRuns")]          # S distinct, S entries, St distinct, St entries
+    if coded and c16:
+        for nm, (dist_e, all_e) in (("spmv_S", (runs[0], runs[1])), ("spmv_St", (runs[2], runs[3])), ("spmv_St_r", (runs[2], runs[3]))):
+            if nm in kern:
+                kern[nm]["must_move_bytes"] = kern[nm]["algorithmic_bytes"] - 3.0 * (all_e - dist_e)
+    ms = kern[dom]["ms"]
+    csr = kern["spmv_St_csr"]["algorithmic_bytes"]
+    csr_gbps = csr / (ms * 1e-3) / 1e9 if ms > 0 else 0.0
+    roofline = {
+        "bound": "hbm", "kernel": ("k_spmv_St_ell<%d,POL,FX> (one lane per row on the kind-major numbering; POL = cache policy of its streams%s)" % (mode, "; MODE 3: r -= alpha A p in the epilogue, FX = 3: the plain single-domain step (coded uInv, no halo rows) — run as k_spmv_St_ell2<POL>, two 64-row units in flight per wave, unless PS_ST_DUAL=0" if fused else "")) if ell else
+                                  ("k_spmv_St_pipe<%d,NV,%s,POL> (NV = 1 or 2 four-entry groups per lane, by the fullest chunk; POL = cache policy of its streams%s)" % (mode, "false" if coded else "true", "; MODE 3: r -= alpha A p in the epilogue" if fused else "") if c16 else "k_spmv_St<0,6,%s>" % ("true" if coded else "false")),
+        "achieved": kern[dom]["GBps"], "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": kern[dom]["frac"],
+        "traffic": traffic, "traffic_source": traffic_source,
+        "algorithmic_bytes_per_launch": kern[dom]["algorithmic_bytes"], "avg_launch_ms": ms,
+        "must_move_bytes": kern[dom].get("must_move_bytes"),
+        "numbering": {0: "voxel-major (kinds of DOF / faces of a voxel adjacent)", 3: "kind-major inside every k-plane of a 16^3 lattice block (DOFs and face rows)"}.get(int(rpl[1]), "mixed (%d)" % int(rpl[1])),
+        "algorithmic_bytes_definition": ("stored format: 3*nnz (16-bit windowed column + int8 value code; padded slots of the row-per-lane layout NOT counted) + %s80 B per chunk "
+                                         "+ 8*cols (t once) + 8*rows (p) + 1*rows (coded uInv) + %s") % ("" if ell else "1*rows (row length) + ", "16*rows (r read + written) + 2*rows (Jacobi diagonal, stored in 16 bits: the upper half of its fp32 value); A p is not stored" if fused else "8*rows (y)") if (coded and c16) else
+                                        "CSR: (12 | 10 | 5)*nnz + 4*(rows+1) + 8*rows (y) + 8*cols (x once) + 16*rows (fused epilogue)",
+        "stream_runs": (lambda r: {"S_distinct_entries": int(r[0]), "S_entries": int(r[1]), "St_distinct_entries": int(r[2]), "St_entries": int(r[3]),
+                                   "note": "chunks with byte-identical (col16, code, row length) runs share one run, so most of the matrix stream is served from cache: algorithmic bytes still count every entry once per launch (the loads are issued), the HBM bytes are in `traffic`"})(solver.array("streamRuns")),
+        "value_format": ("16-bit windowed col + int8 value code (3 B/nnz, lossless)" if c16 else "int32 col + int8 value code (5 B/nnz, lossless)") if coded
+                        else ("16-bit windowed col + fp64 value (10 B/nnz)" if c16 else "int32 col + fp64 value (12 B/nnz)"),
+        "csr_equivalent": {"bytes_per_launch": csr, "GBps": csr_gbps, "frac_of_peak_if_it_moved_them": csr_gbps / HBM_PEAK_GBS,
+                           "definition": "SURVEY 8(d): 12*nnz + 4*(rows+1) + 8*rows + 8*cols + 16*rows, over the production kernel's launch duration (not bytes it moves)"},
+        "other_kernels": {k: v for k, v in kern.items() if k != dom},
+    }
+    return roofline
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -333,6 +405,9 @@ def main():
                          "pass --gpus N selects the strong series with the environment: PS_BENCH_SCALING=strong [PS_BENCH_SCENE=coil PS_BENCH_RES=512]")
     ap.add_argument("--precond", choices=["jacobi", "identity", "chebyshev", "chebyshev64"], default="jacobi",
                     help="jacobi (default: the metric's configuration), identity (the reference's default), chebyshev (this library's polynomial preconditioner, degree 4)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the box calibration, the kernel roofline, the host-boundary step (pcie_inclusive_ms), the other "
+                         "preconditioners, the strong_512 block and the CPU baseline; a plain run (default) prints the headline line alone")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample-res", type=int, default=0, help="resolution of the CPU baseline's sample; 0 (default): the benchmark's own resolution — measured, not extrapolated — when the host has the memory")
     ap.add_argument("--bricks", default=os.environ.get("PS_BENCH_BRICKS", ""), help="N > 1: DXxDYxDZ ranks per axis (e.g. 2x2x2) instead of N z-slabs; "
@@ -341,8 +416,8 @@ def main():
                     help="N > 1: rccl = one GPU per rank over RCCL/xGMI (the measured configuration); tcp = host-staged sockets, all ranks "
                          "may share GPU 0 — a REHEARSAL of the multi-process path on a single-GPU box, not a performance number")
     ap.add_argument("--no-strong-512", action="store_true", default=os.environ.get("PS_BENCH_NO_STRONG", "") not in ("", "0"),
-                    help="skip the strong_512 block (BASELINE config 4: 3 steps of the 512^3 coil cut N ways, appended to the line of every default run)")
-    ap.add_argument("--no-other-preconditioners", action="store_true", help="skip the identity / Chebyshev lines that follow the headline (SURVEY 8(d) config 3)")
+                    help="skip the strong_512 block (BASELINE config 4: 3 steps of the 512^3 coil cut N ways, appended to the line of every --full run)")
+    ap.add_argument("--no-other-preconditioners", action="store_true", help="skip the identity / Chebyshev lines that follow the headline in a --full run (SURVEY 8(d) config 3)")
     ap.add_argument("--strong-res", type=int, default=int(os.environ.get("PS_BENCH_STRONG_RES", "512")), help="resolution of the strong_512 block (tests use a small one)")
     ap.add_argument("--maxit", type=int, default=0, help="cap on solver iterations (profiling runs only; 0 = node default 5000)")
     ap.add_argument("--dump-outputs", metavar="DIR", default="",
@@ -487,7 +562,7 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    box = box_calibration() if rank == 0 else None
+    box = box_calibration() if rank == 0 and args.full else None
     for _ in range(args.warmup):
         solver.step_device()
     barrier()
@@ -502,7 +577,7 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     ms_per_step = elapsed * 1e3 / max(args.steps, 1)
-    if args.dump_outputs:                # before the kernel micro-benchmarks below overwrite the solver's vectors
+    if args.dump_outputs:                # before the kernel micro-benchmarks of --full overwrite the solver's vectors
         dump_outputs(solver, args.dump_outputs, "_rank%d" % rank if world > 1 else "", DUMP_BUDGET_BYTES // world)
 
     st = solver.stats
@@ -516,68 +591,7 @@ def main():
     else:
         nsys_total = nsys
 
-    # roofline of the dominant kernels, measured live with HIP events on the solver stream
-    coded = bool(solver.array("valuesCoded")[0])
-    c16 = int(solver.array("columns16")[0]) == 3
-    kern = {}
-    # the PCG step as the solve ran it: four kernels (S, tiles, St with the residual update in its epilogue, x/p update) on
-    # the coded stream, five (S, tiles, St, r update, x/p update) otherwise — the five-kernel ones stay listed: they are what
-    # the distributed, Chebyshev and fallback-stream solves launch
-    fused = int(solver.array("fusedStep")[0]) == 1
-    rpl = solver.array("rowPerLane")
-    ell = int(rpl[0]) == 3                                  # both products on the row-per-lane kernels
-    names = (["spmv_St_r", "cg_update_xp_u"] if fused else []) + ["spmv_St", "spmv_S", "apply", "tiles", "cg_update_r", "cg_update_xp"]
-    if coded and c16:
-        names += ["spmv_St_fp64", "spmv_S_fp64"]     # the pipelined kernels on fp64 values (10 B/nnz): the non-dyadic-weights fallback
-    names += ["spmv_St_csr", "spmv_S_csr"]            # the one-shot kernels on the plain CSR (12 B/nnz): the last-resort fallback
-    # the five kernels of a CG iteration are timed IN SEQUENCE ("seq:": the loop's predecessor kernel runs, untimed, before
-    # every timed launch: what rocprof sees in a real solve); "replayed_ms" is the same kernel launched back to back
-    in_loop = ("spmv_St_r", "cg_update_xp_u", "spmv_St", "spmv_S", "tiles", "cg_update_r", "cg_update_xp")
-    for name in names:
-        ms, by = solver.bench_kernel(("seq:" + name) if name in in_loop else name, 20)
-        kern[name] = {"ms": ms, "algorithmic_bytes": by, "GBps": by / (ms * 1e-3) / 1e9 if ms > 0 else 0.0,
-                      "frac": by / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS if ms > 0 else 0.0}
-        if name in in_loop:
-            kern[name]["replayed_ms"] = solver.bench_kernel(name, 20)[0]
-    dom = "spmv_St_r" if fused else "spmv_St"
-    mode = 3 if fused else 0
-    traffic, traffic_source = _latest_traffic("k_spmv_St_r" if fused else "k_spmv_St") if (n == 256 and world == 1 and scene_name == "cavity") else (None, None)
-    # achieved = the bytes the production kernel has to move per launch (its stored matrix format + the vectors, each once)
-    # / its launch duration: the HBM utilisation of the kernel as it runs.  The production kernel streams a lossless 3 B/nnz
-    # encoding of the matrix, so this is FEWER bytes than SURVEY section 8(d)'s CSR figure (12 B/nnz + row pointers +
-    # vectors); that figure over the same launch duration is reported beside it ("csr_equivalent": it can exceed the
-    # HBM peak, which only says the kernel beats a CSR SpMV running at the roofline).  Every fraction in "other_kernels" is
-    # that kernel's OWN stored bytes over its OWN measured duration (the fallbacks are timed as themselves).
-    # must-move bytes: the stored bytes minus the part of the 3 B/nnz matrix stream that chunks sharing a run read from cache —
-    # the vectors (each once), the per-row streams, the chunk records and the DISTINCT stream entries: what has to cross the HBM interface
-    # per launch.  `traffic / must_move_bytes` is the re-fetch factor of the gathers (S 2.08x, St 1.34x at the end of r03).
-    runs = [int(v) for v in solver.array("streamRuns")]          # S distinct, S entries, St distinct, St entries
-    if coded and c16:
-        for nm, (dist_e, all_e) in (("spmv_S", (runs[0], runs[1])), ("spmv_St", (runs[2], runs[3])), ("spmv_St_r", (runs[2], runs[3]))):
-            if nm in kern:
-                kern[nm]["must_move_bytes"] = kern[nm]["algorithmic_bytes"] - 3.0 * (all_e - dist_e)
-    ms = kern[dom]["ms"]
-    csr = kern["spmv_St_csr"]["algorithmic_bytes"]
-    csr_gbps = csr / (ms * 1e-3) / 1e9 if ms > 0 else 0.0
-    roofline = {
-        "bound": "hbm", "kernel": ("k_spmv_St_ell<%d,POL,FX> (one lane per row on the kind-major numbering; POL = cache policy of its streams%s)" % (mode, "; MODE 3: r -= alpha A p in the epilogue, FX = 3: the plain single-domain step (coded uInv, no halo rows) — run as k_spmv_St_ell2<POL>, two 64-row units in flight per wave, unless PS_ST_DUAL=0" if fused else "")) if ell else
-                                  ("k_spmv_St_pipe<%d,NV,%s,POL> (NV = 1 or 2 four-entry groups per lane, by the fullest chunk; POL = cache policy of its streams%s)" % (mode, "false" if coded else "true", "; MODE 3: r -= alpha A p in the epilogue" if fused else "") if c16 else "k_spmv_St<0,6,%s>" % ("true" if coded else "false")),
-        "achieved": kern[dom]["GBps"], "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": kern[dom]["frac"],
-        "traffic": traffic, "traffic_source": traffic_source,
-        "algorithmic_bytes_per_launch": kern[dom]["algorithmic_bytes"], "avg_launch_ms": ms,
-        "must_move_bytes": kern[dom].get("must_move_bytes"),
-        "numbering": {0: "voxel-major (kinds of DOF / faces of a voxel adjacent)", 3: "kind-major inside every k-plane of a 16^3 lattice block (DOFs and face rows)"}.get(int(rpl[1]), "mixed (%d)" % int(rpl[1])),
-        "algorithmic_bytes_definition": ("stored format: 3*nnz (16-bit windowed column + int8 value code; padded slots of the row-per-lane layout NOT counted) + %s80 B per chunk "
-                                         "+ 8*cols (t once) + 8*rows (p) + 1*rows (coded uInv) + %s") % ("" if ell else "1*rows (row length) + ", "16*rows (r read + written) + 2*rows (Jacobi diagonal, stored in 16 bits: the upper half of its fp32 value); A p is not stored" if fused else "8*rows (y)") if (coded and c16) else
-                                        "CSR: (12 | 10 | 5)*nnz + 4*(rows+1) + 8*rows (y) + 8*cols (x once) + 16*rows (fused epilogue)",
-        "stream_runs": (lambda r: {"S_distinct_entries": int(r[0]), "S_entries": int(r[1]), "St_distinct_entries": int(r[2]), "St_entries": int(r[3]),
-                                   "note": "chunks with byte-identical (col16, code, row length) runs share one run, so most of the matrix stream is served from cache: algorithmic bytes still count every entry once per launch (the loads are issued), the HBM bytes are in `traffic`"})(solver.array("streamRuns")),
-        "value_format": ("16-bit windowed col + int8 value code (3 B/nnz, lossless)" if c16 else "int32 col + int8 value code (5 B/nnz, lossless)") if coded
-                        else ("16-bit windowed col + fp64 value (10 B/nnz)" if c16 else "int32 col + fp64 value (12 B/nnz)"),
-        "csr_equivalent": {"bytes_per_launch": csr, "GBps": csr_gbps, "frac_of_peak_if_it_moved_them": csr_gbps / HBM_PEAK_GBS,
-                           "definition": "SURVEY 8(d): 12*nnz + 4*(rows+1) + 8*rows + 8*cols + 16*rows, over the production kernel's launch duration (not bytes it moves)"},
-        "other_kernels": {k: v for k, v in kern.items() if k != dom},
-    }
+    roofline = kernel_roofline(solver, n == 256 and world == 1 and scene_name == "cavity") if args.full else None
 
     link = "RCCL halo exchange + all-reduce" if transport_used == "rccl" else "host-staged TCP transport (%s; not the RCCL number)" % transport_used
     if world == 1:
@@ -605,9 +619,9 @@ def main():
         "cg_iterations": iters, "cg_iters_per_s": iters / (solve_ms * 1e-3) if solve_ms > 0 else 0.0,
         "system_dofs": nsys_total, "dof_iterations_per_s": nsys_total * iters / (solve_ms * 1e-3) if solve_ms > 0 else 0.0, "active_faces": solver.nA, "regions": solver.nRegions, "result": int(st.result),
         "stage_ms": {abi.STAGE_NAMES[i]: float(st.stage_ms[i]) for i in range(len(abi.STAGE_NAMES))},
-        "roofline": roofline,
-        "box": box,
     }
+    if args.full:
+        out.update(roofline=roofline, box=box)
     if transport_used:
         out["transport"] = transport_used
     if dist is not None:
@@ -628,18 +642,18 @@ def main():
                 "samples": {"exchange": min(d["exchange_samples"] for d in allst), "allreduce": min(d["allreduce_samples"] for d in allst)},
                 "note": "exchange = one transport timed with events on the rank's comm stream at the end of every 25-iteration batch; it runs UNDER the S / St chunks that need no halo value when overlap is true",
             }
-    if world == 1:
+    if args.full and world == 1:
         # the boundary as the Houdini shim uses it: host fp32 fields in, velocity / valid fields out (polystokes_step)
         t0 = time.perf_counter()
         solver.step(sc, p)
         out["pcie_inclusive_ms"] = (time.perf_counter() - t0) * 1e3
     # BASELINE config 4 / north_star's "1 -> 8-GPU scaling curve at 512^3" from the SAME invocation: the 512^3 coiling column cut
     # N ways (1: single domain; 2: z-slabs; 4: 2x2x1 bricks; 8: 2x2x2 bricks), 1 warm-up + 3 timed steps, after the headline
-    # measurement and on the same communicator — a driver that only passes --gpus N still records the strong series.
+    # measurement and on the same communicator — a --full run that only passes --gpus N still records the strong series.
     # "Jacobi-PCG and identity-PCG both reported" — the headline above is the metric's Jacobi; the reference's
     # live default (identity: exec/HDK_PolyStokesSolver_Preconditioners.cpp:4-9,31-35) and this library's polynomial preconditioner
     # follow from the same invocation, 1 warm-up + 3 steps each, same scene, same resident fields
-    if world == 1 and scene_name == "cavity" and args.maxit == 0 and not args.no_other_preconditioners:
+    if args.full and world == 1 and scene_name == "cavity" and args.maxit == 0 and not args.no_other_preconditioners:
         others = {}
         # chebyshev4: the polynomial with its inner vectors stored as fp32 (PS_PRE_CHEBYSHEV_F32, r06; every sum, r, the outer PCG and its stop
         # rule fp64); chebyshev4_fp64: the all-fp64 polynomial of r04 / r05 under the same key those rounds reported it
@@ -670,7 +684,7 @@ def main():
         p.preconditionerDegree = 0
         out["other_preconditioners"] = others
     redundant = strong and scene_name == "coil" and n == args.strong_res
-    if not args.no_strong_512 and not redundant and args.maxit == 0:
+    if args.full and not args.no_strong_512 and not redundant and args.maxit == 0:
         # the headline is measured: whatever happens in this block (out of memory at 78 M DOFs, a solver exception) must not lose the line,
         # and with N > 1 no rank may be left waiting in a barrier — the ranks agree on success before the next collective
         try:
@@ -684,7 +698,7 @@ def main():
             if int(t.item()) != 1 and ok:
                 blk, ok, why = None, False, "another rank failed"
         out["strong_512"] = blk if ok else {"error": why}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.precond.startswith("chebyshev") and scene_name == "cavity":   # the CPU leg times the reference's own (Jacobi / identity) PCG iteration on the headline scene
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.precond.startswith("chebyshev") and scene_name == "cavity":   # the CPU leg times the reference's own (Jacobi / identity) PCG iteration on the headline scene
         out["cpu_baseline"] = cpu_baseline(n ** 3, nsys, iters, dict(tile=16, pad=2, precond=kw["precond"]), args.cpu_sample_res, second_res=(96 if n > 96 else 0), bench_res=n)
     if rank == 0:
         sys.stdout.flush()

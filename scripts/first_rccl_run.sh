@@ -5,7 +5,7 @@
 #
 # Per GPU count N it runs, one process per GPU (python -m torch.distributed.run, rendezvous on 127.0.0.1; gloo only carries the RCCL unique
 # id, the barriers and the max of the wall time — the data path is the library's own RCCL communicator):
-#   (1) the driver's default invocation            bench.py --gpus N --steps 5 --warmup 2
+#   (1) the full invocation                        bench.py --gpus N --full --steps 5 --warmup 2
 #       -> headline (256^3 per GPU, weak: z-slabs) + its `multi_gpu` block + the `strong_512` block (the 512^3 coil of BASELINE config 4 cut N
 #          ways: single domain, 2 slabs, 2x2x1, 2x2x2 bricks) — the north star's curve from the invocation the driver itself uses;
 #   (2) the strong series on its own, bricks:      bench.py --gpus N --scaling strong --scene coil --res 512 --bricks DIMS --steps 5 --warmup 2
@@ -74,7 +74,7 @@ PY
 : > "$OUT/summary.txt"
 { echo "# first multi-GPU run: $(date -u)  rehearsal=$REH  counts: $COUNTS"; rocm-smi --showtopo 2>/dev/null | head -40; } >> "$OUT/summary.txt"
 for N in $COUNTS; do
-    run default_n$N $N --steps $STEPS --warmup $WARM --res $RES_WEAK --strong-res $STRONG_BLOCK $([ "$REH" = "1" ] && echo --cpu-sample-res 32)
+    run default_n$N $N --full --steps $STEPS --warmup $WARM --res $RES_WEAK --strong-res $STRONG_BLOCK $([ "$REH" = "1" ] && echo --cpu-sample-res 32)
     B=$(bricks_for $N)
     if [ "$N" = "1" ]; then
         run strong_coil_n1 1 --scaling strong --scene coil --res $RES_STRONG --steps $STEPS --warmup $WARM --no-strong-512 --no-cpu-baseline --no-other-preconditioners

@@ -11,7 +11,7 @@ cd /tmp && export TMPDIR=/tmp
 i=0
 for C in "$@"; do
   i=$((i+1))
-  if rocprofv3 --pmc $C --kernel-trace -d $OUT/p$i -o run --output-format csv -- python3 $R/bench.py --steps 1 --warmup 0 --maxit 20 --no-cpu-baseline --no-strong-512 > $OUT/p$i.log 2>&1; then
+  if rocprofv3 --pmc $C --kernel-trace -d $OUT/p$i -o run --output-format csv -- python3 $R/bench.py --full --steps 1 --warmup 0 --maxit 20 --no-cpu-baseline --no-strong-512 > $OUT/p$i.log 2>&1; then
     echo "pass $i ok: $C" >> $OUT/progress
   else
     echo "pass $i FAILED: $C" >> $OUT/progress

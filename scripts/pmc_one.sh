@@ -5,8 +5,8 @@ TAG=$1; ENVS=$2
 R=$PWD; OUT=$R/gpurun_out/$TAG; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 for S in $ENVS; do export $S; done
-rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $OUT/pmc_fetch -o run --output-format csv -- python3 $R/bench.py --steps 1 --warmup 0 --maxit 20 --no-cpu-baseline --no-strong-512 > $OUT/f.log 2>&1
-rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $OUT/pmc_write -o run --output-format csv -- python3 $R/bench.py --steps 1 --warmup 0 --maxit 20 --no-cpu-baseline --no-strong-512 > $OUT/w.log 2>&1
+rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $OUT/pmc_fetch -o run --output-format csv -- python3 $R/bench.py --full --steps 1 --warmup 0 --maxit 20 --no-cpu-baseline --no-strong-512 > $OUT/f.log 2>&1
+rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $OUT/pmc_write -o run --output-format csv -- python3 $R/bench.py --full --steps 1 --warmup 0 --maxit 20 --no-cpu-baseline --no-strong-512 > $OUT/w.log 2>&1
 cd $R
 python3 - "$OUT" <<'PY' > gpurun_out/$TAG.txt
 import csv, glob, sys, collections

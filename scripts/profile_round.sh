@@ -9,14 +9,14 @@ TAG=${1:-prof}
 R=$PWD
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
-python3 bench.py > $OUT/bench.json 2> $OUT/bench.err
+python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 echo "bench done" > $OUT/progress
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -d $OUT/stats -o run --output-format csv -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-strong-512 --no-other-preconditioners > $OUT/stats.log 2>&1
+rocprofv3 --kernel-trace --stats -d $OUT/stats -o run --output-format csv -- python3 $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-strong-512 --no-other-preconditioners > $OUT/stats.log 2>&1
 echo "stats done" >> $OUT/progress
-rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $OUT/pmc_fetch -o run --output-format csv -- python3 $R/bench.py --steps 1 --warmup 0 --maxit 20 --no-cpu-baseline --no-strong-512 --no-other-preconditioners > $OUT/pmc_fetch.log 2>&1
+rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $OUT/pmc_fetch -o run --output-format csv -- python3 $R/bench.py --full --steps 1 --warmup 0 --maxit 20 --no-cpu-baseline --no-strong-512 --no-other-preconditioners > $OUT/pmc_fetch.log 2>&1
 echo "fetch done" >> $OUT/progress
-rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $OUT/pmc_write -o run --output-format csv -- python3 $R/bench.py --steps 1 --warmup 0 --maxit 20 --no-cpu-baseline --no-strong-512 --no-other-preconditioners > $OUT/pmc_write.log 2>&1
+rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $OUT/pmc_write -o run --output-format csv -- python3 $R/bench.py --full --steps 1 --warmup 0 --maxit 20 --no-cpu-baseline --no-strong-512 --no-other-preconditioners > $OUT/pmc_write.log 2>&1
 echo "write done" >> $OUT/progress
 cd $R
 python3 scripts/pmc_summarize.py $OUT > $OUT/pmc_traffic.json

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Setup-stage kernels of one 256^3 cavity step against their rooflines.
 
-usage (GPU box):  rocprofv3 --kernel-trace --stats -d DIR -o run --output-format csv -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline
+usage (GPU box):  rocprofv3 --kernel-trace --stats -d DIR -o run --output-format csv -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline
                   python3 scripts/setup_roofline.py DIR/run_kernel_stats.csv [res] > profiles/r03_setup_roofline.json
 
 Durations: rocprofv3's per-kernel averages of that run (setup runs twice in it: bench.py's device step and its host-boundary step).

@@ -208,7 +208,7 @@ def test_multiprocess_list_mismatch_fails_every_rank(tmp_path):
 
 
 def test_bench_two_ranks_produces_one_line_whatever_the_transport(tmp_path):
-    """`python bench.py --gpus 2` without a launcher: spawns one process per rank, rendezvous over gloo, and prints ONE JSON
+    """`python bench.py --gpus 2 --full` without a launcher: spawns one process per rank, rendezvous over gloo, and prints ONE JSON
     line.  With two GPUs the ranks talk over RCCL; on a one-GPU box RCCL refuses the duplicate device, every rank agrees on that
     (gloo) before any further collective, and all of them switch to the host-staged transport — the line says which."""
     import json
@@ -220,7 +220,7 @@ def test_bench_two_ranks_produces_one_line_whatever_the_transport(tmp_path):
         two_gpus = False
     env = dict(os.environ, MASTER_PORT=str(_free_port_base(1)))
     pr = subprocess.run([sys.executable, os.path.join(os.path.dirname(HERE), "bench.py"), "--gpus", "2", "--res", "32", "--steps", "1", "--warmup", "1",
-                         "--no-cpu-baseline", "--strong-res", "96"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=420, env=env)
+                         "--full", "--no-cpu-baseline", "--strong-res", "96"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=420, env=env)
     assert pr.returncode == 0, pr.stderr[-3000:]
     lines = [l for l in pr.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, pr.stdout[-2000:]
@@ -280,12 +280,12 @@ def test_rccl_communicator_next_to_a_live_torch_context():
 
 
 def test_bench_single_gpu_line_keeps_the_contract(tmp_path):
-    """`python bench.py` (N = 1) on a small stand-in (64^3 cavity, 64^3 coil for the strong block, a 32^3 CPU sample): ONE JSON line with the
+    """`python bench.py --full` (N = 1) on a small stand-in (64^3 cavity, 64^3 coil for the strong block, a 32^3 CPU sample): ONE JSON line with the
     driver's keys, the roofline and cpu_baseline objects, and r05's additions — the identity / Chebyshev lines beside the Jacobi headline
      and the box calibration; --dump-outputs writes the last timed step's fields whole (they fit the budget at 64^3)."""
     import json
     dump = tmp_path / "out"
-    pr = subprocess.run([sys.executable, os.path.join(os.path.dirname(HERE), "bench.py"), "--res", "64", "--steps", "2", "--warmup", "1", "--strong-res", "64",
+    pr = subprocess.run([sys.executable, os.path.join(os.path.dirname(HERE), "bench.py"), "--res", "64", "--steps", "2", "--warmup", "1", "--full", "--strong-res", "64",
                          "--cpu-sample-res", "32", "--dump-outputs", str(dump)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert pr.returncode == 0, pr.stderr[-3000:]
     lines = [l for l in pr.stdout.splitlines() if l.strip()]
@@ -320,6 +320,26 @@ def test_bench_single_gpu_line_keeps_the_contract(tmp_path):
     assert files["dimData.npy"].dtype == np.float64 and files["dimData.npy"].size == 27
     assert list(files["solve.npy"][[0, 2]]) == [d["result"], d["cg_iterations"]]
     assert sum(os.path.getsize(dump / f) for f in files) <= 64 * 1000 * 1000
+
+
+def test_bench_plain_line_is_the_headline_alone(tmp_path):
+    """`python bench.py` without --full: the headline keys and the timed step's outputs, none of the blocks that take runs of their own."""
+    import json
+    dump = tmp_path / "out"
+    pr = subprocess.run([sys.executable, os.path.join(os.path.dirname(HERE), "bench.py"), "--res", "64", "--steps", "2", "--warmup", "1",
+                         "--dump-outputs", str(dump)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+    assert pr.returncode == 0, pr.stderr[-3000:]
+    lines = [l for l in pr.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, pr.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["metric"] == "Stokes-solve wall ms/step (assembly+PCG) on 256^3 grid; CG iters/sec"
+    assert d["unit"] == "ms/step" and d["higher_is_better"] is False and d["dtype"] == "f64" and d["value"] == d["ms_per_step"] > 0
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["result"] == 1 and d["cg_iterations"] > 0
+    for k in ("roofline", "box", "pcie_inclusive_ms", "other_preconditioners", "strong_512", "cpu_baseline"):
+        assert k not in d, k
+    solve = np.load(dump / "solve.npy")
+    assert list(solve[[0, 2]]) == [d["result"], d["cg_iterations"]]
+    assert {"vel" + a + ".npy" for a in "XYZ"} <= set(os.listdir(dump))
 
 
 def test_bench_dump_outputs_sample_within_the_budget(tmp_path):
