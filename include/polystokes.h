@@ -258,6 +258,45 @@ int32_t ps_set_surface_tension(ps_context* ctx, double sigma);
 enum ps_solid_boundary { PS_SOLID_NO_SLIP = 0, PS_SOLID_FREE_SLIP = 1 };
 int32_t ps_set_solid_boundary(ps_context* ctx, int32_t mode);
 
+/* Non-Newtonian viscosity (extension; the reference node takes the viscosity field as a fixed input).  A context setting like
+ * ps_set_solid_boundary: it persists across ps_upload_fields and is read by every later setup.  PS_RHEOLOGY_NEWTONIAN (the default; the
+ * other members are then ignored) launches exactly the kernels of a context that never made the call.  PS_RHEOLOGY_HERSCHEL_BULKLEY makes
+ * the uploaded `viscosity` field the consistency K of the law (a scalar viscosity is a constant field) and replaces it, for the setup, by
+ * mu_c computed on the device after the final labels exist.  A face sample is used iff its label is neither UNSOLVED nor UNASSIGNED (the
+ * `valid` output of ps_download_fields).  For cell c and axes a != b, in fp64 from the fp32 inputs:
+ *   D_aa(c) = (u_a[c+e_a] - u_a[c]) / dx if both a-faces of c are used, else 0;
+ *   G_ab(c) = du_a/dx_b = the mean, over those of the two a-faces f in {c, c+e_a} for which it exists, of (u_a[f+e_b] - u_a[f-e_b]) / (2 dx);
+ *             it exists when both samples lie inside the a-face grid and are used; G_ab(c) = 0 when it exists for neither face;
+ *   D_ab = (G_ab + G_ba) / 2,  gammaDot_c = sqrt(2 sum_a D_aa^2 + 4 sum_{a<b} D_ab^2);
+ *   s = max(gammaDot_c, minShearRate),  mu_c = min(max(K_c s^(n-1) + yieldStress / s, minViscosity), maxViscosity)  (n = flowIndex; with
+ *   n == 1 the power is skipped, so K_c * 1 is exact), stored as fp32.  The uploaded field is kept (the passes need K).
+ * The setup samples mu like an uploaded field (trilinear, no constant-field shortcut); the value and diagonal formats follow from it.
+ * The velocity read is the uploaded `vel` for the first solve of a step.  With passes = k > 0, ps_step_device and polystokes_step repeat
+ * k times on a single domain: a full setup that reads the last pass's output velocity, a solve started from the last pass's [p; tau]
+ * (through the warm-start grids; the first solve honours ps_set_warm_start, PS_WARM_PREVIOUS_STEP carries the last pass's solution),
+ * recovery and write-back.  The rhs always comes from the uploaded `vel`.  Stats hold the last pass's result, error and iterations; the
+ * time entries and stage_ms are summed over the passes.  A pass whose result is neither SUCCESS nor a kept NOCONVERGE ends the step with
+ * that result (an interrupt: PS_INCOMPLETE, the output velocity equal to the input).  ps_setup_device / ps_solve_device are single-shot
+ * (passes ignored).  Slab and brick ranks compute mu on their own grid (every read lies within 3 cells of an owned face, inside the halo
+ * block); passes > 0 on a decomposition makes the step fail on every rank (PS_FAILED, "rheology passes need a single domain").
+ * Orthogonal to surface tension, free-slip solids, the density field and warm start.  PS_INVALID (reason in ps_last_error, the previous
+ * setting kept): r null, an unknown model, passes outside 0..8, flowIndex outside (0, 4], yieldStress negative, minShearRate not positive,
+ * not 0 < minViscosity <= maxViscosity, or a value not finite.
+ * Arrays: "rheologyModel" (int32, 1: the model of the last setup), "rheologyStrainRate" (fp32 cell grid: gammaDot_c of the last setup),
+ * "rheologyViscosity" (fp32 cell grid: the mu_c the last setup used), "rheologyIterations" (int32, one per solve of the last step: the
+ * PCG iterations of each pass); the last three only with the model on. */
+enum ps_rheology_model { PS_RHEOLOGY_NEWTONIAN = 0, PS_RHEOLOGY_HERSCHEL_BULKLEY = 1 };
+typedef struct ps_rheology {
+    int32_t model;          /* ps_rheology_model */
+    int32_t passes;         /* extra Picard passes of ps_step_device / polystokes_step, 0..8 */
+    double flowIndex;       /* n, 0 < n <= 4 */
+    double yieldStress;     /* tau_y >= 0 */
+    double minShearRate;    /* regularisation floor of the shear rate, > 0 */
+    double minViscosity;    /* clamp, 0 < minViscosity <= maxViscosity, both finite */
+    double maxViscosity;
+} ps_rheology;
+int32_t ps_set_rheology(ps_context* ctx, const ps_rheology* r);
+
 /* solveGasSubclass equivalent on host buffers: upload + step + download (HDK_PolyStokes.C:222-609). */
 int32_t polystokes_step(ps_context* ctx, const ps_params* p, const ps_fields_in* in,
                         ps_fields_out* out, ps_stats* stats);

@@ -26,7 +26,7 @@ EXPORTED_SYMBOLS = [
     "ps_set_slab", "ps_set_brick", "ps_comm_unique_id", "ps_comm_init_rccl", "ps_comm_selftest", "ps_comm_init_tcp", "ps_dist_stats",
     "ps_group_create", "ps_group_destroy", "ps_group_rank", "ps_group_step",
     "ps_set_warm_start", "ps_download_solution_fields", "ps_upload_density_field", "ps_set_surface_tension",
-    "ps_set_solid_boundary",
+    "ps_set_solid_boundary", "ps_set_rheology",
 ]
 
 
@@ -118,6 +118,8 @@ def lib():
         L.ps_set_surface_tension.restype = C.c_int32
         L.ps_set_solid_boundary.argtypes = [C.c_void_p, C.c_int32]
         L.ps_set_solid_boundary.restype = C.c_int32
+        L.ps_set_rheology.argtypes = [C.c_void_p, C.POINTER(_abi.Rheology)]
+        L.ps_set_rheology.restype = C.c_int32
         _lib = L
     return _lib
 
@@ -129,7 +131,7 @@ def _kind(name):
     if name.endswith(("Labels", "Indices", ".col", ".ptr", "Region", "Perm", ".chunkInfo", ".chunkRep", ".code")) or name.startswith("faceRow"):
         return "i"
     if name in ("valuesCoded", "columns16", "diagonalsCoded", "fusedStep", "streamRuns", "rowPerLane", "chebInner32", "warmStartUsed", "densityField", "launchWalk",
-                "surfaceTensionReducedFaces", "solidBoundary", "solidSlipEdges"):
+                "surfaceTensionReducedFaces", "solidBoundary", "solidSlipEdges", "rheologyModel", "rheologyIterations"):
         return "i"
     if name in ("ownedX", "ownedY", "ownedZ"):
         return "f"
@@ -194,6 +196,16 @@ class Solver:
         """ps_set_solid_boundary: SOLID_NO_SLIP (0, the default) or SOLID_FREE_SLIP (1: no shear stress on the edges a solid cuts) for every
         later setup of this context, across uploads.  Returns the ps_result: INVALID for another mode (the previous setting kept)."""
         return self._check(self.L.ps_set_solid_boundary(self.h, int(mode)), allow=(1, -2))
+
+    def set_rheology(self, model=_abi.RHEOLOGY_HERSCHEL_BULKLEY, flow_index=1.0, yield_stress=0.0, min_shear_rate=1e-3,
+                     min_viscosity=1e-3, max_viscosity=1e6, passes=0):
+        """ps_set_rheology: the uploaded viscosity becomes the consistency K of the Herschel-Bulkley law
+        mu = clamp(K s^(n-1) + yield_stress / s, min_viscosity, max_viscosity), s = max(shear rate, min_shear_rate), for every later setup
+        of this context, across uploads; `passes` extra Picard passes per step (0..8).  RHEOLOGY_NEWTONIAN (0) is the default.  Returns
+        the ps_result: INVALID for an out-of-range value (the reason in last_error(), the previous setting kept)."""
+        r = _abi.Rheology(int(model), int(passes), float(flow_index), float(yield_stress), float(min_shear_rate), float(min_viscosity),
+                          float(max_viscosity))
+        return self._check(self.L.ps_set_rheology(self.h, C.byref(r)), allow=(1, -2))
 
     def solution_fields(self):
         """ps_download_solution_fields: the last solve's [p; tau] as dense fp32 grids (x fastest), keyed pressure, txx, tyy, tzz, tyz, txz, txy;
@@ -445,6 +457,11 @@ class Group:
     def set_solid_boundary(self, mode):
         """ps_set_solid_boundary on every rank (a context setting: it holds for every later step of the group)."""
         rc = [r.set_solid_boundary(mode) for r in self.ranks]
+        return rc[0]
+
+    def set_rheology(self, *args, **kw):
+        """ps_set_rheology on every rank (a context setting: it holds for every later step of the group)."""
+        rc = [r.set_rheology(*args, **kw) for r in self.ranks]
         return rc[0]
 
     def solve_scene(self, scene, params):

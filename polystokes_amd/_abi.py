@@ -65,6 +65,16 @@ class SolutionOut(C.Structure):
 WARM_NONE, WARM_PREVIOUS_STEP = 0, 1
 # ps_solid_boundary
 SOLID_NO_SLIP, SOLID_FREE_SLIP = 0, 1
+# ps_rheology_model
+RHEOLOGY_NEWTONIAN, RHEOLOGY_HERSCHEL_BULKLEY = 0, 1
+
+
+class Rheology(C.Structure):
+    """ps_rheology (ps_set_rheology): the viscosity law of every later setup of a context"""
+    _fields_ = [("model", C.c_int32), ("passes", C.c_int32), ("flowIndex", C.c_double), ("yieldStress", C.c_double),
+                ("minShearRate", C.c_double), ("minViscosity", C.c_double), ("maxViscosity", C.c_double)]
+
+
 # the grids of ps_download_solution_fields: name -> sample grid (SAMPLE_NAMES / grid_shapes), in ps_solution_out order
 SOLUTION_FIELDS = [("pressure", "center"), ("txx", "center"), ("tyy", "center"), ("tzz", "center"),
                    ("tyz", "edgeYZ"), ("txz", "edgeXZ"), ("txy", "edgeXY")]

@@ -559,8 +559,9 @@ BlockArgs makeArgs(ps_context* c) {
         A.lab[s] = c->labels[s].p; A.act[s] = c->activeIdx[s].p; A.reg[s] = c->reducedIdx[s].p; A.sys[s] = c->sysIdx[s].p;
     }
     for (int a = 0; a < 3; ++a) { A.faceRow[a] = c->faceRow[a].p; A.vel[a] = c->vel[a].p; A.cvel[a] = c->cvel[a].p; A.sysT[a] = c->sysIdxT[a].p; }
-    A.visc = c->viscosity.p;
-    A.viscUniform = c->viscUniform ? 1 : 0; A.viscValue = c->viscUniformValue;
+    const ps_context::ViscSource vs = c->viscSource();   // the uploaded field, or mu of ps_set_rheology
+    A.visc = vs.p;
+    A.viscUniform = vs.uniform; A.viscValue = vs.value;
     A.dens = c->densField ? c->density.p : nullptr; A.densMin = c->densMin; A.densMax = c->densMax;
     A.nCenter = c->nCenter; A.nEdge0 = c->nEdge[0]; A.nEdge1 = c->nEdge[1];
     A.nP = c->nPressures; A.nA = c->nActiveVs;

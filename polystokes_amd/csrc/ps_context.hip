@@ -191,6 +191,9 @@ void ps_context::setupPhase(int phase) {
         setupPhaseDone = -1;
         warmUsedHost = 0; warmX0Valid = false;
         arrays.clear();
+        if (rheoPass == 0) rheoIters.clear();   // (ps_set_rheology: one entry per solve of the step)
+        // Picard passes need the halo of the last pass's output velocity: a decomposition refuses them on every rank (ps_dist.hpp: distStep)
+        if (slabEnabled && rheoSet.model != PS_RHEOLOGY_NEWTONIAN && rheoSet.passes > 0) throw Error("rheology passes need a single domain");
         HIP_CHECK(hipSetDevice(device));
         setupState = std::make_shared<SetupState>(stream);
     }
@@ -236,6 +239,7 @@ void ps_context::setupPhase(int phase) {
     }
     T.mark(3);
     constructActiveIndices();
+    computeRheology();         // ps_set_rheology: mu from the final face labels (nothing with the Newtonian model)
     T.mark(4);
     if (P.doReducedRegions) {
         computeCenterOfMasses();
@@ -305,7 +309,8 @@ int ps_context::solveStage(ps_stats* stats) {
         T.mark(2);
         applySolutionToVelocity();
         // warm start: a kept PCG step (SUCCESS, or NOCONVERGE with keepNonConvergedResults; after the BiCGStab fallback too) carries its x
-        if (warmMode == PS_WARM_PREVIOUS_STEP && P.doSolve && P.solverType == PS_PCG_MATRIX_VECTOR_PRODUCTS && !slabEnabled) carryWarmStart();
+        // (also to the next Picard pass of the step: ps_set_rheology)
+        if ((warmMode == PS_WARM_PREVIOUS_STEP || rheoCarry) && P.doSolve && P.solverType == PS_PCG_MATRIX_VECTOR_PRODUCTS && !slabEnabled) carryWarmStart();
     } else {
         T.mark(2);
         for (int a = 0; a < 3; ++a)
@@ -318,6 +323,7 @@ int ps_context::solveStage(ps_stats* stats) {
     lastStats.stage_ms[PS_STAGE_WRITEBACK] = T.ms(2, 3);
     lastStats.result = result;
     lastStats.usedBiCGStab = usedBiCGStab;
+    if (rheoModelUsed != PS_RHEOLOGY_NEWTONIAN && P.doSolve) rheoIters.push_back(solveIterations);
     isSolved = true;
     registerArrays();
     if (stats) *stats = lastStats;
@@ -379,6 +385,14 @@ void ps_context::registerArrays() {
     reg("solidBoundary", &solidBoundaryUsed, 1, 4);   // the mode of the last setup (ps_set_solid_boundary)
     arrays["solidBoundary"].host = true;
     if (solidBoundaryUsed == PS_SOLID_FREE_SLIP) reg("solidSlipEdges", slipEdges.p, 1, 4);
+    reg("rheologyModel", &rheoModelUsed, 1, 4);   // the model of the last setup (ps_set_rheology)
+    arrays["rheologyModel"].host = true;
+    if (rheoModelUsed != PS_RHEOLOGY_NEWTONIAN) {
+        reg("rheologyStrainRate", rheoRate.p, g.count(0), 4);
+        reg("rheologyViscosity", rheoMu.p, g.count(0), 4);
+        reg("rheologyIterations", rheoIters.data(), (int64_t)rheoIters.size(), 4);   // PCG iterations of each solve of the last step
+        arrays["rheologyIterations"].host = true;
+    }
     if (P.preconditioner == PS_PRE_DIAGONAL) regp("dinv", dinv.p, nSystem, permSys.p, 0);
     if (isSolved) {
         regp("recoveredActiveVelocity", recovered.p, nActiveVs, permRow.p, 0);
@@ -651,9 +665,7 @@ int32_t ps_step_device(ps_context* c, ps_stats* st) {
             c->drainDeferred(true);
             return result;
         }
-        const int rc = c->setup(nullptr);
-        if (rc != PS_SUCCESS) { c->drainDeferred(true); return rc; }
-        const int result = c->solveStage(st);
+        const int result = c->stepWithPasses(st);   // setup + solve (and the Picard passes of ps_set_rheology)
         c->drainDeferred(true);             // (the solve stage ends with the stream synchronised)
         return result;
     })
@@ -717,6 +729,27 @@ int32_t ps_set_solid_boundary(ps_context* c, int32_t mode) {
         return PS_SUCCESS;
     })
 }
+int32_t ps_set_rheology(ps_context* c, const ps_rheology* r) {
+    if (!c) return PS_FAILED;
+    PS_TRY(c, {
+        std::string why;
+        auto finite = [](double v) { return std::isfinite(v); };
+        if (!r) why = "r is null";
+        else if (r->model != PS_RHEOLOGY_NEWTONIAN && r->model != PS_RHEOLOGY_HERSCHEL_BULKLEY)
+            why = "unknown model " + std::to_string(r->model) + " (0: Newtonian, 1: Herschel-Bulkley)";
+        else if (r->model == PS_RHEOLOGY_HERSCHEL_BULKLEY) {
+            if (r->passes < 0 || r->passes > 8) why = "passes must lie in 0..8";
+            else if (!finite(r->flowIndex) || !(r->flowIndex > 0.) || r->flowIndex > 4.) why = "flowIndex must lie in (0, 4]";
+            else if (!finite(r->yieldStress) || r->yieldStress < 0.) why = "yieldStress must be finite and not negative";
+            else if (!finite(r->minShearRate) || !(r->minShearRate > 0.)) why = "minShearRate must be finite and positive";
+            else if (!finite(r->minViscosity) || !finite(r->maxViscosity) || !(r->minViscosity > 0.) || r->maxViscosity < r->minViscosity)
+                why = "minViscosity and maxViscosity must be finite with 0 < minViscosity <= maxViscosity";
+        }
+        if (!why.empty()) { c->err = "ps_set_rheology: " + why; return PS_INVALID; }
+        c->rheoSet = *r;   // read by the next setup (computeRheology) and step (stepWithPasses)
+        return PS_SUCCESS;
+    })
+}
 int32_t ps_set_warm_start(ps_context* c, int32_t mode) {
     if (!c) return PS_FAILED;
     PS_TRY(c, {
@@ -759,9 +792,7 @@ int32_t polystokes_step(ps_context* c, const ps_params* p, const ps_fields_in* i
     if (!c) return PS_FAILED;
     PS_TRY(c, {
         c->upload(p, in);
-        const int rc = c->setup(nullptr);
-        if (rc != PS_SUCCESS) { c->drainDeferred(true); return rc; }
-        const int result = c->solveStage(st);
+        const int result = c->stepWithPasses(st);   // setup + solve (and the Picard passes of ps_set_rheology)
         c->drainDeferred(true);
         if (out) {
             const int rc2 = ps_download_fields(c, out);

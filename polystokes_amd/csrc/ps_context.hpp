@@ -125,6 +125,24 @@ struct ps_context {
     // "solidBoundary"; constructMatrixBlocks copies it).  slipEdges: free-slip edges counted by the St count pass (array "solidSlipEdges").
     int32_t solidBoundarySet = PS_SOLID_NO_SLIP, solidBoundaryUsed = PS_SOLID_NO_SLIP;
     ps::DevBuf<int32_t> slipEdges;
+    // Non-Newtonian viscosity (ps_set_rheology): rheoSet is the context setting, rheoModelUsed the model of the last setup (array
+    // "rheologyModel").  With the model on, computeRheology (ps_rheology.hip) writes mu_c / gammaDot_c into rheoMu / rheoRate from the velocity
+    // of rheoFromOut ? velOut : vel, and viscSource() hands rheoMu to the setup's samplers.  rheoPass / rheoCarry: the Picard pass in flight
+    // (0: the step's first solve) and whether another pass follows it (stepWithPasses); rheoIters: the PCG iterations of each solve of the step.
+    ps_rheology rheoSet{PS_RHEOLOGY_NEWTONIAN, 0, 1., 0., 1e-3, 1e-3, 1e6};
+    int32_t rheoModelUsed = PS_RHEOLOGY_NEWTONIAN;
+    ps::DevBuf<float> rheoMu, rheoRate;
+    bool rheoFromOut = false, rheoCarry = false;
+    int rheoPass = 0;
+    std::vector<int32_t> rheoIters;
+    void computeRheology();                  // ps_rheology.hip: after constructActiveIndices, before the tile matrices
+    int stepWithPasses(ps_stats* stats);     // ps_rheology.hip: setup + solve, then the Picard passes of a single-domain step
+    // The one viscosity field the setup samples (ps_blocks.hip / ps_tiles.hip makeArgs): the uploaded one, or mu with the model on
+    struct ViscSource { const float* p; int uniform; float value; };
+    ViscSource viscSource() const {
+        if (rheoModelUsed != PS_RHEOLOGY_NEWTONIAN) return ViscSource{rheoMu.p, 0, 0.f};
+        return ViscSource{viscosity.p, viscUniform ? 1 : 0, viscUniformValue};
+    }
 
     // ---- inputs (fp32 Houdini voxel arrays, HDK_PolyStokes.C:235-246) ----
     ps::DevBuf<float> surface, collision, viscosity, density, vel[3], cvel[3];

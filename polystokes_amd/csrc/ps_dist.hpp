@@ -1430,6 +1430,7 @@ int distStep(Dist& D, ps_stats* stats) {
         c->lastStats.stage_ms[PS_STAGE_SOLVE] = c->lastStats.solveData[3];
         c->lastStats.result = result;
         c->lastStats.usedBiCGStab = c->usedBiCGStab;
+        if (c->rheoModelUsed != PS_RHEOLOGY_NEWTONIAN && c0->P.doSolve) c->rheoIters.push_back(c->solveIterations);   // (ps_set_rheology)
         c->isSolved = true;
         c->registerArrays();
     }

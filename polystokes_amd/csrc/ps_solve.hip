@@ -740,7 +740,8 @@ int ps_context::solve() {
 
     HIP_CHECK(hipMemsetAsync(dotPartials3.p, 0, VGRID * sizeof(double), stream));
     // warm start (ps_set_warm_start): x0 = the carried solution, r0 = b - A x0 (pcg.h:284); from here on the PCG is the same
-    const bool warm = warmMode == PS_WARM_PREVIOUS_STEP && gatherWarmStart();
+    // (a Picard pass of ps_set_rheology starts from the last pass's solution the same way)
+    const bool warm = (warmMode == PS_WARM_PREVIOUS_STEP || rheoPass > 0) && gatherWarmStart();
     warmUsedHost = warm ? 1 : 0;
     if (warm) {
         applyOperator(x.p, Ap.p, dotPartials.p);

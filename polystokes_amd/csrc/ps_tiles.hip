@@ -741,8 +741,9 @@ TileArgs makeArgs(ps_context* c) {
     A.g = c->g; A.dx = c->dx; A.rho = c->rho;
     for (int s = 0; s < 7; ++s) { A.lab[s] = c->labels[s].p; A.reg[s] = c->reducedIdx[s].p; }
     for (int a = 0; a < 3; ++a) A.vel[a] = c->vel[a].p;
-    A.visc = c->viscosity.p;
-    A.viscUniform = c->viscUniform ? 1 : 0; A.viscValue = c->viscUniformValue;
+    const ps_context::ViscSource vs = c->viscSource();   // the uploaded field, or mu of ps_set_rheology
+    A.visc = vs.p;
+    A.viscUniform = vs.uniform; A.viscValue = vs.value;
     A.dens = c->densField ? c->density.p : nullptr; A.densMin = c->densMin; A.densMax = c->densMax;
     for (int a = 0; a < 3; ++a) A.densFace[a] = c->densFace[a].p;
     A.COM = c->COM.p;

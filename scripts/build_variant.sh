@@ -6,7 +6,7 @@ set -e
 N=$1; shift
 cd $(dirname $0)/../polystokes_amd/csrc
 mkdir -p ../variants _build/$N
-for f in ps_context ps_grid ps_tiles ps_blocks ps_surface; do [ -f _build/$f.o ] || make -s _build/$f.o; done
+for f in ps_context ps_grid ps_tiles ps_blocks ps_surface ps_rheology; do [ -f _build/$f.o ] || make -s _build/$f.o; done
 SRC=ps_solve.hip
 INC=""
 if echo "$@" | grep -q PS_EXP_GATHER_MASK; then
@@ -18,4 +18,4 @@ if echo "$@" | grep -q PS_EXP_GATHER_MASK; then
   SRC=_build/$N/src/ps_solve.hip
 fi
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off "$@" -c $SRC -o _build/$N/ps_solve.o
-/opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o ../variants/lib_$N.so _build/ps_context.o _build/ps_grid.o _build/ps_tiles.o _build/ps_blocks.o _build/ps_surface.o _build/$N/ps_solve.o
+/opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o ../variants/lib_$N.so _build/ps_context.o _build/ps_grid.o _build/ps_tiles.o _build/ps_blocks.o _build/ps_surface.o _build/ps_rheology.o _build/$N/ps_solve.o

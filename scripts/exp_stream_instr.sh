@@ -8,7 +8,7 @@
 set -e
 cd $(dirname $0)/../polystokes_amd/csrc
 mkdir -p ../variants
-for f in ps_context ps_grid ps_tiles ps_blocks ps_surface; do [ -f _build/$f.o ] || make -s _build/$f.o; done
+for f in ps_context ps_grid ps_tiles ps_blocks ps_surface ps_rheology; do [ -f _build/$f.o ] || make -s _build/$f.o; done
 for V in nomcc nocode noboth; do
   D=_build/$V/src; mkdir -p $D; cp *.hpp *.hip $D/
   sed -i 's|"../../include/polystokes.h"|"../../../../../include/polystokes.h"|' $D/ps_common.hpp
@@ -30,6 +30,6 @@ open(p,"w").write(s)
 PY
   fi
   /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -c $D/ps_solve.hip -o _build/$V/ps_solve.o
-  /opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o ../variants/lib_$V.so _build/ps_context.o _build/ps_grid.o _build/ps_tiles.o _build/ps_blocks.o _build/ps_surface.o _build/$V/ps_solve.o
+  /opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o ../variants/lib_$V.so _build/ps_context.o _build/ps_grid.o _build/ps_tiles.o _build/ps_blocks.o _build/ps_surface.o _build/ps_rheology.o _build/$V/ps_solve.o
   echo built $V
 done

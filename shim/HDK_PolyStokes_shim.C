@@ -78,6 +78,13 @@ const ParmRow theRows[] = {
     {'T', "enableSurfaceTension",       "Enable Surface Tension",           nullptr,            0},
     {'F', "surfaceTension",             "Surface Tension",                  nullptr,            0},
     {'T', "solidFreeSlip",              "Free-Slip Solids",                 nullptr,            0},
+    {'T', "nonNewtonian",               "Non-Newtonian Viscosity",          nullptr,            0},
+    {'F', "flowIndex",                  "Flow Index",                       nullptr,            1},
+    {'F', "yieldStress",                "Yield Stress",                     nullptr,            0},
+    {'F', "minShearRate",               "Min Shear Rate",                   nullptr,            1e-3},
+    {'F', "minViscosity",               "Min Viscosity",                    nullptr,            1e-3},
+    {'F', "maxViscosity",               "Max Viscosity",                    nullptr,            1e6},
+    {'I', "rheologyPasses",             "Rheology Passes",                  nullptr,            0},
 };
 constexpr int theRowCount = (int)(sizeof(theRows) / sizeof(theRows[0]));
 }  // namespace
@@ -212,6 +219,18 @@ bool HDK_PolyStokes::solveGasSubclass(SIM_Engine& engine, SIM_Object* obj, SIM_T
     if (solidMode != mySolidMode) {
         if (ps_set_solid_boundary(myCtx, solidMode) != PS_SUCCESS) return fail(ps_last_error(myCtx), UT_ERROR_ABORT);
         mySolidMode = solidMode;
+    }
+    // shim-only: a shear-rate-dependent viscosity (ps_set_rheology, a context setting; host-side only, so it is set every step): the
+    // viscosity field becomes the consistency K of the Herschel-Bulkley law.  Off is Newtonian and launches nothing extra.  A refused value
+    // aborts with the library's reason.
+    {
+        ps_rheology rh;
+        rh.model = getNonNewtonian() ? PS_RHEOLOGY_HERSCHEL_BULKLEY : PS_RHEOLOGY_NEWTONIAN;
+        rh.passes = (int32_t)getRheologyPasses();
+        rh.flowIndex = (double)getFlowIndex();          rh.yieldStress = (double)getYieldStress();
+        rh.minShearRate = (double)getMinShearRate();
+        rh.minViscosity = (double)getMinViscosity();    rh.maxViscosity = (double)getMaxViscosity();
+        if (ps_set_rheology(myCtx, &rh) != PS_SUCCESS) return fail(ps_last_error(myCtx), UT_ERROR_ABORT);
     }
 
     const fpreal dt = timestep;

@@ -49,6 +49,13 @@ public:
     GET_DATA_FUNC_B("enableSurfaceTension",             EnableSurfaceTension);    // ps_set_surface_tension(surfaceTension) (0)
     GET_DATA_FUNC_F("surfaceTension",                   SurfaceTension);          // sigma of the curvature pressure jump (0)
     GET_DATA_FUNC_B("solidFreeSlip",                    SolidFreeSlip);           // ps_set_solid_boundary(PS_SOLID_FREE_SLIP) (0)
+    GET_DATA_FUNC_B("nonNewtonian",                     NonNewtonian);            // ps_set_rheology(PS_RHEOLOGY_HERSCHEL_BULKLEY) (0)
+    GET_DATA_FUNC_F("flowIndex",                        FlowIndex);               // n of the law (1)
+    GET_DATA_FUNC_F("yieldStress",                      YieldStress);             // tau_y (0)
+    GET_DATA_FUNC_F("minShearRate",                     MinShearRate);            // shear-rate floor (1e-3)
+    GET_DATA_FUNC_F("minViscosity",                     MinViscosity);            // clamp of mu (1e-3)
+    GET_DATA_FUNC_F("maxViscosity",                     MaxViscosity);            // clamp of mu (1e6)
+    GET_DATA_FUNC_I("rheologyPasses",                   RheologyPasses);          // Picard passes per step (0)
 
 protected:
     explicit HDK_PolyStokes(const SIM_DataFactory* factory);
