@@ -10,16 +10,17 @@
 // and the basis row C_f (J) is evaluated on the fly in the tile kernels.  St = S^T is built by gather
 // from the DOF side (deterministic, no atomics).
 #include "ps_context.hpp"
+#include "ps_setup_util.hpp"
 
 using namespace ps;
 
 namespace {
 
-constexpr int BS = 256;
+constexpr int BS = SETUP_BS;
 
 struct BlockArgs {
     Grid g;
-    double invDx, rho;
+    double invDx;
     const float* lw[7];
     const float* fw[7];
     const int32_t* lab[7];
@@ -30,11 +31,9 @@ struct BlockArgs {
     const int32_t* faceRow[3];
     const float* vel[3];
     const float* cvel[3];
-    const float* visc;
-    int viscUniform; float viscValue;   // a constant field: its samples without loads (ps_context::upload)
-    const float* dens;                  // cell density field (ps_upload_density_field); null: the scalar rho everywhere
-    double densMin, densMax;
-    int64_t nCenter, nEdge0, nEdge1, nP, nA, faceOff[3];
+    CellField visc;               // ps_context::viscSource
+    FaceDensity dens;             // ps_context::densSource
+    int64_t nP, nA, faceOff[3];
     Own own;
     const int32_t* regionOwned;   // null: all owned
     double valScale;              // invDx / 64
@@ -54,17 +53,6 @@ __device__ inline int8_t encodeVal(const BlockArgs& A, double v) {
     const double r = rint(q);
     if (!(fabs(r) <= 127.) || r * A.valScale != v) { *A.codeFail = 1; return 0; }
     return (int8_t)(int)r;
-}
-
-__device__ inline int64_t stressDOF(const BlockArgs& A, int64_t idx, int type) {   // Solver.h:586-606
-    switch (type) {
-        case 0: return idx;
-        case 1: return idx + A.nCenter;
-        case 2: return idx + 2 * A.nCenter;
-        case 3: return idx + 3 * A.nCenter;
-        case 4: return idx + 3 * A.nCenter + A.nEdge0;
-        default: return idx + 3 * A.nCenter + A.nEdge0 + A.nEdge1;
-    }
 }
 
 // The stencil row of one face in the reference's slot order: p(dir0,dir1), tau_c(dir0,dir1),
@@ -142,25 +130,7 @@ __device__ inline int skinFaceLen(const BlockArgs& A, int axis, int r, int i, in
     double vals[8];
     return faceEntries(A, axis, make_int3(i, j, k), cols, vals);
 }
-__device__ inline int blockScanExcl(int v, int* total) {
-    __shared__ int waveSums[BS / 64];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += t;
-    }
-    if (lane == 63) waveSums[w] = incl;
-    __syncthreads();
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int i = 0; i < BS / 64; ++i) { if (i < w) base += waveSums[i]; tot += waveSums[i]; }
-    __syncthreads();
-    *total = tot;
-    return base + incl - v;
-}
-// the same for six 10-bit counters packed in 64 bits (each thread contributes 0 or 1 per counter: <= 256 per block)
+// blockExclusiveScan (ps_setup_util.hpp) for six 10-bit counters packed in 64 bits (each thread contributes 0 or 1 per counter: <= 256 per block)
 __device__ inline unsigned long long blockScanExclPacked(unsigned long long v, unsigned long long* total) {
     __shared__ unsigned long long waveSums64[BS / 64];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -277,42 +247,9 @@ __global__ void __launch_bounds__(BS) k_skin(BlockArgs A, const int32_t* __restr
 #pragma unroll
         for (int c = 0; c < 6; ++c) { n += (int)(m & 1023ull); m >>= 10; }
         int totalRows;
-        blockScanExcl(n, &totalRows);
+        blockExclusiveScan(n, &totalRows);
         if (threadIdx.x == 0) itemCount[item] = totalRows;
     }
-}
-
-// Density of the face (axis, i, j, k): the cell field sampled at the face centre with the viscosity's sampler (trilinear, clamped to the
-// grid — an interior face gets the mean of its two cells as a + (b - a) * 0.5f, a face on the grid boundary its one cell), clamped to
-// [mindensity, maxdensity].  Without a field: the scalar rho, unclamped (ps_upload_density_field).  ps_tiles.hip has the same helper.
-__device__ inline float densSample(const float* f, const Grid& g, float px, float py, float pz) {
-    const int n[3] = {g.nx, g.ny, g.nz};
-    const float p[3] = {px, py, pz};
-    int i0[3], i1[3];
-    float t[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        float u = p[a] - 0.5f;
-        if (u < 0.f) u = 0.f;
-        if (u > (float)(n[a] - 1)) u = (float)(n[a] - 1);
-        int b = (int)u;
-        if (b >= n[a] - 1) { b = n[a] - 1; i0[a] = b; i1[a] = b; t[a] = 0.f; }
-        else { i0[a] = b; i1[a] = b + 1; t[a] = u - (float)b; }
-    }
-    const int64_t sy = g.nx, sz = (int64_t)g.nx * g.ny;
-    auto at = [&](int i, int j, int k) { return f[i + j * sy + k * sz]; };
-    auto L = [](float a, float b, float tt) { return a + (b - a) * tt; };
-    const float c00 = L(at(i0[0], i0[1], i0[2]), at(i1[0], i0[1], i0[2]), t[0]);
-    const float c10 = L(at(i0[0], i1[1], i0[2]), at(i1[0], i1[1], i0[2]), t[0]);
-    const float c01 = L(at(i0[0], i0[1], i1[2]), at(i1[0], i0[1], i1[2]), t[0]);
-    const float c11 = L(at(i0[0], i1[1], i1[2]), at(i1[0], i1[1], i1[2]), t[0]);
-    return L(L(c00, c10, t[1]), L(c01, c11, t[1]), t[2]);
-}
-__device__ inline double densityAt(const BlockArgs& A, int axis, int i, int j, int k) {
-    if (!A.dens) return A.rho;
-    const float px = (float)i + (axis == 0 ? 0.f : 0.5f), py = (float)j + (axis == 1 ? 0.f : 0.5f), pz = (float)k + (axis == 2 ? 0.f : 0.5f);
-    const double v = (double)densSample(A.dens, A.g, px, py, pz);
-    return v < A.densMin ? A.densMin : (v > A.densMax ? A.densMax : v);
 }
 
 __global__ void k_S_count(BlockArgs A, int axis, int32_t* __restrict__ rowCount) {
@@ -347,7 +284,7 @@ __global__ void k_S_fill(BlockArgs A, int axis, const int32_t* __restrict__ ptr,
         volume = volume < lo ? lo : (volume > 1.0 ? 1.0 : volume);
         const double u = (double)A.vel[axis][c];
         const int3 q = unlin3(d, c);
-        const double rho = densityAt(A, axis, q.x, q.y, q.z);
+        const double rho = A.dens.at(A.g, axis, q.x, q.y, q.z);
         McInv[row] = 1. / (volume * rho);
         rhsA[row] = u * volume * rho;
         if (Mc) Mc[row] = volume * rho;
@@ -446,30 +383,6 @@ __device__ inline void sortRows4(int32_t (&rows)[4], double (&vals)[4]) {   // a
 #undef PS_CSWAP
 }
 
-__device__ inline float viscAt(const BlockArgs& A, float px, float py, float pz) {
-    if (A.viscUniform) return A.viscValue;
-    const int n[3] = {A.g.nx, A.g.ny, A.g.nz};
-    const float p[3] = {px, py, pz};
-    int i0[3], i1[3];
-    float t[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        float u = p[a] - 0.5f;
-        if (u < 0.f) u = 0.f;
-        if (u > (float)(n[a] - 1)) u = (float)(n[a] - 1);
-        int b = (int)u;
-        if (b >= n[a] - 1) { b = n[a] - 1; i0[a] = b; i1[a] = b; t[a] = 0.f; }
-        else { i0[a] = b; i1[a] = b + 1; t[a] = u - (float)b; }
-    }
-    const int64_t sy = A.g.nx, sz = (int64_t)A.g.nx * A.g.ny;
-    auto at = [&](int i, int j, int k) { return A.visc[i + j * sy + k * sz]; };
-    auto L = [](float a, float b, float tt) { return a + (b - a) * tt; };
-    const float c00 = L(at(i0[0], i0[1], i0[2]), at(i1[0], i0[1], i0[2]), t[0]);
-    const float c10 = L(at(i0[0], i1[1], i0[2]), at(i1[0], i1[1], i0[2]), t[0]);
-    const float c01 = L(at(i0[0], i0[1], i1[2]), at(i1[0], i0[1], i1[2]), t[0]);
-    const float c11 = L(at(i0[0], i1[1], i1[2]), at(i1[0], i1[1], i1[2]), t[0]);
-    return L(L(c00, c10, t[1]), L(c01, c11, t[1]), t[2]);
-}
 __device__ inline double clampd(double v, double lo, double hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 __device__ inline void sortRows(int n, int32_t* rows, double* vals) {
@@ -498,7 +411,7 @@ __global__ void k_St_cells(BlockArgs A, int32_t* __restrict__ cnt, const int32_t
     double uinvv = 0., uv = 0.;
     if (FILL) {
         const double vw = clampd((double)A.fw[0][c], 0.1, 1.0) * (double)A.lw[0][c];
-        const double visc = (double)viscAt(A, (float)q.x + 0.5f, (float)q.y + 0.5f, (float)q.z + 0.5f);
+        const double visc = (double)A.visc.sample(A.g, (float)q.x + 0.5f, (float)q.y + 0.5f, (float)q.z + 0.5f);
         const double invVisc = clampd(1. / visc, 0., 1.e10);
         uinvv = invVisc * clampd(vw, 1.e-2, 1.);
         uv = visc * clampd(1. / vw, 0., 1.e2);
@@ -545,7 +458,7 @@ __global__ void k_St_edges(BlockArgs A, int ea, int32_t* __restrict__ cnt, const
     rhsPT[j] = rhs;
     const double vw = clampd((double)A.fw[4 + ea][c], 0.1, 1.0) * (double)A.lw[4 + ea][c];
     const float ox = ea == 0 ? 0.5f : 0.f, oy = ea == 1 ? 0.5f : 0.f, oz = ea == 2 ? 0.5f : 0.f;
-    const double visc = (double)viscAt(A, (float)q.x + ox, (float)q.y + oy, (float)q.z + oz);
+    const double visc = (double)A.visc.sample(A.g, (float)q.x + ox, (float)q.y + oy, (float)q.z + oz);
     const double invVisc = clampd(1. / visc, 0., 1e10);
     uInv[t] = A.own.sample(4 + ea, q.x, q.y, q.z) ? 2. * invVisc * vw : 0.;
     if (uDiag) uDiag[t] = 0.5 * visc * clampd(1. / vw, 0., 1.e2);
@@ -553,22 +466,18 @@ __global__ void k_St_edges(BlockArgs A, int ea, int32_t* __restrict__ cnt, const
 
 BlockArgs makeArgs(ps_context* c) {
     BlockArgs A;
-    A.g = c->g; A.invDx = c->invDx; A.rho = c->rho;
+    A.g = c->g; A.invDx = c->invDx;
     for (int s = 0; s < 7; ++s) {
         A.lw[s] = c->liquidW[s].p; A.fw[s] = c->fluidW[s].p;
         A.lab[s] = c->labels[s].p; A.act[s] = c->activeIdx[s].p; A.reg[s] = c->reducedIdx[s].p; A.sys[s] = c->sysIdx[s].p;
     }
     for (int a = 0; a < 3; ++a) { A.faceRow[a] = c->faceRow[a].p; A.vel[a] = c->vel[a].p; A.cvel[a] = c->cvel[a].p; A.sysT[a] = c->sysIdxT[a].p; }
-    const ps_context::ViscSource vs = c->viscSource();   // the uploaded field, or mu of ps_set_rheology
-    A.visc = vs.p;
-    A.viscUniform = vs.uniform; A.viscValue = vs.value;
-    A.dens = c->densField ? c->density.p : nullptr; A.densMin = c->densMin; A.densMax = c->densMax;
-    A.nCenter = c->nCenter; A.nEdge0 = c->nEdge[0]; A.nEdge1 = c->nEdge[1];
+    A.visc = c->viscSource(); A.dens = c->densSource();
     A.nP = c->nPressures; A.nA = c->nActiveVs;
     A.faceOff[0] = 0; A.faceOff[1] = c->nFace[0]; A.faceOff[2] = c->nFace[0] + c->nFace[1];
     A.own = c->own();
     A.valScale = c->valScale;
-    A.codeFail = c->counters.p + 20;
+    A.codeFail = c->counters.p + CTR_CODE_FAIL;
     A.regionOwned = (c->slabEnabled && c->regionCount > 0) ? c->regionOwned.p : nullptr;
     A.freeSlip = c->solidBoundaryUsed == PS_SOLID_FREE_SLIP ? 1 : 0;
     A.slipEdges = A.freeSlip ? c->slipEdges.p : nullptr;
@@ -642,11 +551,6 @@ __global__ void __launch_bounds__(BS) k_col16_build(const int32_t* __restrict__ 
 // bases stay per chunk — so every chunk whose payload equals an earlier chunk's is pointed at that chunk's run: the kernels then
 // stream one copy of each distinct run and find it in cache.  (1) a 64-bit hash per payload, (2) a device hash table keeps the
 // smallest chunk index per hash, (3) every other chunk compares its bytes with that representative's and, if equal, takes its run.
-constexpr unsigned long long HASH_EMPTY = 0xffffffffffffffffull;
-__device__ inline unsigned long long mix64(unsigned long long x) {
-    x ^= x >> 33; x *= 0xff51afd7ed558ccdull; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull; x ^= x >> 33;
-    return x;
-}
 __global__ void __launch_bounds__(64) k_chunk_hash(const int4* __restrict__ chunkInfo, const uint16_t* __restrict__ col16, const int8_t* __restrict__ code4,
                                                    const uint8_t* __restrict__ len8, unsigned long long* __restrict__ hash, int weak) {
     const int chunk = blockIdx.x;
@@ -668,12 +572,7 @@ __global__ void k_chunk_rep_insert(const unsigned long long* __restrict__ hash, 
     const int chunk = blockIdx.x * blockDim.x + threadIdx.x;
     if (chunk >= nChunks) return;
     const unsigned long long h = hash[chunk];
-    unsigned slot = (unsigned)(h >> 17) & mask;
-    for (unsigned probe = 0; probe <= mask; ++probe, slot = (slot + 1) & mask) {
-        unsigned long long cur = keys[slot];
-        if (cur == HASH_EMPTY) { cur = atomicCAS(&keys[slot], HASH_EMPTY, h); if (cur == HASH_EMPTY) cur = h; }
-        if (cur == h) { atomicMin(&vals[slot], chunk); return; }
-    }
+    hashInsertMin(keys, vals, mask, (unsigned)(h >> 17) & mask, h, chunk);
 }
 // one workgroup per chunk: look the representative up, compare the payloads, redirect the run and the row-byte source.
 // rowCode (may be null): the value-set codes of the kernel's diagonal (uCode per DOF; mcCode per ACTIVE face row, codeRows of them):
@@ -768,7 +667,7 @@ __global__ void __launch_bounds__(BS) k_ell_fill(const int4* __restrict__ chunkI
     const int len = (int)len8[ci.z + min((int)threadIdx.x, rows - 1)];   // rows >= 1
     int total;
     const int mine = (int)threadIdx.x < rows ? len : 0;
-    const int e0 = blockScanExcl(mine, &total);
+    const int e0 = blockExclusiveScan(mine, &total);
     __shared__ int lastE0;
     if ((int)threadIdx.x == rows - 1) lastE0 = e0;
     __syncthreads();
@@ -799,19 +698,16 @@ void ps_context::buildEll(ps::DevCSR& M) {
     colBegin.alloc((size_t)nChunks + 1); codeBegin.alloc((size_t)nChunks + 1); wpack.alloc((size_t)nChunks);
     HIP_CHECK(hipMemsetAsync(colBegin.p + nChunks, 0, sizeof(int32_t), stream));
     HIP_CHECK(hipMemsetAsync(codeBegin.p + nChunks, 0, sizeof(int32_t), stream));
-    HIP_CHECK(hipMemsetAsync(counters.p + 25, 0, sizeof(int32_t), stream));
+    HIP_CHECK(hipMemsetAsync(counters.p + CTR_ELL_TOO_LONG, 0, sizeof(int32_t), stream));
     hipLaunchKernelGGL(k_ell_plan, dim3((unsigned)nChunks), dim3(BS), 0, stream, (const int4*)M.chunkInfo.p, (const uint8_t*)M.len8.p, (const int32_t*)M.chunkRep.p,
-                       colBegin.p, codeBegin.p, wpack.p, counters.p + 25);
+                       colBegin.p, codeBegin.p, wpack.p, counters.p + CTR_ELL_TOO_LONG);
     scanBlock.alloc((size_t)gridFor(nChunks + 1, PS_SCAN_TILE) + 16);                   // (both unsynchronised scans below use it)
-    (void)exclusiveScanI32(colBegin.p, nChunks + 1, 56);
-    (void)exclusiveScanI32(codeBegin.p, nChunks + 1, 57);
-    int32_t tot[2] = {0, 0}, tooLong = 0;                                        // one round trip for the two totals and the width check
-    {
-        int32_t w[33];
-        fetchCounters(25, 33, w);                                                // counters[25 .. 57] in one copy
-        tooLong = w[0]; tot[0] = w[31]; tot[1] = w[32];
-    }
-    const int64_t totCol = tot[0], totCode = tot[1];
+    (void)exclusiveScanI32(colBegin.p, nChunks + 1, CTR_ELL_COLS);
+    (void)exclusiveScanI32(codeBegin.p, nChunks + 1, CTR_ELL_CODES);
+    int32_t w[3];                                                                // one round trip for the width check and the two totals
+    fetchCounters(CTR_ELL_TOO_LONG, 3, w);
+    const int32_t tooLong = w[0];
+    const int64_t totCol = w[1], totCode = w[2];
     if (totCol < 0 || totCode < 0 || (uint64_t)totCol * 2 >= 0xffffffffull || tooLong != 0) return;   // a row longer than 8 / 32-bit offsets: keep the other kernels
     M.ellCols = totCol; M.ellCodes = totCode; M.ellUniqueCols = totCol;
     M.ecol.alloc((size_t)totCol + 64); M.ecode.alloc((size_t)totCode + 64); M.echunk.alloc((size_t)nChunks);
@@ -843,7 +739,7 @@ void ps_context::buildVal4(ps::DevCSR& M) {
 // Compressed SpMV stream (DevCSR::col16 ...); decided per matrix.  With coded values it is 3 B per entry; when the values are
 // not code * scale (user-supplied weights, PS_FORCE_FP64_VALUES=1) the same windowed 16-bit columns go with the fp64 values
 // (10 B per entry, DevCSR::val4) and the same pipelined kernels run.  PS_COL32=1 keeps the one-shot CSR kernels.
-void ps_context::buildCol16(ps::DevCSR& M, int slot, const std::vector<int32_t>& cuts, const uint8_t* rowCode, int codeRows) {
+void ps_context::buildCol16(ps::DevCSR& M, Counter slot, const std::vector<int32_t>& cuts, const uint8_t* rowCode, int codeRows) {
     M.col16ok = false;
     M.ellok = false;
     M.nChunks = 0;
@@ -877,11 +773,11 @@ void ps_context::buildCol16(ps::DevCSR& M, int slot, const std::vector<int32_t>&
     HIP_CHECK(hipMemcpyAsync(chunkRows.p, rowsOf.data(), (size_t)nChunks * sizeof(int2), hipMemcpyHostToDevice, stream));
     DevBuf<int32_t>& start4 = scrStart4;
     start4.alloc((size_t)nChunks + 1);
-    HIP_CHECK(hipMemsetAsync(counters.p + 25, 0, sizeof(int32_t), stream));
-    hipLaunchKernelGGL(k_chunk_len4, dim3(gridFor(nChunks + 1, BS)), dim3(BS), 0, stream, M.ptr.p, (const int2*)chunkRows.p, nChunks, start4.p, counters.p + 25);
+    HIP_CHECK(hipMemsetAsync(counters.p + CTR_CHUNK_MAX, 0, sizeof(int32_t), stream));
+    hipLaunchKernelGGL(k_chunk_len4, dim3(gridFor(nChunks + 1, BS)), dim3(BS), 0, stream, M.ptr.p, (const int2*)chunkRows.p, nChunks, start4.p, counters.p + CTR_CHUNK_MAX);
     const int64_t total4 = exclusiveScanI32(start4.p, nChunks + 1);   // (synchronises: rowsOf may go out of scope after this)
     if (total4 < 0) return;                                           // would overflow 32 bits: keep the CSR kernels
-    const int maxLen = readCounter(25);
+    const int maxLen = readCounter(CTR_CHUNK_MAX);
     M.nv = std::max(1, (maxLen + 4 * BS - 1) / (4 * BS));
     if (M.nv > 2) return;
     // the kernels address everything through 32-bit buffer descriptors: every array they touch must stay below 4 GiB
@@ -990,10 +886,10 @@ void ps_context::buildDiagonalCodes() {
         if (n <= 0) return false;
         dict.alloc(256); code.alloc((size_t)n);
         unsigned long long* table = (unsigned long long*)dict.p;
-        HIP_CHECK(hipMemsetAsync(counters.p + 26, 0, sizeof(int32_t), stream));
+        HIP_CHECK(hipMemsetAsync(counters.p + CTR_DICT_OVERFLOW, 0, sizeof(int32_t), stream));
         hipLaunchKernelGGL(k_dict_init, dim3(1), dim3(256), 0, stream, table);
-        hipLaunchKernelGGL(k_dict_build, dim3(2048), dim3(BS), 0, stream, vals.p, n, table, counters.p + 26);
-        if (readCounter(26) != 0) return false;
+        hipLaunchKernelGGL(k_dict_build, dim3(2048), dim3(BS), 0, stream, vals.p, n, table, counters.p + CTR_DICT_OVERFLOW);
+        if (readCounter(CTR_DICT_OVERFLOW) != 0) return false;
         hipLaunchKernelGGL(k_dict_code, dim3(1024), dim3(BS), 0, stream, vals.p, n, (const unsigned long long*)table, code.p);
         hipLaunchKernelGGL(k_dict_finish, dim3(1), dim3(256), 0, stream, table);
         return true;
@@ -1014,8 +910,8 @@ void ps_context::buildStreams(bool share) {
     }
     if (!blockStartSys.empty() && (int64_t)blockStartSys.back() == nSystem) cutsT = blockStartSys;
     shareRuns = share;
-    buildCol16(S, 22, cutsS, mcCoded ? mcCode.p : nullptr, (int)nActiveVs);
-    buildCol16(St, 23, cutsT, uCoded ? uCode.p : nullptr, (int)nSystem);
+    buildCol16(S, CTR_COL16_FAIL_S, cutsS, mcCoded ? mcCode.p : nullptr, (int)nActiveVs);
+    buildCol16(St, CTR_COL16_FAIL_ST, cutsT, uCoded ? uCode.p : nullptr, (int)nSystem);
     if (share) { buildEll(S); buildEll(St); } else S.ellok = St.ellok = false;   // (the unshared rebuild is bench.py's fp64-value stream: the 4-entries-per-lane kernels)
 }
 
@@ -1030,7 +926,7 @@ void ps_context::constructMatrixBlocks() {
     if (nSystem >= 0x7fffffff || nActiveVs >= 0x7fffffff) throw Error("system too large for 32-bit DOF indices");
 
     valScale = invDx / 64.;
-    HIP_CHECK(hipMemsetAsync(counters.p + 20, 0, sizeof(int32_t), stream));
+    HIP_CHECK(hipMemsetAsync(counters.p + CTR_CODE_FAIL, 0, sizeof(int32_t), stream));
     solidBoundaryUsed = solidBoundarySet;   // (ps_set_solid_boundary; read by makeArgs)
     if (solidBoundaryUsed == PS_SOLID_FREE_SLIP) {
         slipEdges.alloc(1);
@@ -1125,7 +1021,7 @@ void ps_context::constructMatrixBlocks() {
         if (tot < 0) throw Error("nnz(S) overflows 32-bit row pointers");
         S.nnz = tot;
     }
-    // The fp64 values are not stored while the codes hold them exactly (every entry is checked as it is coded: counters[20]): nothing on the
+    // The fp64 values are not stored while the codes hold them exactly (every entry is checked as it is coded: CTR_CODE_FAIL): nothing on the
     // solve path reads them then, exports and the fp64-stream benchmarks decode them on demand (ensureValues) — 2 x 8 B per entry less to write
     // in setup and to keep (2.5 GB at 256^3).  They are written when the codes are refused (PS_FORCE_FP64_VALUES=1) or turn out not to fit:
     // the fill kernels then run once more with the value arrays.
@@ -1174,16 +1070,12 @@ void ps_context::constructMatrixBlocks() {
         fillSt(forceFp64Values);
     }
     {
-        const bool ok = readCounter(20) == 0;
+        const bool ok = readCounter(CTR_CODE_FAIL) == 0;
         if (!ok && !forceFp64Values) { fillS(true); fillSt(true); }   // some value is not code * scale: the kernels will stream the values
         S.packed = St.packed = ok && !forceFp64Values;
-        const int32_t flag = S.packed ? 1 : 0;
-        HIP_CHECK(hipMemcpyAsync(counters.p + 21, &flag, sizeof(flag), hipMemcpyHostToDevice, stream));
-        HIP_CHECK(hipStreamSynchronize(stream));
+        valuesCodedHost = S.packed ? 1 : 0;
         buildDiagonalCodes();   // before the streams: chunks that share a run also share their rows' diagonal codes
         buildStreams(true);
-        const int32_t c16 = (S.col16ok ? 1 : 0) | (St.col16ok ? 2 : 0);
-        HIP_CHECK(hipMemcpyAsync(counters.p + 24, &c16, sizeof(c16), hipMemcpyHostToDevice, stream));
-        HIP_CHECK(hipStreamSynchronize(stream));
+        columns16Host = (S.col16ok ? 1 : 0) | (St.col16ok ? 2 : 0);
     }
 }

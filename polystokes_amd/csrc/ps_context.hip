@@ -9,6 +9,7 @@
 #include <fstream>
 
 #include "ps_context.hpp"
+#include "ps_setup_util.hpp"
 
 using namespace ps;
 
@@ -33,15 +34,10 @@ void uploadField(DevBuf<float>& d, const float* src, int64_t n, hipStream_t s) {
 }
 
 // several arrays filled by one launch: blockIdx.y = the array, grid-stride over its entries
-struct Fill21 { int32_t* p[21]; int64_t n[21]; };
-__global__ void k_fill32_multi(Fill21 F, int32_t v) {
+__global__ void k_fill_i32_many(FillList F, int32_t v) {
     int32_t* __restrict__ a = F.p[blockIdx.y];
     const int64_t n = F.n[blockIdx.y];
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) a[i] = v;
-}
-__global__ void k_fill32(int32_t* a, int64_t n, int32_t v) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) a[i] = v;
 }
 
 __global__ void k_gather_perm8(double* __restrict__ dst, const double* __restrict__ src, const int32_t* __restrict__ perm, int64_t off, int64_t n) {
@@ -56,6 +52,18 @@ __global__ void k_scatter_perm8(double* __restrict__ dst, const double* __restri
 const char* kSampleName[7] = {"center", "faceX", "faceY", "faceZ", "edgeYZ", "edgeXZ", "edgeXY"};
 
 }  // namespace
+
+void ps_context::fillI32(const FillList& F, int32_t v) {
+    int64_t most = 1;
+    for (int q = 0; q < F.count; ++q) most = std::max(most, F.n[q]);
+    hipLaunchKernelGGL(k_fill_i32_many, dim3((unsigned)std::min<int64_t>(512, gridFor(most, 256)), (unsigned)F.count), dim3(256), 0, stream, F, v);
+}
+
+CellField ps_context::viscSource() const {
+    if (rheoModelUsed != PS_RHEOLOGY_NEWTONIAN) return CellField{rheoMu.p, 0, 0.f};
+    return CellField{viscosity.p, viscUniform ? 1 : 0, viscUniformValue};
+}
+FaceDensity ps_context::densSource() const { return FaceDensity{densField ? density.p : nullptr, rho, densMin, densMax}; }
 
 void ps_context::upload(const ps_params* p, const ps_fields_in* in) {
     if (!p || !in) throw Error("null params/fields");
@@ -91,11 +99,7 @@ void ps_context::upload(const ps_params* p, const ps_fields_in* in) {
     uploadField(viscosity, in->viscosity, nc, stream);
     {   // a constant viscosity field (the usual case: a scalar parameter) needs no sampling: trilinear interpolation of a constant returns
         // it bit for bit (a + (b - a) t with a == b), so the setup kernels skip the 8 loads per sample (ps_tiles.hip, ps_blocks.hip)
-        const float v0 = in->viscosity[0];
-        bool same = true;
-        for (int64_t i = 1; i < nc && same; ++i) same = in->viscosity[i] == v0;
-        viscUniform = same && std::isfinite(v0);
-        viscUniformValue = v0;
+        viscUniform = fieldIsUniform(in->viscosity, nc, &viscUniformValue) && std::isfinite(viscUniformValue);
     }
     for (int a = 0; a < 3; ++a) {
         uploadField(vel[a], in->vel[a], g.count(1 + a), stream);
@@ -116,7 +120,7 @@ void ps_context::upload(const ps_params* p, const ps_fields_in* in) {
         }
     }
     for (int q = 0; q < 3; ++q) cellScratch[q].alloc((size_t)nc);
-    counters.alloc(64);
+    counters.alloc(CTR_COUNT);
     HIP_CHECK(hipStreamSynchronize(stream));
     uploaded = true; isSetup = false; isSolved = false;
     arrays.clear();          // the registered device pointers may have been re-allocated above
@@ -127,7 +131,7 @@ void ps_context::upload(const ps_params* p, const ps_fields_in* in) {
 }
 
 // ps_upload_density_field.  A constant field (all values equal) runs the scalar path at its clamped value, as a constant viscosity skips
-// the sampling (viscUniform); any other field is uploaded and sampled per face by the setup kernels (ps_blocks.hip / ps_tiles.hip: densityAt).
+// the sampling (viscUniform); any other field is uploaded and sampled per face by the setup kernels (ps_setup_util.hpp: FaceDensity, handed out by densSource).
 // Returns the reason an input is refused (the field is then dropped), or an empty string.
 std::string ps_context::uploadDensity(const float* field) {
     densField = false;
@@ -140,9 +144,8 @@ std::string ps_context::uploadDensity(const float* field) {
     const int64_t nc = g.count(0);
     for (int64_t i = 0; i < nc; ++i)
         if (!std::isfinite(field[i])) return "ps_upload_density_field: non-finite value at cell " + std::to_string(i);
-    const float v0 = field[0];
-    bool same = true;
-    for (int64_t i = 1; i < nc && same; ++i) same = field[i] == v0;
+    float v0;
+    const bool same = fieldIsUniform(field, nc, &v0);
     densMin = lo; densMax = hi;
     if (same) { const double v = (double)v0; rho = v < lo ? lo : (v > hi ? hi : v); return {}; }
     HIP_CHECK(hipSetDevice(device));
@@ -205,15 +208,9 @@ void ps_context::setupPhase(int phase) {
         bboxValid = false;
         // Solver ctor: labels / indices start UNASSIGNED (Solver.cpp:86-152)
         {   // the 21 label / index arrays in ONE launch (r06: 21 launches of 5 - 20 us each before)
-            Fill21 F;
-            int64_t most = 1;
-            for (int s = 0; s < 7; ++s) {
-                const int64_t n = g.count(s);
-                F.p[3 * s] = labels[s].p; F.p[3 * s + 1] = activeIdx[s].p; F.p[3 * s + 2] = reducedIdx[s].p;
-                F.n[3 * s] = F.n[3 * s + 1] = F.n[3 * s + 2] = n;
-                most = std::max(most, n);
-            }
-            hipLaunchKernelGGL(k_fill32_multi, dim3((unsigned)std::min<int64_t>(512, gridFor(most, 256)), 21), dim3(256), 0, stream, F, (int32_t)PS_UNASSIGNED);
+            FillList F;
+            for (int s = 0; s < 7; ++s) { F.add(labels[s].p, g.count(s)); F.add(activeIdx[s].p, g.count(s)); F.add(reducedIdx[s].p, g.count(s)); }
+            fillI32(F, (int32_t)PS_UNASSIGNED);
         }
         regionCount = 0;
         T.mark(0);
@@ -333,6 +330,8 @@ int ps_context::solveStage(ps_stats* stats) {
 void ps_context::registerArrays() {
     arrays.clear();
     auto reg = [&](const std::string& n, const void* p, int64_t c, int e) { arrays[n] = ArrayInfo{p, c, e}; };
+    // a status array read from host memory of the context: no copy per step, no device buffer behind it
+    auto regHost = [&](const std::string& n, const void* p, int64_t c, int e) { reg(n, p, c, e); arrays[n].host = true; };
     for (int s = 0; s < 7; ++s) {
         const int64_t n = g.count(s);
         reg(std::string(kSampleName[s]) + "LiquidWeights", liquidW[s].p, n, 4);
@@ -369,59 +368,45 @@ void ps_context::registerArrays() {
     regp("solutionVector", x.p, nSystem, permSys.p, 0);
     regp("guessVector", guess.p, nSystem, permSys.p, 0);
     if (warmX0Valid) regp("warmStartVector", warmX0.p, nSystem, permSys.p, 0);   // (mode PS_WARM_PREVIOUS_STEP, after a PCG solve)
-    // 1: the last PCG solve started from the solution carried over from an earlier step (ps_set_warm_start); read from host memory, so that
-    // the default path does not gain a copy per step
-    reg("warmStartUsed", &warmUsedHost, 1, 4);
-    arrays["warmStartUsed"].host = true;
+    regHost("warmStartUsed", &warmUsedHost, 1, 4);   // 1: the last PCG solve started from the solution carried over from an earlier step (ps_set_warm_start)
     densFieldHost = densField ? 1 : 0;   // 1: the last setup sampled a non-constant density field (ps_upload_density_field)
-    reg("densityField", &densFieldHost, 1, 4);
-    arrays["densityField"].host = true;
-    reg("surfaceTension", &sigmaUsed, 1, 8);   // the sigma of the last setup (ps_set_surface_tension)
-    arrays["surfaceTension"].host = true;
+    regHost("densityField", &densFieldHost, 1, 4);
+    regHost("surfaceTension", &sigmaUsed, 1, 8);   // the sigma of the last setup (ps_set_surface_tension)
     if (sigmaUsed != 0.) {
         reg("surfaceCurvature", kappaC.p, g.count(0), 4);
         reg("surfaceTensionReducedFaces", stReduced.p, 1, 4);
     }
-    reg("solidBoundary", &solidBoundaryUsed, 1, 4);   // the mode of the last setup (ps_set_solid_boundary)
-    arrays["solidBoundary"].host = true;
+    regHost("solidBoundary", &solidBoundaryUsed, 1, 4);   // the mode of the last setup (ps_set_solid_boundary)
     if (solidBoundaryUsed == PS_SOLID_FREE_SLIP) reg("solidSlipEdges", slipEdges.p, 1, 4);
-    reg("rheologyModel", &rheoModelUsed, 1, 4);   // the model of the last setup (ps_set_rheology)
-    arrays["rheologyModel"].host = true;
+    regHost("rheologyModel", &rheoModelUsed, 1, 4);   // the model of the last setup (ps_set_rheology)
     if (rheoModelUsed != PS_RHEOLOGY_NEWTONIAN) {
         reg("rheologyStrainRate", rheoRate.p, g.count(0), 4);
         reg("rheologyViscosity", rheoMu.p, g.count(0), 4);
-        reg("rheologyIterations", rheoIters.data(), (int64_t)rheoIters.size(), 4);   // PCG iterations of each solve of the last step
-        arrays["rheologyIterations"].host = true;
+        regHost("rheologyIterations", rheoIters.data(), (int64_t)rheoIters.size(), 4);   // PCG iterations of each solve of the last step
     }
     if (P.preconditioner == PS_PRE_DIAGONAL) regp("dinv", dinv.p, nSystem, permSys.p, 0);
     if (isSolved) {
         regp("recoveredActiveVelocity", recovered.p, nActiveVs, permRow.p, 0);
         reg("recoveredReducedVelocity", recovered.p ? recovered.p + nActiveVs : nullptr, nReducedVs, 8);
     }
-    reg("valuesCoded", counters.p + 21, 1, 4);
+    regHost("valuesCoded", &valuesCodedHost, 1, 4);
     diagFlagsHost = (uCoded ? 1 : 0) | (mcCoded ? 2 : 0);
-    HIP_CHECK(hipMemcpyAsync(counters.p + 27, &diagFlagsHost, sizeof(int32_t), hipMemcpyHostToDevice, stream));
-    reg("diagonalsCoded", counters.p + 27, 1, 4);
-    reg("columns16", counters.p + 24, 1, 4);
+    regHost("diagonalsCoded", &diagFlagsHost, 1, 4);
+    regHost("columns16", &columns16Host, 1, 4);
     // 1: the last PCG solve ran the four-kernel step (residual update inside the St kernel, ps_solve.hip)
-    HIP_CHECK(hipMemcpyAsync(counters.p + 28, &fusedStepHost, sizeof(int32_t), hipMemcpyHostToDevice, stream));
-    reg("fusedStep", counters.p + 28, 1, 4);
+    regHost("fusedStep", &fusedStepHost, 1, 4);
     // the walks of the persistent SpMV launches of the last single-domain PCG solve (5 records of 8: ps_context.hpp launchWalkHost)
-    reg("launchWalk", launchWalkHost, 5 * LAUNCH_WALK_FIELDS, 4);
-    arrays["launchWalk"].host = true;
+    regHost("launchWalk", launchWalkHost, 5 * LAUNCH_WALK_FIELDS, 4);
     // 1: the last solve / preconditioner apply kept the Chebyshev polynomial's inner vectors in fp32 (PS_PRE_CHEBYSHEV_F32 where its kernels run)
     chebInner32Host = chebInner32 ? 1 : 0;
-    HIP_CHECK(hipMemcpyAsync(counters.p + 36, &chebInner32Host, sizeof(int32_t), hipMemcpyHostToDevice, stream));
-    reg("chebInner32", counters.p + 36, 1, 4);
+    regHost("chebInner32", &chebInner32Host, 1, 4);
     // entries of the distinct runs of the compressed streams / all entries: S, then St (equal without sharing; 0 without a stream)
     streamRunsHost[0] = S.col16ok ? (int32_t)S.uniqueLen : 0; streamRunsHost[1] = S.col16ok ? (int32_t)S.streamLen : 0;
     streamRunsHost[2] = St.col16ok ? (int32_t)St.uniqueLen : 0; streamRunsHost[3] = St.col16ok ? (int32_t)St.streamLen : 0;
-    HIP_CHECK(hipMemcpyAsync(counters.p + 29, streamRunsHost, 4 * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-    reg("streamRuns", counters.p + 29, 4, 4);
+    regHost("streamRuns", streamRunsHost, 4, 4);
     // bit 0 / 1: S / St run the row-per-lane kernels (DevCSR::ecol); [1]: the numbering mode (ilPlaneMajor)
     rowPerLaneHost[0] = ((S.ellok && S.packed) ? 1 : 0) | ((St.ellok && St.packed) ? 2 : 0); rowPerLaneHost[1] = ilPlaneMajor;
-    HIP_CHECK(hipMemcpyAsync(counters.p + 34, rowPerLaneHost, 2 * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-    reg("rowPerLane", counters.p + 34, 2, 4);
+    regHost("rowPerLane", rowPerLaneHost, 2, 4);
     reg("sysPerm", permSys.p, nSystem, 4);
     reg("rowPerm", permRow.p, nActiveVs, 4);
     reg("S.ptr", S.ptr.p, S.rows + 1, 4); reg("S.col", S.col.p, S.nnz, 4); reg("S.val", S.val.p, S.nnz, 8);

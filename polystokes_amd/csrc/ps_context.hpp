@@ -74,6 +74,41 @@ struct ArrayInfo {
     bool host = false;               // dptr is host memory of the context (no device copy behind it)
 };
 
+// The slots of ps_context::counters (int32 each): flags and totals that kernels write and the host reads (readCounter / fetchCounters).
+// Every user clears its own slot before the launch; slots that one fetch reads are adjacent (asserted below).
+enum Counter : int {
+    CTR_CHANGED = 0,         // k_cc_step: a component label changed; k_fix_eval: a fix flag changed (zeroChangeFlags clears both)
+    CTR_ANY_FIX = 1,         // k_fix_eval: the sweep holds a fix
+    CTR_SCAN_TOTAL = 8,      // k_scan_single: the total of a synchronising scan (exclusiveScanI32, orderedIndexAssign, interleavedIndexAssignEx)
+    CTR_IL_PROBE = 10,       // k_il_assign: the running prefix at the two probe positions (10, 11), fetched with CTR_SCAN_TOTAL
+    CTR_CODE_FAIL = 20,      // encodeVal (k_S_fill, k_St_cells, k_St_edges): a stencil value is not code * valScale
+    CTR_COL16_FAIL_S = 22,   // k_col16_build on S: a chunk needs more than 16 column windows
+    CTR_COL16_FAIL_ST = 23,  // ... on St
+    CTR_CHUNK_MAX = 25,      // k_chunk_len4: entries of the fullest chunk
+    CTR_DICT_OVERFLOW = 26,  // k_dict_build: a diagonal takes more than 256 values
+    CTR_NOT_DYADIC = 40,     // k_dyadic_check: a weight is not a multiple of 1/8
+    CTR_HALO_UNMARKED = 41,  // k_count_unmarked_halo (ps_dist.hpp: decideExchangeMode)
+    CTR_ACTIVE_TOTAL = 48,   // k_scan_single: the active samples of the seven grids (48 .. 54: constructActiveIndices)
+    CTR_ELL_TOO_LONG = 55,   // k_ell_plan: a row is longer than the row-per-lane form holds
+    CTR_ELL_COLS = 56,       // k_scan_single: column slots of the row-per-lane form (buildEll)
+    CTR_ELL_CODES = 57,      // ... and its code bytes
+    CTR_COUNT = 64
+};
+static_assert(CTR_ANY_FIX == CTR_CHANGED + 1, "constructCenterReducedIndices fetches the two flags together");
+static_assert(CTR_IL_PROBE == CTR_SCAN_TOTAL + 2, "interleavedIndexAssignEx fetches the total and the two probes together");
+static_assert(CTR_ELL_TOO_LONG == CTR_ACTIVE_TOTAL + 7 && CTR_ELL_COLS == CTR_ELL_TOO_LONG + 1 && CTR_ELL_CODES == CTR_ELL_COLS + 1,
+              "seven totals, then buildEll's three values: each group is one fetch");
+
+// Arrays filled with one value by ONE launch (ps_context::fillI32): the 21 label / index arrays of a setup, the ten of the internal numbering
+struct FillList {
+    int32_t* p[21]; int64_t n[21];
+    int count = 0;
+    void add(int32_t* ptr, int64_t len) { p[count] = ptr; n[count] = len; ++count; }
+};
+
+struct CellField;     // ps_setup_util.hpp: what the setup kernels sample
+struct FaceDensity;
+
 }  // namespace ps
 
 struct ps_context {
@@ -137,12 +172,10 @@ struct ps_context {
     std::vector<int32_t> rheoIters;
     void computeRheology();                  // ps_rheology.hip: after constructActiveIndices, before the tile matrices
     int stepWithPasses(ps_stats* stats);     // ps_rheology.hip: setup + solve, then the Picard passes of a single-domain step
-    // The one viscosity field the setup samples (ps_blocks.hip / ps_tiles.hip makeArgs): the uploaded one, or mu with the model on
-    struct ViscSource { const float* p; int uniform; float value; };
-    ViscSource viscSource() const {
-        if (rheoModelUsed != PS_RHEOLOGY_NEWTONIAN) return ViscSource{rheoMu.p, 0, 0.f};
-        return ViscSource{viscosity.p, viscUniform ? 1 : 0, viscUniformValue};
-    }
+    // The one viscosity field the setup samples (ps_blocks.hip / ps_tiles.hip makeArgs): the uploaded one, or mu with the model on; and the
+    // one face density: the uploaded field with its clamp bounds, or the scalar rho (ps_context.hip)
+    ps::CellField viscSource() const;
+    ps::FaceDensity densSource() const;
 
     // ---- inputs (fp32 Houdini voxel arrays, HDK_PolyStokes.C:235-246) ----
     ps::DevBuf<float> surface, collision, viscosity, density, vel[3], cvel[3];
@@ -214,6 +247,8 @@ struct ps_context {
     ps::DevBuf<uint8_t> uCode, mcCode;
     ps::DevBuf<double> uDict, mcDict;      // 256 entries each
     bool uCoded = false, mcCoded = false;
+    // status arrays read from host memory (registerArrays: regHost): "valuesCoded", "columns16" (constructMatrixBlocks), "diagonalsCoded", "fusedStep"
+    int32_t valuesCodedHost = 0, columns16Host = 0;
     int32_t diagFlagsHost = 0;
     int32_t fusedStepHost = 0;
     // The walks of the persistent SpMV launches of the last single-domain PCG solve (array "launchWalk", read from host memory): 5 records of
@@ -354,7 +389,7 @@ struct ps_context {
     void computeReducedViscosityMatricesInteriorOnly();
     void assembleReducedBlocks();                         // AssembleBlocks.cpp:147-244,356-367
     void constructMatrixBlocks();                         // ps_blocks.hip
-    void buildCol16(ps::DevCSR& M, int counterSlot, const std::vector<int32_t>& cuts, const uint8_t* rowCode, int codeRows);   // ps_blocks.hip; cuts: row indices where a chunk should start
+    void buildCol16(ps::DevCSR& M, ps::Counter failSlot, const std::vector<int32_t>& cuts, const uint8_t* rowCode, int codeRows);   // ps_blocks.hip; cuts: row indices where a chunk should start
     void buildEll(ps::DevCSR& M);                         // the row-per-lane form of M's compressed stream (ps_blocks.hip)
     void buildStreams(bool share);                        // both compressed streams (ps_blocks.hip)
     bool shareRuns = true;
@@ -395,10 +430,11 @@ struct ps_context {
                                      int64_t* ownedRange);
     void buildInternalNumbering();                                            // ps_grid.hip
     int64_t exclusiveScanI32(int32_t* data, int64_t n, int counterSlot = -1);   // ps_grid.hip (counterSlot >= 0: total to counters[slot], no synchronisation)
-    int32_t readCounter(int idx);
-    void fetchCounters(int idx, int n, int32_t* out);   // counters[idx .. idx + n) in one round trip through the page-locked mirror (synchronises the stream: copies queued before it have landed too)
-    int32_t* pinnedCounters = nullptr;       // page-locked mirror of `counters` (64 words): a count read lands there directly instead of through the runtime's staging copy
-    void zeroCounters();
+    int32_t readCounter(ps::Counter idx);
+    void fetchCounters(ps::Counter idx, int n, int32_t* out);   // counters[idx .. idx + n) in one round trip through the page-locked mirror (synchronises the stream: copies queued before it have landed too)
+    int32_t* pinnedCounters = nullptr;       // page-locked mirror of `counters` (CTR_COUNT words): a count read lands there directly instead of through the runtime's staging copy
+    void zeroChangeFlags();                  // CTR_CHANGED, CTR_ANY_FIX
+    void fillI32(const ps::FillList& F, int32_t v);   // ps_context.hip
 };
 
 // kernel micro-benchmark dispatch (ps_solve.hip), used by ps_bench_kernel

@@ -998,14 +998,14 @@ struct Dist {
             DevBuf<unsigned char>& mark = c->scrMark;
             mark.alloc((size_t)c->nSystem);
             HIP_CHECK(hipMemsetAsync(mark.p, 0, (size_t)c->nSystem, c->stream));
-            HIP_CHECK(hipMemsetAsync(c->counters.p + 41, 0, sizeof(int32_t), c->stream));
+            HIP_CHECK(hipMemsetAsync(c->counters.p + CTR_HALO_UNMARKED, 0, sizeof(int32_t), c->stream));
             for (int a = 0; a < ps_context::NLINK; ++a) {
                 if (c->nLowHalo[a] > 0) hipLaunchKernelGGL(k_mark_list, dim3(gridFor(c->nLowHalo[a], BS)), dim3(BS), 0, c->stream, (const int32_t*)c->listLowHalo[a].p, c->nLowHalo[a], mark.p);
                 if (c->nUpHalo[a] > 0) hipLaunchKernelGGL(k_mark_list, dim3(gridFor(c->nUpHalo[a], BS)), dim3(BS), 0, c->stream, (const int32_t*)c->listUpHalo[a].p, c->nUpHalo[a], mark.p);
             }
             hipLaunchKernelGGL(k_count_unmarked_halo, dim3(gridFor(c->S.nnz, BS)), dim3(BS), 0, c->stream, (const int32_t*)c->S.col.p, (int64_t)c->S.nnz, (int)c->ownLo, (int)c->ownHi,
-                               (const unsigned char*)mark.p, c->counters.p + 41);
-            if (c->readCounter(41) != 0) need = true;
+                               (const unsigned char*)mark.p, c->counters.p + CTR_HALO_UNMARKED);
+            if (c->readCounter(CTR_HALO_UNMARKED) != 0) need = true;
         }
         const bool fwd = sumFlag(need ? 1. : 0.) > 0.;
         for (ps_context* c : R)

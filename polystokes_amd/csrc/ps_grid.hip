@@ -5,53 +5,25 @@
 #include <limits.h>
 
 #include "ps_context.hpp"
+#include "ps_setup_util.hpp"
 
 using namespace ps;
 
 namespace {
 
-constexpr int BS = 256;
+constexpr int BS = SETUP_BS;
 
 // sample offsets inside a voxel (Solver.h:193-222), order centre, faceX, faceY, faceZ, edgeYZ, edgeXZ, edgeXY: 0.5 (true) or 0 per axis
 constexpr bool kSampleOffsetHalf[7][3] = {{true, true, true}, {false, true, true}, {true, false, true}, {true, true, false},
                                           {true, false, false}, {false, true, false}, {false, false, true}};
-
-// SIM_RawField::getValue(pos) restated: trilinear between voxel centres, streak border, fp32,
-// lerp(a,b,t) = a + (b-a)*t, x then y then z.  The library is built with -ffp-contract=off so the
-// result is bit-identical to the CPU restatement.
-__device__ inline float sampleCenterField(const float* __restrict__ f, int nx, int ny, int nz, float px, float py, float pz) {
-    const int n[3] = {nx, ny, nz};
-    const float p[3] = {px, py, pz};
-    int i0[3], i1[3];
-    float t[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        float u = p[a] - 0.5f;
-        if (u < 0.f) u = 0.f;
-        if (u > (float)(n[a] - 1)) u = (float)(n[a] - 1);
-        int b = (int)u;
-        if (b >= n[a] - 1) { b = n[a] - 1; i0[a] = b; i1[a] = b; t[a] = 0.f; }
-        else { i0[a] = b; i1[a] = b + 1; t[a] = u - (float)b; }
-    }
-    const int64_t sx = 1, sy = nx, sz = (int64_t)nx * ny;
-    auto at = [&](int i, int j, int k) { return f[i * sx + j * sy + k * sz]; };
-    auto L = [](float a, float b, float tt) { return a + (b - a) * tt; };
-    const float c00 = L(at(i0[0], i0[1], i0[2]), at(i1[0], i0[1], i0[2]), t[0]);
-    const float c10 = L(at(i0[0], i1[1], i0[2]), at(i1[0], i1[1], i0[2]), t[0]);
-    const float c01 = L(at(i0[0], i0[1], i1[2]), at(i1[0], i0[1], i1[2]), t[0]);
-    const float c11 = L(at(i0[0], i1[1], i1[2]), at(i1[0], i1[1], i1[2]), t[0]);
-    const float c0 = L(c00, c10, t[1]);
-    const float c1 = L(c01, c11, t[1]);
-    return L(c0, c1, t[2]);
-}
 
 // computeSDFWeightsSampled(sdf, 2, invert=false, minweight=0): Solver.cpp:292-326 (HDK body out of tree,
 // restated: fraction of the 2x2x2 sub-samples of the voxel box whose SDF value is < 0).
 // All seven sample grids in one launch.  Along an axis the sub-samples of the voxel index q sit at u = q - 0.75, q - 0.25 or q + 0.25
 // (cell-centre coordinates): the grids centred on that axis use the last two, the grids on a face of it the first two.  So the 56
 // sub-samples of the seven grids at (i, j, k) are 27 distinct points, and their trilinear values share the lerps: 27 along x (two
-// loads each), 27 along y, 27 along z — the SAME operations on the same operands as sampleCenterField above does for each of them
-// (x, then y, then z; the index / clamp arithmetic per axis is that function's), so every value is bit-identical; 54 loads per voxel
+// loads each), 27 along y, 27 along z — the SAME operations on the same operands as sampleCenterField (ps_setup_util.hpp) does for each of them
+// (x, then y, then z; the index / clamp arithmetic per axis is that function's axisSample), so every value is bit-identical; 54 loads per voxel
 // instead of 448 (the r02 kernels, one launch per grid, were bound by exactly those loads: 14 launches, 2.6 ms at 256^3).
 struct AxisSamples { int i0[3], i1[3]; float t[3]; };
 __device__ inline AxisSamples axisSamples(int q, int n) {
@@ -59,12 +31,8 @@ __device__ inline AxisSamples axisSamples(int q, int n) {
     const float pos[3] = {((float)q + 0.f) + -0.25f, ((float)q + 0.f) + 0.25f, ((float)q + 0.5f) + 0.25f};   // (index + offset) +- 0.25, formed as the oracle forms it
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        float u = pos[c] - 0.5f;
-        if (u < 0.f) u = 0.f;
-        if (u > (float)(n - 1)) u = (float)(n - 1);
-        int b = (int)u;
-        if (b >= n - 1) { b = n - 1; A.i0[c] = b; A.i1[c] = b; A.t[c] = 0.f; }
-        else { A.i0[c] = b; A.i1[c] = b + 1; A.t[c] = u - (float)b; }
+        const AxisSample a = axisSample(pos[c], n);
+        A.i0[c] = a.i0; A.i1[c] = a.i1; A.t[c] = a.t;
     }
     return A;
 }
@@ -273,16 +241,6 @@ __global__ void k_tiles_and_relabel(Grid g, int32_t* __restrict__ lab, int doTil
 __global__ void k_relabel(int32_t* __restrict__ lab, int64_t n, int from, int to) {
     const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (c < n && lab[c] == from) lab[c] = to;
-}
-struct FillMany { int32_t* p[16]; int64_t n[16]; };   // blockIdx.y = the array, grid-stride over its entries
-__global__ void k_fill_i32_many(FillMany F, int v) {
-    int32_t* __restrict__ a = F.p[blockIdx.y];
-    const int64_t n = F.n[blockIdx.y];
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) a[i] = v;
-}
-__global__ void k_fill_i32(int32_t* __restrict__ a, int64_t n, int v) {
-    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c < n) a[c] = v;
 }
 
 // findFaceLabelFromCenter, Classifier.cpp:784-832
@@ -662,28 +620,6 @@ constexpr int SCAN_ITEMS = 8;                      // per thread
 constexpr int SCAN_TILE = BS * SCAN_ITEMS;         // per block
 static_assert(SCAN_TILE == PS_SCAN_TILE, "ps_context.hpp: PS_SCAN_TILE");
 
-__device__ inline int blockExclusiveScan(int v, int* total) {
-    __shared__ int waveSums[BS / 64];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += t;
-    }
-    if (lane == 63) waveSums[w] = incl;
-    __syncthreads();
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int i = 0; i < BS / 64; ++i) {
-        if (i < w) base += waveSums[i];
-        tot += waveSums[i];
-    }
-    __syncthreads();
-    *total = tot;
-    return base + incl - v;
-}
-
 // the voxel after q in the traversal order (its position is t): the x-neighbour, the next row / plane of the 16^3 tile, or — leaving the
 // tile — a full decode.  (One full decode per position, six 64-bit divisions each, was most of the 1.9 ms of these kernels at 256^3.)
 __device__ inline void orderAdvance(const int3 d, int order, int64_t t, int3& q) {
@@ -808,7 +744,7 @@ struct ILDesc {
     int ownFilter;             // 1: only owned voxels are numbered (face rows); 0: every active voxel (DOFs)
     int planeMajor;
     const int32_t* blockMap;   // sequence position -> lattice block (a decomposition numbers its owned blocks first); null: lattice order
-    int64_t probe[2];          // virtual positions whose running prefix is reported in counters[10], [11]
+    int64_t probe[2];          // virtual positions whose running prefix is reported in counters[CTR_IL_PROBE], [CTR_IL_PROBE + 1]
 };
 __device__ inline bool ilFlag(const ILDesc& D, const Grid& g, const Set7<const int32_t>& lab, int grp, int64_t c) {
     const int s = D.sample[grp];
@@ -950,10 +886,10 @@ Set7<const T> cset(DevBuf<T>* b) {
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------
-int32_t ps_context::readCounter(int idx) {
+int32_t ps_context::readCounter(Counter idx) {
     // into page-locked memory (r05): a device-to-host copy of 4 bytes into a stack variable goes through the runtime's staging buffer — about half of the
     // ~30 us a count-only round trip of the setup costs (36 of them per setup: profiles/r05_setup_timeline_coil128.txt)
-    if (!pinnedCounters && hipHostMalloc((void**)&pinnedCounters, 64 * sizeof(int32_t), hipHostMallocDefault) != hipSuccess) pinnedCounters = nullptr;
+    if (!pinnedCounters && hipHostMalloc((void**)&pinnedCounters, CTR_COUNT * sizeof(int32_t), hipHostMallocDefault) != hipSuccess) pinnedCounters = nullptr;
     if (pinnedCounters) {
         HIP_CHECK(hipMemcpyAsync(pinnedCounters + idx, counters.p + idx, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
         HIP_CHECK(hipStreamSynchronize(stream));
@@ -965,14 +901,14 @@ int32_t ps_context::readCounter(int idx) {
     return v;
 }
 // several counters in one round trip (synchronises the stream)
-void ps_context::fetchCounters(int idx, int n, int32_t* out) {
-    if (!pinnedCounters && hipHostMalloc((void**)&pinnedCounters, 64 * sizeof(int32_t), hipHostMallocDefault) != hipSuccess) pinnedCounters = nullptr;
+void ps_context::fetchCounters(Counter idx, int n, int32_t* out) {
+    if (!pinnedCounters && hipHostMalloc((void**)&pinnedCounters, CTR_COUNT * sizeof(int32_t), hipHostMallocDefault) != hipSuccess) pinnedCounters = nullptr;
     int32_t* dst = pinnedCounters ? pinnedCounters + idx : out;
     HIP_CHECK(hipMemcpyAsync(dst, counters.p + idx, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
     HIP_CHECK(hipStreamSynchronize(stream));
     if (pinnedCounters) for (int q = 0; q < n; ++q) out[q] = pinnedCounters[idx + q];
 }
-void ps_context::zeroCounters() { HIP_CHECK(hipMemsetAsync(counters.p, 0, 64 * sizeof(int32_t), stream)); }
+void ps_context::zeroChangeFlags() { HIP_CHECK(hipMemsetAsync(counters.p + CTR_CHANGED, 0, 2 * sizeof(int32_t), stream)); }
 
 // In-place exclusive scan of a device int32 array; returns the total (host).
 // counterSlot >= 0: the total goes to counters[counterSlot] and the call returns -1 without synchronising (as orderedIndexAssign).  Consecutive
@@ -980,17 +916,17 @@ void ps_context::zeroCounters() { HIP_CHECK(hipMemsetAsync(counters.p, 0, 64 * s
 // queued kernel uses) — the caller allocates it first.
 int64_t ps_context::exclusiveScanI32(int32_t* data, int64_t n, int counterSlot) {
     if (n <= 0) { if (counterSlot >= 0) HIP_CHECK(hipMemsetAsync(counters.p + counterSlot, 0, sizeof(int32_t), stream)); return counterSlot >= 0 ? -1 : 0; }
-    const int slot = counterSlot >= 0 ? counterSlot : 8;
+    const int slot = counterSlot >= 0 ? counterSlot : CTR_SCAN_TOTAL;
     const int nb = gridFor(n, SCAN_TILE);
     if (nb == 1) {
         hipLaunchKernelGGL(k_scan_single, dim3(1), dim3(1024), 0, stream, data, n, counters.p + slot);
-        return counterSlot >= 0 ? -1 : readCounter(8);
+        return counterSlot >= 0 ? -1 : readCounter(CTR_SCAN_TOTAL);
     }
     scanBlock.alloc((size_t)nb);
     hipLaunchKernelGGL(k_scan_blocksum, dim3(nb), dim3(BS), 0, stream, data, n, scanBlock.p);
     hipLaunchKernelGGL(k_scan_single, dim3(1), dim3(1024), 0, stream, scanBlock.p, (int64_t)nb, counters.p + slot);
     hipLaunchKernelGGL(k_scan_apply, dim3(nb), dim3(BS), 0, stream, data, n, scanBlock.p);
-    return counterSlot >= 0 ? -1 : readCounter(8);
+    return counterSlot >= 0 ? -1 : readCounter(CTR_SCAN_TOTAL);
 }
 
 // serialAssignFieldIndices (Classifier.cpp:1738-1770) as a two-level scan over traversal positions.
@@ -1001,11 +937,11 @@ int32_t ps_context::orderedIndexAssign(int s, int mode, DevBuf<int32_t>& out, in
     const int nb = gridFor(n, SCAN_TILE);
     scanBlock.alloc((size_t)nb);           // (one buffer for consecutive calls: the launches are ordered on the stream; sized for the largest grid on first use)
     const int32_t* src = mode == 0 ? labels[s].p : cellScratch[0].p;
-    const int slot = counterSlot >= 0 ? counterSlot : 8;
+    const int slot = counterSlot >= 0 ? counterSlot : CTR_SCAN_TOTAL;
     hipLaunchKernelGGL(k_ordered_count, dim3(nb), dim3(BS), 0, stream, g, s, mode, src, scanBlock.p);
     hipLaunchKernelGGL(k_scan_single, dim3(1), dim3(1024), 0, stream, scanBlock.p, (int64_t)nb, counters.p + slot);
     hipLaunchKernelGGL(k_ordered_assign, dim3(nb), dim3(BS), 0, stream, g, s, mode, src, scanBlock.p, out.p);
-    return counterSlot >= 0 ? -1 : readCounter(8);
+    return counterSlot >= 0 ? -1 : readCounter(CTR_SCAN_TOTAL);
 }
 
 // Solver.cpp:238-289
@@ -1083,10 +1019,10 @@ void ps_context::constructCenterReducedIndices(int part) {
     if (local)
         hipLaunchKernelGGL(k_cc_local, dim3((g.nx + B - 1) / B, (g.ny + B - 1) / B, (g.nz + B - 1) / B), dim3(256), (size_t)B * B * B * 5, stream, g, B, (const uint8_t*)link, cc);
     for (int guard = 0; guard < 100000; ++guard) {
-        zeroCounters();
+        zeroChangeFlags();
         for (int it = 0; it < ((local && guard == 0) ? 1 : 4); ++it)
-            hipLaunchKernelGGL(k_cc_step, gr, bl, 0, stream, g, (const uint8_t*)link, cc, counters.p);
-        if (!readCounter(0)) break;
+            hipLaunchKernelGGL(k_cc_step, gr, bl, 0, stream, g, (const uint8_t*)link, cc, counters.p + CTR_CHANGED);
+        if (!readCounter(CTR_CHANGED)) break;
     }
     int32_t* rootRank = cellScratch[1].p;
     {
@@ -1109,10 +1045,10 @@ void ps_context::constructCenterReducedIndices(int part) {
             int anyF = 0;
             bool applied = false;
             for (int it = 0; it < 100000; ++it) {
-                zeroCounters();
-                hipLaunchKernelGGL(k_fix_eval, gr, bl, 0, stream, g, labels[0].p, reducedIdx[0].p, F0, F1, anyF, counters.p);
+                zeroChangeFlags();
+                hipLaunchKernelGGL(k_fix_eval, gr, bl, 0, stream, g, labels[0].p, reducedIdx[0].p, F0, F1, anyF, counters.p + CTR_CHANGED);
                 int32_t fl[2];
-                fetchCounters(0, 2, fl);
+                fetchCounters(CTR_CHANGED, 2, fl);                     // (CTR_CHANGED, CTR_ANY_FIX)
                 std::swap(F0, F1);
                 anyF = fl[1];
                 if (!fl[0]) break;
@@ -1193,10 +1129,10 @@ void ps_context::constructActiveIndices() {
     for (int s = 0; s < 7; ++s) {
         const int64_t n = g.count(s);
         hipLaunchKernelGGL(k_relabel, dim3(gridFor(n, BS)), dim3(BS), 0, stream, labels[s].p, n, (int)PS_GENERICFLUID, (int)PS_ACTIVEFLUID);
-        (void)orderedIndexAssign(s, 0, activeIdx[s], 48 + s);      // totals -> counters[48 .. 54], one round trip for the seven
+        (void)orderedIndexAssign(s, 0, activeIdx[s], CTR_ACTIVE_TOTAL + s);      // one round trip for the seven totals
     }
     int32_t cnt[7];
-    fetchCounters(48, 7, cnt);
+    fetchCounters(CTR_ACTIVE_TOTAL, 7, cnt);
     nCenter = cnt[0];
     for (int a = 0; a < 3; ++a) { nFace[a] = cnt[1 + a]; nEdge[a] = cnt[4 + a]; }
 }
@@ -1256,16 +1192,16 @@ int64_t ps_context::interleavedIndexAssignEx(int ngroups, const int* samples, co
     Set8<int32_t> o;
     for (int q = 0; q < 8; ++q) o.p[q] = q < ngroups ? outs[q] : nullptr;
     hipLaunchKernelGGL(k_il_count, dim3(nbk), dim3(BS), 0, stream, D, g, cset(labels), scanBlock.p);
-    hipLaunchKernelGGL(k_scan_single, dim3(1), dim3(1024), 0, stream, scanBlock.p, (int64_t)nbk, counters.p + 8);
+    hipLaunchKernelGGL(k_scan_single, dim3(1), dim3(1024), 0, stream, scanBlock.p, (int64_t)nbk, counters.p + CTR_SCAN_TOTAL);
     const int nBlocks = (int)(run / per);
     DevBuf<int32_t>& bstart = scrStart4;      // scratch kept with the context (also the stream build's)
     bstart.alloc((size_t)nBlocks + 1);
-    hipLaunchKernelGGL(k_il_assign, dim3(nbk), dim3(BS), 0, stream, D, g, cset(labels), scanBlock.p, o, counters.p + 10, bstart.p);
-    int32_t cnt[4] = {0, 0, 0, 0};                      // counters[8 .. 11]: the total, -, the two probes — one round trip with the block starts
+    hipLaunchKernelGGL(k_il_assign, dim3(nbk), dim3(BS), 0, stream, D, g, cset(labels), scanBlock.p, o, counters.p + CTR_IL_PROBE, bstart.p);
+    int32_t cnt[4] = {0, 0, 0, 0};                      // CTR_SCAN_TOTAL, -, the two of CTR_IL_PROBE — one round trip with the block starts
     std::vector<int32_t>& hs = ownedRange ? blockStartSys : blockStartRow;
     hs.assign((size_t)nBlocks + 1, 0);
     HIP_CHECK(hipMemcpyAsync(hs.data(), bstart.p, (size_t)nBlocks * 4, hipMemcpyDeviceToHost, stream));
-    fetchCounters(8, 4, cnt);                            // (synchronises: the block starts have landed too)
+    fetchCounters(CTR_SCAN_TOTAL, 4, cnt);                            // (synchronises: the block starts have landed too)
     const int64_t total = cnt[0];
     hs[(size_t)nBlocks] = (int32_t)total;
     ilBlocks = nBlocks;
@@ -1293,10 +1229,10 @@ void ps_context::buildInternalNumbering() {
         static const bool oneShot = envInt(PS_ENV("PS_PIPE_GRID"), 1) == 0;
         int mode = 0;
         if (!noEll && !forceF64 && !col32 && !oneShot) {
-            HIP_CHECK(hipMemsetAsync(counters.p + 40, 0, sizeof(int32_t), stream));
-            for (int s2 : {1, 2, 3}) hipLaunchKernelGGL(k_dyadic_check, dim3(1024), dim3(BS), 0, stream, (const float*)fluidW[s2].p, g.count(s2), counters.p + 40);
-            for (int s2 : {0, 4, 5, 6}) hipLaunchKernelGGL(k_dyadic_check, dim3(1024), dim3(BS), 0, stream, (const float*)liquidW[s2].p, g.count(s2), counters.p + 40);
-            if (readCounter(40) == 0) mode = 3;
+            HIP_CHECK(hipMemsetAsync(counters.p + CTR_NOT_DYADIC, 0, sizeof(int32_t), stream));
+            for (int s2 : {1, 2, 3}) hipLaunchKernelGGL(k_dyadic_check, dim3(1024), dim3(BS), 0, stream, (const float*)fluidW[s2].p, g.count(s2), counters.p + CTR_NOT_DYADIC);
+            for (int s2 : {0, 4, 5, 6}) hipLaunchKernelGGL(k_dyadic_check, dim3(1024), dim3(BS), 0, stream, (const float*)liquidW[s2].p, g.count(s2), counters.p + CTR_NOT_DYADIC);
+            if (readCounter(CTR_NOT_DYADIC) == 0) mode = 3;
         }
         const char* e = PS_ENV("PS_IL");
         ilPlaneMajor = e ? (atoi(e) & 3) : mode;
@@ -1305,14 +1241,11 @@ void ps_context::buildInternalNumbering() {
     const int64_t nSys = 4 * nCenter + nEdge[0] + nEdge[1] + nEdge[2];
     const int64_t nAct = nFace[0] + nFace[1] + nFace[2];
     {   // the ten index arrays of the numbering start at -1: ONE launch (r06: ten before)
-        FillMany F;
-        int q = 0;
-        int64_t most = 1;
-        auto add = [&](int32_t* ptr, int64_t n) { F.p[q] = ptr; F.n[q] = n; ++q; most = std::max(most, n); };
-        for (int s : {0, 4, 5, 6}) { sysIdx[s].alloc((size_t)g.count(s)); add(sysIdx[s].p, g.count(s)); }
-        for (int a = 0; a < 3; ++a) { sysIdxT[a].alloc((size_t)g.count(0)); add(sysIdxT[a].p, g.count(0)); }
-        for (int a = 0; a < 3; ++a) add(faceRow[a].p, g.count(1 + a));
-        hipLaunchKernelGGL(k_fill_i32_many, dim3((unsigned)std::min<int64_t>(512, gridFor(most, BS)), (unsigned)q), dim3(BS), 0, stream, F, -1);
+        FillList F;
+        for (int s : {0, 4, 5, 6}) { sysIdx[s].alloc((size_t)g.count(s)); F.add(sysIdx[s].p, g.count(s)); }
+        for (int a = 0; a < 3; ++a) { sysIdxT[a].alloc((size_t)g.count(0)); F.add(sysIdxT[a].p, g.count(0)); }
+        for (int a = 0; a < 3; ++a) F.add(faceRow[a].p, g.count(1 + a));
+        fillI32(F, -1);
     }
     {
         // seven groups, one per kind of DOF: p, txx, tyy, tzz (all on the cell grid), then the YZ / XZ / XY edge stresses

@@ -1,8 +1,8 @@
 // Non-Newtonian viscosity (ps_set_rheology, an extension): the strain rate of the velocity field and the Herschel-Bulkley viscosity it
 // gives, one setup kernel; and the Picard passes of a single-domain step.  Nothing here runs with the Newtonian model.
 //
-// The kernel writes mu_c and gammaDot_c per cell; the setup then samples mu as it samples an uploaded viscosity field (viscAt / viscSample,
-// ps_context::viscSource), so the tile matrices, the stress diagonal and every format decision after it follow unchanged.
+// The kernel writes mu_c and gammaDot_c per cell; the setup then samples mu as it samples an uploaded viscosity field (CellField::sample of
+// ps_setup_util.hpp, handed out by ps_context::viscSource), so the tile matrices, the stress diagonal and every format decision after it follow unchanged.
 #include "ps_context.hpp"
 
 #include <chrono>

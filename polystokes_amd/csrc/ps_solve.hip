@@ -662,8 +662,7 @@ void ps_context::applyPreconditionerDevice(const double* rvec, double* z, double
         chebPartials.alloc((size_t)std::max<int64_t>(3 * VGRID, gridFor(n, BS)) + 16);
         double* zfin = z;
         chebInner32 = chebInner32Req && mk(this, nullptr).cheb32Ok();
-        chebInner32Host = chebInner32 ? 1 : 0;
-        HIP_CHECK(hipMemcpyAsync(counters.p + 36, &chebInner32Host, sizeof(int32_t), hipMemcpyHostToDevice, stream));   // (array "chebInner32")
+        chebInner32Host = chebInner32 ? 1 : 0;   // (array "chebInner32")
         chebyshevApply(rvec, z, scratch, chebPartials.p, nullptr, false, &zfin);
         if (chebInner32) {      // the result is an fp32 vector in one of the two buffers: widen it through a third
             tmp5.alloc((size_t)n);

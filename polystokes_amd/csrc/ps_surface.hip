@@ -70,6 +70,7 @@ __global__ void k_surface_curvature_at_interface(Grid g, const float* __restrict
     double step = move ? -p0 / g2 : 0.;                 // x_c + step * gi (world x - phi grad phi / |grad phi|^2 with grad phi = gi / dx, over dx)
     if (move && fabs(p0) > ST_MAX_STEP * gn) step *= ST_MAX_STEP * gn / fabs(p0);   // |step * gi| = |phi| / |gi| cells, capped
     const double x[3] = {(double)q.x, (double)q.y, (double)q.z};
+    // (not sampleCenterField of ps_setup_util.hpp: other arithmetic — fp64, floor, positions in cell indices, a NaN lands on 0)
     const int n[3] = {d.x, d.y, d.z};
     int i0[3], i1[3];
     double t[3];

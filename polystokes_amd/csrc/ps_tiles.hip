@@ -10,29 +10,28 @@
 // vectors at a time in LDS and accumulates the 26x26 block; partial blocks are then summed per region
 // in a fixed order (deterministic, no atomics).
 #include "ps_context.hpp"
+#include "ps_setup_util.hpp"
 
 using namespace ps;
 
 namespace {
 
-constexpr int BS = 256;
+constexpr int BS = SETUP_BS;
 constexpr int FBATCH = 128;
 constexpr int OUTW = PS_RD * PS_RD + PS_RD;   // 676 block entries + 26 rhs entries
 
-// MODE_MASS_FIELD: MODE_MASS with a density field — each face's row scaled by its own density (densityAt) instead of the scalar rho
+// MODE_MASS_FIELD: MODE_MASS with a density field — each face's row scaled by its own density (FaceDensity::at) instead of the scalar rho
 enum { MODE_MASS = 0, MODE_LSQ = 1, MODE_VISC = 2, MODE_MASS_FIELD = 3 };
 
 struct TileArgs {
     Grid g;
-    double dx, rho;
+    double dx;
     const int32_t* lab[7];
     const int32_t* reg[7];
     const float* vel[3];
-    const float* visc;
-    int viscUniform; float viscValue;   // a constant field: its samples without loads (bit-identical: ps_context::upload)
-    const float* dens;                  // cell density field (ps_upload_density_field); null: the scalar rho everywhere
-    double densMin, densMax;
-    const double* densFace[3];          // its clamped face samples (k_face_density), read by the MODE_MASS_FIELD sums
+    CellField visc;                     // ps_context::viscSource
+    FaceDensity dens;                   // ps_context::densSource
+    const double* densFace[3];          // a density field's clamped face samples (k_face_density), read by the MODE_MASS_FIELD sums
     const double* COM;
     int3 off;                       // global index of the local cell (0, 0, 0) (ps_kernels_tiles.hpp: rowOffset)
     const int32_t* bbox;
@@ -46,59 +45,6 @@ __device__ inline int labAt(const TileArgs& A, int s, const int3 d, int i, int j
 }
 __device__ inline int regAt(const TileArgs& A, int s, const int3 d, int i, int j, int k) {
     return oob3(d, i, j, k) ? PS_UNASSIGNED : A.reg[s][lin3(d, i, j, k)];
-}
-
-__device__ inline float viscSample(const TileArgs& A, float px, float py, float pz) {
-    if (A.viscUniform) return A.viscValue;
-    // same restatement of SIM_RawField::getValue as ps_grid.hip::sampleCenterField
-    const int n[3] = {A.g.nx, A.g.ny, A.g.nz};
-    const float p[3] = {px, py, pz};
-    int i0[3], i1[3];
-    float t[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        float u = p[a] - 0.5f;
-        if (u < 0.f) u = 0.f;
-        if (u > (float)(n[a] - 1)) u = (float)(n[a] - 1);
-        int b = (int)u;
-        if (b >= n[a] - 1) { b = n[a] - 1; i0[a] = b; i1[a] = b; t[a] = 0.f; }
-        else { i0[a] = b; i1[a] = b + 1; t[a] = u - (float)b; }
-    }
-    const int64_t sy = A.g.nx, sz = (int64_t)A.g.nx * A.g.ny;
-    auto at = [&](int i, int j, int k) { return A.visc[i + j * sy + k * sz]; };
-    auto L = [](float a, float b, float tt) { return a + (b - a) * tt; };
-    const float c00 = L(at(i0[0], i0[1], i0[2]), at(i1[0], i0[1], i0[2]), t[0]);
-    const float c10 = L(at(i0[0], i1[1], i0[2]), at(i1[0], i1[1], i0[2]), t[0]);
-    const float c01 = L(at(i0[0], i0[1], i1[2]), at(i1[0], i0[1], i1[2]), t[0]);
-    const float c11 = L(at(i0[0], i1[1], i1[2]), at(i1[0], i1[1], i1[2]), t[0]);
-    return L(L(c00, c10, t[1]), L(c01, c11, t[1]), t[2]);
-}
-
-// Density of the face (axis, i, j, k), as ps_blocks.hip:densityAt (the face rows' McInv / Mc): the cell field sampled at the face centre
-// with the viscosity's sampler, clamped to [mindensity, maxdensity] (a field is present: k_face_density samples every face once)
-__device__ inline double densityAt(const TileArgs& A, int axis, int i, int j, int k) {
-    const int n[3] = {A.g.nx, A.g.ny, A.g.nz};
-    const float p[3] = {(float)i + (axis == 0 ? 0.f : 0.5f), (float)j + (axis == 1 ? 0.f : 0.5f), (float)k + (axis == 2 ? 0.f : 0.5f)};
-    int i0[3], i1[3];
-    float t[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        float u = p[a] - 0.5f;
-        if (u < 0.f) u = 0.f;
-        if (u > (float)(n[a] - 1)) u = (float)(n[a] - 1);
-        int b = (int)u;
-        if (b >= n[a] - 1) { b = n[a] - 1; i0[a] = b; i1[a] = b; t[a] = 0.f; }
-        else { i0[a] = b; i1[a] = b + 1; t[a] = u - (float)b; }
-    }
-    const int64_t sy = A.g.nx, sz = (int64_t)A.g.nx * A.g.ny;
-    auto at = [&](int ii, int jj, int kk) { return A.dens[ii + jj * sy + kk * sz]; };
-    auto L = [](float a, float b, float tt) { return a + (b - a) * tt; };
-    const float c00 = L(at(i0[0], i0[1], i0[2]), at(i1[0], i0[1], i0[2]), t[0]);
-    const float c10 = L(at(i0[0], i1[1], i0[2]), at(i1[0], i1[1], i0[2]), t[0]);
-    const float c01 = L(at(i0[0], i0[1], i1[2]), at(i1[0], i0[1], i1[2]), t[0]);
-    const float c11 = L(at(i0[0], i1[1], i1[2]), at(i1[0], i1[1], i1[2]), t[0]);
-    const double v = (double)L(L(c00, c10, t[1]), L(c01, c11, t[1]), t[2]);
-    return v < A.densMin ? A.densMin : (v > A.densMax ? A.densMax : v);
 }
 
 __device__ inline void faceOffset(const TileArgs& A, int axis, int i, int j, int k, int region, double* o) {
@@ -134,7 +80,7 @@ __device__ void viscosityRowT(const TileArgs& A, int i, int j, int k, double* gv
             if (!isReducedL(labAt(A, 0, cd, c.x, c.y, c.z))) continue;
             if (comp(c, FA) < 0 || comp(c, FA) >= comp(fd, FA)) continue;
             const double divSign = divDir == 0 ? -1. : 1.;
-            const double visc = (double)viscSample(A, (float)c.x + 0.5f, (float)c.y + 0.5f, (float)c.z + 0.5f);
+            const double visc = (double)A.visc.sample(A.g, (float)c.x + 0.5f, (float)c.y + 0.5f, (float)c.z + 0.5f);
 #pragma unroll
             for (int gradDir = 0; gradDir < 2; ++gradDir) {
                 int3 af = c;
@@ -164,7 +110,7 @@ __device__ void viscosityRowT(const TileArgs& A, int i, int j, int k, double* gv
             addc(e, 3 - FA - edgeAxis, divDir);
             if (labAt(A, 4 + edgeAxis, ed, e.x, e.y, e.z) != PS_REDUCED) continue;
             const float ox = edgeAxis == 0 ? 0.5f : 0.f, oy = edgeAxis == 1 ? 0.5f : 0.f, oz = edgeAxis == 2 ? 0.5f : 0.f;
-            const float visc = viscSample(A, (float)e.x + ox, (float)e.y + oy, (float)e.z + oz);
+            const float visc = A.visc.sample(A.g, (float)e.x + ox, (float)e.y + oy, (float)e.z + oz);
 #pragma unroll
             for (int gradAxis = 0; gradAxis < 3; ++gradAxis) {
                 if (gradAxis == edgeAxis) continue;
@@ -270,7 +216,7 @@ __global__ void __launch_bounds__(BS) k_region_outer(TileArgs A, double* __restr
                     for (int f = 0; f < FBATCH; ++f) s += sa[f][em[q]] * sb[f][en[q]];
                 } else if (MASS) {
                     if (DENS) { for (int f = 0; f < FBATCH; ++f) s += (sr[f] * sa[f][em[q]]) * sa[f][en[q]]; }
-                    else { for (int f = 0; f < FBATCH; ++f) s += (A.rho * sa[f][em[q]]) * sa[f][en[q]]; }
+                    else { for (int f = 0; f < FBATCH; ++f) s += (A.dens.rho * sa[f][em[q]]) * sa[f][en[q]]; }
                 } else {
                     for (int f = 0; f < FBATCH; ++f) s += sa[f][em[q]] * sa[f][en[q]];
                 }
@@ -369,7 +315,7 @@ __global__ void __launch_bounds__(BS) k_region_outer_mfma(TileArgs A, double* __
                 faceOffset(A, axis, i, j, k, r, o);
                 basisRow(o[0], o[1], o[2], axis, vec);
                 if (MASS && !doB) {
-                    const double rf = DENS ? A.densFace[axis][lin3(fd, i, j, k)] : A.rho;
+                    const double rf = DENS ? A.densFace[axis][lin3(fd, i, j, k)] : A.dens.rho;
 #pragma unroll
                     for (int n = 0; n < PS_RD; ++n) vec[n] *= rf;
                 }
@@ -433,13 +379,13 @@ __global__ void __launch_bounds__(BS) k_region_outer_mfma(TileArgs A, double* __
     }
 }
 
-// the density of every face of one axis (densityAt), sampled once for the tile mass sums
+// the density of every face of one axis (FaceDensity::at, as the face rows' McInv / Mc get it), sampled once for the tile mass sums
 __global__ void k_face_density(TileArgs A, int axis, double* __restrict__ out) {
     const int3 fd = A.g.dims(1 + axis);
     const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= (int64_t)fd.x * fd.y * fd.z) return;
     const int3 q = unlin3(fd, c);
-    out[c] = densityAt(A, axis, q.x, q.y, q.z);
+    out[c] = A.dens.at(A.g, axis, q.x, q.y, q.z);
 }
 
 // out[r] = sum of the region's item partials, in item order
@@ -471,7 +417,7 @@ __device__ inline TileWord tileWord(const TileArgs& A, int r, int i, int j, int 
         const int64_t c = lin3(cd, i, j, k);
         const int rg = A.reg[0][c];
         w.geom |= (unsigned long long)(A.lab[0][c] & 0xff) | ((unsigned long long)(rg == r ? 1 : (rg >= 0 ? 2 : 0)) << 8);
-        if (!A.viscUniform) w.visc = __float_as_uint(A.visc[c]);
+        if (!A.visc.uniform) w.visc = __float_as_uint(A.visc.p[c]);
     } else w.geom |= 0xffull;
 #pragma unroll
     for (int s = 1; s < 7; ++s) {
@@ -488,10 +434,6 @@ __device__ inline TileWord tileWord(const TileArgs& A, int r, int i, int j, int 
     }
     return w;
 }
-__device__ inline unsigned long long tmix(unsigned long long x) {
-    x ^= x >> 33; x *= 0xff51afd7ed558ccdull; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull; x ^= x >> 33;
-    return x;
-}
 constexpr long long TILE_SIG_MAX_POS = 1 << 16;   // boxes beyond this (the single region of the non-tiled mode) are not compared
 __global__ void __launch_bounds__(BS) k_tile_signature(TileArgs A, unsigned long long* __restrict__ sig, int32_t* __restrict__ unique) {
     const int r = blockIdx.x;
@@ -504,8 +446,8 @@ __global__ void __launch_bounds__(BS) k_tile_signature(TileArgs A, unsigned long
         for (int pos = threadIdx.x; pos < (int)total; pos += BS) {
             const TileWord w = tileWord(A, r, bx0 + pos % ex, by0 + (pos / ex) % ey, bz0 + pos / (ex * ey));
             foreign |= w.foreign;
-            h1 += tmix(((unsigned long long)pos << 46) ^ w.geom);
-            h2 += tmix((((unsigned long long)pos * 0x9e3779b97f4a7c15ull) ^ w.geom) + ((unsigned long long)w.visc << 17) + 0x632be59bd9b4e019ull);
+            h1 += mix64(((unsigned long long)pos << 46) ^ w.geom);
+            h2 += mix64((((unsigned long long)pos * 0x9e3779b97f4a7c15ull) ^ w.geom) + ((unsigned long long)w.visc << 17) + 0x632be59bd9b4e019ull);
         }
     __shared__ unsigned long long sh[2][BS / 64];
     __shared__ int sf[BS / 64];
@@ -516,8 +458,8 @@ __global__ void __launch_bounds__(BS) k_tile_signature(TileArgs A, unsigned long
     if (threadIdx.x == 0) {
         unsigned long long a = 0, b = 0; int f = 0;
         for (int q = 0; q < BS / 64; ++q) { a += sh[0][q]; b += sh[1][q]; f |= sf[q]; }
-        a = tmix(a ^ (((unsigned long long)ex << 42) | ((unsigned long long)ey << 21) | (unsigned long long)ez));
-        sig[2 * r] = a == 0xffffffffffffffffull ? 0ull : a;
+        a = mix64(a ^ (((unsigned long long)ex << 42) | ((unsigned long long)ey << 21) | (unsigned long long)ez));
+        sig[2 * r] = a == HASH_EMPTY ? 0ull : a;
         sig[2 * r + 1] = b;
         unique[r] = f;
     }
@@ -527,12 +469,7 @@ __global__ void k_tile_rep_insert(const unsigned long long* __restrict__ sig, co
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= R || unique[r]) return;
     const unsigned long long h = sig[2 * r];
-    unsigned slot = (unsigned)(h >> 20) & mask;
-    for (unsigned probe = 0; probe <= mask; ++probe, slot = (slot + 1) & mask) {
-        unsigned long long cur = keys[slot];
-        if (cur == 0xffffffffffffffffull) { cur = atomicCAS(&keys[slot], 0xffffffffffffffffull, h); if (cur == 0xffffffffffffffffull) cur = h; }
-        if (cur == h) { atomicMin(&vals[slot], r); return; }
-    }
+    hashInsertMin(keys, vals, mask, (unsigned)(h >> 20) & mask, h, r);
 }
 // rep[r] = the region whose blocks r takes (itself unless its pattern equals, word for word, that of the smallest region with its signature)
 __global__ void __launch_bounds__(BS) k_tile_rep_verify(TileArgs A, const unsigned long long* __restrict__ sig, const int32_t* __restrict__ unique,
@@ -738,13 +675,10 @@ __global__ void __launch_bounds__(64) k_binv(double invDt, const double* __restr
 
 TileArgs makeArgs(ps_context* c) {
     TileArgs A;
-    A.g = c->g; A.dx = c->dx; A.rho = c->rho;
+    A.g = c->g; A.dx = c->dx;
     for (int s = 0; s < 7; ++s) { A.lab[s] = c->labels[s].p; A.reg[s] = c->reducedIdx[s].p; }
     for (int a = 0; a < 3; ++a) A.vel[a] = c->vel[a].p;
-    const ps_context::ViscSource vs = c->viscSource();   // the uploaded field, or mu of ps_set_rheology
-    A.visc = vs.p;
-    A.viscUniform = vs.uniform; A.viscValue = vs.value;
-    A.dens = c->densField ? c->density.p : nullptr; A.densMin = c->densMin; A.densMax = c->densMax;
+    A.visc = c->viscSource(); A.dens = c->densSource();
     for (int a = 0; a < 3; ++a) A.densFace[a] = c->densFace[a].p;
     A.COM = c->COM.p;
     A.off = make_int3(c->gOff[0], c->gOff[1], c->gOff[2]);
