@@ -127,16 +127,8 @@ __global__ void __launch_bounds__(BS) k_warm_gather(SolutionGrids G, const float
 __global__ void k_to_diag(const double* __restrict__ a, diag_t* __restrict__ out, int64_t n) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) out[i] = diagStore(a[i]);
 }
-__device__ inline double sumLocal(const double* __restrict__ partial, int count) {   // this thread's share (fixed stride order)
-    double acc = 0.;
-    for (int i = threadIdx.x; i < count; i += BS) acc += partial[i];
-    return acc;
-}
-__device__ inline double sumPartials(const double* __restrict__ partial, int count) {
-    double acc = 0.;
-    for (int i = threadIdx.x; i < count; i += BS) acc += partial[i];
-    return blockReduceSum(acc);
-}
+// sum of `count` partials, valid in thread 0 (sumLocal, stopTest: ps_kernels_spmv.hpp, shared with the fused St epilogue)
+__device__ inline double sumPartials(const double* __restrict__ partial, int count) { return blockReduceSum(sumLocal(partial, count)); }
 __global__ void __launch_bounds__(BS) k_cg_scal0(CGScalars* sc, const double* __restrict__ partial, int count, double tol, int maxit, int vecNT) {
     const double s = sumPartials(partial, count);
     if (threadIdx.x == 0) {
@@ -246,14 +238,6 @@ __global__ void __launch_bounds__(BS) k_cg_update_p(const CGScalars* __restrict_
 // the start of iteration k+1 (or by k_cg_check before the host polls); when it fires every later kernel is a no-op and
 // x already holds the iterate the reference returns.  Cost: one unused p update and one unused operator apply.
 // With `red` (distributed solve) the sums come all-reduced from the ranks: red = {p.Ap, x.x} resp. {r.r, r.z}.
-__device__ inline bool stopTest(CGScalars* sc, double xx, int iterIndex, bool writer) {
-    const double rr = sc->rr;
-    double rre = rr;                                   // pcg.h:319-325
-    if (rr / xx < rre) rre = rr / xx;
-    const bool fire = rre < sc->tol2;
-    if (writer) { sc->xx = xx; sc->rre = rre; if (fire) { sc->done = 1; sc->iter = iterIndex; } }
-    return fire;
-}
 __global__ void __launch_bounds__(BS) k_cg_check(CGScalars* sc, const double* __restrict__ red, const double* __restrict__ xxPartial, int vb, int lastIter) {
     if (sc->done) return;
     const double xx = red ? red[0] : blockSumAll(sumLocal(xxPartial, vb));

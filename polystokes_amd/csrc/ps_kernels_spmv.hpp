@@ -190,7 +190,9 @@ struct FusedR {
     double* r; const diag_t* dinvF;       // residual (updated in place), stored Jacobi diagonal (ps_common.hpp: diag_t; null: identity)
     double* rPart;                        // out: partials of r.r at [block], of r.z at [gridDim + block]
     // Chebyshev preconditioner: the polynomial's first term on the new r, z_1 = dinv r / theta -> cz (null: not asked for; then r.z
-    // above is that of the Jacobi diagonal)
+    // above is that of the Jacobi diagonal).  At most ONE of dinvF and cz is set (every site that fills a FusedR: the Chebyshev step, the
+    // Jacobi / identity step and spmv_St_r in ps_solve.hip, the rank's step in ps_dist.hpp): with cz the r.z partial is the polynomial's
+    // share alone and dinvF is not read (fusedRowFinish).
     const diag_t* dinvC; double invTheta; double* cz;
     // Slab decomposition (ps_dist.hpp): red = {S + T + 1/2 U summed over the ranks, ||x||^2 over the ranks} replaces the partial
     // sums above; only rows in [ownLo, ownHi) are this rank's DOFs — the others (halo DOFs) carry contributions to a neighbour's
@@ -203,21 +205,24 @@ struct FusedR {
 };
 // Walk of a persistent workgroup over the chunk ids: runs of G = 1 << sh consecutive chunks are dealt to the 8 XCDs round robin
 // (workgroup b runs on XCD b & 7), inside an XCD to its workgroups in order; sh < 0: plain grid-stride walk
-struct ChunkWalk {
-    int sh, x, l, per, rs;   // rs: a workgroup takes runs of 1 << rs CONSECUTIVE chunks (bits 16.. of the launch parameter): its waves then find the
-                             // lines the previous chunk gathered in the CU's L1
-    __device__ explicit ChunkWalk(int g)
-        : sh((g & 0xffff) > 0 ? 31 - __builtin_clz((unsigned)(g & 0xffff)) : -1), x(blockIdx.x & 7), l(blockIdx.x >> 3), per(gridDim.x >> 3), rs((g >> 16) & 7) {}
-    __device__ int at(int it) const {
-        const int j = it >> rs, o = it & ((1 << rs) - 1);
-        int run;
-        if (sh < 0) run = blockIdx.x + j * gridDim.x;
-        else {
-            const int q = l + j * per;
-            run = ((((q >> sh) << 3) + x) << sh) + (q & ((1 << sh) - 1));
-        }
-        return (run << rs) + o;
+// rs: a workgroup takes runs of 1 << rs CONSECUTIVE chunks (bits 16.. of the launch parameter g): its waves then find the lines the previous
+// chunk gathered in the CU's L1.  Plain integers, for the kernels and for the host (ps_solve.hip: Launch::noteWalk).
+__host__ __device__ inline int chunkWalkShift(int g) { return (g & 0xffff) > 0 ? 31 - __builtin_clz((unsigned)(g & 0xffff)) : -1; }
+__host__ __device__ inline int chunkWalkRun(int g) { return (g >> 16) & 7; }
+__host__ __device__ inline int chunkWalkAt(int it, int block, int grid, int sh, int rs) {   // step `it` of workgroup `block` of `grid` -> chunk (>= the chunk count: the walk is over)
+    const int j = it >> rs, o = it & ((1 << rs) - 1);
+    int run;
+    if (sh < 0) run = block + j * grid;
+    else {
+        const int q = (block >> 3) + j * (grid >> 3);
+        run = ((((q >> sh) << 3) + (block & 7)) << sh) + (q & ((1 << sh) - 1));
     }
+    return (run << rs) + o;
+}
+struct ChunkWalk {
+    int sh, rs;
+    __device__ explicit ChunkWalk(int g) : sh(chunkWalkShift(g)), rs(chunkWalkRun(g)) {}
+    __device__ int at(int it) const { return chunkWalkAt(it, (int)blockIdx.x, (int)gridDim.x, sh, rs); }
 };
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 // Every access of the loop body goes through a buffer descriptor (buffer_load/store ... offen): 32-bit byte offsets
@@ -390,39 +395,180 @@ __device__ inline double rowSum(const double* prod, int ea, int len) {
     for (int k = 0; k < ML; ++k) s = k < len ? s + v[k] : s;
     return s;
 }
+// ---- pieces the persistent kernels share ------------------------------------------------------------------------------------
+// Each of them exists ONCE: the kernels below differ in how the stream is laid out and walked, not in what a row's epilogue computes, and the
+// forced forms are compared against one oracle — the copies had to stay bit-identical to each other.
+//
+// Scalars of the PCG step that every workgroup forms itself (ps_kernels_cg.hpp: k_cg_update_r, k_cg_check use the same two helpers)
+__device__ inline double sumLocal(const double* __restrict__ partial, int count) {   // this thread's share (fixed stride order)
+    double acc = 0.;
+    for (int i = threadIdx.x; i < count; i += BS) acc += partial[i];
+    return acc;
+}
+__device__ inline bool stopTest(CGScalars* sc, double xx, int iterIndex, bool writer) {
+    const double rr = sc->rr;
+    double rre = rr;                                   // pcg.h:319-325
+    if (rr / xx < rre) rre = rr / xx;
+    const bool fire = rre < sc->tol2;
+    if (writer) { sc->xx = xx; sc->rre = rre; if (fire) { sc->done = 1; sc->iter = iterIndex; } }
+    return fire;
+}
+// Prologue of the fused residual update, as k_cg_update_r: [stop test of iteration it-1], alpha = rsold / p.Ap — identical in every
+// workgroup (each sums the partials itself, in the same order), workgroup 0 records the scalars.  reduced: the sums come all-reduced in
+// fr.red.  Returns false when the stop test fired (same verdict in every workgroup: the kernel returns).
+__device__ __forceinline__ bool fusedPrologue(const FusedR& fr, bool reduced, double& alpha) {
+    CGScalars* sc = fr.sc;
+    const bool writer = blockIdx.x == 0 && threadIdx.x == 0;
+    if (fr.it > 0 && stopTest(sc, reduced ? fr.red[1] : blockSumAll(sumLocal(fr.xxPart, fr.xxCount)), fr.it - 1, writer)) return false;
+    const double pAp = reduced ? -fr.red[0]
+                               : -(blockSumAll(sumLocal(fr.sPart, fr.sCount)) + blockSumAll(sumLocal(fr.tPart, fr.tCount)) + 0.5 * blockSumAll(sumLocal(fr.uPart, fr.uCount)));
+    alpha = sc->rsold2[fr.it & 1] / pAp;               // pcg.h:314
+    if (writer) { sc->pAp = pAp; sc->alpha = alpha; }
+    return true;
+}
+
+// A per-row diagonal — the face mass McInv of the S kernels, the stress diagonal uInv of the St kernels — comes as one-byte codes into a
+// 256-entry table in LDS (CODED; ps_context.hpp: mcCode / uCode) or, when it takes more than 256 values (a density or viscosity FIELD), as
+// the fp64 array: 7 more bytes per row.  fill: the table (first read after a barrier of the caller); load: the row's byte at `srow` (the row
+// of the chunk whose run this is: the byte streams go with the runs) or its 8 bytes at `row`, AUX = the site's cache policy; value: the lookup.
+struct DiagRow { int code; double v; };
+template <bool CODED> struct RowDiag {
+    __device__ static inline void fill(double* dict, const double* __restrict__ table) { if (CODED) dict[threadIdx.x] = table[threadIdx.x]; }
+    template <int AUX> __device__ static inline DiagRow load(__amdgpu_buffer_rsrc_t r, unsigned row, unsigned srow) {
+        if constexpr (CODED) return DiagRow{(int)__builtin_amdgcn_raw_buffer_load_b8(r, (int)srow, 0, AUX), 0.};
+        else return DiagRow{0, __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r, (int)(row * 8u), 0, AUX))};
+    }
+    __device__ static inline double value(const double* dict, const DiagRow& d) { if constexpr (CODED) return dict[d.code]; else return d.v; }
+};
+// the form chosen at run time (the kernels that take both arrays): rc = the codes, rv = the fp64 array
+template <int CAUX, int VAUX> __device__ inline DiagRow rowDiagLoad(bool coded, __amdgpu_buffer_rsrc_t rc, __amdgpu_buffer_rsrc_t rv, unsigned row, unsigned srow) {
+    if (coded) return RowDiag<true>::load<CAUX>(rc, row, srow);
+    return RowDiag<false>::load<VAUX>(rv, row, srow);
+}
+__device__ inline double rowDiagValue(bool coded, const double* dict, const DiagRow& d) { return coded ? RowDiag<true>::value(dict, d) : RowDiag<false>::value(dict, d); }
+
+// ---- row epilogues
+// S: t[row] = (row < nA ? dt McInv[row] : 1) s (MODE 0; MODE 1: s), stAcc += s t on the ACTIVE rows — their share of x . A x = sum s_f t_f
+// (idle lanes: row = ROW_NONE is past nA and past the output buffer: the store is dropped)
+template <int MODE, bool NT, class TV>
+__device__ __forceinline__ void sRowFinish(__amdgpu_buffer_rsrc_t rOut, unsigned row, int nA, double dt, double mc, double s, double& stAcc) {
+    const double sc = (MODE == 0 && (int)row < nA) ? dt * mc : 1.;
+    if (MODE == 0) stAcc += (int)row < nA ? s * (s * sc) : 0.;
+    VecIO<TV>::template store<NT>(rOut, row, s * sc);
+}
+// St: (A x)[row] = -(St t)[row] - 1/2 uInv[row] x[row]
+__device__ __forceinline__ double stRowY(double s, double u, double x) {
+    double y = -s;
+    y -= 0.5 * u * x;
+    return y;
+}
+// MODE 2, one Chebyshev term: z_{j+1} = z_j + c1 (z_j - z_{j-1}) + c2 dinv (r - A z_j), r.z of the updated z AS STORED (TV; 0 past the
+// last row: every load returned 0)
+struct ChebRow { double cr, ci, cd; };   // r, dinv, z_{j-1} (0: no buffer) of the row
+template <class TV>
+__device__ __forceinline__ ChebRow chebLoads(__amdgpu_buffer_rsrc_t rCr, __amdgpu_buffer_rsrc_t rCi, __amdgpu_buffer_rsrc_t rCd, unsigned row) {
+    return ChebRow{bufLoadF64(rCr, row * 8u), (double)bufLoadDiag<false>(rCi, row), VecIO<TV>::load(rCd, row)};
+}
+template <class TV>
+__device__ __forceinline__ double chebRowFinish(const ChebArgs& cheb, const ChebRow& c, double az, double z, double& dacc) {
+    const double y = VecIO<TV>::stored(z + (cheb.c1 * (z - c.cd) + cheb.c2 * (c.ci * (c.cr - az))));
+    dacc += c.cr * y;
+    return y;
+}
+// MODE 3, the residual update on a row whose y = (A p)[row] is still in a register (never stored).  The flags are compile-time constants
+// where the kernel knows them (k_spmv_St_ell2: HALO, CZ) and run-time tests of fr.yOut / fr.cz where it does not (the _pipe and one-unit
+// kernels); fr.dinvF is a run-time test everywhere.
+//   ranged: rows outside [fr.ownLo, fr.ownHi) are not this rank's (false: every live row is);  halo: such a row's y goes to fr.yOut;
+//   cz: the Chebyshev polynomial's first term z_1 = dinv r / theta -> fr.cz (elements TZ), r.z formed with z_1 AS STORED; without it
+//   r.z is that of the Jacobi diagonal fr.dinvF (null: none asked for) — never both (FusedR).
+struct FusedBufs { __amdgpu_buffer_rsrc_t r, dinv, dinvC, cz, y; };
+template <class TZ>
+__device__ inline FusedBufs fusedBufs(const FusedR& fr, int rows, bool on, bool halo, bool cz) {
+    return FusedBufs{bufRsrc(fr.r, on ? (size_t)rows * 8 : 0), bufRsrc(fr.dinvF, (on && !cz && fr.dinvF) ? (size_t)rows * sizeof(diag_t) : 0),
+                     bufRsrc(fr.dinvC, (on && cz) ? (size_t)rows * sizeof(diag_t) : 0), bufRsrc(fr.cz, (on && cz) ? (size_t)rows * sizeof(TZ) : 0),
+                     bufRsrc(fr.yOut, (on && halo) ? (size_t)rows * 8 : 0)};
+}
+struct FusedRow { double cr, ci; float fd; };   // r, the polynomial's diagonal (cz), the Jacobi diagonal (1: identity) of the row
+template <bool NT>
+__device__ __forceinline__ FusedRow fusedLoads(const FusedR& fr, const FusedBufs& B, unsigned row, bool cz) {
+    FusedRow L{__builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(B.r, (int)(row * 8u), 0, NT ? PS_EPI_AUX : 0)), 0., 1.f};
+    if (cz) L.ci = (double)bufLoadDiag<NT>(B.dinvC, row);
+    else if (fr.dinvF) L.fd = bufLoadDiag<NT>(B.dinv, row);
+    return L;
+}
+template <bool NT, class TZ>
+__device__ __forceinline__ void fusedRowFinish(const FusedR& fr, const FusedBufs& B, unsigned row, bool live, bool ranged, bool halo, bool cz, double alpha, double y,
+                                               const FusedRow& L, double& dacc, double& dacc2) {
+    const bool mine = ranged ? ((int)row >= fr.ownLo && (int)row < fr.ownHi) : live;   // (idle lanes: ROW_NONE is beyond ownHi)
+    if (halo) bufStoreF64nt<NT>(B.y, (!mine && live) ? row * 8u : 0xfffffff8u, y);    // a neighbour's row: its share of A p
+    const double rv = mine ? L.cr - alpha * y : 0.;                                   // pcg.h:316
+    dacc += rv * rv;
+    if (cz) {                                                                          // k_cheb_first on this row
+        const double v = VecIO<TZ>::stored(L.ci * rv * fr.invTheta);
+        VecIO<TZ>::template store<NT>(B.cz, row, v);
+        dacc2 += rv * v;
+    } else if (fr.dinvF) dacc2 += (!ranged || mine) ? rv * ((double)L.fd * rv) : 0.;   // (the diagonal of a halo row is not this rank's: may be anything)
+    bufStoreF64nt<NT>(B.r, (!ranged || mine) ? row * 8u : 0xfffffff8u, rv);
+}
+// the workgroup's partials of r.r at fr.rPart[block], of r.z at fr.rPart[stride + block]
+__device__ __forceinline__ void fusedPartials(const FusedR& fr, double dacc, double dacc2, bool cz, int stride) {
+    const double b0 = blockReduceSum(dacc), b1 = (cz || fr.dinvF) ? blockReduceSum(dacc2) : 0.;
+    if (threadIdx.x == 0) { fr.rPart[blockIdx.x] = b0; fr.rPart[stride + blockIdx.x] = b1; }
+}
+
+// The St row of the kernels that take MODE at compile time and everything else at run time (k_spmv_St_pipe, k_spmv_St_ell):
+// MODE 0: out = A x, partial of x . A x;  MODE 1: out = -(St t) + add;  MODE 2 / 3: above
+struct StBufs { __amdgpu_buffer_rsrc_t e0, e1, uc, out, cr, ci, cd; FusedBufs f; };
+template <int MODE>
+__device__ inline StBufs stBufs(int rows, const double* uInv, const double* xin, const double* add, double* out, const ChebArgs& cheb, const uint8_t* uCode, bool coded,
+                                const FusedR& fr) {
+    return StBufs{bufRsrc(MODE == 1 ? add : xin, (size_t)rows * 8), bufRsrc(uInv, (size_t)rows * 8), bufRsrc(uCode, coded ? (size_t)rows : 0),
+                  bufRsrc(out, (size_t)rows * 8), bufRsrc(cheb.r, MODE == 2 ? (size_t)rows * 8 : 0), bufRsrc(cheb.dinv, MODE == 2 ? (size_t)rows * sizeof(diag_t) : 0),
+                  bufRsrc(cheb.zprev, (MODE == 2 && cheb.zprev) ? (size_t)rows * 8 : 0),
+                  fusedBufs<double>(fr, rows, MODE == 3, fr.yOut != nullptr, fr.cz != nullptr)};
+}
+struct StRow { double e0; DiagRow u; ChebRow c; FusedRow f; };
+template <int MODE, bool NT, int CAUX>
+__device__ __forceinline__ StRow stRowLoads(const StBufs& B, const FusedR& fr, bool coded, unsigned row, unsigned srow) {
+    StRow L{bufLoadF64epi<NT>(B.e0, row * 8u), DiagRow{0, 0.}, ChebRow{0., 0., 0.}, FusedRow{0., 0., 1.f}};   // e0: x (MODE 0, 2, 3) / the vector added (MODE 1)
+    if (MODE != 1) L.u = rowDiagLoad<CAUX, NT ? PS_EPI_AUX : 0>(coded, B.uc, B.e1, row, srow);
+    if (MODE == 2) L.c = chebLoads<double>(B.cr, B.ci, B.cd, row);
+    if (MODE == 3) L.f = fusedLoads<NT>(fr, B.f, row, fr.cz != nullptr);
+    return L;
+}
+template <int MODE, bool NT>
+__device__ __forceinline__ void stRowFinish(const StBufs& B, const ChebArgs& cheb, const FusedR& fr, const double* dict, bool coded, double alpha, unsigned row, bool live,
+                                            const StRow& L, double s, double& dacc, double& dacc2) {
+    if (MODE == 1) { bufStoreF64nt<NT>(B.out, row * 8u, -s + L.e0); return; }
+    const double y = stRowY(s, rowDiagValue(coded, dict, L.u), L.e0);
+    if (MODE == 0) { dacc += L.e0 * y; bufStoreF64nt<NT>(B.out, row * 8u, y); }   // p.Ap: running sum over this block's chunks (0 past the last row)
+    else if (MODE == 2) bufStoreF64nt<NT>(B.out, row * 8u, chebRowFinish<double>(cheb, L.c, y, L.e0, dacc));
+    else fusedRowFinish<NT, double>(fr, B.f, row, live, true, fr.yOut != nullptr, fr.cz != nullptr, alpha, y, L.f, dacc, dacc2);
+}
+
 // chunkInfo entry (DevCSR::chunkInfo): x = first entry of the run, y = entries | rows << 16, z = first row, w = first row of the
 // chunk whose run this is (== z unless the run is shared: the per-row BYTE streams — lengths, value-set codes — are read there too)
 struct Chunk { int q0, q1, row0, rows, src; };
 __host__ __device__ inline Chunk decodeChunk(int4 v) { return Chunk{v.x, v.x + (v.y & 0xffff), v.z, (int)((unsigned)v.y >> 16), v.w}; }
 constexpr unsigned ROW_NONE = 0x1fffffffu;   // row index of an idle lane: beyond any array (rows * 8 < 4 GiB), positive as an int
-// Both kernels: gathers of the current chunk, prefetch of the next, products to LDS (entry e of the chunk at
+// The loop of k_spmv_S_pipe / k_spmv_St_pipe: gathers of the current chunk, prefetch of the next, products to LDS (entry e of the chunk at
 // prod[(e & 3) * PL + (e >> 2)]: conflict-free writes), row offsets from the length bytes (wave scans + 4 wave totals).
-template <int MODE, int NV, bool F64, int POL>
-__global__ void __launch_bounds__(BS) k_spmv_S_pipe(const uint16_t* __restrict__ col16, const int8_t* __restrict__ code4, const double* __restrict__ val4, int streamLen,
-                                                    const int32_t* __restrict__ winBase, const int4* __restrict__ chunkInfo,
-                                                    const uint8_t* __restrict__ len8, double scale, const double* __restrict__ x, int cols, int rows,
-                                                    int nA, double dt, const double* __restrict__ McInv, double* __restrict__ out,
-                                                    const int* __restrict__ done, int nChunks, int xcdAware,
-                                                    const uint8_t* __restrict__ mcCode, const double* __restrict__ mcDict, double* __restrict__ stPart) {
-    // stPart (MODE 0, may be null): per workgroup, the sum over its ACTIVE rows of s_f t_f = dt McInv_f s_f^2 — the active-face
-    // share of x . A x, so that the residual update can run inside the St kernel (ps_solve.hip: fused step)
-    if (done && *done) return;
+// loads(row, srow): the kernel issues the per-row loads of its epilogue (before the gathers);  finish(row, live, loaded, s): the row's sum
+// (at most ML entries) -> the epilogue.  Returns false when the workgroup has no chunk (nothing was done).
+#define PS_INLINE_LAMBDA __attribute__((always_inline))   // the callables of the loops are called once per unit: they must vanish, or what they capture goes to memory
+template <int NV, bool F64, bool SNT, bool BNT, int ML, class Loads, class Row>
+__device__ __forceinline__ bool pipeLoop(const uint16_t* __restrict__ col16, const int8_t* __restrict__ code4, const double* __restrict__ val4, int streamLen,
+                                         const int32_t* __restrict__ winBase, const int4* __restrict__ chunkInfo, const uint8_t* __restrict__ len8, double scale,
+                                         __amdgpu_buffer_rsrc_t rX, int rows, int nChunks, int xcdAware, const Loads& loads, const Row& finish) {
     constexpr int PL = BS * NV;
-    constexpr bool NT = (POL & 1) != 0, SNT = (POL & 2) != 0;   // stores + per-row epilogue streams | the matrix stream
-    constexpr bool BNT = NT && SNT;                               // the per-row byte streams go with the runs: cached when runs are shared
     __shared__ double prod[4 * PL];
     __shared__ __align__(16) int wtot[BS / 64];
-    __shared__ double dict[MODE == 0 ? 256 : 1];      // value-set coded McInv (ps_context.hpp: mcCode): first read after the loop's first barrier
-    if (MODE == 0 && mcCode) dict[threadIdx.x] = mcDict[threadIdx.x];
     static_assert(BS == 256, "four waves per block");
-    const __amdgpu_buffer_rsrc_t rCol = bufRsrc(col16, (size_t)streamLen * 2), rCode = bufRsrc(code4, F64 ? 0 : (size_t)streamLen),
-                                 rLen = bufRsrc(len8, (size_t)rows), rX = bufRsrc(x, (size_t)cols * 8), rMc = bufRsrc(McInv, (size_t)nA * 8),
-                                 rMcc = bufRsrc(mcCode, mcCode ? (size_t)nA : 0), rOut = bufRsrc(out, (size_t)rows * 8);
+    const __amdgpu_buffer_rsrc_t rCol = bufRsrc(col16, (size_t)streamLen * 2), rCode = bufRsrc(code4, F64 ? 0 : (size_t)streamLen), rLen = bufRsrc(len8, (size_t)rows);
     const ChunkWalk W(xcdAware);
     int it = 0;
     int chunk = W.at(0);
-    if (chunk >= nChunks) { if (MODE == 0 && stPart && threadIdx.x == 0) stPart[blockIdx.x] = 0.; return; }
-    double stAcc = 0.;
+    if (chunk >= nChunks) return false;
     Chunk pr = decodeChunk(chunkInfo[chunk]);
     Stream4<NV, F64> cur, nxt;
     loadStream4<NV, F64, SNT>(rCol, rCode, val4, pr.q0, pr.q1, cur);
@@ -434,12 +580,7 @@ __global__ void __launch_bounds__(BS) k_spmv_S_pipe(const uint16_t* __restrict__
         const bool live = (int)threadIdx.x < pr.rows;                                   // lanes past the chunk's rows: every access out of range
         const unsigned row = live ? (unsigned)pr.row0 + threadIdx.x : ROW_NONE, srow = live ? (unsigned)pr.src + threadIdx.x : ROW_NONE;
         const int len = (int)__builtin_amdgcn_raw_buffer_load_b8(rLen, (int)srow, 0, BNT ? PS_EPI_AUX : 0);   // 0 past the last row
-        double sc = 1.;
-        int mcc = 0;
-        if (MODE == 0) {
-            if (mcCode) mcc = (int)__builtin_amdgcn_raw_buffer_load_b8(rMcc, (int)srow, 0, BNT ? PS_EPI_AUX : 0);
-            else { const double m = bufLoadF64(rMc, row * 8u); sc = (int)row < nA ? dt * m : 1.; }
-        }
+        const auto L = loads(row, srow);
         double xv[4 * NV];
 #pragma unroll
         for (int w = 0; w < NV; ++w) {
@@ -470,22 +611,47 @@ __global__ void __launch_bounds__(BS) k_spmv_S_pipe(const uint16_t* __restrict__
             const int4 wt = *reinterpret_cast<const int4*>(wtot);
             const int wv = threadIdx.x >> 6;
             const int ea = incl - len + (wv > 0 ? wt.x : 0) + (wv > 1 ? wt.y : 0) + (wv > 2 ? wt.z : 0);
-            const double s = rowSum<8, PL>(prod, ea, len);
-            if (MODE == 0 && mcCode) sc = (int)row < nA ? dt * dict[mcc] : 1.;
-            if (MODE == 0) stAcc += (int)row < nA ? s * (s * sc) : 0.;
-            bufStoreF64nt<NT>(rOut, row * 8u, s * sc);                             // dropped past the last row
+            finish(row, live, L, rowSum<ML, PL>(prod, ea, len));
         }
-        __syncthreads();
+        __syncthreads();    // protects the LDS reuse
         if (!hasNext) break;
         chunk = nchunk; pr = npr; cur = nxt; myBase = nBase;
         nchunk = nn; npr = nnpr;
         ++it;
     }
+    return true;
+}
+// MODE 0: out[row] = (row < nA ? dt*McInv[row] : 1) * (S x)[row]  (operator, forward half);  MODE 1: out[row] = (S x)[row]  (velocity recovery)
+template <int MODE, int NV, bool F64, int POL>
+__global__ void __launch_bounds__(BS) k_spmv_S_pipe(const uint16_t* __restrict__ col16, const int8_t* __restrict__ code4, const double* __restrict__ val4, int streamLen,
+                                                    const int32_t* __restrict__ winBase, const int4* __restrict__ chunkInfo,
+                                                    const uint8_t* __restrict__ len8, double scale, const double* __restrict__ x, int cols, int rows,
+                                                    int nA, double dt, const double* __restrict__ McInv, double* __restrict__ out,
+                                                    const int* __restrict__ done, int nChunks, int xcdAware,
+                                                    const uint8_t* __restrict__ mcCode, const double* __restrict__ mcDict, double* __restrict__ stPart) {
+    // stPart (MODE 0, may be null): per workgroup, the sum over its ACTIVE rows of s_f t_f = dt McInv_f s_f^2 — the active-face
+    // share of x . A x, so that the residual update can run inside the St kernel (ps_solve.hip: fused step)
+    if (done && *done) return;
+    constexpr bool NT = (POL & 1) != 0, SNT = (POL & 2) != 0;   // stores + per-row epilogue streams | the matrix stream
+    constexpr bool BNT = NT && SNT;                               // the per-row byte streams go with the runs: cached when runs are shared
+    __shared__ double dict[MODE == 0 ? 256 : 1];      // value-set coded McInv: first read after the loop's first barrier
+    const bool coded = mcCode != nullptr;
+    if (MODE == 0 && coded) RowDiag<true>::fill(dict, mcDict);
+    const __amdgpu_buffer_rsrc_t rX = bufRsrc(x, (size_t)cols * 8), rMc = bufRsrc(McInv, (size_t)nA * 8), rMcc = bufRsrc(mcCode, coded ? (size_t)nA : 0),
+                                 rOut = bufRsrc(out, (size_t)rows * 8);
+    double stAcc = 0.;
+    const bool any = pipeLoop<NV, F64, SNT, BNT, 8>(col16, code4, val4, streamLen, winBase, chunkInfo, len8, scale, rX, rows, nChunks, xcdAware,
+        [&](unsigned row, unsigned srow) PS_INLINE_LAMBDA { return MODE == 0 ? rowDiagLoad<BNT ? PS_EPI_AUX : 0, 0>(coded, rMcc, rMc, row, srow) : DiagRow{0, 0.}; },
+        [&](unsigned row, bool, const DiagRow& m, double s) PS_INLINE_LAMBDA {
+            sRowFinish<MODE, NT, double>(rOut, row, nA, dt, MODE == 0 ? rowDiagValue(coded, dict, m) : 1., s, stAcc);
+        });
+    if (!any) { if (MODE == 0 && stPart && threadIdx.x == 0) stPart[blockIdx.x] = 0.; return; }
     if (MODE == 0 && stPart) {
         const double bs = blockReduceSum(stAcc);
         if (threadIdx.x == 0) stPart[blockIdx.x] = bs;
     }
 }
+// MODE 0 .. 3: stRowFinish.  (It writes its r.z partials at gridDim.x + block: fr.rStride is not looked at — the decomposition does not launch it.)
 template <int MODE, int NV, bool F64, int POL>
 __global__ void __launch_bounds__(BS) k_spmv_St_pipe(const uint16_t* __restrict__ col16, const int8_t* __restrict__ code4, const double* __restrict__ val4, int streamLen,
                                                      const int32_t* __restrict__ winBase, const int4* __restrict__ chunkInfo,
@@ -495,145 +661,29 @@ __global__ void __launch_bounds__(BS) k_spmv_St_pipe(const uint16_t* __restrict_
                                                      int nChunks, int xcdAware, ChebArgs cheb,
                                                      const uint8_t* __restrict__ uCode, const double* __restrict__ uDict, FusedR fr) {
     if (done && *done) return;
-    constexpr int PL = BS * NV;
     constexpr bool NT = (POL & 1) != 0, SNT = (POL & 2) != 0;   // stores + per-row epilogue streams | the matrix stream
     constexpr bool BNT = NT && SNT;                               // the per-row byte streams go with the runs: cached when runs are shared
-    __shared__ double prod[4 * PL];
-    __shared__ __align__(16) int wtot[BS / 64];
-    __shared__ double dict[MODE != 1 ? 256 : 1];      // value-set coded uInv (ps_context.hpp: uCode)
-    if (MODE != 1 && uCode) dict[threadIdx.x] = uDict[threadIdx.x];
+    __shared__ double dict[MODE != 1 ? 256 : 1];      // value-set coded uInv
+    const bool coded = uCode != nullptr;
+    if (MODE != 1 && coded) RowDiag<true>::fill(dict, uDict);
     double alpha = 0.;
-    if (MODE == 3) {
-        // same prologue as k_cg_update_r: [stop test of iteration it-1], alpha = rsold / p.Ap — identical in every workgroup
-        CGScalars* sc = fr.sc;
-        auto sumArr = [&](const double* a, int cnt) { double acc = 0.; for (int i = threadIdx.x; i < cnt; i += BS) acc += a[i]; return blockSumAll(acc); };
-        const bool writer = blockIdx.x == 0 && threadIdx.x == 0;
-        if (fr.it > 0) {
-            const double xx = fr.red ? fr.red[1] : sumArr(fr.xxPart, fr.xxCount);
-            const double rr = sc->rr;
-            double rre = rr;                               // pcg.h:319-325
-            if (rr / xx < rre) rre = rr / xx;
-            const bool fire = rre < sc->tol2;
-            if (writer) { sc->xx = xx; sc->rre = rre; if (fire) { sc->done = 1; sc->iter = fr.it - 1; } }
-            if (fire) return;                              // same verdict in every workgroup
-        }
-        const double pAp = fr.red ? -fr.red[0] : -(sumArr(fr.sPart, fr.sCount) + sumArr(fr.tPart, fr.tCount) + 0.5 * sumArr(fr.uPart, fr.uCount));
-        alpha = sc->rsold2[fr.it & 1] / pAp;               // pcg.h:314
-        if (writer) { sc->pAp = pAp; sc->alpha = alpha; }
-    }
-    static_assert(BS == 256, "four waves per block");
-    const __amdgpu_buffer_rsrc_t rCol = bufRsrc(col16, (size_t)streamLen * 2), rCode = bufRsrc(code4, F64 ? 0 : (size_t)streamLen),
-                                 rLen = bufRsrc(len8, (size_t)rows), rT = bufRsrc(t, (size_t)cols * 8),
-                                 rE0 = bufRsrc(MODE == 1 ? add : xin, (size_t)rows * 8), rE1 = bufRsrc(uInv, (size_t)rows * 8),
-                                 rOut = bufRsrc(out, (size_t)rows * 8),
-                                 rCr = bufRsrc(cheb.r, MODE == 2 ? (size_t)rows * 8 : 0), rCi = bufRsrc(cheb.dinv, MODE == 2 ? (size_t)rows * sizeof(diag_t) : 0),
-                                 rCd = bufRsrc(cheb.zprev, (MODE == 2 && cheb.zprev) ? (size_t)rows * 8 : 0), rUc = bufRsrc(uCode, uCode ? (size_t)rows : 0),
-                                 rFr = bufRsrc(fr.r, MODE == 3 ? (size_t)rows * 8 : 0), rFd = bufRsrc(fr.dinvF, (MODE == 3 && fr.dinvF) ? (size_t)rows * sizeof(diag_t) : 0),
-                                 rF64 = bufRsrc(fr.dinvC, (MODE == 3 && fr.cz) ? (size_t)rows * sizeof(diag_t) : 0), rFcz = bufRsrc(fr.cz, (MODE == 3 && fr.cz) ? (size_t)rows * 8 : 0),
-                                 rFy = bufRsrc(fr.yOut, (MODE == 3 && fr.yOut) ? (size_t)rows * 8 : 0);
-    const ChunkWalk W(xcdAware);
-    int it = 0;
-    int chunk = W.at(0);
-    if (chunk >= nChunks) {
+    if (MODE == 3 && !fusedPrologue(fr, fr.red != nullptr, alpha)) return;
+    const __amdgpu_buffer_rsrc_t rT = bufRsrc(t, (size_t)cols * 8);
+    const StBufs B = stBufs<MODE>(rows, uInv, xin, add, out, cheb, uCode, coded, fr);
+    double dacc = 0., dacc2 = 0.;
+    const bool any = pipeLoop<NV, F64, SNT, BNT, 6>(col16, code4, val4, streamLen, winBase, chunkInfo, len8, scale, rT, rows, nChunks, xcdAware,
+        [&](unsigned row, unsigned srow) PS_INLINE_LAMBDA { return stRowLoads<MODE, NT, BNT ? PS_EPI_AUX : 0>(B, fr, coded, row, srow); },
+        [&](unsigned row, bool live, const StRow& L, double s) PS_INLINE_LAMBDA { stRowFinish<MODE, NT>(B, cheb, fr, dict, coded, alpha, row, live, L, s, dacc, dacc2); });
+    if (!any) {
         if ((MODE == 0 || MODE == 2) && threadIdx.x == 0) partial[blockIdx.x] = 0.;
         if (MODE == 3 && threadIdx.x == 0) { fr.rPart[blockIdx.x] = 0.; fr.rPart[gridDim.x + blockIdx.x] = 0.; }
         return;
-    }
-    double dacc = 0., dacc2 = 0.;
-    Chunk pr = decodeChunk(chunkInfo[chunk]);
-    Stream4<NV, F64> cur, nxt;
-    loadStream4<NV, F64, SNT>(rCol, rCode, val4, pr.q0, pr.q1, cur);
-    int myBase = winBase[chunk * 16 + (threadIdx.x & 15)], nBase = 0;
-    int nchunk = W.at(1);
-    Chunk npr{0, 0, 0, 0, 0};
-    if (nchunk < nChunks) npr = decodeChunk(chunkInfo[nchunk]);
-    while (true) {
-        const bool live = (int)threadIdx.x < pr.rows;                                   // lanes past the chunk's rows: every access out of range
-        const unsigned row = live ? (unsigned)pr.row0 + threadIdx.x : ROW_NONE, srow = live ? (unsigned)pr.src + threadIdx.x : ROW_NONE;
-        const int len = (int)__builtin_amdgcn_raw_buffer_load_b8(rLen, (int)srow, 0, BNT ? PS_EPI_AUX : 0);   // 0 past the last row
-        const double e0 = bufLoadF64epi<NT>(rE0, row * 8u);                                       // x (MODE 0, 2) / the vector added (MODE 1)
-        double e1 = 0., cr = 0., ci = 0., cd = 0.;
-        int uc = 0;
-        if (MODE != 1) { if (uCode) uc = (int)__builtin_amdgcn_raw_buffer_load_b8(rUc, (int)srow, 0, BNT ? PS_EPI_AUX : 0); else e1 = bufLoadF64epi<NT>(rE1, row * 8u); }
-        if (MODE == 2) { cr = bufLoadF64(rCr, row * 8u); ci = (double)bufLoadDiag<false>(rCi, row); cd = bufLoadF64(rCd, row * 8u); }   // cd = z_{j-1} (0: no buffer)
-        float fdv = 1.f;
-        if (MODE == 3) {
-            cr = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rFr, (int)(row * 8u), 0, NT ? PS_EPI_AUX : 0));
-            if (fr.dinvF) fdv = bufLoadDiag<NT>(rFd, row);
-            if (fr.cz) ci = (double)bufLoadDiag<NT>(rF64, row);
-        }
-        double xv[4 * NV];
-#pragma unroll
-        for (int w = 0; w < NV; ++w) {
-            if (w > 0 && pr.q0 + 4 * w * BS >= pr.q1) break;                  // block-uniform: this group of the chunk is empty
-#pragma unroll
-            for (int j = 0; j < 4; ++j) xv[4 * w + j] = bufGatherF64(rT, streamCol(cur.c[w], j, myBase) * 8u);
-        }
-        Vals4<F64 ? NV : 0> cv;
-        if constexpr (F64) loadVals4<NV, SNT>(val4, pr.q0, pr.q1, cv);
-        const bool hasNext = nchunk < nChunks;
-        if (hasNext) {
-            loadStream4<NV, F64, SNT>(rCol, rCode, val4, npr.q0, npr.q1, nxt);
-            nBase = winBase[nchunk * 16 + (threadIdx.x & 15)];
-        }
-        const int nn = W.at(it + 2);
-        Chunk nnpr{0, 0, 0, 0, 0};
-        if (nn < nChunks) nnpr = decodeChunk(chunkInfo[nn]);
-#pragma unroll
-        for (int w = 0; w < NV; ++w) {
-            if (w > 0 && pr.q0 + 4 * w * BS >= pr.q1) break;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) prod[j * PL + threadIdx.x + w * BS] = prodVal<F64>(cur, cv, w, j, scale) * xv[4 * w + j];
-        }
-        const int incl = waveInclusiveScan(len);
-        if ((threadIdx.x & 63) == 63) wtot[threadIdx.x >> 6] = incl;
-        __syncthreads();
-        {
-            const int4 wt = *reinterpret_cast<const int4*>(wtot);
-            const int wv = threadIdx.x >> 6;
-            const int ea = incl - len + (wv > 0 ? wt.x : 0) + (wv > 1 ? wt.y : 0) + (wv > 2 ? wt.z : 0);
-            const double s = rowSum<6, PL>(prod, ea, len);
-            if (MODE != 1 && uCode) e1 = dict[uc];
-            double y;
-            if (MODE == 0) { y = -s; y -= 0.5 * e1 * e0; dacc += e0 * y; }   // p.Ap: running sum over this block's chunks (0 past the last row)
-            else if (MODE == 1) y = -s + e0;
-            else if (MODE == 3) {
-                y = -s; y -= 0.5 * e1 * e0;                                      // (A p)[row], not stored
-                const bool mine = (int)row >= fr.ownLo && (int)row < fr.ownHi;   // (idle lanes: false)
-                if (fr.yOut) bufStoreF64nt<NT>(rFy, (!mine && live) ? row * 8u : 0xfffffff8u, y);   // a neighbour's row: its share of A p
-                const double rv = mine ? cr - alpha * y : 0.;                    // pcg.h:316
-                dacc += rv * rv;
-                dacc2 += (fr.dinvF && mine) ? rv * ((double)fdv * rv) : 0.;      // (the diagonal of a halo row is not this rank's: may be anything)
-                if (fr.cz) {                                                     // k_cheb_first on this row
-                    const double v = ci * rv * fr.invTheta;
-                    bufStoreF64nt<NT>(rFcz, row * 8u, v);
-                    dacc2 += rv * v;
-                }
-                y = rv;
-            }
-            else {
-                double az = -s; az -= 0.5 * e1 * e0;
-                const double dn = cheb.c1 * (e0 - cd) + cheb.c2 * (ci * (cr - az));
-                y = e0 + dn;
-                dacc += cr * y;                                                  // r.z of the updated z
-            }
-            if (MODE == 3) bufStoreF64nt<NT>(rFr, ((int)row >= fr.ownLo && (int)row < fr.ownHi) ? row * 8u : 0xfffffff8u, y);
-            else bufStoreF64nt<NT>(rOut, row * 8u, y);
-        }
-        __syncthreads();    // protects the LDS reuse
-        if (!hasNext) break;
-        chunk = nchunk; pr = npr; cur = nxt; myBase = nBase;
-        nchunk = nn; npr = nnpr;
-        ++it;
     }
     if (MODE == 0 || MODE == 2) {
         const double bs = blockReduceSum(dacc);
         if (threadIdx.x == 0) partial[blockIdx.x] = bs;   // gridDim.x partials (Launch::stBlocks)
     }
-    if (MODE == 3) {
-        const double b0 = blockReduceSum(dacc), b1 = (fr.dinvF || fr.cz) ? blockReduceSum(dacc2) : 0.;
-        if (threadIdx.x == 0) { fr.rPart[blockIdx.x] = b0; fr.rPart[gridDim.x + blockIdx.x] = b1; }
-    }
+    if (MODE == 3) fusedPartials(fr, dacc, dacc2, fr.cz != nullptr, (int)gridDim.x);
 }
 
 
@@ -729,6 +779,54 @@ __device__ inline double ellSumW(int W, const EllRegs& r, const EllX& X, double 
     if (W == 2) return ellSum<2>(r, X, scale);
     return 0.;
 }
+// The loop of the one-unit kernels k_spmv_S_ell / k_spmv_St_ell: a wave owns unit `wave` of every chunk of its workgroup's ChunkWalk.
+// LIST: `list` holds the chunks this launch works on, nChunks of them — the slab decomposition runs the chunks that touch no
+// halo column while the halo values are still in flight, and the others afterwards (ps_dist.hpp).  A template parameter: the
+// single-domain kernels must not pay registers for it (the plain MODE 3 St kernel sits at the edge of 7 waves per SIMD)
+// loads(row): the per-row loads of the kernel's epilogue;  finish(row, live, loaded, s): the row's sum -> the epilogue
+template <bool SNT, bool LIST, class Loads, class Row>
+__device__ __forceinline__ void ellLoop(__amdgpu_buffer_rsrc_t rCol, __amdgpu_buffer_rsrc_t rCode, __amdgpu_buffer_rsrc_t rX, const int32_t* __restrict__ winBase,
+                                        const int4* __restrict__ echunk, double scale, int nChunks, int xcdAware, const int32_t* __restrict__ list,
+                                        const Loads& loads, const Row& finish) {
+    const ChunkWalk Wk(xcdAware);
+    const unsigned lane = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    int it = 0;
+    int chunk = Wk.at(0);                                               // POSITIONS in the walk (< nChunks); the chunk itself is list[position] when there is a list
+    if (chunk >= nChunks) return;
+    const int id0 = LIST ? list[chunk] : chunk;
+    EllUnit cu = ellUnit(echunk[id0], wv);
+    EllRegs cur = ellLoad<SNT>(rCol, rCode, cu, lane), nxt{0u, 0u, 0u, 0u, 0u, 0u};
+    int myBase = winBase[id0 * 16 + (lane & 15)], nBase = 0;
+    int nchunk = Wk.at(1), nid = 0;
+    int4 nci = make_int4(0, 0, 0, 0);
+    if (nchunk < nChunks) { nid = LIST ? list[nchunk] : nchunk; nci = echunk[nid]; }
+    while (true) {
+        // (1) the per-row streams of the epilogue and this unit's gathers first: their address arithmetic waits on nothing but the window lookups
+        const bool live = (int)lane < cu.rows;
+        const unsigned row = live ? (unsigned)cu.row0 + lane : ROW_NONE;
+        const auto L = loads(row);
+        const EllX X = ellGatherW(cu.W, cur, myBase, rX);
+        // (2) behind them: the next unit's stream and the record of the chunk after it
+        const bool hasNext = nchunk < nChunks;
+        EllUnit nu{0, 0, 0, 0, 0};
+        if (hasNext) {
+            nu = ellUnit(nci, wv);
+            nxt = ellLoad<SNT>(rCol, rCode, nu, lane);
+            nBase = winBase[nid * 16 + (lane & 15)];
+        }
+        const int nn = Wk.at(it + 2);
+        int nnid = 0;
+        int4 nnci = make_int4(0, 0, 0, 0);
+        if (nn < nChunks) { nnid = LIST ? list[nn] : nn; nnci = echunk[nnid]; }
+        // (3) products, the row's sum and the epilogue
+        finish(row, live, L, ellSumW(cu.W, cur, X, scale));
+        if (!hasNext) break;
+        chunk = nchunk; cu = nu; cur = nxt; myBase = nBase;
+        nchunk = nn; nci = nnci; nid = nnid;
+        ++it;
+    }
+}
 // MODE 0 / 1 as k_spmv_S_pipe
 template <int MODE, int POL, bool LIST>
 __global__ void __launch_bounds__(BS) k_spmv_S_ell(const uint16_t* __restrict__ ecol, const int8_t* __restrict__ ecode, unsigned colBytes, unsigned codeBytes,
@@ -737,64 +835,20 @@ __global__ void __launch_bounds__(BS) k_spmv_S_ell(const uint16_t* __restrict__ 
                                                    double* __restrict__ out, const int* __restrict__ done, int nChunks, int xcdAware,
                                                    const uint8_t* __restrict__ mcCode, const double* __restrict__ mcDict, double* __restrict__ stPart,
                                                    const int32_t* __restrict__ list) {
-    // LIST: `list` holds the chunks this launch works on, nChunks of them — the slab decomposition runs the chunks that touch no
-    // halo column while the halo values are still in flight, and the others afterwards (ps_dist.hpp).  A template parameter: the
-    // single-domain kernels must not pay registers for it (the plain MODE 3 St kernel sits at the edge of 7 waves per SIMD)
     if (done && *done) return;
     constexpr bool NT = (POL & 1) != 0, SNT = (POL & 2) != 0;
     __shared__ double dict[MODE == 0 ? 256 : 1];
-    if (MODE == 0 && mcCode) dict[threadIdx.x] = mcDict[threadIdx.x];
+    const bool coded = mcCode != nullptr;
+    if (MODE == 0 && coded) RowDiag<true>::fill(dict, mcDict);
     __syncthreads();                                                    // the only barrier before the final reduction
     const __amdgpu_buffer_rsrc_t rCol = bufRsrc(ecol, colBytes), rCode = bufRsrc(ecode, codeBytes), rX = bufRsrc(x, (size_t)cols * 8),
-                                 rMc = bufRsrc(McInv, (size_t)nA * 8), rMcc = bufRsrc(mcCode, mcCode ? (size_t)nA : 0), rOut = bufRsrc(out, (size_t)rows * 8);
-    const ChunkWalk Wk(xcdAware);
-    const unsigned lane = threadIdx.x & 63;
-    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+                                 rMc = bufRsrc(McInv, (size_t)nA * 8), rMcc = bufRsrc(mcCode, coded ? (size_t)nA : 0), rOut = bufRsrc(out, (size_t)rows * 8);
     double stAcc = 0.;
-    int it = 0;
-    int chunk = Wk.at(0);                                               // POSITIONS in the walk (< nChunks); the chunk itself is list[position] when there is a list
-    if (chunk < nChunks) {
-        const int id0 = LIST ? list[chunk] : chunk;
-        EllUnit cu = ellUnit(echunk[id0], wv);
-        EllRegs cur = ellLoad<SNT>(rCol, rCode, cu, lane), nxt{0u, 0u, 0u, 0u, 0u, 0u};
-        int myBase = winBase[id0 * 16 + (lane & 15)], nBase = 0;
-        int nchunk = Wk.at(1), nid = 0;
-        int4 nci = make_int4(0, 0, 0, 0);
-        if (nchunk < nChunks) { nid = LIST ? list[nchunk] : nchunk; nci = echunk[nid]; }
-        while (true) {
-            // (1) this unit's gathers first: their address arithmetic waits on nothing but the window lookups
-            const bool live = (int)lane < cu.rows;
-            const unsigned row = live ? (unsigned)cu.row0 + lane : ROW_NONE;
-            double sc = 1.;
-            int mcc = 0;
-            if (MODE == 0) {
-                if (mcCode) mcc = (int)__builtin_amdgcn_raw_buffer_load_b8(rMcc, (int)row, 0, NT ? PS_EPI_AUX : 0);
-                else { const double m = bufLoadF64(rMc, row * 8u); sc = (int)row < nA ? dt * m : 1.; }
-            }
-            const EllX X = ellGatherW(cu.W, cur, myBase, rX);
-            // (2) behind them: the next unit's stream and the record of the chunk after it
-            const bool hasNext = nchunk < nChunks;
-            EllUnit nu{0, 0, 0, 0, 0};
-            if (hasNext) {
-                nu = ellUnit(nci, wv);
-                nxt = ellLoad<SNT>(rCol, rCode, nu, lane);
-                nBase = winBase[nid * 16 + (lane & 15)];
-            }
-            const int nn = Wk.at(it + 2);
-            int nnid = 0;
-            int4 nnci = make_int4(0, 0, 0, 0);
-            if (nn < nChunks) { nnid = LIST ? list[nn] : nn; nnci = echunk[nnid]; }
-            // (3) products, epilogue
-            const double s = ellSumW(cu.W, cur, X, scale);
-            if (MODE == 0 && mcCode) sc = (int)row < nA ? dt * dict[mcc] : 1.;
-            if (MODE == 0) stAcc += (int)row < nA ? s * (s * sc) : 0.;
-            bufStoreF64nt<NT>(rOut, row * 8u, s * sc);                       // dropped past the chunk's last row (row = ROW_NONE)
-            if (!hasNext) break;
-            chunk = nchunk; cu = nu; cur = nxt; myBase = nBase;
-            nchunk = nn; nci = nnci; nid = nnid;
-            ++it;
-        }
-    }
+    ellLoop<SNT, LIST>(rCol, rCode, rX, winBase, echunk, scale, nChunks, xcdAware, list,
+        [&](unsigned row) PS_INLINE_LAMBDA { return MODE == 0 ? rowDiagLoad<NT ? PS_EPI_AUX : 0, 0>(coded, rMcc, rMc, row, row) : DiagRow{0, 0.}; },
+        [&](unsigned row, bool, const DiagRow& m, double s) PS_INLINE_LAMBDA {
+            sRowFinish<MODE, NT, double>(rOut, row, nA, dt, MODE == 0 ? rowDiagValue(coded, dict, m) : 1., s, stAcc);   // dropped past the chunk's last row (row = ROW_NONE)
+        });
     if (MODE == 0 && stPart) {
         const double bs = blockReduceSum(stAcc);
         if (threadIdx.x == 0) stPart[blockIdx.x] = bs;
@@ -821,188 +875,105 @@ __global__ void __launch_bounds__(BS) k_spmv_St_ell(const uint16_t* __restrict__
     if (FX & 4) { fr.yOut = nullptr; fr.ownLo = 0; fr.ownHi = rows; }   // a rank of a decomposition, chunks of OWNED rows only (the launch under the exchange): no halo row to hand on
     const bool coded = (FX & 1) ? true : uCode != nullptr;
     __shared__ double dict[MODE != 1 ? 256 : 1];
-    if (MODE != 1 && coded) dict[threadIdx.x] = uDict[threadIdx.x];
+    if (MODE != 1 && coded) RowDiag<true>::fill(dict, uDict);
     double alpha = 0.;
-    if (MODE == 3) {   // as k_spmv_St_pipe: [stop test of iteration it-1], alpha = rsold / p.Ap — identical in every workgroup
-        CGScalars* sc = fr.sc;
-        auto sumArr = [&](const double* a, int cnt) { double acc = 0.; for (int i = threadIdx.x; i < cnt; i += BS) acc += a[i]; return blockSumAll(acc); };
-        const bool writer = blockIdx.x == 0 && threadIdx.x == 0;
-        if (fr.it > 0) {
-            const double xx = fr.red ? fr.red[1] : sumArr(fr.xxPart, fr.xxCount);
-            const double rr = sc->rr;
-            double rre = rr;                               // pcg.h:319-325
-            if (rr / xx < rre) rre = rr / xx;
-            const bool fire = rre < sc->tol2;
-            if (writer) { sc->xx = xx; sc->rre = rre; if (fire) { sc->done = 1; sc->iter = fr.it - 1; } }
-            if (fire) return;                              // same verdict in every workgroup
-        }
-        const double pAp = fr.red ? -fr.red[0] : -(sumArr(fr.sPart, fr.sCount) + sumArr(fr.tPart, fr.tCount) + 0.5 * sumArr(fr.uPart, fr.uCount));
-        alpha = sc->rsold2[fr.it & 1] / pAp;               // pcg.h:314
-        if (writer) { sc->pAp = pAp; sc->alpha = alpha; }
-    }
+    if (MODE == 3 && !fusedPrologue(fr, fr.red != nullptr, alpha)) return;
     __syncthreads();                                       // dict
-    const __amdgpu_buffer_rsrc_t rCol = bufRsrc(ecol, colBytes), rCode = bufRsrc(ecode, codeBytes), rT = bufRsrc(t, (size_t)cols * 8),
-                                 rE0 = bufRsrc(MODE == 1 ? add : xin, (size_t)rows * 8), rE1 = bufRsrc(uInv, (size_t)rows * 8),
-                                 rOut = bufRsrc(out, (size_t)rows * 8),
-                                 rCr = bufRsrc(cheb.r, MODE == 2 ? (size_t)rows * 8 : 0), rCi = bufRsrc(cheb.dinv, MODE == 2 ? (size_t)rows * sizeof(diag_t) : 0),
-                                 rCd = bufRsrc(cheb.zprev, (MODE == 2 && cheb.zprev) ? (size_t)rows * 8 : 0), rUc = bufRsrc(uCode, coded ? (size_t)rows : 0),
-                                 rFr = bufRsrc(fr.r, MODE == 3 ? (size_t)rows * 8 : 0), rFd = bufRsrc(fr.dinvF, (MODE == 3 && fr.dinvF) ? (size_t)rows * sizeof(diag_t) : 0),
-                                 rF64 = bufRsrc(fr.dinvC, (MODE == 3 && fr.cz) ? (size_t)rows * sizeof(diag_t) : 0), rFcz = bufRsrc(fr.cz, (MODE == 3 && fr.cz) ? (size_t)rows * 8 : 0),
-                                 rFy = bufRsrc(fr.yOut, (MODE == 3 && fr.yOut) ? (size_t)rows * 8 : 0);
-    const ChunkWalk Wk(xcdAware);
-    const unsigned lane = threadIdx.x & 63;
-    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const __amdgpu_buffer_rsrc_t rCol = bufRsrc(ecol, colBytes), rCode = bufRsrc(ecode, codeBytes), rT = bufRsrc(t, (size_t)cols * 8);
+    const StBufs B = stBufs<MODE>(rows, uInv, xin, add, out, cheb, uCode, coded, fr);
     double dacc = 0., dacc2 = 0.;
-    int it = 0;
-    int chunk = Wk.at(0);                                               // POSITIONS in the walk (< nChunks); the chunk itself is list[position] when there is a list
-    if (chunk < nChunks) {
-        const int id0 = LIST ? list[chunk] : chunk;
-        EllUnit cu = ellUnit(echunk[id0], wv);
-        EllRegs cur = ellLoad<SNT>(rCol, rCode, cu, lane), nxt{0u, 0u, 0u, 0u, 0u, 0u};
-        int myBase = winBase[id0 * 16 + (lane & 15)], nBase = 0;
-        int nchunk = Wk.at(1), nid = 0;
-        int4 nci = make_int4(0, 0, 0, 0);
-        if (nchunk < nChunks) { nid = LIST ? list[nchunk] : nchunk; nci = echunk[nid]; }
-        while (true) {
-            const bool live = (int)lane < cu.rows;
-            const unsigned row = live ? (unsigned)cu.row0 + lane : ROW_NONE;
-            // (1) the per-row streams of the epilogue and this unit's gathers
-            const double e0 = bufLoadF64epi<NT>(rE0, row * 8u);                                       // x (MODE 0, 2, 3) / the vector added (MODE 1)
-            double e1 = 0., cr = 0., ci = 0., cd = 0.;
-            int uc = 0;
-            if (MODE != 1) { if (coded) uc = (int)__builtin_amdgcn_raw_buffer_load_b8(rUc, (int)row, 0, NT ? PS_EPI_AUX : 0); else e1 = bufLoadF64epi<NT>(rE1, row * 8u); }
-            if (MODE == 2) { cr = bufLoadF64(rCr, row * 8u); ci = (double)bufLoadDiag<false>(rCi, row); cd = bufLoadF64(rCd, row * 8u); }   // cd = z_{j-1} (0: no buffer)
-            float fdv = 1.f;
-            if (MODE == 3) {
-                cr = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rFr, (int)(row * 8u), 0, NT ? PS_EPI_AUX : 0));
-                if (fr.dinvF) fdv = bufLoadDiag<NT>(rFd, row);
-                if (fr.cz) ci = (double)bufLoadDiag<NT>(rF64, row);
-            }
-            const EllX X = ellGatherW(cu.W, cur, myBase, rT);
-            // (2) behind them: the next unit's stream and the record of the chunk after it
-            const bool hasNext = nchunk < nChunks;
-            EllUnit nu{0, 0, 0, 0, 0};
-            if (hasNext) {
-                nu = ellUnit(nci, wv);
-                nxt = ellLoad<SNT>(rCol, rCode, nu, lane);
-                nBase = winBase[nid * 16 + (lane & 15)];
-            }
-            const int nn = Wk.at(it + 2);
-            int nnid = 0;
-            int4 nnci = make_int4(0, 0, 0, 0);
-            if (nn < nChunks) { nnid = LIST ? list[nn] : nn; nnci = echunk[nnid]; }
-            // (3) the row's sum and the fused epilogue
-            const double s = ellSumW(cu.W, cur, X, scale);
-            if (MODE != 1 && coded) e1 = dict[uc];
-            double y;
-            if (MODE == 0) { y = -s; y -= 0.5 * e1 * e0; dacc += e0 * y; }   // p.Ap: running sum over this block's chunks (0 past the last row)
-            else if (MODE == 1) y = -s + e0;
-            else if (MODE == 3) {
-                y = -s; y -= 0.5 * e1 * e0;                                      // (A p)[row], not stored
-                const bool mine = (int)row >= fr.ownLo && (int)row < fr.ownHi;   // (idle lanes: false)
-                if (fr.yOut) bufStoreF64nt<NT>(rFy, (!mine && live) ? row * 8u : 0xfffffff8u, y);   // a neighbour's row: its share of A p
-                const double rv = mine ? cr - alpha * y : 0.;                    // pcg.h:316
-                dacc += rv * rv;
-                dacc2 += (fr.dinvF && mine) ? rv * ((double)fdv * rv) : 0.;      // (the diagonal of a halo row is not this rank's: may be anything)
-                if (fr.cz) {                                                     // k_cheb_first on this row
-                    const double v = ci * rv * fr.invTheta;
-                    bufStoreF64nt<NT>(rFcz, row * 8u, v);
-                    dacc2 += rv * v;
-                }
-                y = rv;
-            }
-            else {
-                double az = -s; az -= 0.5 * e1 * e0;
-                const double dn = cheb.c1 * (e0 - cd) + cheb.c2 * (ci * (cr - az));
-                y = e0 + dn;
-                dacc += cr * y;                                                  // r.z of the updated z
-            }
-            if (MODE == 3) bufStoreF64nt<NT>(rFr, ((int)row >= fr.ownLo && (int)row < fr.ownHi) ? row * 8u : 0xfffffff8u, y);
-            else bufStoreF64nt<NT>(rOut, row * 8u, y);
-            if (!hasNext) break;
-            chunk = nchunk; cu = nu; cur = nxt; myBase = nBase;
-            nchunk = nn; nci = nnci; nid = nnid;
-            ++it;
-        }
-    }
+    ellLoop<SNT, LIST>(rCol, rCode, rT, winBase, echunk, scale, nChunks, xcdAware, list,
+        [&](unsigned row) PS_INLINE_LAMBDA { return stRowLoads<MODE, NT, NT ? PS_EPI_AUX : 0>(B, fr, coded, row, row); },
+        [&](unsigned row, bool live, const StRow& L, double s) PS_INLINE_LAMBDA { stRowFinish<MODE, NT>(B, cheb, fr, dict, coded, alpha, row, live, L, s, dacc, dacc2); });
     if (MODE == 0 || MODE == 2) {
         const double bs = blockReduceSum(dacc);
         if (threadIdx.x == 0) partial[blockIdx.x] = bs;   // gridDim.x partials (Launch::stBlocks)
     }
-    if (MODE == 3) {
-        const double b0 = blockReduceSum(dacc), b1 = (fr.dinvF || fr.cz) ? blockReduceSum(dacc2) : 0.;
-        if (threadIdx.x == 0) { fr.rPart[blockIdx.x] = b0; fr.rPart[(fr.rStride > 0 ? fr.rStride : (int)gridDim.x) + blockIdx.x] = b1; }
-    }
+    if (MODE == 3) fusedPartials(fr, dacc, dacc2, fr.cz != nullptr, fr.rStride > 0 ? fr.rStride : (int)gridDim.x);
 }
 
 // ---- two units in flight per wave (r04; default for the single-domain operator product, PS_S_DUAL=0 switches back) -------------------
 // k_spmv_S_ell with twice the memory-level parallelism per wave: a workgroup takes TWO chunks per step, waves 0-1 the first, waves 2-3 the
 // second; a wave owns units 2 (w & 1) and 2 (w & 1) + 1 of its chunk and has the streams, the gathers and the epilogue loads of both in
 // flight before it sums either.  Same products, same order per row: bit-identical t; the per-workgroup partials of sum s.t group differently.
-// TV: element type of x and of the output (double; float = the inner applies of the single-precision Chebyshev polynomial, VecIO)
-// MC: the face mass McInv comes as one-byte codes into a 256-entry table (true) or, when it takes more than 256 values — a density FIELD
-// (ps_upload_density_field) —, as the fp64 array itself, passed in mcCode's place and read through the same buffer policy (false: 7 more
-// bytes per active row; the St kernels' UC = false for the stress diagonal)
-// The coded form launches as k_spmv_S_ell2, the uncoded one as k_spmv_S_ell2u (one body, spmvSEll2).
-template <int POL, bool LIST, class TV, bool MC>
-__device__ __forceinline__ void spmvSEll2(const uint16_t* __restrict__ ecol, const int8_t* __restrict__ ecode, unsigned colBytes, unsigned codeBytes,
-                                          const int32_t* __restrict__ winBase, const int4* __restrict__ echunk, double scale,
-                                          const TV* __restrict__ x, int cols, int rows, int nA, double dt, TV* __restrict__ out,
-                                          const int* __restrict__ done, int nChunks, const uint8_t* __restrict__ mcCode, const double* __restrict__ mcDict,
-                                          double* __restrict__ stPart, const int32_t* __restrict__ list) {   // LIST: as k_spmv_S_ell (nChunks = entries of the list)
-    if (done && *done) return;
-    constexpr bool NT = (POL & 1) != 0, SNT = (POL & 2) != 0;
-    __shared__ double dict[MC ? 256 : 1];
-    if (MC) dict[threadIdx.x] = mcDict[threadIdx.x];
-    __syncthreads();
-    const __amdgpu_buffer_rsrc_t rCol = bufRsrc(ecol, colBytes), rCode = bufRsrc(ecode, codeBytes), rX = bufRsrc(x, (size_t)cols * sizeof(TV)),
-                                 rMcc = bufRsrc(mcCode, MC ? (size_t)nA : (size_t)nA * 8), rOut = bufRsrc(out, (size_t)rows * sizeof(TV));
+//
+// The walk: pairs of consecutive chunks, runs of 32 pairs dealt to the XCDs round robin (workgroup b runs on XCD b & 7); workgroup l of an
+// XCD takes steps q = l, l + per, ... below pairWalkEnd.  Plain integers, for the kernels and for the host (ps_solve.hip: Launch::noteWalk, pipeBlocks).
+__host__ __device__ inline int pairWalkEnd(int nChunks) { return ((((nChunks + 1) >> 1) + 255) >> 8) << 5; }   // steps beyond the last run of 32 pairs per XCD
+// step q on XCD xcd -> the pair, then the wave's half of it -> the chunk, or -1
+__host__ __device__ inline int pairWalkChunk(int q, int xcd, int half, int nChunks) {
+    const int pair = ((((q >> 5) << 3) + xcd) << 5) + (q & 31);
+    const int ch = 2 * pair + half;
+    return (pair < ((nChunks + 1) >> 1) && ch < nChunks) ? ch : -1;
+}
+template <bool LIST> struct PairWalk {   // LIST: as ellLoop (nChunks = entries of the list)
+    int nChunks, xcd, half, per, qEnd;
+    const int32_t* list;
+    __device__ PairWalk(int n, int half_, const int32_t* list_)
+        : nChunks(n), xcd(blockIdx.x & 7), half(half_), per(gridDim.x >> 3), qEnd(pairWalkEnd(n)), list(list_) {}
+    __device__ int first() const { return blockIdx.x >> 3; }
+    __device__ int at(int q) const {
+        const int ch = q < qEnd ? pairWalkChunk(q, xcd, half, nChunks) : -1;
+        return (LIST && ch >= 0) ? list[ch] : ch;
+    }
+};
+// The loop of the two-unit kernels.  loads(row) / finish(row, live, loaded, s) as in ellLoop, called for unit A, then for unit B: sums
+// that the epilogue accumulates keep their A-then-B order.
+template <bool SNT, bool LIST, class TX, class Loads, class Row>
+__device__ __forceinline__ void ell2Loop(__amdgpu_buffer_rsrc_t rCol, __amdgpu_buffer_rsrc_t rCode, __amdgpu_buffer_rsrc_t rX, const int32_t* __restrict__ winBase,
+                                         const int4* __restrict__ echunk, double scale, int nChunks, const int32_t* __restrict__ list, const Loads& loads, const Row& finish) {
     const unsigned lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int half = wv >> 1, u0 = 2 * (wv & 1);
-    double stAcc = 0.;
-    // pairs of consecutive chunks, runs of 32 pairs dealt to the XCDs round robin (workgroup b runs on XCD b & 7)
-    const int nPairs = (nChunks + 1) >> 1;
-    const int xcd = blockIdx.x & 7, l = blockIdx.x >> 3, per = gridDim.x >> 3;
-    // step q of this workgroup -> its chunk (or -1): the pair, then this wave's half of it
-    auto chunkAt = [&](int q) -> int {
-        const int pair = ((((q >> 5) << 3) + xcd) << 5) + (q & 31);
-        const int ch = 2 * pair + half;
-        return (pair < nPairs && ch < nChunks) ? (LIST ? list[ch] : ch) : -1;
-    };
-    const int qEnd = ((nPairs + 255) >> 8) << 5;          // steps beyond the last run of 32 pairs per XCD
-    int q = l;
-    int chunk = q < qEnd ? chunkAt(q) : -1;
+    const int u0 = 2 * (wv & 1);
+    const PairWalk<LIST> W(nChunks, wv >> 1, list);
+    int q = W.first();
+    int chunk = W.at(q);
     int4 ci = make_int4(0, 0, 0, 0);
     int myBase = 0;
     if (chunk >= 0) { ci = echunk[chunk]; myBase = winBase[chunk * 16 + (lane & 15)]; }
-    while (q < qEnd) {
-        const int qn = q + per;
-        const int nchunk = qn < qEnd ? chunkAt(qn) : -1;
+    while (q < W.qEnd) {
+        const int qn = q + W.per;
+        const int nchunk = W.at(qn);
         int4 nci = make_int4(0, 0, 0, 0);
         int nBase = 0;
         if (chunk >= 0) {
             const EllUnit ua = ellUnit(ci, u0), ub = ellUnit(ci, u0 + 1);
             const EllRegs sa = ellLoad<SNT>(rCol, rCode, ua, lane), sb = ellLoad<SNT>(rCol, rCode, ub, lane);
             if (nchunk >= 0) { nci = echunk[nchunk]; nBase = winBase[nchunk * 16 + (lane & 15)]; }     // the next step's record, behind this step's streams
-            const unsigned rowA = (int)lane < ua.rows ? (unsigned)ua.row0 + lane : ROW_NONE, rowB = (int)lane < ub.rows ? (unsigned)ub.row0 + lane : ROW_NONE;
-            int mA = 0, mB = 0;
-            double mvA = 0., mvB = 0.;      // (rows past nA read 0 through the buffer's range; their scale is 1 below)
-            if (MC) {
-                mA = (int)__builtin_amdgcn_raw_buffer_load_b8(rMcc, (int)rowA, 0, NT ? PS_EPI_AUX : 0);
-                mB = (int)__builtin_amdgcn_raw_buffer_load_b8(rMcc, (int)rowB, 0, NT ? PS_EPI_AUX : 0);
-            } else { mvA = bufLoadF64epi<NT>(rMcc, rowA * 8u); mvB = bufLoadF64epi<NT>(rMcc, rowB * 8u); }
-            const EllX XA = ellGatherW<TV>(ua.W, sa, myBase, rX);
-            const EllX XB = ellGatherW<TV>(ub.W, sb, myBase, rX);
+            const bool liveA = (int)lane < ua.rows, liveB = (int)lane < ub.rows;
+            const unsigned rowA = liveA ? (unsigned)ua.row0 + lane : ROW_NONE, rowB = liveB ? (unsigned)ub.row0 + lane : ROW_NONE;
+            const auto LA = loads(rowA);
+            const auto LB = loads(rowB);
+            const EllX XA = ellGatherW<TX>(ua.W, sa, myBase, rX);
+            const EllX XB = ellGatherW<TX>(ub.W, sb, myBase, rX);
             const double a = ellSumW(ua.W, sa, XA, scale), b = ellSumW(ub.W, sb, XB, scale);
-            const double scA = (int)rowA < nA ? dt * (MC ? dict[mA] : mvA) : 1., scB = (int)rowB < nA ? dt * (MC ? dict[mB] : mvB) : 1.;
-            stAcc += (int)rowA < nA ? a * (a * scA) : 0.;
-            stAcc += (int)rowB < nA ? b * (b * scB) : 0.;
-            VecIO<TV>::template store<NT>(rOut, rowA, a * scA);
-            VecIO<TV>::template store<NT>(rOut, rowB, b * scB);
+            finish(rowA, liveA, LA, a);
+            finish(rowB, liveB, LB, b);
         } else if (nchunk >= 0) { nci = echunk[nchunk]; nBase = winBase[nchunk * 16 + (lane & 15)]; }
         q = qn; chunk = nchunk; ci = nci; myBase = nBase;
     }
+}
+// TV: element type of x and of the output (double; float = the inner applies of the single-precision Chebyshev polynomial, VecIO)
+// MC: the face mass McInv comes coded (true) or as the fp64 array itself, passed in mcCode's place and read through the same buffer policy
+// (RowDiag; the St kernels' UC for the stress diagonal)
+// The coded form launches as k_spmv_S_ell2, the uncoded one as k_spmv_S_ell2u (one body, spmvSEll2).
+template <int POL, bool LIST, class TV, bool MC>
+__device__ __forceinline__ void spmvSEll2(const uint16_t* __restrict__ ecol, const int8_t* __restrict__ ecode, unsigned colBytes, unsigned codeBytes,
+                                          const int32_t* __restrict__ winBase, const int4* __restrict__ echunk, double scale,
+                                          const TV* __restrict__ x, int cols, int rows, int nA, double dt, TV* __restrict__ out,
+                                          const int* __restrict__ done, int nChunks, const uint8_t* __restrict__ mcCode, const double* __restrict__ mcDict,
+                                          double* __restrict__ stPart, const int32_t* __restrict__ list) {
+    if (done && *done) return;
+    constexpr bool NT = (POL & 1) != 0, SNT = (POL & 2) != 0;
+    __shared__ double dict[MC ? 256 : 1];
+    RowDiag<MC>::fill(dict, mcDict);
+    __syncthreads();
+    const __amdgpu_buffer_rsrc_t rCol = bufRsrc(ecol, colBytes), rCode = bufRsrc(ecode, codeBytes), rX = bufRsrc(x, (size_t)cols * sizeof(TV)),
+                                 rMcc = bufRsrc(mcCode, MC ? (size_t)nA : (size_t)nA * 8), rOut = bufRsrc(out, (size_t)rows * sizeof(TV));
+    double stAcc = 0.;
+    ell2Loop<SNT, LIST, TV>(rCol, rCode, rX, winBase, echunk, scale, nChunks, list,
+        [&](unsigned row) PS_INLINE_LAMBDA { return RowDiag<MC>::template load<NT ? PS_EPI_AUX : 0>(rMcc, row, row); },   // (rows past nA read 0 through the buffer's range; their scale is 1)
+        [&](unsigned row, bool, const DiagRow& m, double s) PS_INLINE_LAMBDA { sRowFinish<0, NT, TV>(rOut, row, nA, dt, RowDiag<MC>::value(dict, m), s, stAcc); });
     if (stPart) {
         const double bs = blockReduceSum(stAcc);
         if (threadIdx.x == 0) stPart[blockIdx.x] = bs;
@@ -1031,8 +1002,8 @@ __global__ void __launch_bounds__(BS) k_spmv_S_ell2u(PS_S_ELL2_PARAMS) { spmvSEl
 // HALO (DIST only, r06): the launch may hold halo rows — rows outside [fr.ownLo, fr.ownHi) whose y is this rank's share of a neighbour's A p: it goes
 // to fr.yOut and r is left alone there (k_spmv_St_ell's generic MODE 3 did this on one unit per wave; the rank's launch over the chunks next
 // to a cut and the whole-rank launch of the sequential exchange now run two units per wave like the owned-rows launch)
-// UC (r06): the stress diagonal uInv comes as one-byte codes into a 256-entry table (true) or, when it takes more than 256 values — a viscosity FIELD —, as the
-// fp64 array itself, passed in uCode's place (false: 7 more bytes per row; until r06 such scenes ran the one-unit kernels and the fp64 polynomial)
+// UC (r06): the stress diagonal uInv comes coded (true) or, when it takes more than 256 values — a viscosity FIELD —, as the fp64 array itself, passed
+// in uCode's place (RowDiag; until r06 such scenes ran the one-unit kernels and the fp64 polynomial)
 template <int POL, bool CZ, bool DIST, bool LIST, class TZ = double, bool HALO = false, bool UC = true>
 __global__ void __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(6, 6))) k_spmv_St_ell2(const uint16_t* __restrict__ ecol, const int8_t* __restrict__ ecode, unsigned colBytes, unsigned codeBytes,
                                                      const int32_t* __restrict__ winBase, const int4* __restrict__ echunk, double scale,
@@ -1041,104 +1012,28 @@ __global__ void __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(6, 6)))
                                                      const int32_t* __restrict__ list) {
     if (done && *done) return;
     constexpr bool NT = (POL & 1) != 0, SNT = (POL & 2) != 0;
+    static_assert(!HALO || DIST, "halo rows exist on a rank of a decomposition only");
     __shared__ double dict[UC ? 256 : 1];
-    if (UC) dict[threadIdx.x] = uDict[threadIdx.x];
+    RowDiag<UC>::fill(dict, uDict);
     double alpha;
-    {   // as k_spmv_St_ell MODE 3
-        CGScalars* sc = fr.sc;
-        auto sumArr = [&](const double* a, int cnt) { double acc = 0.; for (int i = threadIdx.x; i < cnt; i += BS) acc += a[i]; return blockSumAll(acc); };
-        const bool writer = blockIdx.x == 0 && threadIdx.x == 0;
-        if (fr.it > 0) {
-            const double xx = DIST ? fr.red[1] : sumArr(fr.xxPart, fr.xxCount);
-            const double rr = sc->rr;
-            double rre = rr;                               // pcg.h:319-325
-            if (rr / xx < rre) rre = rr / xx;
-            const bool fire = rre < sc->tol2;
-            if (writer) { sc->xx = xx; sc->rre = rre; if (fire) { sc->done = 1; sc->iter = fr.it - 1; } }
-            if (fire) return;
-        }
-        const double pAp = DIST ? -fr.red[0] : -(sumArr(fr.sPart, fr.sCount) + sumArr(fr.tPart, fr.tCount) + 0.5 * sumArr(fr.uPart, fr.uCount));
-        alpha = sc->rsold2[fr.it & 1] / pAp;               // pcg.h:314
-        if (writer) { sc->pAp = pAp; sc->alpha = alpha; }
-    }
+    if (!fusedPrologue(fr, DIST, alpha)) return;
     __syncthreads();
     const __amdgpu_buffer_rsrc_t rCol = bufRsrc(ecol, colBytes), rCode = bufRsrc(ecode, codeBytes), rT = bufRsrc(t, (size_t)cols * 8),
-                                 rE0 = bufRsrc(xin, (size_t)rows * 8), rUc = bufRsrc(uCode, UC ? (size_t)rows : (size_t)rows * 8),
-                                 rFr = bufRsrc(fr.r, (size_t)rows * 8), rFd = bufRsrc(fr.dinvF, (!CZ && fr.dinvF) ? (size_t)rows * sizeof(diag_t) : 0),
-                                 rF64 = bufRsrc(fr.dinvC, CZ ? (size_t)rows * sizeof(diag_t) : 0), rFcz = bufRsrc(fr.cz, CZ ? (size_t)rows * sizeof(TZ) : 0),
-                                 rFy = bufRsrc(fr.yOut, HALO ? (size_t)rows * 8 : 0);
-    static_assert(!HALO || DIST, "halo rows exist on a rank of a decomposition only");
-    const unsigned lane = threadIdx.x & 63;
-    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int half = wv >> 1, u0 = 2 * (wv & 1);
+                                 rE0 = bufRsrc(xin, (size_t)rows * 8), rUc = bufRsrc(uCode, UC ? (size_t)rows : (size_t)rows * 8);
+    const FusedBufs B = fusedBufs<TZ>(fr, rows, true, HALO, CZ);
+    struct Loaded { double e; DiagRow u; FusedRow f; };
     double dacc = 0., dacc2 = 0.;
-    const int nPairs = (nChunks + 1) >> 1;
-    const int xcd = blockIdx.x & 7, l = blockIdx.x >> 3, per = gridDim.x >> 3;
-    auto chunkAt = [&](int q) -> int {
-        const int pair = ((((q >> 5) << 3) + xcd) << 5) + (q & 31);
-        const int ch = 2 * pair + half;
-        return (pair < nPairs && ch < nChunks) ? (LIST ? list[ch] : ch) : -1;
-    };
-    const int qEnd = ((nPairs + 255) >> 8) << 5;
-    int q = l;
-    int chunk = q < qEnd ? chunkAt(q) : -1;
-    int4 ci = make_int4(0, 0, 0, 0);
-    int myBase = 0;
-    if (chunk >= 0) { ci = echunk[chunk]; myBase = winBase[chunk * 16 + (lane & 15)]; }
-    while (q < qEnd) {
-        const int qn = q + per;
-        const int nchunk = qn < qEnd ? chunkAt(qn) : -1;
-        int4 nci = make_int4(0, 0, 0, 0);
-        int nBase = 0;
-        if (chunk >= 0) {
-            const EllUnit ua = ellUnit(ci, u0), ub = ellUnit(ci, u0 + 1);
-            const EllRegs sa = ellLoad<SNT>(rCol, rCode, ua, lane), sb = ellLoad<SNT>(rCol, rCode, ub, lane);
-            if (nchunk >= 0) { nci = echunk[nchunk]; nBase = winBase[nchunk * 16 + (lane & 15)]; }
-            const bool liveA = (int)lane < ua.rows, liveB = (int)lane < ub.rows;
-            const unsigned rowA = liveA ? (unsigned)ua.row0 + lane : ROW_NONE, rowB = liveB ? (unsigned)ub.row0 + lane : ROW_NONE;
-            const double eA = bufLoadF64epi<NT>(rE0, rowA * 8u), eB = bufLoadF64epi<NT>(rE0, rowB * 8u);
-            int ucA = 0, ucB = 0;
-            double uvA = 0., uvB = 0.;
-            if (UC) {
-                ucA = (int)__builtin_amdgcn_raw_buffer_load_b8(rUc, (int)rowA, 0, NT ? PS_UC_AUX : 0);
-                ucB = (int)__builtin_amdgcn_raw_buffer_load_b8(rUc, (int)rowB, 0, NT ? PS_UC_AUX : 0);
-            } else { uvA = bufLoadF64epi<NT>(rUc, rowA * 8u); uvB = bufLoadF64epi<NT>(rUc, rowB * 8u); }
-            const double crA = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rFr, (int)(rowA * 8u), 0, NT ? PS_EPI_AUX : 0));
-            const double crB = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rFr, (int)(rowB * 8u), 0, NT ? PS_EPI_AUX : 0));
-            float fdA = 1.f, fdB = 1.f;
-            double ciA = 0., ciB = 0.;
-            if (CZ) { ciA = (double)bufLoadDiag<NT>(rF64, rowA); ciB = (double)bufLoadDiag<NT>(rF64, rowB); }
-            else if (fr.dinvF) {
-                fdA = bufLoadDiag<NT>(rFd, rowA);
-                fdB = bufLoadDiag<NT>(rFd, rowB);
-            }
-            const EllX XA = ellGatherW(ua.W, sa, myBase, rT);
-            const EllX XB = ellGatherW(ub.W, sb, myBase, rT);
-            const double a = ellSumW(ua.W, sa, XA, scale), b = ellSumW(ub.W, sb, XB, scale);
-            double yA = -a; yA -= 0.5 * (UC ? dict[ucA] : uvA) * eA;
-            double yB = -b; yB -= 0.5 * (UC ? dict[ucB] : uvB) * eB;
-            const bool mineA = HALO ? ((int)rowA >= fr.ownLo && (int)rowA < fr.ownHi) : liveA, mineB = HALO ? ((int)rowB >= fr.ownLo && (int)rowB < fr.ownHi) : liveB;   // (idle lanes: ROW_NONE is beyond ownHi)
-            if (HALO) {                                                      // a neighbour's row: its share of A p
-                bufStoreF64nt<NT>(rFy, (!mineA && liveA) ? rowA * 8u : 0xfffffff8u, yA);
-                bufStoreF64nt<NT>(rFy, (!mineB && liveB) ? rowB * 8u : 0xfffffff8u, yB);
-            }
-            const double rvA = mineA ? crA - alpha * yA : 0., rvB = mineB ? crB - alpha * yB : 0.;   // pcg.h:316
-            dacc += rvA * rvA; dacc += rvB * rvB;
-            if (CZ) {                                                        // k_cheb_first on these rows
-                const double vA = VecIO<TZ>::stored(ciA * rvA * fr.invTheta), vB = VecIO<TZ>::stored(ciB * rvB * fr.invTheta);
-                VecIO<TZ>::template store<NT>(rFcz, rowA, vA); VecIO<TZ>::template store<NT>(rFcz, rowB, vB);
-                dacc2 += rvA * vA; dacc2 += rvB * vB;
-            } else if (fr.dinvF) { dacc2 += rvA * ((double)fdA * rvA); dacc2 += rvB * ((double)fdB * rvB); }
-            bufStoreF64nt<NT>(rFr, (!HALO || mineA) ? rowA * 8u : 0xfffffff8u, rvA);
-            bufStoreF64nt<NT>(rFr, (!HALO || mineB) ? rowB * 8u : 0xfffffff8u, rvB);
-        } else if (nchunk >= 0) { nci = echunk[nchunk]; nBase = winBase[nchunk * 16 + (lane & 15)]; }
-        q = qn; chunk = nchunk; ci = nci; myBase = nBase;
-    }
-    const double b0 = blockReduceSum(dacc), b1 = (CZ || fr.dinvF) ? blockReduceSum(dacc2) : 0.;
-    if (threadIdx.x == 0) { fr.rPart[blockIdx.x] = b0; fr.rPart[((DIST && fr.rStride > 0) ? fr.rStride : (int)gridDim.x) + blockIdx.x] = b1; }
+    ell2Loop<SNT, LIST, double>(rCol, rCode, rT, winBase, echunk, scale, nChunks, list,
+        [&](unsigned row) PS_INLINE_LAMBDA {
+            return Loaded{bufLoadF64epi<NT>(rE0, row * 8u), RowDiag<UC>::template load<NT ? (UC ? PS_UC_AUX : PS_EPI_AUX) : 0>(rUc, row, row), fusedLoads<NT>(fr, B, row, CZ)};
+        },
+        [&](unsigned row, bool live, const Loaded& L, double s) PS_INLINE_LAMBDA {
+            fusedRowFinish<NT, TZ>(fr, B, row, live, HALO, HALO, CZ, alpha, stRowY(s, RowDiag<UC>::value(dict, L.u), L.e), L.f, dacc, dacc2);
+        });
+    fusedPartials(fr, dacc, dacc2, CZ, (DIST && fr.rStride > 0) ? fr.rStride : (int)gridDim.x);
 }
 
-// ... and for MODE 2 (one term of the Chebyshev preconditioner in the epilogue; coded uInv): two units in flight per wave.
+// ... and for MODE 2 (one term of the Chebyshev preconditioner in the epilogue): two units in flight per wave.
 // TV: element type of t, xin (z_j), cheb.zprev (z_{j-1}) and out (z_{j+1}); r and every sum stay fp64
 #ifdef PS_ST2C_WAVES      // A/B build knob (scripts/build_variant.sh): waves per SIMD the Chebyshev-term kernel is compiled for
 #define PS_ST2C_ATTR __attribute__((amdgpu_waves_per_eu(PS_ST2C_WAVES, PS_ST2C_WAVES)))
@@ -1154,62 +1049,22 @@ __global__ void __launch_bounds__(BS) PS_ST2C_ATTR k_spmv_St_ell2c(const uint16_
     if (done && *done) return;
     constexpr bool NT = (POL & 1) != 0, SNT = (POL & 2) != 0;
     __shared__ double dict[UC ? 256 : 1];
-    if (UC) dict[threadIdx.x] = uDict[threadIdx.x];
+    RowDiag<UC>::fill(dict, uDict);
     __syncthreads();
     const __amdgpu_buffer_rsrc_t rCol = bufRsrc(ecol, colBytes), rCode = bufRsrc(ecode, codeBytes), rT = bufRsrc(t, (size_t)cols * sizeof(TV)),
                                  rE0 = bufRsrc(xin, (size_t)rows * sizeof(TV)), rUc = bufRsrc(uCode, UC ? (size_t)rows : (size_t)rows * 8), rOut = bufRsrc(out, (size_t)rows * sizeof(TV)),
                                  rCr = bufRsrc(cheb.r, (size_t)rows * 8), rCi = bufRsrc(cheb.dinv, (size_t)rows * sizeof(diag_t)),
                                  rCd = bufRsrc(cheb.zprev, cheb.zprev ? (size_t)rows * sizeof(TV) : 0);   // (cheb.zprev points at TV elements)
-    const unsigned lane = threadIdx.x & 63;
-    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int half = wv >> 1, u0 = 2 * (wv & 1);
+    struct Loaded { double e; DiagRow u; ChebRow c; };
     double dacc = 0.;
-    const int nPairs = (nChunks + 1) >> 1;
-    const int xcd = blockIdx.x & 7, l = blockIdx.x >> 3, per = gridDim.x >> 3;
-    auto chunkAt = [&](int q) -> int {
-        const int pair = ((((q >> 5) << 3) + xcd) << 5) + (q & 31);
-        const int ch = 2 * pair + half;
-        return (pair < nPairs && ch < nChunks) ? ch : -1;
-    };
-    const int qEnd = ((nPairs + 255) >> 8) << 5;
-    int q = l;
-    int chunk = q < qEnd ? chunkAt(q) : -1;
-    int4 ci = make_int4(0, 0, 0, 0);
-    int myBase = 0;
-    if (chunk >= 0) { ci = echunk[chunk]; myBase = winBase[chunk * 16 + (lane & 15)]; }
-    while (q < qEnd) {
-        const int qn = q + per;
-        const int nchunk = qn < qEnd ? chunkAt(qn) : -1;
-        int4 nci = make_int4(0, 0, 0, 0);
-        int nBase = 0;
-        if (chunk >= 0) {
-            const EllUnit ua = ellUnit(ci, u0), ub = ellUnit(ci, u0 + 1);
-            const EllRegs sa = ellLoad<SNT>(rCol, rCode, ua, lane), sb = ellLoad<SNT>(rCol, rCode, ub, lane);
-            if (nchunk >= 0) { nci = echunk[nchunk]; nBase = winBase[nchunk * 16 + (lane & 15)]; }
-            const unsigned rowA = (int)lane < ua.rows ? (unsigned)ua.row0 + lane : ROW_NONE, rowB = (int)lane < ub.rows ? (unsigned)ub.row0 + lane : ROW_NONE;
-            const double eA = VecIO<TV>::template loadEpi<NT>(rE0, rowA), eB = VecIO<TV>::template loadEpi<NT>(rE0, rowB);
-            int ucA = 0, ucB = 0;
-            double uvA = 0., uvB = 0.;
-            if (UC) {
-                ucA = (int)__builtin_amdgcn_raw_buffer_load_b8(rUc, (int)rowA, 0, NT ? PS_UC_AUX : 0);
-                ucB = (int)__builtin_amdgcn_raw_buffer_load_b8(rUc, (int)rowB, 0, NT ? PS_UC_AUX : 0);
-            } else { uvA = bufLoadF64epi<NT>(rUc, rowA * 8u); uvB = bufLoadF64epi<NT>(rUc, rowB * 8u); }
-            const double crA = bufLoadF64(rCr, rowA * 8u), crB = bufLoadF64(rCr, rowB * 8u);
-            const double ciA = (double)bufLoadDiag<false>(rCi, rowA), ciB = (double)bufLoadDiag<false>(rCi, rowB);
-            const double cdA = VecIO<TV>::load(rCd, rowA), cdB = VecIO<TV>::load(rCd, rowB);     // z_{j-1} (0: no buffer)
-            const EllX XA = ellGatherW<TV>(ua.W, sa, myBase, rT);
-            const EllX XB = ellGatherW<TV>(ub.W, sb, myBase, rT);
-            const double a = ellSumW(ua.W, sa, XA, scale), b = ellSumW(ub.W, sb, XB, scale);
-            double azA = -a; azA -= 0.5 * (UC ? dict[ucA] : uvA) * eA;
-            double azB = -b; azB -= 0.5 * (UC ? dict[ucB] : uvB) * eB;
-            const double yA = VecIO<TV>::stored(eA + (cheb.c1 * (eA - cdA) + cheb.c2 * (ciA * (crA - azA))));
-            const double yB = VecIO<TV>::stored(eB + (cheb.c1 * (eB - cdB) + cheb.c2 * (ciB * (crB - azB))));
-            dacc += crA * yA; dacc += crB * yB;                          // r.z of the updated z AS STORED (0 past the last row: every load returned 0)
-            VecIO<TV>::template store<NT>(rOut, rowA, yA);
-            VecIO<TV>::template store<NT>(rOut, rowB, yB);
-        } else if (nchunk >= 0) { nci = echunk[nchunk]; nBase = winBase[nchunk * 16 + (lane & 15)]; }
-        q = qn; chunk = nchunk; ci = nci; myBase = nBase;
-    }
+    ell2Loop<SNT, false, TV>(rCol, rCode, rT, winBase, echunk, scale, nChunks, nullptr,
+        [&](unsigned row) PS_INLINE_LAMBDA {
+            return Loaded{VecIO<TV>::template loadEpi<NT>(rE0, row), RowDiag<UC>::template load<NT ? (UC ? PS_UC_AUX : PS_EPI_AUX) : 0>(rUc, row, row), chebLoads<TV>(rCr, rCi, rCd, row)};
+        },
+        [&](unsigned row, bool, const Loaded& L, double s) PS_INLINE_LAMBDA {
+            VecIO<TV>::template store<NT>(rOut, row, chebRowFinish<TV>(cheb, L.c, stRowY(s, RowDiag<UC>::value(dict, L.u), L.e), L.e, dacc));
+        });
     const double bs = blockReduceSum(dacc);
     if (threadIdx.x == 0) partial[blockIdx.x] = bs;
 }
+#undef PS_INLINE_LAMBDA

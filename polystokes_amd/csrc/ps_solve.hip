@@ -10,6 +10,11 @@
 //                          k_spmv_S_pipe / k_spmv_St_pipe (persistent, software-pipelined, compressed 3 B/nnz stream) —
 //                          a 256-thread block owns 256 consecutive rows, products go through LDS, each thread sums its
 //                          own short row; epilogues fuse the diagonal scalings, the -1/2 uInv x term and the p.Ap partials.
+//                          k_spmv_*_ell (a lane owns a row) and k_spmv_*_ell2 / _ell2c (two units in flight per wave).  What they share exists
+//                          once: the loops pipeLoop / ellLoop / ell2Loop (stream, prefetch, walk; the kernel passes its per-row loads and its
+//                          row epilogue as callables), the walks chunkWalkAt / pairWalkChunk / pairWalkEnd (also called by Launch::noteWalk and
+//                          pipeBlocks below), fusedPrologue (stop test, alpha), the row epilogues sRowFinish / stRowY / chebRowFinish /
+//                          fusedRowFinish, and RowDiag (a diagonal as 1-byte codes into an LDS table or as the fp64 array).
 //   ps_kernels_tiles.hpp : k_tile_gather / k_tile_solve / k_tile_expand — per-tile J^T, 26x26 BInv, J.
 //   ps_kernels_cg.hpp    : k_cg_update_r / k_cg_update_xp (the PCG step of pcg_external_matrix_A, lib/include/pcg.h:268-340,
 //                          with the scalar reductions and the stop rule folded in; scalars stay on the device), the legacy
@@ -178,8 +183,8 @@ struct Launch {
 
     // ---- the walk of a launch (array "launchWalk"): the first launch of each slot (0: S, 1 + mode: St) in a recording solve writes
     // {1, kernel, nChunks, grid, walk parameter, 1 if the pair walk, least / most steps with a chunk of one workgroup} — host arithmetic on the
-    // plan that restates the kernels' walks: the pair walk of the two-unit kernels (runs of 32 pairs per XCD, steps l, l + per, .. below qEnd)
-    // and ChunkWalk (ps_kernels_spmv.hpp) of the one-unit and pipelined kernels; the one-shot CSR kernels take one step
+    // plan with the kernels' own walk functions (ps_kernels_spmv.hpp): the pair walk of the two-unit kernels (pairWalkChunk: runs of 32 pairs per
+    // XCD, steps l, l + per, .. below pairWalkEnd) and chunkWalkAt of the one-unit and pipelined kernels; the one-shot CSR kernels take one step
     void noteWalk(int slot, const Plan& p) const {
         if (!walk || !p.run) return;
         int32_t* w = walk + slot * ps_context::LAUNCH_WALK_FIELDS;
@@ -188,23 +193,13 @@ struct Launch {
         int lo = 1, hi = 1;
         if (p.kernel != CSR) {
             lo = INT32_MAX; hi = 0;
-            const int nPairs = (p.nChunks + 1) >> 1, qEnd = ((nPairs + 255) >> 8) << 5, per = p.grid >> 3;
-            const int g = p.xcd, sh = (g & 0xffff) > 0 ? 31 - __builtin_clz((unsigned)(g & 0xffff)) : -1, rs = (g >> 16) & 7, gridPer = p.grid >> 3;
+            const int qEnd = pairWalkEnd(p.nChunks), per = p.grid >> 3, sh = chunkWalkShift(p.xcd), rs = chunkWalkRun(p.xcd);
             for (int b = 0; b < p.grid; ++b) {
                 int steps = 0;
-                if (pair) {   // steps whose pair exists (chunkAt(q) >= 0 for the first half); the others run the loop without a chunk
-                    const int x = b & 7;
-                    for (int q = b >> 3; q < qEnd; q += per) steps += ((((q >> 5) << 3) + x) << 5) + (q & 31) < nPairs;
-                } else {
-                    for (int it = 0;; ++it) {   // ChunkWalk::at
-                        const int j = it >> rs, o = it & ((1 << rs) - 1);
-                        int64_t run;
-                        if (sh < 0) run = b + (int64_t)j * p.grid;
-                        else { const int64_t q = (b >> 3) + (int64_t)j * gridPer; run = ((((q >> sh) << 3) + (b & 7)) << sh) + (q & ((1 << sh) - 1)); }
-                        if ((run << rs) + o >= p.nChunks) break;
-                        ++steps;
-                    }
-                }
+                if (pair)   // steps whose pair exists (a chunk for the first half); the others run the loop without a chunk
+                    for (int q = b >> 3; q < qEnd; q += per) steps += pairWalkChunk(q, b & 7, 0, p.nChunks) >= 0;
+                else
+                    while (chunkWalkAt(steps, b, p.grid, sh, rs) < p.nChunks) ++steps;
                 lo = std::min(lo, steps); hi = std::max(hi, steps);
             }
         }
@@ -380,7 +375,7 @@ struct Launch {
         // two steps and everybody waited for them: 59 us where two launches of half the chunks took 2 x 20.6.  Shrink the grid to the size at which every
         // workgroup takes the same number of steps (never above the cap; the 256^3 single domain keeps its 6144 / 1536: 9 / 36 steps each).
         if (xcd > 0 && g >= 8 && c->S.ellok && c->St.ellok) {
-            const int nPairs = (nChunks + 1) >> 1, qEnd = ((nPairs + 255) >> 8) << 5;
+            const int qEnd = pairWalkEnd(nChunks);
             const int steps = std::max(1, (qEnd * 8 + g - 1) / g), per = (qEnd + steps - 1) / steps;
             if (per * 8 <= g) g = per * 8;
         }
