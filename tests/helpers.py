@@ -65,6 +65,21 @@ def materialise_blocks(solver):
     return G, Dt, JG, JDt
 
 
+def per_row(solver, per_face):
+    """a per-face quantity (three face grids) in the order of the active rows (McInv, Mc, activeRHSVector: reference numbering); solver: a
+    Solver or an Oracle"""
+    vals = np.full(solver.nA, np.nan)
+    off = 0
+    for a in range(3):
+        act = solver.array("face" + "XYZ"[a] + "ActiveIndices")
+        m = act >= 0
+        base = off if act[m].min(initial=off) < off else 0      # axis-local or global numbering: both handled
+        vals[act[m] + base] = np.asarray(per_face[a]).ravel()[m]
+        off += int(m.sum())
+    assert off == solver.nA and not np.isnan(vals).any()
+    return vals
+
+
 def relerr(a, b):
     a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
     d = np.abs(a - b).max() if a.size else 0.0

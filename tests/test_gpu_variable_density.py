@@ -13,7 +13,7 @@ import pytest
 
 from polystokes_amd import _abi as abi
 from polystokes_amd import scenes
-from helpers import basis_rows, rigid_rotation_scene
+from helpers import basis_rows, per_row, rigid_rotation_scene
 
 pytestmark = pytest.mark.gpu
 
@@ -60,20 +60,6 @@ def _face_density(sc, p):
         r[tuple(idx)] = f[tuple(sl)]
         out.append(np.clip(r.astype(np.float64), p.mindensity, p.maxdensity))
     return out
-
-
-def _per_row(solver, per_face):
-    """a per-face quantity (three face grids) in the order of the active rows (McInv, Mc, activeRHSVector: reference numbering)"""
-    vals = np.full(solver.nA, np.nan)
-    off = 0
-    for a in range(3):
-        act = solver.array("face" + "XYZ"[a] + "ActiveIndices")
-        m = act >= 0
-        base = off if act[m].min(initial=off) < off else 0      # axis-local or global numbering: both handled
-        vals[act[m] + base] = per_face[a].ravel()[m]
-        off += int(m.sum())
-    assert off == solver.nA and not np.isnan(vals).any()
-    return vals
 
 
 def _run(solver, sc, p):
@@ -173,7 +159,7 @@ def _check_face_mass(gpu, name, kind, clamp):
         p.mindensity, p.maxdensity = clamp
     _run(gpu, sc, p)
     assert int(gpu.array("densityField")[0]) == 1
-    rho = _per_row(gpu, _face_density(sc, p))
+    rho = per_row(gpu, _face_density(sc, p))
     if clamp is not None:
         assert (rho == clamp[0]).any() and (rho == clamp[1]).any() and ((rho > clamp[0]) & (rho < clamp[1])).any()
     mc, mcinv, rhs = gpu.array("Mc"), gpu.array("McInv"), gpu.array("activeRHSVector")
