@@ -143,7 +143,8 @@ typedef struct ps_fields_out {
 /* exportStats(): dimData (27) + solveData (6), Solver.cpp:574-606, same order. */
 typedef struct ps_stats {
     double dimData[27];
-    double solveData[6];                /* error, iterations, solve CPU ms, solve wall ms, setup CPU ms, setup wall ms */
+    double solveData[6];                /* error, iterations, solve CPU ms, solve wall ms, setup CPU ms, setup wall ms
+                                         * (a mixed-precision solve, ps_set_solve_precision: the true error, the sum over its passes) */
     int32_t result;                     /* ps_result */
     int32_t usedBiCGStab;               /* CG hit maxit and the fallback ran (Solver.cpp:784-799) */
     double stage_ms[16];                /* device time per stage, see PS_STAGE_* */
@@ -296,6 +297,33 @@ typedef struct ps_rheology {
     double maxViscosity;
 } ps_rheology;
 int32_t ps_set_rheology(ps_context* ctx, const ps_rheology* r);
+
+/* Mixed-precision PCG (extension; the reference solves in fp64 throughout).  A context setting like ps_set_solid_boundary: it persists across
+ * ps_upload_fields and is read by every later PCG solve.  PS_PRECISION_FP64 (the default) launches exactly the kernels of a context that never
+ * made the call.  PS_PRECISION_MIXED keeps the solution x in fp64 and runs the PCG in passes on fp32 vectors: a pass solves A d = r with
+ * r = b - A x formed in fp64 by the fp64 operator, and stores the correction d, the direction p, the residual r, A p and the face-row
+ * vector t of the operator as fp32; every product, every partial sum and every scalar of the recurrence stays fp64, and r.r, r.z, d.d are
+ * formed from the values as stored.  A pass ends when its recurrence meets the stop rule min(r.r, r.r / x.x) < tolerance^2 (pcg.h:319-325) or
+ * when r.r has fallen to (1e-4)^2 of the true r.r it started from (fp32 carries 2^-24: about three digits are left for drift); then
+ * x += d in fp64, r = b - A x is formed again, and the rule is evaluated on these true fp64 values: that evaluation alone decides SUCCESS.
+ * x.x in a pass: the first pass of a cold solve has x = d and uses d.d as the fp64 solve does; any other pass uses x.x of the x it started
+ * from (the evaluation at its end corrects it).  maxSolverIterations is one budget over all passes; when it runs out the fp64 BiCGStab
+ * fallback runs from zero as in the fp64 solve.  At most 8 passes; a pass whose true ||r|| is not below half of the one it started from has
+ * reached the floor of fp32, and the solve continues as the fp64 PCG from the current x.  Interrupts are polled between batches as in the
+ * fp64 solve (PS_INCOMPLETE, velocity untouched).  A carried x0 (ps_set_warm_start, a Picard pass of ps_set_rheology) is a first pass with
+ * x != 0.  ps_stats.solveData[0] is the true value of the last evaluation, solveData[1] the sum of the passes' iterations, each pass
+ * counted by the iterations it ran (the fp64 solve reports the index of the iteration that met the rule, one less).
+ * It runs in a single domain, with PS_PCG_MATRIX_VECTOR_PRODUCTS, preconditioner identity or Jacobi, on systems whose products run the
+ * two-units-per-wave row-per-lane kernels (coded stencil values, 16-bit columns, at least 8 workgroups; the stress diagonal and the face mass
+ * either value-set coded or fp64 fields), in both step forms.  Everywhere else — the Chebyshev preconditioners, solverType EIGEN, the other
+ * stream formats, slab and brick ranks, in-process groups, ps_solve_exported_system — the setting is ignored and the solve is the fp64 one,
+ * launch for launch.  The fp32 vectors (3 or 4 x 4 B per DOF, 4 B per face row) are allocated by the first mixed solve and released by
+ * ps_set_solve_precision(ctx, PS_PRECISION_FP64).  PS_INVALID (reason in ps_last_error, the previous setting kept): another mode.
+ * Arrays: "solvePrecisionUsed" (int32, 1: 0 = the last PCG solve ran in fp64, 1 = mixed throughout, 2 = started mixed and finished in
+ * fp64), "solvePassIterations" (int32, one per fp32 pass; only when used != 0), "solveTrueResidual" (fp64, 1: sqrt(min(r.r, r.r / x.x)) of
+ * r = b - A x in fp64 at the end of the last pass; only when used != 0). */
+enum ps_solve_precision { PS_PRECISION_FP64 = 0, PS_PRECISION_MIXED = 1 };
+int32_t ps_set_solve_precision(ps_context* ctx, int32_t mode);
 
 /* solveGasSubclass equivalent on host buffers: upload + step + download (HDK_PolyStokes.C:222-609). */
 int32_t polystokes_step(ps_context* ctx, const ps_params* p, const ps_fields_in* in,

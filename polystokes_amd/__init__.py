@@ -26,7 +26,7 @@ EXPORTED_SYMBOLS = [
     "ps_set_slab", "ps_set_brick", "ps_comm_unique_id", "ps_comm_init_rccl", "ps_comm_selftest", "ps_comm_init_tcp", "ps_dist_stats",
     "ps_group_create", "ps_group_destroy", "ps_group_rank", "ps_group_step",
     "ps_set_warm_start", "ps_download_solution_fields", "ps_upload_density_field", "ps_set_surface_tension",
-    "ps_set_solid_boundary", "ps_set_rheology",
+    "ps_set_solid_boundary", "ps_set_rheology", "ps_set_solve_precision",
 ]
 
 
@@ -120,6 +120,8 @@ def lib():
         L.ps_set_solid_boundary.restype = C.c_int32
         L.ps_set_rheology.argtypes = [C.c_void_p, C.POINTER(_abi.Rheology)]
         L.ps_set_rheology.restype = C.c_int32
+        L.ps_set_solve_precision.argtypes = [C.c_void_p, C.c_int32]
+        L.ps_set_solve_precision.restype = C.c_int32
         _lib = L
     return _lib
 
@@ -131,7 +133,8 @@ def _kind(name):
     if name.endswith(("Labels", "Indices", ".col", ".ptr", "Region", "Perm", ".chunkInfo", ".chunkRep", ".code")) or name.startswith("faceRow"):
         return "i"
     if name in ("valuesCoded", "columns16", "diagonalsCoded", "fusedStep", "streamRuns", "rowPerLane", "chebInner32", "warmStartUsed", "densityField", "launchWalk",
-                "surfaceTensionReducedFaces", "solidBoundary", "solidSlipEdges", "rheologyModel", "rheologyIterations"):
+                "surfaceTensionReducedFaces", "solidBoundary", "solidSlipEdges", "rheologyModel", "rheologyIterations",
+                "solvePrecisionUsed", "solvePassIterations"):
         return "i"
     if name in ("ownedX", "ownedY", "ownedZ"):
         return "f"
@@ -206,6 +209,13 @@ class Solver:
         r = _abi.Rheology(int(model), int(passes), float(flow_index), float(yield_stress), float(min_shear_rate), float(min_viscosity),
                           float(max_viscosity))
         return self._check(self.L.ps_set_rheology(self.h, C.byref(r)), allow=(1, -2))
+
+    def set_solve_precision(self, mode):
+        """ps_set_solve_precision: PRECISION_FP64 (0, the default) or PRECISION_MIXED (1: the PCG runs in passes on fp32 vectors around the
+        fp64 x, and the stop rule is decided on the fp64 residual b - A x) for every later PCG solve of this context, across uploads.  Returns
+        the ps_result: INVALID for another mode (the previous setting kept).  Arrays "solvePrecisionUsed", "solvePassIterations",
+        "solveTrueResidual" say what the last solve did."""
+        return self._check(self.L.ps_set_solve_precision(self.h, int(mode)), allow=(1, -2))
 
     def solution_fields(self):
         """ps_download_solution_fields: the last solve's [p; tau] as dense fp32 grids (x fastest), keyed pressure, txx, tyy, tzz, tyz, txz, txy;
@@ -457,6 +467,11 @@ class Group:
     def set_solid_boundary(self, mode):
         """ps_set_solid_boundary on every rank (a context setting: it holds for every later step of the group)."""
         rc = [r.set_solid_boundary(mode) for r in self.ranks]
+        return rc[0]
+
+    def set_solve_precision(self, mode):
+        """ps_set_solve_precision on every rank (a decomposition solves in fp64 whatever the setting: "solvePrecisionUsed" reads 0)."""
+        rc = [r.set_solve_precision(mode) for r in self.ranks]
         return rc[0]
 
     def set_rheology(self, *args, **kw):

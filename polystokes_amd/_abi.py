@@ -67,6 +67,8 @@ WARM_NONE, WARM_PREVIOUS_STEP = 0, 1
 SOLID_NO_SLIP, SOLID_FREE_SLIP = 0, 1
 # ps_rheology_model
 RHEOLOGY_NEWTONIAN, RHEOLOGY_HERSCHEL_BULKLEY = 0, 1
+# ps_solve_precision
+PRECISION_FP64, PRECISION_MIXED = 0, 1
 
 
 class Rheology(C.Structure):

@@ -193,6 +193,7 @@ void ps_context::setupPhase(int phase) {
         isSetup = false; isSolved = false;   // a setup that throws must not leave the previous step's system looking valid
         setupPhaseDone = -1;
         warmUsedHost = 0; warmX0Valid = false;
+        solvePrecisionUsedHost = 0; passIters.clear();
         arrays.clear();
         if (rheoPass == 0) rheoIters.clear();   // (ps_set_rheology: one entry per solve of the step)
         // Picard passes need the halo of the last pass's output velocity: a decomposition refuses them on every rank (ps_dist.hpp: distStep)
@@ -369,6 +370,12 @@ void ps_context::registerArrays() {
     regp("guessVector", guess.p, nSystem, permSys.p, 0);
     if (warmX0Valid) regp("warmStartVector", warmX0.p, nSystem, permSys.p, 0);   // (mode PS_WARM_PREVIOUS_STEP, after a PCG solve)
     regHost("warmStartUsed", &warmUsedHost, 1, 4);   // 1: the last PCG solve started from the solution carried over from an earlier step (ps_set_warm_start)
+    // the last PCG solve: 0 fp64, 1 mixed precision throughout, 2 started mixed and finished in fp64 (ps_set_solve_precision)
+    regHost("solvePrecisionUsed", &solvePrecisionUsedHost, 1, 4);
+    if (solvePrecisionUsedHost != 0) {
+        regHost("solvePassIterations", passIters.data(), (int64_t)passIters.size(), 4);   // PCG iterations of each fp32 pass
+        regHost("solveTrueResidual", &trueResidualHost, 1, 8);   // the stop rule's value on r = b - A x in fp64 at the end of the last pass
+    }
     densFieldHost = densField ? 1 : 0;   // 1: the last setup sampled a non-constant density field (ps_upload_density_field)
     regHost("densityField", &densFieldHost, 1, 4);
     regHost("surfaceTension", &sigmaUsed, 1, 8);   // the sigma of the last setup (ps_set_surface_tension)
@@ -711,6 +718,23 @@ int32_t ps_set_solid_boundary(ps_context* c, int32_t mode) {
             return PS_INVALID;
         }
         c->solidBoundarySet = mode;   // read by the next setup (constructMatrixBlocks)
+        return PS_SUCCESS;
+    })
+}
+int32_t ps_set_solve_precision(ps_context* c, int32_t mode) {
+    if (!c) return PS_FAILED;
+    PS_TRY(c, {
+        if (mode != PS_PRECISION_FP64 && mode != PS_PRECISION_MIXED) {
+            c->err = "ps_set_solve_precision: unknown mode " + std::to_string(mode) + " (0: fp64, 1: mixed)";
+            return PS_INVALID;
+        }
+        c->solvePrecisionSet = mode;   // read by every later PCG solve (ps_context::solve)
+        if (mode == PS_PRECISION_FP64 && c->d32.p) {   // the fp32 vectors go with the mode: dropped and, with the stream idle, released here
+            HIP_CHECK(hipSetDevice(c->device));
+            HIP_CHECK(hipStreamSynchronize(c->stream));
+            c->dropMixedBuffers();
+            c->drainDeferred(true);
+        }
         return PS_SUCCESS;
     })
 }

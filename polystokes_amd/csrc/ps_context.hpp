@@ -63,6 +63,9 @@ struct CGScalars {
     int pendIter;
     int vecNT;       // 1: the vector kernels use non-temporal loads / stores (ps_context::ntLevel() == 2)
     double rsold2[2];   // r.z of the previous iteration, double-buffered by iteration parity (fused-scalar step kernels)
+    // a pass of the mixed-precision solve (k_cg_scal0_pass writes them, stopTest<true> reads them; the fp64 kernels touch neither): the pass
+    // also ends at r.r < rrFloor, and with xxFix > 0 its stop test takes x.x = xxFix (the fp64 x at the pass's start) instead of the running sum
+    double rrFloor, xxFix;
 };
 
 struct ArrayInfo {
@@ -278,6 +281,16 @@ struct ps_context {
     ps::DevBuf<double> warmX0;               // the x0 the last PCG solve of a mode-1 context used (array "warmStartVector"), internal numbering
     bool warmX0Valid = false;
     int32_t warmUsedHost = 0;                // 1: the last PCG solve started from the carried solution (array "warmStartUsed")
+    // Mixed-precision solve (ps_set_solve_precision, extension; ps_solve.hip: solve): solvePrecisionSet is the context setting.  In mode
+    // PS_PRECISION_MIXED a single-domain Jacobi / identity PCG solve on the two-unit row-per-lane kernels runs as passes on fp32 vectors — the
+    // correction d32, p32, r32, the face-row vector ts32 and, in the five-kernel step, Ap32: allocated by the first such solve, dropped when
+    // the mode returns to fp64 — around the fp64 x.  solvePrecisionUsedHost / passIters / trueResidualHost: arrays "solvePrecisionUsed",
+    // "solvePassIterations", "solveTrueResidual" of the last PCG solve.
+    int32_t solvePrecisionSet = PS_PRECISION_FP64, solvePrecisionUsedHost = 0;
+    ps::DevBuf<float> d32, p32, r32, ts32, Ap32;
+    std::vector<int32_t> passIters;
+    double trueResidualHost = 0;
+    void dropMixedBuffers() { d32.free(); p32.free(); r32.free(); ts32.free(); Ap32.free(); }
     int64_t solutionGridCount(int q) const { return g.count(q < 4 ? 0 : q); }   // grid q of the store: 0..3 cell grid, 4..6 edge grids
     void scatterSolution(float* dst, int q0, int nq);   // ps_solve.hip: grids q0 .. q0+nq-1 of x, back to back in dst
     void carryWarmStart();                              // ps_solve.hip: x -> warmStore (after a kept step)

@@ -55,6 +55,43 @@ __device__ inline void stD2(double2* p, double2 v, bool nt) {
     psd2 q; q.x = v.x; q.y = v.y;
     __builtin_nontemporal_store(q, reinterpret_cast<psd2*>(p));
 }
+// 16 bytes of a Krylov vector per lane and access, as doubles: two doubles, or four floats (the mixed-precision solve, ps_solve.hip:
+// PS_PRECISION_MIXED, keeps d, p, r and A p in fp32).  iv = index of the group; stored: the value a later kernel reads back.
+template <class TV> struct Vec16;
+template <> struct Vec16<double> {
+    static constexpr int W = 2;
+    __device__ static inline void load(const double* v, int64_t iv, bool nt, double (&o)[2]) { const double2 q = ldD2((const double2*)v + iv, nt); o[0] = q.x; o[1] = q.y; }
+    __device__ static inline void store(double* v, int64_t iv, bool nt, const double (&o)[2]) { stD2((double2*)v + iv, make_double2(o[0], o[1]), nt); }
+    __device__ static inline double stored(double v) { return v; }
+};
+template <> struct Vec16<float> {
+    static constexpr int W = 4;
+    typedef float psf4 __attribute__((ext_vector_type(4)));
+    __device__ static inline void load(const float* v, int64_t iv, bool nt, double (&o)[4]) {
+        const psf4* q = reinterpret_cast<const psf4*>(v) + iv;
+        const psf4 f = nt ? __builtin_nontemporal_load(q) : *q;
+        o[0] = (double)f.x; o[1] = (double)f.y; o[2] = (double)f.z; o[3] = (double)f.w;
+    }
+    __device__ static inline void store(float* v, int64_t iv, bool nt, const double (&o)[4]) {
+        psf4 f; f.x = (float)o[0]; f.y = (float)o[1]; f.z = (float)o[2]; f.w = (float)o[3];
+        psf4* q = reinterpret_cast<psf4*>(v) + iv;
+        if (nt) __builtin_nontemporal_store(f, q); else *q = f;
+    }
+    __device__ static inline double stored(double v) { return (double)(float)v; }
+};
+// the W entries of the stored Jacobi diagonal / of the fp64 stress diagonal / the W one-byte codes that go with group iv
+template <int W> __device__ inline void ldDiagW(const diag_t* __restrict__ d, int64_t iv, bool nt, double (&o)[W]) {
+#pragma unroll
+    for (int k = 0; k < W / 2; ++k) { const double2 q = ldDiag2(d, iv * (W / 2) + k, nt); o[2 * k] = q.x; o[2 * k + 1] = q.y; }
+}
+template <int W> __device__ inline void ldF64W(const double* __restrict__ u, int64_t iv, bool nt, double (&o)[W]) {
+#pragma unroll
+    for (int k = 0; k < W / 2; ++k) { const double2 q = ldD2((const double2*)u + iv * (W / 2) + k, nt); o[2 * k] = q.x; o[2 * k + 1] = q.y; }
+}
+template <int W> __device__ inline uint32_t ldCodesW(const uint8_t* __restrict__ c, int64_t iv, bool nt) {
+    if constexpr (W == 2) return nt ? __builtin_nontemporal_load((const uint16_t*)c + iv) : ((const uint16_t*)c)[iv];
+    else return nt ? __builtin_nontemporal_load((const uint32_t*)c + iv) : ((const uint32_t*)c)[iv];
+}
 __global__ void k_scale_rows(double* __restrict__ out, const double* __restrict__ a, const double* __restrict__ b, int64_t n) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) out[i] = a[i] * b[i];
 }
@@ -98,6 +135,39 @@ __global__ void __launch_bounds__(BS) k_cg_init_warm(const double* __restrict__ 
     const double s = blockReduceSum(acc);
     if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
+// ---- mixed-precision solve (ps_set_solve_precision; ps_solve.hip: solve) ----------------------------------------------------
+// Start of a pass, the fp32 form of k_cg_init_f (Ax null: x = 0, r = b) and k_cg_init_warm (Ax = A x): the pass solves A d = r64 with
+// d = 0, r = fp32(r64), z = pre(r), p = fp32(z).  Partials: r.z of the values as stored at [block]; of the TRUE r64 . r64 at [grid + block] and
+// of x . x at [2 grid + block] — the fp64 evaluation of the stop rule on b - A x (k_cg_scal0_pass)
+__global__ void __launch_bounds__(BS) k_cg_init_pass(const double* __restrict__ b, const double* __restrict__ Ax, const double* __restrict__ x,
+                                                     const diag_t* __restrict__ dinv, float* __restrict__ d, float* __restrict__ r,
+                                                     float* __restrict__ p, int64_t n, double* __restrict__ partial) {
+    double arz = 0., arr = 0., axx = 0.;
+    for (int64_t i = (int64_t)blockIdx.x * BS + threadIdx.x; i < n; i += (int64_t)gridDim.x * BS) {
+        const double r64 = Ax ? b[i] - Ax[i] : b[i];
+        const float rs = (float)r64;
+        const float zs = (float)(dinv ? diagValue(dinv[i]) * (double)rs : (double)rs);
+        d[i] = 0.f; r[i] = rs; p[i] = zs;
+        arz += (double)rs * (double)zs;
+        arr += r64 * r64;
+        if (Ax) { const double xv = x[i]; axx += xv * xv; }
+    }
+    const double s0 = blockReduceSum(arz), s1 = blockReduceSum(arr), s2 = blockReduceSum(axx);
+    if (threadIdx.x == 0) { partial[blockIdx.x] = s0; partial[gridDim.x + blockIdx.x] = s1; partial[2 * gridDim.x + blockIdx.x] = s2; }
+}
+// End of a pass: x += d in fp64 (cold: x = d, the first pass of a cold solve)
+__global__ void __launch_bounds__(BS) k_cg_end_pass(const float* __restrict__ d, double* __restrict__ x, int64_t n, int cold) {
+    const bool vec = ((((uintptr_t)d | (uintptr_t)x) & 15) == 0);
+    const int64_t n4 = vec ? n / 4 : 0;
+    for (int64_t i = (int64_t)blockIdx.x * BS + threadIdx.x; i < n4; i += (int64_t)gridDim.x * BS) {
+        double dv[4], lo[2] = {0., 0.}, hi[2] = {0., 0.};
+        Vec16<float>::load(d, i, false, dv);
+        if (!cold) { Vec16<double>::load(x, 2 * i, false, lo); Vec16<double>::load(x, 2 * i + 1, false, hi); }
+        lo[0] += dv[0]; lo[1] += dv[1]; hi[0] += dv[2]; hi[1] += dv[3];
+        Vec16<double>::store(x, 2 * i, false, lo); Vec16<double>::store(x, 2 * i + 1, false, hi);
+    }
+    for (int64_t i = 4 * n4 + (int64_t)blockIdx.x * BS + threadIdx.x; i < n; i += (int64_t)gridDim.x * BS) x[i] = (cold ? 0. : x[i]) + (double)d[i];
+}
 // The solution as seven dense x-fastest grids (ps_context::warmStore): blockIdx.y = grid, its samples grid-stride; map = the grid's index
 // map (sample -> internal DOF, -1: none).  Every index is checked against -1 and the system size.
 struct SolutionGrids { const int32_t* map[7]; int64_t off[7]; int64_t cnt[7]; };
@@ -129,14 +199,28 @@ __global__ void k_to_diag(const double* __restrict__ a, diag_t* __restrict__ out
 }
 // sum of `count` partials, valid in thread 0 (sumLocal, stopTest: ps_kernels_spmv.hpp, shared with the fused St epilogue)
 __device__ inline double sumPartials(const double* __restrict__ partial, int count) { return blockReduceSum(sumLocal(partial, count)); }
+__device__ inline void cgScalInit(CGScalars* sc, double s, double tol, int maxit, int vecNT) {   // (one thread)
+    sc->rsold = s; sc->rsold2[0] = s; sc->rsold2[1] = 0.; sc->rre = 0.; sc->iter = maxit; sc->maxit = maxit; sc->tol2 = tol * tol;
+    sc->done = (s == 0.) ? 1 : 0;      // deviation: b == 0 -> return at once (reference divides 0/0, pcg.h:314)
+    if (s == 0.) sc->iter = 0;
+    sc->alpha = sc->beta = sc->pAp = sc->rr = sc->xx = sc->rz = 0.;
+    sc->pend = 0; sc->pendIter = 0; sc->vecNT = vecNT;
+}
 __global__ void __launch_bounds__(BS) k_cg_scal0(CGScalars* sc, const double* __restrict__ partial, int count, double tol, int maxit, int vecNT) {
     const double s = sumPartials(partial, count);
+    if (threadIdx.x == 0) cgScalInit(sc, s, tol, maxit, vecNT);
+}
+// The same at the start of a pass of the mixed-precision solve (k_cg_init_pass wrote the partials: r.z, then the true r.r, then x.x).  The true
+// values stay in rr / xx / rre for the host — the evaluation that decides the solve —; the pass ends at r.r < floor2 * (true r.r), and with
+// frozenXX its stop test uses this x.x throughout (stopTest<true>)
+__global__ void __launch_bounds__(BS) k_cg_scal0_pass(CGScalars* sc, const double* __restrict__ partial, int count, double tol, int maxit, int vecNT, double floor2, int frozenXX) {
+    const double s = sumPartials(partial, count), rr = sumPartials(partial + count, count), xx = sumPartials(partial + 2 * count, count);
     if (threadIdx.x == 0) {
-        sc->rsold = s; sc->rsold2[0] = s; sc->rsold2[1] = 0.; sc->rre = 0.; sc->iter = maxit; sc->maxit = maxit; sc->tol2 = tol * tol;
-        sc->done = (s == 0.) ? 1 : 0;      // deviation: b == 0 -> return at once (reference divides 0/0, pcg.h:314)
-        if (s == 0.) sc->iter = 0;
-        sc->alpha = sc->beta = sc->pAp = sc->rr = sc->xx = sc->rz = 0.;
-        sc->pend = 0; sc->pendIter = 0; sc->vecNT = vecNT;
+        cgScalInit(sc, s, tol, maxit, vecNT);
+        double rre = rr;                              // pcg.h:319-325 on r = b - A x
+        if (rr / xx < rre) rre = rr / xx;
+        sc->rr = rr; sc->xx = xx; sc->rre = rre;
+        sc->rrFloor = floor2 * rr; sc->xxFix = frozenXX ? xx : 0.;
     }
 }
 // stage A of the p.Ap reduction: RED_BLOCKS blocks each sum a contiguous slice of the SpMV block partials
@@ -238,16 +322,27 @@ __global__ void __launch_bounds__(BS) k_cg_update_p(const CGScalars* __restrict_
 // the start of iteration k+1 (or by k_cg_check before the host polls); when it fires every later kernel is a no-op and
 // x already holds the iterate the reference returns.  Cost: one unused p update and one unused operator apply.
 // With `red` (distributed solve) the sums come all-reduced from the ranks: red = {p.Ap, x.x} resp. {r.r, r.z}.
-__global__ void __launch_bounds__(BS) k_cg_check(CGScalars* sc, const double* __restrict__ red, const double* __restrict__ xxPartial, int vb, int lastIter) {
+template <bool PASS>
+__device__ inline void cgCheck(CGScalars* sc, const double* __restrict__ red, const double* __restrict__ xxPartial, int vb, int lastIter) {
     if (sc->done) return;
     const double xx = red ? red[0] : blockSumAll(sumLocal(xxPartial, vb));
-    stopTest(sc, xx, lastIter, threadIdx.x == 0);
+    stopTest<PASS>(sc, xx, lastIter, threadIdx.x == 0);
+}
+__global__ void __launch_bounds__(BS) k_cg_check(CGScalars* sc, const double* __restrict__ red, const double* __restrict__ xxPartial, int vb, int lastIter) {
+    cgCheck<false>(sc, red, xxPartial, vb, lastIter);
+}
+__global__ void __launch_bounds__(BS) k_cg_check_pass(CGScalars* sc, const double* __restrict__ xxPartial, int vb, int lastIter) {   // a pass of the mixed-precision solve
+    cgCheck<true>(sc, nullptr, xxPartial, vb, lastIter);
 }
 // [stop test of iteration it-1] ; alpha ; r -= alpha Ap ; partials of r.r and r.z
-__global__ void __launch_bounds__(BS) k_cg_update_r(CGScalars* sc, const double* __restrict__ red, const double* __restrict__ pApPartial, int pApCount,
-                                                    const double* __restrict__ xxPartial, int xxCount, int it, const double* __restrict__ Ap,
-                                                    const diag_t* __restrict__ dinv, double* __restrict__ r, int64_t n, double* __restrict__ partial) {
+// TV: element type of Ap and r (float: a pass of the mixed-precision solve — k_cg_update_r_f32; r.r and r.z from r as stored, the pass's stop test)
+template <class TV>
+__device__ inline void cgUpdateR(CGScalars* sc, const double* __restrict__ red, const double* __restrict__ pApPartial, int pApCount,
+                                 const double* __restrict__ xxPartial, int xxCount, int it, const TV* __restrict__ Ap,
+                                 const diag_t* __restrict__ dinv, TV* __restrict__ r, int64_t n, double* __restrict__ partial) {
     if (sc->done) return;
+    constexpr bool PASS = !std::is_same<TV, double>::value;
+    constexpr int W = Vec16<TV>::W;
     const bool writer = blockIdx.x == 0 && threadIdx.x == 0;
     double pAp, xx = 0.;
     if (red) { pAp = red[0]; xx = red[1]; }
@@ -255,41 +350,55 @@ __global__ void __launch_bounds__(BS) k_cg_update_r(CGScalars* sc, const double*
         if (it > 0) xx = blockSumAll(sumLocal(xxPartial, xxCount));
         pAp = blockSumAll(sumLocal(pApPartial, pApCount));
     }
-    if (it > 0 && stopTest(sc, xx, it - 1, writer)) return;           // same verdict in every block
+    if (it > 0 && stopTest<PASS>(sc, xx, it - 1, writer)) return;     // same verdict in every block
     const double alpha = sc->rsold2[it & 1] / pAp;                      // pcg.h:314
     if (writer) { sc->pAp = pAp; sc->alpha = alpha; }
     double arr = 0., arz = 0.;
     const bool nt = sc->vecNT != 0;
-    const bool vec = ((((uintptr_t)Ap | (uintptr_t)r) & 15) == 0) && (((uintptr_t)dinv & DIAG_PAIR_MASK) == 0);
-    const int64_t n2 = vec ? n / 2 : 0;
-    const double2* A2 = (const double2*)Ap;
-    double2* r2 = (double2*)r;
-    for (int64_t i = (int64_t)blockIdx.x * BS + threadIdx.x; i < n2; i += (int64_t)gridDim.x * BS) {
-        const double2 av = ldD2(A2 + i, nt && PS_VEC_NT_AP);
-        double2 rv = ldD2(r2 + i, nt && PS_VEC_NT_R);
-        rv.x = rv.x - alpha * av.x; rv.y = rv.y - alpha * av.y;
-        stD2(r2 + i, rv, nt && PS_VEC_NT_R);
-        arr += rv.x * rv.x; arr += rv.y * rv.y;
-        if (dinv) { const double2 dv = ldDiag2(dinv, i, nt && PS_VEC_NT_D); arz += rv.x * (dv.x * rv.x); arz += rv.y * (dv.y * rv.y); }
+    const bool vec = ((((uintptr_t)Ap | (uintptr_t)r) & 15) == 0) && (((uintptr_t)dinv & (W * sizeof(diag_t) - 1)) == 0);
+    const int64_t nv = vec ? n / W : 0;
+    for (int64_t i = (int64_t)blockIdx.x * BS + threadIdx.x; i < nv; i += (int64_t)gridDim.x * BS) {
+        double av[W], rv[W];
+        Vec16<TV>::load(Ap, i, nt && PS_VEC_NT_AP, av);
+        Vec16<TV>::load(r, i, nt && PS_VEC_NT_R, rv);
+#pragma unroll
+        for (int k = 0; k < W; ++k) rv[k] = Vec16<TV>::stored(rv[k] - alpha * av[k]);
+        Vec16<TV>::store(r, i, nt && PS_VEC_NT_R, rv);
+#pragma unroll
+        for (int k = 0; k < W; ++k) arr += rv[k] * rv[k];
+        if (dinv) {
+            double dv[W];
+            ldDiagW<W>(dinv, i, nt && PS_VEC_NT_D, dv);
+#pragma unroll
+            for (int k = 0; k < W; ++k) arz += rv[k] * (dv[k] * rv[k]);
+        }
     }
-    for (int64_t i = 2 * n2 + (int64_t)blockIdx.x * BS + threadIdx.x; i < n; i += (int64_t)gridDim.x * BS) {
-        const double rv = r[i] - alpha * Ap[i];
-        r[i] = rv;
+    for (int64_t i = W * nv + (int64_t)blockIdx.x * BS + threadIdx.x; i < n; i += (int64_t)gridDim.x * BS) {
+        const double rv = Vec16<TV>::stored((double)r[i] - alpha * (double)Ap[i]);
+        r[i] = (TV)rv;
         arr += rv * rv;
         if (dinv) arz += rv * (diagValue(dinv[i]) * rv);
     }
     const double s0 = blockReduceSum(arr), s2 = dinv ? blockReduceSum(arz) : 0.;
     if (threadIdx.x == 0) { partial[blockIdx.x] = s0; partial[gridDim.x + blockIdx.x] = s2; }
 }
+#define PS_CG_UPDATE_R_PARAMS(TV) CGScalars* sc, const double* __restrict__ red, const double* __restrict__ pApPartial, int pApCount, const double* __restrict__ xxPartial, \
+                                  int xxCount, int it, const TV* __restrict__ Ap, const diag_t* __restrict__ dinv, TV* __restrict__ r, int64_t n, double* __restrict__ partial
+__global__ void __launch_bounds__(BS) k_cg_update_r(PS_CG_UPDATE_R_PARAMS(double)) { cgUpdateR<double>(sc, red, pApPartial, pApCount, xxPartial, xxCount, it, Ap, dinv, r, n, partial); }
+__global__ void __launch_bounds__(BS) k_cg_update_r_f32(PS_CG_UPDATE_R_PARAMS(float)) { cgUpdateR<float>(sc, red, pApPartial, pApCount, xxPartial, xxCount, it, Ap, dinv, r, n, partial); }
+#undef PS_CG_UPDATE_R_PARAMS
 // beta ; x += alpha p ; p = z + beta p (z = D^-1 r) ; partials of x.x
 // UPP (fused residual update, FusedR in ps_kernels_spmv.hpp): also the partials of sum_j uInv_j p_j^2 of the NEW p — the diagonal
 // share of the next p . A p — from the coded diagonal (1 B per entry + 256-entry table in LDS) or the fp64 one.
-template <bool UPP>
+// TV: element type of r, x and p (float: a pass of the mixed-precision solve, where x is the pass's correction d — k_cg_update_xp_f32 / _u_f32;
+// x.x and the uInv p^2 partials are formed from the values as stored)
+template <bool UPP, class TV = double>
 __device__ inline void cgUpdateXp(CGScalars* sc, const double* __restrict__ red, const double* __restrict__ rPartial, int rCount, int jacobi,
-                                  int it, const double* __restrict__ r, const diag_t* __restrict__ dinv, double* __restrict__ x,
-                                  double* __restrict__ p, int64_t n, double* __restrict__ partial,
+                                  int it, const TV* __restrict__ r, const diag_t* __restrict__ dinv, TV* __restrict__ x,
+                                  TV* __restrict__ p, int64_t n, double* __restrict__ partial,
                                   const uint8_t* __restrict__ uCode, const double* __restrict__ uDict, const double* __restrict__ uInv, double* __restrict__ uPart) {
     if (sc->done) return;
+    constexpr int W = Vec16<TV>::W;
     __shared__ double dict[UPP ? 256 : 1];
     if (UPP && uCode) dict[threadIdx.x] = uDict[threadIdx.x];   // visible after the barriers of blockSumAll below
     double rr, rz;
@@ -303,32 +412,45 @@ __device__ inline void cgUpdateXp(CGScalars* sc, const double* __restrict__ red,
     const bool nt = sc->vecNT != 0;
     if (blockIdx.x == 0 && threadIdx.x == 0) { sc->rr = rr; sc->rz = rz; sc->beta = beta; sc->rsold2[(it + 1) & 1] = rz; sc->rsold = rz; }
     double axx = 0., aup = 0.;
-    const bool vec = ((((uintptr_t)p | (uintptr_t)r | (uintptr_t)x) & 15) == 0) && (((uintptr_t)dinv & DIAG_PAIR_MASK) == 0) &&
-                     (!UPP || ((((uintptr_t)uCode & 1) == 0) && (((uintptr_t)uInv & 15) == 0)));
-    const int64_t n2 = vec ? n / 2 : 0;
-    const double2* r2 = (const double2*)r;
-    double2* p2 = (double2*)p; double2* x2 = (double2*)x;
-    for (int64_t i = (int64_t)blockIdx.x * BS + threadIdx.x; i < n2; i += (int64_t)gridDim.x * BS) {
-        double2 z = ldD2(r2 + i, nt && PS_VEC_NT_RX);
-        if (dinv) { const double2 dv = ldDiag2(dinv, i, nt && PS_VEC_NT_D); z.x = dv.x * z.x; z.y = dv.y * z.y; }
-        double2 pv = ldD2(p2 + i, nt && PS_VEC_NT_PL), xv = ldD2(x2 + i, nt && PS_VEC_NT_X);
-        xv.x = xv.x + alpha * pv.x; xv.y = xv.y + alpha * pv.y;
-        pv.x = z.x + beta * pv.x; pv.y = z.y + beta * pv.y;
-        stD2(x2 + i, xv, nt && PS_VEC_NT_X); stD2(p2 + i, pv, nt && PS_VEC_NT_P);
-        axx += xv.x * xv.x; axx += xv.y * xv.y;
+    const bool vec = ((((uintptr_t)p | (uintptr_t)r | (uintptr_t)x) & 15) == 0) && (((uintptr_t)dinv & (W * sizeof(diag_t) - 1)) == 0) &&
+                     (!UPP || ((((uintptr_t)uCode & (W - 1)) == 0) && (((uintptr_t)uInv & 15) == 0)));
+    const int64_t nv = vec ? n / W : 0;
+    for (int64_t i = (int64_t)blockIdx.x * BS + threadIdx.x; i < nv; i += (int64_t)gridDim.x * BS) {
+        double z[W], pv[W], xv[W];
+        Vec16<TV>::load(r, i, nt && PS_VEC_NT_RX, z);
+        if (dinv) {
+            double dv[W];
+            ldDiagW<W>(dinv, i, nt && PS_VEC_NT_D, dv);
+#pragma unroll
+            for (int k = 0; k < W; ++k) z[k] = dv[k] * z[k];
+        }
+        Vec16<TV>::load(p, i, nt && PS_VEC_NT_PL, pv);
+        Vec16<TV>::load(x, i, nt && PS_VEC_NT_X, xv);
+#pragma unroll
+        for (int k = 0; k < W; ++k) xv[k] = Vec16<TV>::stored(xv[k] + alpha * pv[k]);
+#pragma unroll
+        for (int k = 0; k < W; ++k) pv[k] = Vec16<TV>::stored(z[k] + beta * pv[k]);
+        Vec16<TV>::store(x, i, nt && PS_VEC_NT_X, xv);
+        Vec16<TV>::store(p, i, nt && PS_VEC_NT_P, pv);
+#pragma unroll
+        for (int k = 0; k < W; ++k) axx += xv[k] * xv[k];
         if (UPP) {
-            double u0, u1;
-            if (uCode) { const uint16_t cc = (nt && PS_VEC_NT_U) ? __builtin_nontemporal_load((const uint16_t*)uCode + i) : ((const uint16_t*)uCode)[i]; u0 = dict[cc & 255]; u1 = dict[cc >> 8]; }
-            else { const double2 uv = ldD2((const double2*)uInv + i, nt); u0 = uv.x; u1 = uv.y; }
-            aup += u0 * (pv.x * pv.x); aup += u1 * (pv.y * pv.y);
+            double u[W];
+            if (uCode) {
+                const uint32_t cc = ldCodesW<W>(uCode, i, nt && PS_VEC_NT_U);
+#pragma unroll
+                for (int k = 0; k < W; ++k) u[k] = dict[(cc >> (8 * k)) & 255u];
+            } else ldF64W<W>(uInv, i, nt, u);
+#pragma unroll
+            for (int k = 0; k < W; ++k) aup += u[k] * (pv[k] * pv[k]);
         }
     }
-    for (int64_t i = 2 * n2 + (int64_t)blockIdx.x * BS + threadIdx.x; i < n; i += (int64_t)gridDim.x * BS) {
-        const double z = dinv ? diagValue(dinv[i]) * r[i] : r[i];
+    for (int64_t i = W * nv + (int64_t)blockIdx.x * BS + threadIdx.x; i < n; i += (int64_t)gridDim.x * BS) {
+        const double z = dinv ? diagValue(dinv[i]) * (double)r[i] : (double)r[i];
         const double pv = p[i];
-        const double xv = x[i] + alpha * pv;
-        const double pn = z + beta * pv;
-        x[i] = xv; p[i] = pn;
+        const double xv = Vec16<TV>::stored((double)x[i] + alpha * pv);
+        const double pn = Vec16<TV>::stored(z + beta * pv);
+        x[i] = (TV)xv; p[i] = (TV)pn;
         axx += xv * xv;
         if (UPP) aup += (uCode ? dict[uCode[i]] : uInv[i]) * (pn * pn);
     }
@@ -339,20 +461,27 @@ __device__ inline void cgUpdateXp(CGScalars* sc, const double* __restrict__ red,
         if (threadIdx.x == 0) uPart[blockIdx.x] = s2;
     }
 }
-__global__ void __launch_bounds__(BS) k_cg_update_xp(CGScalars* sc, const double* __restrict__ red, const double* __restrict__ rPartial, int rCount, int jacobi,
-                                                     int it, const double* __restrict__ r, const diag_t* __restrict__ dinv, double* __restrict__ x,
-                                                     double* __restrict__ p, int64_t n, double* __restrict__ partial) {
+#define PS_CG_XP_PARAMS(TV) CGScalars* sc, const double* __restrict__ red, const double* __restrict__ rPartial, int rCount, int jacobi, int it, const TV* __restrict__ r, \
+                            const diag_t* __restrict__ dinv, TV* __restrict__ x, TV* __restrict__ p, int64_t n, double* __restrict__ partial
+#define PS_CG_XP_U_PARAMS const uint8_t* __restrict__ uCode, const double* __restrict__ uDict, const double* __restrict__ uInv, double* __restrict__ uPart
+__global__ void __launch_bounds__(BS) k_cg_update_xp(PS_CG_XP_PARAMS(double)) {
     cgUpdateXp<false>(sc, red, rPartial, rCount, jacobi, it, r, dinv, x, p, n, partial, nullptr, nullptr, nullptr, nullptr);
 }
-__global__ void __launch_bounds__(BS) k_cg_update_xp_u(CGScalars* sc, const double* __restrict__ red, const double* __restrict__ rPartial, int rCount, int jacobi,
-                                                       int it, const double* __restrict__ r, const diag_t* __restrict__ dinv, double* __restrict__ x,
-                                                       double* __restrict__ p, int64_t n, double* __restrict__ partial,
-                                                       const uint8_t* __restrict__ uCode, const double* __restrict__ uDict, const double* __restrict__ uInv, double* __restrict__ uPart) {
+__global__ void __launch_bounds__(BS) k_cg_update_xp_u(PS_CG_XP_PARAMS(double), PS_CG_XP_U_PARAMS) {
     cgUpdateXp<true>(sc, red, rPartial, rCount, jacobi, it, r, dinv, x, p, n, partial, uCode, uDict, uInv, uPart);
 }
-// partials of sum_j uInv_j p_j^2 (the first search direction of a fused-step solve)
-__global__ void __launch_bounds__(BS) k_uinv_pp(const double* __restrict__ p, const uint8_t* __restrict__ uCode, const double* __restrict__ uDict,
-                                                const double* __restrict__ uInv, int64_t n, double* __restrict__ uPart) {
+__global__ void __launch_bounds__(BS) k_cg_update_xp_f32(PS_CG_XP_PARAMS(float)) {
+    cgUpdateXp<false, float>(sc, red, rPartial, rCount, jacobi, it, r, dinv, x, p, n, partial, nullptr, nullptr, nullptr, nullptr);
+}
+__global__ void __launch_bounds__(BS) k_cg_update_xp_u_f32(PS_CG_XP_PARAMS(float), PS_CG_XP_U_PARAMS) {
+    cgUpdateXp<true, float>(sc, red, rPartial, rCount, jacobi, it, r, dinv, x, p, n, partial, uCode, uDict, uInv, uPart);
+}
+#undef PS_CG_XP_U_PARAMS
+#undef PS_CG_XP_PARAMS
+// partials of sum_j uInv_j p_j^2 (the first search direction of a fused-step solve; TV = float: of a pass of the mixed-precision solve)
+template <class TV>
+__device__ inline void uinvPp(const TV* __restrict__ p, const uint8_t* __restrict__ uCode, const double* __restrict__ uDict,
+                              const double* __restrict__ uInv, int64_t n, double* __restrict__ uPart) {
     __shared__ double dict[256];
     if (uCode) dict[threadIdx.x] = uDict[threadIdx.x];
     __syncthreads();
@@ -364,6 +493,10 @@ __global__ void __launch_bounds__(BS) k_uinv_pp(const double* __restrict__ p, co
     const double s = blockReduceSum(acc);
     if (threadIdx.x == 0) uPart[blockIdx.x] = s;
 }
+__global__ void __launch_bounds__(BS) k_uinv_pp(const double* __restrict__ p, const uint8_t* __restrict__ uCode, const double* __restrict__ uDict,
+                                                const double* __restrict__ uInv, int64_t n, double* __restrict__ uPart) { uinvPp(p, uCode, uDict, uInv, n, uPart); }
+__global__ void __launch_bounds__(BS) k_uinv_pp_f32(const float* __restrict__ p, const uint8_t* __restrict__ uCode, const double* __restrict__ uDict,
+                                                    const double* __restrict__ uInv, int64_t n, double* __restrict__ uPart) { uinvPp(p, uCode, uDict, uInv, n, uPart); }
 
 // ---- four-kernel step across slabs (ps_dist.hpp) ---------------------------------------------------------------------------
 // this rank's share of p.Ap in its factored form and of ||x||^2: out = {sum S + sum T + 1/2 sum U, sum xx}   (one block, fixed order)

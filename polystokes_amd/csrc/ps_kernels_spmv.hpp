@@ -405,21 +405,26 @@ __device__ inline double sumLocal(const double* __restrict__ partial, int count)
     for (int i = threadIdx.x; i < count; i += BS) acc += partial[i];
     return acc;
 }
+// PASS: a pass of the mixed-precision solve (ps_solve.hip: solve, PS_PRECISION_MIXED) — x.x frozen at the pass's start where the pass does not
+// build x itself (sc->xxFix > 0), and the pass also ends once r.r has fallen to sc->rrFloor; the fp64 kernels read neither field
+template <bool PASS = false>
 __device__ inline bool stopTest(CGScalars* sc, double xx, int iterIndex, bool writer) {
     const double rr = sc->rr;
+    if (PASS && sc->xxFix > 0.) xx = sc->xxFix;
     double rre = rr;                                   // pcg.h:319-325
     if (rr / xx < rre) rre = rr / xx;
-    const bool fire = rre < sc->tol2;
+    const bool fire = rre < sc->tol2 || (PASS && rr < sc->rrFloor);
     if (writer) { sc->xx = xx; sc->rre = rre; if (fire) { sc->done = 1; sc->iter = iterIndex; } }
     return fire;
 }
 // Prologue of the fused residual update, as k_cg_update_r: [stop test of iteration it-1], alpha = rsold / p.Ap — identical in every
 // workgroup (each sums the partials itself, in the same order), workgroup 0 records the scalars.  reduced: the sums come all-reduced in
 // fr.red.  Returns false when the stop test fired (same verdict in every workgroup: the kernel returns).
+template <bool PASS = false>
 __device__ __forceinline__ bool fusedPrologue(const FusedR& fr, bool reduced, double& alpha) {
     CGScalars* sc = fr.sc;
     const bool writer = blockIdx.x == 0 && threadIdx.x == 0;
-    if (fr.it > 0 && stopTest(sc, reduced ? fr.red[1] : blockSumAll(sumLocal(fr.xxPart, fr.xxCount)), fr.it - 1, writer)) return false;
+    if (fr.it > 0 && stopTest<PASS>(sc, reduced ? fr.red[1] : blockSumAll(sumLocal(fr.xxPart, fr.xxCount)), fr.it - 1, writer)) return false;
     const double pAp = reduced ? -fr.red[0]
                                : -(blockSumAll(sumLocal(fr.sPart, fr.sCount)) + blockSumAll(sumLocal(fr.tPart, fr.tCount)) + 0.5 * blockSumAll(sumLocal(fr.uPart, fr.uCount)));
     alpha = sc->rsold2[fr.it & 1] / pAp;               // pcg.h:314
@@ -447,6 +452,7 @@ template <int CAUX, int VAUX> __device__ inline DiagRow rowDiagLoad(bool coded, 
 }
 __device__ inline double rowDiagValue(bool coded, const double* dict, const DiagRow& d) { return coded ? RowDiag<true>::value(dict, d) : RowDiag<false>::value(dict, d); }
 
+constexpr unsigned ROW_NONE = 0x1fffffffu;   // row index of an idle lane: beyond any array (rows * 8 < 4 GiB), positive as an int
 // ---- row epilogues
 // S: t[row] = (row < nA ? dt McInv[row] : 1) s (MODE 0; MODE 1: s), stAcc += s t on the ACTIVE rows — their share of x . A x = sum s_f t_f
 // (idle lanes: row = ROW_NONE is past nA and past the output buffer: the store is dropped)
@@ -481,34 +487,35 @@ __device__ __forceinline__ double chebRowFinish(const ChebArgs& cheb, const Cheb
 //   ranged: rows outside [fr.ownLo, fr.ownHi) are not this rank's (false: every live row is);  halo: such a row's y goes to fr.yOut;
 //   cz: the Chebyshev polynomial's first term z_1 = dinv r / theta -> fr.cz (elements TZ), r.z formed with z_1 AS STORED; without it
 //   r.z is that of the Jacobi diagonal fr.dinvF (null: none asked for) — never both (FusedR).
+//   TV: element type r is stored in (float: the mixed-precision solve — fr.r then points at floats, and r.r / r.z are formed with r AS STORED)
 struct FusedBufs { __amdgpu_buffer_rsrc_t r, dinv, dinvC, cz, y; };
-template <class TZ>
+template <class TZ, class TV = double>
 __device__ inline FusedBufs fusedBufs(const FusedR& fr, int rows, bool on, bool halo, bool cz) {
-    return FusedBufs{bufRsrc(fr.r, on ? (size_t)rows * 8 : 0), bufRsrc(fr.dinvF, (on && !cz && fr.dinvF) ? (size_t)rows * sizeof(diag_t) : 0),
+    return FusedBufs{bufRsrc(fr.r, on ? (size_t)rows * sizeof(TV) : 0), bufRsrc(fr.dinvF, (on && !cz && fr.dinvF) ? (size_t)rows * sizeof(diag_t) : 0),
                      bufRsrc(fr.dinvC, (on && cz) ? (size_t)rows * sizeof(diag_t) : 0), bufRsrc(fr.cz, (on && cz) ? (size_t)rows * sizeof(TZ) : 0),
                      bufRsrc(fr.yOut, (on && halo) ? (size_t)rows * 8 : 0)};
 }
 struct FusedRow { double cr, ci; float fd; };   // r, the polynomial's diagonal (cz), the Jacobi diagonal (1: identity) of the row
-template <bool NT>
+template <bool NT, class TV = double>
 __device__ __forceinline__ FusedRow fusedLoads(const FusedR& fr, const FusedBufs& B, unsigned row, bool cz) {
-    FusedRow L{__builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(B.r, (int)(row * 8u), 0, NT ? PS_EPI_AUX : 0)), 0., 1.f};
+    FusedRow L{VecIO<TV>::template loadEpi<NT>(B.r, row), 0., 1.f};
     if (cz) L.ci = (double)bufLoadDiag<NT>(B.dinvC, row);
     else if (fr.dinvF) L.fd = bufLoadDiag<NT>(B.dinv, row);
     return L;
 }
-template <bool NT, class TZ>
+template <bool NT, class TZ, class TV = double>
 __device__ __forceinline__ void fusedRowFinish(const FusedR& fr, const FusedBufs& B, unsigned row, bool live, bool ranged, bool halo, bool cz, double alpha, double y,
                                                const FusedRow& L, double& dacc, double& dacc2) {
     const bool mine = ranged ? ((int)row >= fr.ownLo && (int)row < fr.ownHi) : live;   // (idle lanes: ROW_NONE is beyond ownHi)
     if (halo) bufStoreF64nt<NT>(B.y, (!mine && live) ? row * 8u : 0xfffffff8u, y);    // a neighbour's row: its share of A p
-    const double rv = mine ? L.cr - alpha * y : 0.;                                   // pcg.h:316
+    const double rv = mine ? VecIO<TV>::stored(L.cr - alpha * y) : 0.;                // pcg.h:316
     dacc += rv * rv;
     if (cz) {                                                                          // k_cheb_first on this row
         const double v = VecIO<TZ>::stored(L.ci * rv * fr.invTheta);
         VecIO<TZ>::template store<NT>(B.cz, row, v);
         dacc2 += rv * v;
     } else if (fr.dinvF) dacc2 += (!ranged || mine) ? rv * ((double)L.fd * rv) : 0.;   // (the diagonal of a halo row is not this rank's: may be anything)
-    bufStoreF64nt<NT>(B.r, (!ranged || mine) ? row * 8u : 0xfffffff8u, rv);
+    VecIO<TV>::template store<NT>(B.r, (!ranged || mine) ? row : ROW_NONE, rv);
 }
 // the workgroup's partials of r.r at fr.rPart[block], of r.z at fr.rPart[stride + block]
 __device__ __forceinline__ void fusedPartials(const FusedR& fr, double dacc, double dacc2, bool cz, int stride) {
@@ -550,7 +557,6 @@ __device__ __forceinline__ void stRowFinish(const StBufs& B, const ChebArgs& che
 // chunk whose run this is (== z unless the run is shared: the per-row BYTE streams — lengths, value-set codes — are read there too)
 struct Chunk { int q0, q1, row0, rows, src; };
 __host__ __device__ inline Chunk decodeChunk(int4 v) { return Chunk{v.x, v.x + (v.y & 0xffff), v.z, (int)((unsigned)v.y >> 16), v.w}; }
-constexpr unsigned ROW_NONE = 0x1fffffffu;   // row index of an idle lane: beyond any array (rows * 8 < 4 GiB), positive as an int
 // The loop of k_spmv_S_pipe / k_spmv_St_pipe: gathers of the current chunk, prefetch of the next, products to LDS (entry e of the chunk at
 // prod[(e & 3) * PL + (e >> 2)]: conflict-free writes), row offsets from the length bytes (wave scans + 4 wave totals).
 // loads(row, srow): the kernel issues the per-row loads of its epilogue (before the gathers);  finish(row, live, loaded, s): the row's sum
@@ -1004,32 +1010,44 @@ __global__ void __launch_bounds__(BS) k_spmv_S_ell2u(PS_S_ELL2_PARAMS) { spmvSEl
 // to a cut and the whole-rank launch of the sequential exchange now run two units per wave like the owned-rows launch)
 // UC (r06): the stress diagonal uInv comes coded (true) or, when it takes more than 256 values — a viscosity FIELD —, as the fp64 array itself, passed
 // in uCode's place (RowDiag; until r06 such scenes ran the one-unit kernels and the fp64 polynomial)
-template <int POL, bool CZ, bool DIST, bool LIST, class TZ = double, bool HALO = false, bool UC = true>
+// TV: element type of the Krylov vectors the kernel gathers and streams — t, xin (p) and fr.r.  float: a pass of the mixed-precision solve
+// (ps_solve.hip: PS_PRECISION_MIXED; the pointers then point at floats, r.r and r.z are formed from r AS STORED, and the stop test is the pass's)
+// AP (TV = float only): the plain product of the five-kernel step instead of the residual update — no prologue, (A p)[row] -> fr.r as TV,
+// the workgroup's partial of p . A p -> fr.rPart[block]; of fr only r and rPart are read
+template <int POL, bool CZ, bool DIST, bool LIST, class TZ = double, bool HALO = false, bool UC = true, class TV = double, bool AP = false>
 __global__ void __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(6, 6))) k_spmv_St_ell2(const uint16_t* __restrict__ ecol, const int8_t* __restrict__ ecode, unsigned colBytes, unsigned codeBytes,
                                                      const int32_t* __restrict__ winBase, const int4* __restrict__ echunk, double scale,
-                                                     const double* __restrict__ t, int cols, int rows, const double* __restrict__ xin,
+                                                     const TV* __restrict__ t, int cols, int rows, const TV* __restrict__ xin,
                                                      const int* __restrict__ done, int nChunks, const uint8_t* __restrict__ uCode, const double* __restrict__ uDict, FusedR fr,
                                                      const int32_t* __restrict__ list) {
     if (done && *done) return;
-    constexpr bool NT = (POL & 1) != 0, SNT = (POL & 2) != 0;
+    constexpr bool NT = (POL & 1) != 0, SNT = (POL & 2) != 0, PASS = !std::is_same<TV, double>::value;
     static_assert(!HALO || DIST, "halo rows exist on a rank of a decomposition only");
+    static_assert(!AP || (PASS && !CZ && !DIST && !HALO), "the plain product: single-domain passes of the mixed-precision solve only");
     __shared__ double dict[UC ? 256 : 1];
     RowDiag<UC>::fill(dict, uDict);
     double alpha;
-    if (!fusedPrologue(fr, DIST, alpha)) return;
+    if constexpr (AP) alpha = 0.; else if (!fusedPrologue<PASS>(fr, DIST, alpha)) return;
     __syncthreads();
-    const __amdgpu_buffer_rsrc_t rCol = bufRsrc(ecol, colBytes), rCode = bufRsrc(ecode, codeBytes), rT = bufRsrc(t, (size_t)cols * 8),
-                                 rE0 = bufRsrc(xin, (size_t)rows * 8), rUc = bufRsrc(uCode, UC ? (size_t)rows : (size_t)rows * 8);
-    const FusedBufs B = fusedBufs<TZ>(fr, rows, true, HALO, CZ);
+    const __amdgpu_buffer_rsrc_t rCol = bufRsrc(ecol, colBytes), rCode = bufRsrc(ecode, codeBytes), rT = bufRsrc(t, (size_t)cols * sizeof(TV)),
+                                 rE0 = bufRsrc(xin, (size_t)rows * sizeof(TV)), rUc = bufRsrc(uCode, UC ? (size_t)rows : (size_t)rows * 8);
+    const FusedBufs B = fusedBufs<TZ, TV>(fr, rows, true, HALO, CZ);
     struct Loaded { double e; DiagRow u; FusedRow f; };
     double dacc = 0., dacc2 = 0.;
-    ell2Loop<SNT, LIST, double>(rCol, rCode, rT, winBase, echunk, scale, nChunks, list,
+    ell2Loop<SNT, LIST, TV>(rCol, rCode, rT, winBase, echunk, scale, nChunks, list,
         [&](unsigned row) PS_INLINE_LAMBDA {
-            return Loaded{bufLoadF64epi<NT>(rE0, row * 8u), RowDiag<UC>::template load<NT ? (UC ? PS_UC_AUX : PS_EPI_AUX) : 0>(rUc, row, row), fusedLoads<NT>(fr, B, row, CZ)};
+            return Loaded{VecIO<TV>::template loadEpi<NT>(rE0, row), RowDiag<UC>::template load<NT ? (UC ? PS_UC_AUX : PS_EPI_AUX) : 0>(rUc, row, row),
+                          AP ? FusedRow{0., 0., 1.f} : fusedLoads<NT, TV>(fr, B, row, CZ)};
         },
         [&](unsigned row, bool live, const Loaded& L, double s) PS_INLINE_LAMBDA {
-            fusedRowFinish<NT, TZ>(fr, B, row, live, HALO, HALO, CZ, alpha, stRowY(s, RowDiag<UC>::value(dict, L.u), L.e), L.f, dacc, dacc2);
+            const double y = stRowY(s, RowDiag<UC>::value(dict, L.u), L.e);
+            if constexpr (AP) { dacc += L.e * y; VecIO<TV>::template store<NT>(B.r, row, y); }   // (idle lanes: e = 0, the store is dropped)
+            else fusedRowFinish<NT, TZ, TV>(fr, B, row, live, HALO, HALO, CZ, alpha, y, L.f, dacc, dacc2);
         });
+    if constexpr (AP) {
+        const double bs = blockReduceSum(dacc);
+        if (threadIdx.x == 0) fr.rPart[blockIdx.x] = bs;
+    } else
     fusedPartials(fr, dacc, dacc2, CZ, (DIST && fr.rStride > 0) ? fr.rStride : (int)gridDim.x);
 }
 

@@ -19,7 +19,9 @@
 //   ps_kernels_cg.hpp    : k_cg_update_r / k_cg_update_xp (the PCG step of pcg_external_matrix_A, lib/include/pcg.h:268-340,
 //                          with the scalar reductions and the stop rule folded in; scalars stay on the device), the legacy
 //                          k_cg_update_xr / _p / scal* used by the exported-system path, BiCGStab helpers, Jacobi diagonal,
-//                          velocity recovery / write-back.
+//                          velocity recovery / write-back.  The step kernels' bodies take the element type of the Krylov vectors: their _f32 forms
+//                          and k_cg_init_pass / k_cg_scal0_pass / k_cg_check_pass / k_cg_end_pass run the passes of the mixed-precision solve
+//                          (ps_set_solve_precision: fp32 d, p, r, A p, t around the fp64 x; ps_context::solve).
 //   this file            : the launch dispatch (Launch: planS / planSt choose the kernel and grid of a product, one launcher per kernel family runs it),
 //                          ps_context::applyOperator / assemble / solve / recover.
 //   ps_dist.hpp          : the z-slab distributed solve (RCCL or in-process ranks) and its C ABI.
@@ -86,6 +88,7 @@ struct Launch {
     const int32_t* stList = nullptr; int nStList = 0;
     bool stOwnedOnly = false;        // the St chunk list holds owned rows only (the decomposition's launch under the exchange): FX bit 2
     bool cz32 = false;   // MODE 3 with the polynomial's first term: fr.cz points at floats (k_spmv_St_ell2<.., float>)
+    bool v32 = false;    // a pass of the mixed-precision solve: the Krylov vectors and the face-row vector are fp32 (spmvS32 / tiles32 / spmvSt32 with the step's partials)
     bool ntSpmv = true;   // cache policy of the pipelined kernels' streams (ps_context::ntLevel >= 1)
     int pipeGrid;   // 0: one-shot kernels; >0: persistent software-pipelined kernels with this many blocks
     int stGrid = 0; // > 0: the St kernel's own cap
@@ -179,6 +182,14 @@ struct Launch {
     bool cheb32Ok() const {
         const Plan s = planS(0, false, 0), t = planSt(2, false, 0, false, FusedR{});
         return s.run && s.kernel == ELL2 && s.xcd > 0 && t.run && t.kernel == ELL2C && t.xcd > 0 && (c->regionCount == 0 || tileFused());
+    }
+
+    // ---- the passes of the mixed-precision solve (ps_set_solve_precision): p, r, A p and the face-row vector stored as fp32, on the same kernels
+    // as the fp32 polynomial — the pair-walking two-unit S kernel and the fused tile apply (cheb32Ok's condition on them) — and on the two-unit
+    // St kernel of the plain single-domain step, which carries the residual update (four-kernel step) or writes A p (five-kernel step)
+    bool mixedOk() const {
+        const Plan s = planS(0, false, 0), t = planSt(3, false, 0, false, FusedR{});
+        return s.run && s.kernel == ELL2 && s.xcd > 0 && t.run && t.kernel == ELL2 && t.xcd > 0 && (c->regionCount == 0 || tileFused());
     }
 
     // ---- the walk of a launch (array "launchWalk"): the first launch of each slot (0: S, 1 + mode: St) in a recording solve writes
@@ -298,11 +309,24 @@ struct Launch {
         const Plan p = planS(0, false, 0);
         if (p.kernel != ELL2) throw Error("internal: single-precision S apply without the two-unit kernel");
         noteWalk(0, p);
-        sEll2(p, x, out, (double*)nullptr, (const int32_t*)nullptr);
+        sEll2(p, x, out, v32 ? sPart : (double*)nullptr, (const int32_t*)nullptr);
     }
     void tiles32(float* ts) const {   // the fused apply only, at the default threads per region
         if (c->regionCount == 0) return;
-        withAtLeast<256, 128, 64>(tileThreads(), [&](auto TB) { tileApply<0, float>(TB, ts + nA, (double*)nullptr); });
+        withAtLeast<256, 128, 64>(tileThreads(), [&](auto TB) { tileApply<0, float>(TB, ts + nA, v32 ? wvPart : (double*)nullptr); });
+    }
+    // the St product of a pass of the mixed-precision solve (mixedOk): t, p and fr.r point at floats.  ap: the plain product — A p -> fr.r,
+    // the partials of p . A p -> fr.rPart (five-kernel step); otherwise the residual update of the four-kernel step.  Returns the workgroups.
+    int spmvSt32(bool ap, const float* t, const float* xin, const FusedR& fr) const {
+        const Plan p = planSt(3, false, 0, false, FusedR{});
+        if (p.kernel != ELL2) throw Error("internal: single-precision St product without the two-unit kernel");
+        noteWalk(ap ? 1 : 4, p);
+        const ps::DevCSR& M = c->St;
+        const uint8_t* uArg = c->uCoded ? (const uint8_t*)c->uCode.p : (const uint8_t*)c->uInv.p;
+        withBool(c->uCoded, [&](auto UC) { withPolicy(p.pol, [&](auto POL) { withBool(ap, [&](auto AP) {
+            ellLaunch(k_spmv_St_ell2<POL, false, false, false, double, false, UC, float, AP>, p, M, t, (int)M.cols, rowsSt, xin, done, p.nChunks, uArg, c->uDict.p, fr, (const int32_t*)nullptr);
+        }); }); });
+        return p.grid;
     }
     int spmvSt2c32(const float* t, const float* xin, float* out, double* partial, const ChebArgs& ca) const {   // returns the number of partials written
         const Plan p = planSt(2, false, 0, false, FusedR{});
@@ -438,6 +462,10 @@ constexpr int64_t FUSED_STEP_MIN_ROWS = 1200000;   // see solve() (r05: 2 M -> 1
 constexpr int64_t NT_LEVEL1_MIN_ROWS = 4000000, NT_LEVEL2_MIN_ROWS = 10000000;   // see ps_context::ntLevel
 int dotBlocks(int64_t n) { return (int)std::min<int64_t>(VGRID, std::max<int64_t>(1, (n + BS - 1) / BS)); }
 constexpr int CG_BATCH = 25;   // PCG iterations between two stop tests on the host (ps_context::solve, Dist::solve)
+// The mixed-precision solve (ps_context::solve): a pass ends at the latest when r.r has fallen to MIXED_PASS_REDUCTION^2 of the true r.r it
+// started from (fp32 carries 2^-24: about three digits are left for drift; profiles/mixed_precision.md), and there are at most MIXED_MAX_PASSES
+constexpr double MIXED_PASS_REDUCTION = 1e-4;
+constexpr int MIXED_MAX_PASSES = 8;
 
 double chebRatio() { static const double r = PS_ENV("PS_CHEB_RATIO") ? atof(PS_ENV("PS_CHEB_RATIO")) : PS_CHEB_INTERVAL_RATIO; return r; }   // lmax / lmin (PS_CHEB_RATIO: experiments only — the oracle uses the constant)
 // The Chebyshev iteration on [lmax / chebRatio(), lmax] (ps_context::chebyshevApply, Dist::chebyshevDist): z_1 = D^-1 r / theta, then
@@ -679,6 +707,8 @@ int ps_context::solve() {
     const double tol = P.tolerance;
     usedBiCGStab = 0;
     interrupted = false;
+    solvePrecisionUsedHost = 0;
+    passIters.clear();
     if (P.solverType == PS_EIGEN) return solveEigenCG();
     if (P.solverType != PS_PCG_MATRIX_VECTOR_PRODUCTS) { err = "Unsupported Solver."; return PS_UNSUPPORTED_SOLVER; }
     std::fill(std::begin(launchWalkHost), std::end(launchWalkHost), 0);
@@ -735,8 +765,88 @@ int ps_context::solve() {
     HIP_CHECK(hipMemsetAsync(dotPartials3.p, 0, VGRID * sizeof(double), stream));
     // warm start (ps_set_warm_start): x0 = the carried solution, r0 = b - A x0 (pcg.h:284); from here on the PCG is the same
     // (a Picard pass of ps_set_rheology starts from the last pass's solution the same way)
-    const bool warm = (warmMode == PS_WARM_PREVIOUS_STEP || rheoPass > 0) && gatherWarmStart();
+    bool warm = (warmMode == PS_WARM_PREVIOUS_STEP || rheoPass > 0) && gatherWarmStart();
     warmUsedHost = warm ? 1 : 0;
+    CGScalars h{};
+    int itBase = 0;           // iterations the fp32 passes took: the fp64 loop below gets the rest of the budget
+    bool pcg64 = true;        // false: the passes used the budget up (-> BiCGStab)
+
+    // ---- mixed precision (ps_set_solve_precision; include/polystokes.h, DESIGN.md "Mixed-precision PCG"): x stays fp64; a pass runs the step
+    // below on fp32 vectors (d32 in x's place) for A d = b - A x, then x += d, and the stop rule is evaluated on the fp64 b - A x
+    if (solvePrecisionSet == PS_PRECISION_MIXED && !cheb && !slabEnabled && L.mixedOk()) {
+        solvePrecisionUsedHost = 1;
+        d32.alloc((size_t)n); p32.alloc((size_t)n); r32.alloc((size_t)n); ts32.alloc((size_t)nRows + 1);
+        if (!fused) Ap32.alloc((size_t)n);
+        L.v32 = true;
+        const int vecNT = ntLevel() >= 2 ? 1 : 0;
+        double rrStart = 0.;
+        bool resume64 = false;
+        for (int pass = 0; ; ++pass) {
+            // the true residual of the current x (fp64 operator, as k_cg_init_warm), rounded into the pass's r; its r.r and x.x: the evaluation
+            const bool haveX = warm || pass > 0;
+            if (haveX) applyOperator(x.p, Ap.p, dotPartials.p);
+            hipLaunchKernelGGL(k_cg_init_pass, dim3(vb), dim3(BS), 0, stream, (const double*)b.p, haveX ? (const double*)Ap.p : (const double*)nullptr, (const double*)x.p, dv,
+                               d32.p, r32.p, p32.p, n, dotPartials.p);
+            hipLaunchKernelGGL(k_cg_scal0_pass, dim3(1), dim3(BS), 0, stream, sc, (const double*)dotPartials.p, vb, tol, maxit, vecNT, MIXED_PASS_REDUCTION * MIXED_PASS_REDUCTION, haveX ? 1 : 0);
+            if (fused) hipLaunchKernelGGL(k_uinv_pp_f32, dim3(vb), dim3(BS), 0, stream, (const float*)p32.p, ucode, (const double*)uDict.p, (const double*)uInv.p, n, fU);
+            HIP_CHECK(hipMemcpyAsync(&h, sc, sizeof(h), hipMemcpyDeviceToHost, stream));
+            HIP_CHECK(hipStreamSynchronize(stream));
+            const double trueRR = h.rr;
+            solveError = std::sqrt(h.rre);
+            trueResidualHost = solveError;
+            if (pass > 0 && h.rre < tol * tol) { solveIterations = itBase; return PS_SUCCESS; }
+            if (h.done) {   // r = 0 exactly (b == 0: as the fp64 solve, x = 0)
+                if (!haveX) HIP_CHECK(hipMemsetAsync(x.p, 0, (size_t)n * sizeof(double), stream));
+                solveIterations = itBase;
+                return PS_SUCCESS;
+            }
+            // stagnation: the pass did not halve the true ||r|| (the floor of fp32), or the passes are used up -> fp64 PCG from this x
+            if (pass > 0 && (!(trueRR < 0.25 * rrStart) || pass == MIXED_MAX_PASSES)) { resume64 = true; break; }
+            if (itBase >= maxit) { pcg64 = false; break; }
+            rrStart = trueRR;
+            const int budget = maxit - itBase;
+            int it = 0;
+            bool finished = false;
+            while (it < budget && !finished) {
+                const int upto = std::min(budget, it + CG_BATCH);
+                for (; it < upto; ++it) {
+                    L.spmvS32(p32.p, ts32.p);
+                    L.tiles32(ts32.p);
+                    if (fused) {
+                        const FusedR fr{sc, fS, sBlocks, fT, (int)regionCount, fU, vb, dotPartials3.p, vb, it, (double*)r32.p, dv, fR, nullptr, 0., nullptr, nullptr, 0, (int)n, nullptr};
+                        L.spmvSt32(false, ts32.p, p32.p, fr);
+                        hipLaunchKernelGGL(k_cg_update_xp_u_f32, dim3(vb), dim3(BS), 0, stream, sc, (const double*)nullptr, (const double*)fR, stBF, dv ? 1 : 0, it, (const float*)r32.p, dv, d32.p,
+                                           p32.p, n, dotPartials3.p, ucode, (const double*)uDict.p, (const double*)uInv.p, fU);
+                        continue;
+                    }
+                    FusedR fr{};
+                    fr.r = (double*)Ap32.p; fr.rPart = dotPartials.p;
+                    const int pApCount = L.spmvSt32(true, ts32.p, p32.p, fr);
+                    hipLaunchKernelGGL(k_cg_update_r_f32, dim3(vb), dim3(BS), 0, stream, sc, (const double*)nullptr, (const double*)dotPartials.p, pApCount, (const double*)dotPartials3.p, vb, it,
+                                       (const float*)Ap32.p, dv, r32.p, n, dotPartialsR.p);
+                    hipLaunchKernelGGL(k_cg_update_xp_f32, dim3(vb), dim3(BS), 0, stream, sc, (const double*)nullptr, (const double*)dotPartialsR.p, vb, dv ? 1 : 0, it, (const float*)r32.p, dv,
+                                       d32.p, p32.p, n, dotPartials3.p);
+                }
+                hipLaunchKernelGGL(k_cg_check_pass, dim3(1), dim3(BS), 0, stream, sc, (const double*)dotPartials3.p, vb, it - 1);
+                HIP_CHECK(hipMemcpyAsync(&h, sc, sizeof(h), hipMemcpyDeviceToHost, stream));
+                HIP_CHECK(hipStreamSynchronize(stream));
+                if (h.done) finished = true;
+                if (!finished && interruptCb && interruptCb(interruptUser)) { interrupted = true; break; }
+            }
+            const int ran = h.done ? h.iter + 1 : it;   // the iterations whose update d holds
+            passIters.push_back(ran);
+            itBase += ran;
+            if (interrupted) { solveIterations = itBase; return PS_INCOMPLETE; }
+            hipLaunchKernelGGL(k_cg_end_pass, dim3(vb), dim3(BS), 0, stream, (const float*)d32.p, x.p, n, haveX ? 0 : 1);
+            if (!h.done) { pcg64 = false; break; }      // the budget ran out inside the pass
+        }
+        L.v32 = false;
+        if (resume64) { solvePrecisionUsedHost = 2; warm = true; }
+        HIP_CHECK(hipMemsetAsync(dotPartials3.p, 0, VGRID * sizeof(double), stream));
+    }
+    const int budget = maxit - itBase;
+    if (!pcg64) { h = CGScalars{}; }
+    else {
     if (warm) {
         applyOperator(x.p, Ap.p, dotPartials.p);
         hipLaunchKernelGGL(k_cg_init_warm, dim3(vb), dim3(BS), 0, stream, (const double*)b.p, (const double*)Ap.p, dv, r.p, pvec.p, n, dotPartials.p);
@@ -755,11 +865,10 @@ int ps_context::solve() {
     hipLaunchKernelGGL(k_cg_scal0, dim3(1), dim3(BS), 0, stream, sc, dotPartials.p, vb, tol, maxit, ntLevel() >= 2 ? 1 : 0);
     // the first direction's share of p.Ap on the diagonal
     if (fused) hipLaunchKernelGGL(k_uinv_pp, dim3(vb), dim3(BS), 0, stream, (const double*)pvec.p, ucode, (const double*)uDict.p, (const double*)uInv.p, n, fU);
-    CGScalars h{};
     int it = 0;
     bool finished = false;
-    while (it < maxit && !finished) {
-        const int upto = std::min(maxit, it + CG_BATCH);
+    while (it < budget && !finished) {
+        const int upto = std::min(budget, it + CG_BATCH);
         for (; it < upto; ++it) {
             L.spmvS(0, pvec.p, ts.p);
             L.tiles(0, ts.p);
@@ -814,9 +923,11 @@ int ps_context::solve() {
         if (h.done) finished = true;
         if (!finished && interruptCb && interruptCb(interruptUser)) { interrupted = true; break; }
     }
-    if (interrupted) { solveIterations = it; solveError = std::sqrt(h.rre); return PS_INCOMPLETE; }
-    solveIterations = h.done ? h.iter : maxit;
-    solveError = std::sqrt(h.rre);
+    if (interrupted) { solveIterations = itBase + it; solveError = std::sqrt(h.rre); return PS_INCOMPLETE; }
+    }
+    solveIterations = h.done ? itBase + h.iter : maxit;
+    if (pcg64) solveError = std::sqrt(h.rre);
+    if (solvePrecisionUsedHost == 2) trueResidualHost = solveError;   // (the fp64 recurrence's value, as any fp64 solve reports)
 
     if (solveIterations == maxit) {
         usedBiCGStab = 1;          // the BiCGStab fallback
