@@ -329,6 +329,46 @@ int32_t ps_set_solve_precision(ps_context* ctx, int32_t mode);
 int32_t polystokes_step(ps_context* ctx, const ps_params* p, const ps_fields_in* in,
                         ps_fields_out* out, ps_stats* stats);
 
+/* Device-resident callers (extension): the five calls above that move SIM fields, on arrays that already live on the context's GPU.
+ * The structs are the ones of the host calls; every non-null field pointer in them is device memory of the context's device, while the
+ * scalars, nx / ny / nz and orig are read on the host as before.  The host entry points are unchanged.
+ *
+ * layout says how EVERY field of the call is stored.  For a field whose sample grid has the extents (d0, d1, d2) along x, y, z (the table at
+ * the top of this file), sample (i, j, k) is the float at
+ *   PS_LAYOUT_X_FASTEST (0):  i + d0*(j + d1*k)    the rule of the host calls
+ *   PS_LAYOUT_Z_FASTEST (1):  k + d2*(j + d1*i)    a C-contiguous array indexed [i][j][k] (a torch or numpy tensor of shape (d0, d1, d2))
+ * Both are dense; general strides, other element types and streams under graph capture are not supported.
+ *
+ * stream is the caller's hipStream_t (NULL: the default stream).  The library never runs its own work on it; it orders its own stream
+ * against it with events.  An upload makes the context's stream wait for everything queued on `stream` before the call, so inputs written
+ * by kernels or copies queued there are seen; it returns with the inputs consumed (the caller may overwrite them) and, like the host upload,
+ * with the host synchronised.  A download first waits likewise for what `stream` holds, runs on the context's stream, makes `stream` wait
+ * for it and returns WITHOUT synchronising the host: work queued on `stream` after the call sees the outputs, and a host reader synchronises
+ * `stream` first.  out->vel[a] may alias in->vel[a].  Pointers need 4-byte alignment only (a tensor view with a storage offset is fine).
+ *
+ * ps_upload_fields_device leaves the context in the state ps_upload_fields leaves it in for the same values (same buffers byte for byte, same
+ * uniform-viscosity shortcut, density field dropped, decomposition dropped) and reports the same errors for the host-side checks;
+ * slab / brick ranks and ps_group_rank contexts take it like the host upload, ps_set_slab / ps_set_brick follow it.
+ * ps_upload_density_field_device follows ps_upload_density_field: a non-finite value is PS_INVALID with "non-finite value at cell N", N the
+ * smallest such index in x-fastest numbering whatever the layout; a constant field runs the scalar path at its clamped value; the same clamp
+ * errors; NULL drops the field.  ps_step_device_fields is polystokes_step: upload, the step (with the Picard passes of ps_set_rheology),
+ * download, the three export flags.  ps_download_solution_fields_device writes the grids of ps_download_solution_fields.
+ *
+ * Refusals: PS_INVALID with the reason in ps_last_error, nothing read through any pointer, the context unchanged and usable:
+ *   - a layout other than 0 or 1;
+ *   - a required field that is null (the messages of ps_upload_fields: "Surface field is missing." ...);
+ *   - a pointer that is not 4-byte aligned;
+ *   - a pointer that hipPointerGetAttributes does not report as device memory of the context's device: host, pinned host, managed and
+ *     other-device memory are all refused;
+ *   - an allocation that ends before the field does (hipMemGetAddressRange). */
+enum ps_field_layout { PS_LAYOUT_X_FASTEST = 0, PS_LAYOUT_Z_FASTEST = 1 };
+int32_t ps_upload_fields_device(ps_context* ctx, const ps_params* p, const ps_fields_in* in, int32_t layout, void* stream);
+int32_t ps_upload_density_field_device(ps_context* ctx, const float* density, int32_t layout, void* stream);
+int32_t ps_download_fields_device(ps_context* ctx, const ps_fields_out* out, int32_t layout, void* stream);
+int32_t ps_download_solution_fields_device(ps_context* ctx, const ps_solution_out* out, int32_t layout, void* stream);
+int32_t ps_step_device_fields(ps_context* ctx, const ps_params* p, const ps_fields_in* in, const ps_fields_out* out,
+                              ps_stats* stats, int32_t layout, void* stream);
+
 /* y = A x for host vectors of length nPressures+nStresses:
  * ApplyPressureStressMatrix::apply (lib/include/ApplyPressureStressMatrix.h:102-184). */
 int32_t ps_apply_operator(ps_context* ctx, const double* x, double* y);

@@ -27,6 +27,8 @@ EXPORTED_SYMBOLS = [
     "ps_group_create", "ps_group_destroy", "ps_group_rank", "ps_group_step",
     "ps_set_warm_start", "ps_download_solution_fields", "ps_upload_density_field", "ps_set_surface_tension",
     "ps_set_solid_boundary", "ps_set_rheology", "ps_set_solve_precision",
+    "ps_upload_fields_device", "ps_upload_density_field_device", "ps_download_fields_device", "ps_download_solution_fields_device",
+    "ps_step_device_fields",
 ]
 
 
@@ -122,8 +124,97 @@ def lib():
         L.ps_set_rheology.restype = C.c_int32
         L.ps_set_solve_precision.argtypes = [C.c_void_p, C.c_int32]
         L.ps_set_solve_precision.restype = C.c_int32
+        L.ps_upload_fields_device.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(FieldsIn), C.c_int32, C.c_void_p]
+        L.ps_upload_fields_device.restype = C.c_int32
+        L.ps_upload_density_field_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+        L.ps_upload_density_field_device.restype = C.c_int32
+        L.ps_download_fields_device.argtypes = [C.c_void_p, C.POINTER(FieldsOut), C.c_int32, C.c_void_p]
+        L.ps_download_fields_device.restype = C.c_int32
+        L.ps_download_solution_fields_device.argtypes = [C.c_void_p, C.POINTER(_abi.SolutionOut), C.c_int32, C.c_void_p]
+        L.ps_download_solution_fields_device.restype = C.c_int32
+        L.ps_step_device_fields.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(FieldsIn), C.POINTER(FieldsOut), C.POINTER(Stats),
+                                            C.c_int32, C.c_void_p]
+        L.ps_step_device_fields.restype = C.c_int32
         _lib = L
     return _lib
+
+
+def device_address(a):
+    """The device address behind `a`: None, an int, an object with `.ptr` (_hip.DeviceBuffer), a torch tensor (`data_ptr()`), or anything
+    with `__cuda_array_interface__`."""
+    if a is None:
+        return None
+    if isinstance(a, int):
+        return a
+    if hasattr(a, "ptr"):
+        return int(a.ptr)
+    if hasattr(a, "data_ptr"):
+        return int(a.data_ptr())
+    if hasattr(a, "__cuda_array_interface__"):
+        return int(a.__cuda_array_interface__["data"][0])
+    raise TypeError(f"no device address in {type(a).__name__}")
+
+
+def stream_handle(stream):
+    """None (the default stream), an int, or an object with `.cuda_stream` (a torch stream, _hip.Stream)."""
+    if stream is None:
+        return None
+    return int(stream) if isinstance(stream, int) else int(stream.cuda_stream)
+
+
+def to_layout(a, layout):
+    """A (z, y, x) numpy array as the flat order of `layout`: itself for LAYOUT_X_FASTEST, its [i, j, k]-indexed transpose for LAYOUT_Z_FASTEST."""
+    a = np.asarray(a, dtype=np.float32)
+    return np.ascontiguousarray(a if layout == _abi.LAYOUT_X_FASTEST else a.transpose(2, 1, 0))
+
+
+def from_layout(flat, shape_zyx, layout):
+    """Inverse of to_layout: the flat floats of a field of numpy shape (z, y, x), read back as a (z, y, x) array."""
+    flat = np.asarray(flat).ravel()
+    if layout == _abi.LAYOUT_X_FASTEST:
+        return flat.reshape(shape_zyx)
+    return np.ascontiguousarray(flat.reshape(shape_zyx[::-1]).transpose(2, 1, 0))
+
+
+class DeviceScene:
+    """A Scene whose arrays live on the GPU (_hip.DeviceBuffer) in one layout: what a device-resident caller hands to the ps_*_device calls."""
+
+    def __init__(self, scene, layout=_abi.LAYOUT_X_FASTEST, pad=0):
+        from . import _hip
+        put = lambda a: _hip.DeviceBuffer.from_numpy(to_layout(a, layout), pad)
+        self.layout, self.host = layout, scene
+        for k in ("nx", "ny", "nz", "dx", "dt", "density", "name", "surface_tension"):
+            setattr(self, k, getattr(scene, k))
+        self.vel = [put(a) for a in scene.vel]
+        self.collisionvel = [put(a) for a in scene.collisionvel]
+        self.surface, self.collision, self.viscosity = put(scene.surface), put(scene.collision), put(scene.viscosity)
+        self.weights = None if scene.weights is None else [put(a) for a in scene.weights]
+        self.density_field = None if scene.density_field is None else put(scene.density_field)
+
+
+def device_scene(scene, layout=_abi.LAYOUT_X_FASTEST, pad=0):
+    """`scene` on the device; for LAYOUT_Z_FASTEST each (z, y, x) array is stored as np.ascontiguousarray(a.transpose(2, 1, 0)).
+    pad: spare floats in front of every array inside its allocation (pointers that are only 4-byte aligned)."""
+    return DeviceScene(scene, layout, pad)
+
+
+def fields_in_device(fields):
+    """ps_fields_in from an object with Scene's attributes whose arrays are device arrays (see device_address)."""
+    fi = FieldsIn()
+    fi.nx, fi.ny, fi.nz = fields.nx, fields.ny, fields.nz
+    fi.dx, fi.dt = fields.dx, fields.dt
+    fi.orig[0] = fi.orig[1] = fi.orig[2] = 0.0
+    fi.density = fields.density
+    cv = getattr(fields, "collisionvel", None)
+    for a in range(3):
+        fi.vel[a] = device_address(fields.vel[a])
+        fi.collisionvel[a] = device_address(cv[a]) if cv is not None else None
+    fi.surface, fi.collision, fi.viscosity = (device_address(fields.surface), device_address(fields.collision),
+                                              device_address(fields.viscosity))
+    w = getattr(fields, "weights", None)
+    for i in range(14):
+        fi.weights[i] = device_address(w[i]) if w is not None else None
+    return fi
 
 
 _DT = {(1, "i"): np.int8, (4, "i"): np.int32, (4, "f"): np.float32, (8, "f"): np.float64, (4, "u"): np.uint32}
@@ -307,6 +398,65 @@ class Solver:
 
     def last_error(self):
         return self.L.ps_last_error(self.h).decode()
+
+    # ---- device-resident fields (ps_*_device): `fields` carries Scene's attributes with device arrays (device_scene, torch tensors, ...) ----
+    def upload_device(self, params, fields, layout=0, stream=None):
+        """ps_upload_fields_device.  Returns the ps_result (INVALID for a refused call, the reason in last_error()); FAILED raises."""
+        fi = fields_in_device(fields)
+        rc = self._check(self.L.ps_upload_fields_device(self.h, C.byref(params), C.byref(fi), int(layout), stream_handle(stream)),
+                         allow=(1, -2))
+        if rc == 1:
+            self.scene, self.params = fields, params
+            self._scene_surface_tension(fields)
+        return rc
+
+    def upload_density_field_device(self, field, layout=0, stream=None):
+        """ps_upload_density_field_device (None drops the field).  Returns the ps_result, INVALID for a refused field."""
+        return self._check(self.L.ps_upload_density_field_device(self.h, device_address(field), int(layout), stream_handle(stream)),
+                           allow=(1, -2))
+
+    def _device_out(self, out):
+        """(ps_fields_out, vel buffers, valid buffers): `out` = (vel[3], valid[3]) of device arrays (entries may be None), or None to allocate."""
+        from . import _hip
+        sh = _abi.grid_shapes(self.scene.nx, self.scene.ny, self.scene.nz)
+        n = [int(np.prod(sh["face" + a])) for a in "XYZ"]
+        vel, valid = out if out is not None else ([_hip.DeviceBuffer(n[a]) for a in range(3)], [_hip.DeviceBuffer(n[a]) for a in range(3)])
+        fo = FieldsOut()
+        for a in range(3):
+            fo.vel[a], fo.valid[a] = device_address(vel[a]), device_address(valid[a])
+        return fo, vel, valid
+
+    def download_device(self, layout=0, stream=None, out=None):
+        """ps_download_fields_device into `out` (see _device_out).  Returns (rc, vel, valid); the host is NOT synchronised: work queued on
+        `stream` after the call sees the outputs."""
+        fo, vel, valid = self._device_out(out)
+        rc = self._check(self.L.ps_download_fields_device(self.h, C.byref(fo), int(layout), stream_handle(stream)), allow=(1, -2))
+        return rc, vel, valid
+
+    def solution_fields_device(self, layout=0, stream=None, out=None):
+        """ps_download_solution_fields_device: dict of device arrays keyed like solution_fields() (allocated unless `out` gives them)."""
+        from . import _hip
+        sh = _abi.grid_shapes(self.scene.nx, self.scene.ny, self.scene.nz)
+        if out is None:
+            out = {name: _hip.DeviceBuffer(int(np.prod(sh[grid]))) for name, grid in _abi.SOLUTION_FIELDS}
+        so = _abi.SolutionOut()
+        so.pressure = device_address(out.get("pressure"))
+        for a, name in enumerate(("txx", "tyy", "tzz")):
+            so.tauDiag[a] = device_address(out.get(name))
+        for a, name in enumerate(("tyz", "txz", "txy")):
+            so.tauEdge[a] = device_address(out.get(name))
+        self._check(self.L.ps_download_solution_fields_device(self.h, C.byref(so), int(layout), stream_handle(stream)))
+        return out
+
+    def step_device_fields(self, params, fields, layout=0, stream=None, out=None):
+        """ps_step_device_fields: polystokes_step on device arrays.  Returns (rc, vel, valid) (see download_device; INVALID: refused)."""
+        self.scene, self.params = fields, params
+        self._scene_surface_tension(fields)
+        fi = fields_in_device(fields)
+        fo, vel, valid = self._device_out(out)
+        rc = self._check(self.L.ps_step_device_fields(self.h, C.byref(params), C.byref(fi), C.byref(fo), C.byref(self.stats), int(layout),
+                                                      stream_handle(stream)), allow=(0, 1, -2, -3, -4))
+        return rc, vel, valid
 
     def setup(self):
         return self._check(self.L.ps_setup_device(self.h, C.byref(self.stats)))

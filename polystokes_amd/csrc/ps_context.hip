@@ -65,14 +65,19 @@ CellField ps_context::viscSource() const {
 }
 FaceDensity ps_context::densSource() const { return FaceDensity{densField ? density.p : nullptr, rho, densMin, densMax}; }
 
-void ps_context::upload(const ps_params* p, const ps_fields_in* in) {
+const char* ps_context::missingField(const ps_fields_in* in) {
+    if (!in->vel[0] || !in->vel[1] || !in->vel[2]) return "Velocity field is missing.";
+    if (!in->surface) return "Surface field is missing.";
+    if (!in->collision) return "Collision field is missing.";
+    if (!in->viscosity) return "Viscosity field is missing.";
+    return nullptr;
+}
+
+void ps_context::uploadCheck(const ps_params* p, const ps_fields_in* in) const {
     if (!p || !in) throw Error("null params/fields");
     if (in->nx <= 0 || in->ny <= 0 || in->nz <= 0) throw Error("bad resolution");
     if (in->nx > 1022 || in->ny > 1022 || in->nz > 1022) throw Error("resolution above 1022 per axis is not supported");
-    if (!in->vel[0] || !in->vel[1] || !in->vel[2]) throw Error("Velocity field is missing.");
-    if (!in->surface) throw Error("Surface field is missing.");
-    if (!in->collision) throw Error("Collision field is missing.");
-    if (!in->viscosity) throw Error("Viscosity field is missing.");
+    if (const char* m = missingField(in)) throw Error(m);
     if (p->matrixSetup != PS_PRESSURE_STRESS) throw Error("Unsupported matrix setup.");
     // numeric sanity the node's UI ranges guarantee (HDK_PolyStokes.C:88-208); a raw ABI caller gets an error instead of a
     // division by zero in `cell % tileSize` or a non-finite operator
@@ -84,6 +89,9 @@ void ps_context::upload(const ps_params* p, const ps_fields_in* in) {
     if (p->preconditioner != PS_PRE_IDENTITY && p->preconditioner != PS_PRE_DIAGONAL && p->preconditioner != PS_PRE_CHEBYSHEV && p->preconditioner != PS_PRE_CHEBYSHEV_F32)
         throw Error("Unsupported preconditioner.");
     if (p->preconditionerDegree < 0 || p->preconditionerDegree > 64) throw Error("preconditionerDegree must lie in 0..64");
+}
+
+void ps_context::uploadReset(const ps_params* p, const ps_fields_in* in) {
     P = *p;
     // PS_PRE_CHEBYSHEV_F32 is PS_PRE_CHEBYSHEV with permission to keep the polynomial's inner vectors in fp32 where the kernels for it run
     chebInner32Req = p->preconditioner == PS_PRE_CHEBYSHEV_F32;
@@ -93,6 +101,9 @@ void ps_context::upload(const ps_params* p, const ps_fields_in* in) {
     dx = in->dx; invDx = 1. / dx; dt = in->dt; invDt = 1. / dt; rho = (double)in->density;
     rhoScalar = rho; densField = false;   // every upload drops a density field (ps_upload_density_field): it described the previous grid
     HIP_CHECK(hipSetDevice(device));
+}
+
+void ps_context::ingestHost(const ps_fields_in* in) {
     const int64_t nc = g.count(0);
     uploadField(surface, in->surface, nc, stream);
     uploadField(collision, in->collision, nc, stream);
@@ -122,12 +133,22 @@ void ps_context::upload(const ps_params* p, const ps_fields_in* in) {
     for (int q = 0; q < 3; ++q) cellScratch[q].alloc((size_t)nc);
     counters.alloc(CTR_COUNT);
     HIP_CHECK(hipStreamSynchronize(stream));
+}
+
+void ps_context::uploadTail() {
     uploaded = true; isSetup = false; isSolved = false;
     arrays.clear();          // the registered device pointers may have been re-allocated above
     slabEnabled = false;     // a decomposition describes ONE grid: set it again after every upload (ps_set_slab / ps_set_brick)
     deviceShareRows = 0; nXseg[0] = nXseg[1] = 0;
     blockMapOwned = -1;
     gOff[0] = gOff[1] = gOff[2] = 0;
+}
+
+void ps_context::upload(const ps_params* p, const ps_fields_in* in) {
+    uploadCheck(p, in);
+    uploadReset(p, in);
+    ingestHost(in);
+    uploadTail();
 }
 
 // ps_upload_density_field.  A constant field (all values equal) runs the scalar path at its clamped value, as a constant viscosity skips
@@ -612,6 +633,8 @@ void ps_context_destroy(ps_context* c) {
     ps_dist_release(c);   // communicator / sockets first, then the stream they use
     hipStream_t s = c->ownsStream ? c->stream : nullptr;
     if (c->pinnedCounters) (void)hipHostFree(c->pinnedCounters);
+    if (c->pinnedScan) (void)hipHostFree(c->pinnedScan);
+    for (auto& e : c->fieldEv) if (e) (void)hipEventDestroy(e);
     delete c;                              // (releases the context's deferred list, then its buffers)
     ps::releaseDeferred(ps::orphanFrees());
     if (s) (void)hipStreamDestroy(s);
@@ -807,6 +830,89 @@ int32_t polystokes_step(ps_context* c, const ps_params* p, const ps_fields_in* i
             const int rc2 = ps_download_fields(c, out);
             if (rc2 != PS_SUCCESS) return rc2;
         }
+        if (p->exportMatrices && p->exportDataPrefix) ps_export_matrices(c, p->exportDataPrefix);
+        if (p->exportComponentMatrices && p->exportDataPrefix) ps_export_component_matrices(c, p->exportDataPrefix);
+        if (p->exportStats && p->exportDataPrefix) ps_export_stats(c, st, p->exportDataPrefix);
+        return result;
+    })
+}
+
+// ---- device-resident fields: the same calls on GPU arrays in either axis order (ps_fields.hip) ----
+// A refusal (PS_INVALID) is decided before anything of the context changes and before anything is read through a pointer.
+int32_t ps_upload_fields_device(ps_context* c, const ps_params* p, const ps_fields_in* in, int32_t layout, void* stream) {
+    if (!c) return PS_FAILED;
+    PS_TRY(c, {
+        HIP_CHECK(hipSetDevice(c->device));
+        const std::string why = c->refuseFieldsIn(in, layout);
+        if (!why.empty()) { c->err = "ps_upload_fields_device: " + why; return PS_INVALID; }
+        c->upload(p, in, layout, (hipStream_t)stream);
+        return PS_SUCCESS;
+    })
+}
+int32_t ps_upload_density_field_device(ps_context* c, const float* density, int32_t layout, void* stream) {
+    if (!c) return PS_FAILED;
+    PS_TRY(c, {
+        if (!c->uploaded) { c->err = "ps_upload_density_field: call ps_upload_fields first"; return PS_INVALID; }
+        HIP_CHECK(hipSetDevice(c->device));
+        std::string why;
+        if (const char* m = ps_context::layoutRefusal(layout)) why = m;
+        else if (density) why = c->checkDeviceField(density, c->g.count(0), "density");
+        if (!why.empty()) { c->err = "ps_upload_density_field_device: " + why; return PS_INVALID; }
+        why = c->uploadDensityDevice(density, layout, (hipStream_t)stream);
+        if (!why.empty()) { c->err = why; return PS_INVALID; }
+        return PS_SUCCESS;
+    })
+}
+int32_t ps_download_fields_device(ps_context* c, const ps_fields_out* out, int32_t layout, void* stream) {
+    if (!c || !out) return PS_FAILED;
+    PS_TRY(c, {
+        if (!c->uploaded) throw Error("ps_upload_fields has not been called");
+        HIP_CHECK(hipSetDevice(c->device));
+        std::string why;
+        if (const char* m = ps_context::layoutRefusal(layout)) why = m;
+        for (int a = 0; a < 3 && why.empty(); ++a) {
+            if (out->vel[a]) why = c->checkDeviceField(out->vel[a], c->g.count(1 + a), "out vel");
+            if (why.empty() && out->valid[a]) why = c->checkDeviceField(out->valid[a], c->g.count(1 + a), "out valid");
+        }
+        if (!why.empty()) { c->err = "ps_download_fields_device: " + why; return PS_INVALID; }
+        c->downloadDevice(out, layout, (hipStream_t)stream);
+        return PS_SUCCESS;
+    })
+}
+int32_t ps_download_solution_fields_device(ps_context* c, const ps_solution_out* out, int32_t layout, void* stream) {
+    if (!c || !out) return PS_FAILED;
+    PS_TRY(c, {
+        if (c->slabEnabled) throw Error("ps_download_solution_fields is a single-domain call");
+        if (!c->isSetup || !c->isSolved) throw Error("ps_download_solution_fields: no solve since the last setup");
+        HIP_CHECK(hipSetDevice(c->device));
+        const float* dst[7] = {out->pressure, out->tauDiag[0], out->tauDiag[1], out->tauDiag[2], out->tauEdge[0], out->tauEdge[1], out->tauEdge[2]};
+        std::string why;
+        if (const char* m = ps_context::layoutRefusal(layout)) why = m;
+        for (int q = 0; q < 7 && why.empty(); ++q) if (dst[q]) why = c->checkDeviceField(dst[q], c->solutionGridCount(q), "solution grid");
+        if (!why.empty()) { c->err = "ps_download_solution_fields_device: " + why; return PS_INVALID; }
+        c->downloadSolutionDevice(out, layout, (hipStream_t)stream);
+        return PS_SUCCESS;
+    })
+}
+// polystokes_step on device arrays: upload, step, download, the three export flags
+int32_t ps_step_device_fields(ps_context* c, const ps_params* p, const ps_fields_in* in, const ps_fields_out* out, ps_stats* st, int32_t layout,
+                              void* stream) {
+    if (!c) return PS_FAILED;
+    PS_TRY(c, {
+        HIP_CHECK(hipSetDevice(c->device));
+        std::string why = c->refuseFieldsIn(in, layout);
+        if (why.empty() && out && in && in->nx > 0 && in->ny > 0 && in->nz > 0 && in->nx <= 1022 && in->ny <= 1022 && in->nz <= 1022) {
+            const ps::Grid gg{in->nx, in->ny, in->nz, 0};
+            for (int a = 0; a < 3 && why.empty(); ++a) {
+                if (out->vel[a]) why = c->checkDeviceField(out->vel[a], gg.count(1 + a), "out vel");
+                if (why.empty() && out->valid[a]) why = c->checkDeviceField(out->valid[a], gg.count(1 + a), "out valid");
+            }
+        }
+        if (!why.empty()) { c->err = "ps_step_device_fields: " + why; return PS_INVALID; }
+        c->upload(p, in, layout, (hipStream_t)stream);
+        const int result = c->stepWithPasses(st);   // setup + solve (and the Picard passes of ps_set_rheology)
+        c->drainDeferred(true);
+        if (out) c->downloadDevice(out, layout, (hipStream_t)stream);
         if (p->exportMatrices && p->exportDataPrefix) ps_export_matrices(c, p->exportDataPrefix);
         if (p->exportComponentMatrices && p->exportDataPrefix) ps_export_component_matrices(c, p->exportDataPrefix);
         if (p->exportStats && p->exportDataPrefix) ps_export_stats(c, st, p->exportDataPrefix);

@@ -109,6 +109,26 @@ struct FillList {
     void add(int32_t* ptr, int64_t len) { p[count] = ptr; n[count] = len; ++count; }
 };
 
+// Fields moved by ONE launch of k_fields_copy / k_fields_swap_xz (ps_fields.hip): the up to 9 + 14 inputs of an upload, the 6 outputs of a
+// download.  fast / mid / slow: the extents of the SOURCE's fastest, middle (always y) and slowest axis.
+struct FieldTable {
+    static constexpr int MAX = 23;
+    const float* src[MAX]; float* dst[MAX];
+    int32_t fast[MAX], mid[MAX], slow[MAX];
+    int count = 0;
+    // d: the sample grid's extents along x, y, z; srcZFastest: the source is stored k + d.z (j + d.y i), else i + d.x (j + d.y k)
+    void add(const float* s, float* d_, int3 d, bool srcZFastest) {
+        src[count] = s; dst[count] = d_;
+        fast[count] = srcZFastest ? d.z : d.x; mid[count] = d.y; slow[count] = srcZFastest ? d.x : d.z;
+        ++count;
+    }
+    int64_t entries(int q) const { return (int64_t)fast[q] * mid[q] * slow[q]; }
+};
+void launchFieldsCopy(const FieldTable& T, hipStream_t s);      // ps_fields.hip: dst = src, entry by entry
+void launchFieldsSwapXZ(const FieldTable& T, hipStream_t s);    // ... dst = src with the x and z axes exchanged
+enum ScanWord { SCAN_BAD = 0, SCAN_DIFFERS = 1, SCAN_FIRST = 2, SCAN_WORDS = 3 };   // k_field_scan: smallest non-finite index (~0: none), f[i] != f[0] somewhere, bits of f[0]
+void launchFieldScan(const float* f, int64_t n, bool nonFinite, uint32_t* out, hipStream_t s);
+
 struct CellField;     // ps_setup_util.hpp: what the setup kernels sample
 struct FaceDensity;
 
@@ -153,6 +173,32 @@ struct ps_context {
     int32_t densFieldHost = 0;      // array "densityField": the last setup used a non-constant field
     bool uploaded = false, isSetup = false, isSolved = false;
     std::string uploadDensity(const float* field);
+    // Device-resident fields (ps_*_device, ps_fields.hip): the caller's arrays are GPU memory in layout 0 (x fastest) or 1 (z fastest).
+    // An upload is uploadCheck, uploadReset, one of the two ingests, uploadTail; the host path's ingest is the uploadField calls.
+    // fieldEv: [0] recorded on the caller's stream and waited for by ours before we touch its arrays, [1] recorded on ours after a download
+    // and waited for by the caller's (created on first use, destroyed with the context).  fieldScan / pinnedScan: k_field_scan's words and
+    // their page-locked mirror.  fieldScratch: the x-fastest image of a solution grid on its way to a z-fastest destination.
+    hipEvent_t fieldEv[2] = {nullptr, nullptr};
+    ps::DevBuf<uint32_t> fieldScan;
+    uint32_t* pinnedScan = nullptr;
+    ps::DevBuf<float> fieldScratch;
+    void uploadCheck(const ps_params* p, const ps_fields_in* in) const;   // throws; changes nothing
+    static const char* missingField(const ps_fields_in* in);              // the message for a required field that is null, or null
+    void uploadReset(const ps_params* p, const ps_fields_in* in);
+    void ingestHost(const ps_fields_in* in);
+    void ingestDevice(const ps_fields_in* in, int layout, hipStream_t caller);
+    void uploadTail();
+    std::string checkDeviceField(const void* ptr, int64_t count, const char* name) const;   // empty, or why the pointer is refused
+    static const char* layoutRefusal(int layout);                         // the message for a layout that is neither 0 nor 1, or null
+    std::string refuseFieldsIn(const ps_fields_in* in, int layout) const;
+    void waitForCaller(hipStream_t caller);      // our stream waits for everything queued on the caller's so far
+    void releaseToCaller(hipStream_t caller);    // the caller's stream waits for everything queued on ours so far
+    void moveFields(const ps::FieldTable& T, int layout) { if (layout == 0) ps::launchFieldsCopy(T, stream); else ps::launchFieldsSwapXZ(T, stream); }
+    const uint32_t* scanField(const float* f, int64_t n, bool nonFinite);   // k_field_scan + fetch; synchronises the stream
+    void upload(const ps_params* p, const ps_fields_in* in, int layout, hipStream_t caller);   // the device upload
+    std::string uploadDensityDevice(const float* field, int layout, hipStream_t caller);
+    void downloadDevice(const ps_fields_out* out, int layout, hipStream_t caller);
+    void downloadSolutionDevice(const ps_solution_out* out, int layout, hipStream_t caller);
     // Surface tension (ps_set_surface_tension): sigmaSet is the context setting, sigmaUsed the value of the last setup (array "surfaceTension").
     // With sigma > 0 the setup adds the ghost-pressure impulse to rhsA / rhsR (ps_surface.hip); the buffers exist only then.
     double sigmaSet = 0, sigmaUsed = 0;
