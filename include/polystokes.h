@@ -325,6 +325,33 @@ int32_t ps_set_rheology(ps_context* ctx, const ps_rheology* r);
 enum ps_solve_precision { PS_PRECISION_FP64 = 0, PS_PRECISION_MIXED = 1 };
 int32_t ps_set_solve_precision(ps_context* ctx, int32_t mode);
 
+/* Velocity extrapolation (extension; in Houdini the DOP network extrapolates after the node, a device-resident caller has nothing that does).
+ * A context setting like ps_set_solid_boundary: it persists across ps_upload_fields and is read by every later step.  layers = 0 (the default)
+ * is off and launches exactly the kernels of a context that never made the call.  layers = n > 0 carries the written velocity n faces deep
+ * into the faces `valid` marks 0, on the device, right after the write-back.  Per axis a, on the face grid of that axis (the extents at the top
+ * of this file), independently of the other two:
+ *   L[f] = 0 where valid[f] == 1 (SOLID faces included: they hold the collision velocity and are sources like any valid face), -1 elsewhere;
+ *   for k = 1 .. n: every face with L == -1 of whose six grid neighbours (-x, +x, -y, +y, -z, +z, inside the same face grid) at least one has
+ *   0 <= L < k takes the fp32 rounding of sum / count — sum the fp64 sum of those neighbours' fp32 values in that order, starting from 0,
+ *   count their number as a double — and L = k.  Neighbours assigned in the same sweep do not count (a Jacobi sweep: the result does not depend
+ *   on the traversal order).
+ * Faces no sweep reaches keep the input velocity, as without the setting; `valid` is not changed.
+ * It runs after the write-back of every step whose velocity is written — SUCCESS, NOCONVERGE with keepNonConvergedResults, a doSolve = 0
+ * step — in ps_step_device, ps_solve_device, polystokes_step and ps_step_device_fields, and every download returns the extrapolated
+ * velocity.  A step that leaves the velocity alone (interrupted, failed, an unsupported solver, NOCONVERGE without keepNonConvergedResults) runs
+ * none of it: the output is the input, bit for bit.  With the Picard passes of ps_set_rheology it runs after every pass's write-back; the next
+ * pass reads used faces only, which no sweep changes, so the result is the extrapolation of the last pass's output.
+ * Single domain only: slab and brick ranks, in-process groups and TCP / RCCL ranks ignore the setting (a rank's halo faces are not solved
+ * values; the sweeps would need an exchange of their own).  The time is part of stage_ms[PS_STAGE_WRITEBACK].
+ * Memory: one byte per face for L, (nx+1) ny nz + nx (ny+1) nz + nx ny (nz+1) bytes, plus PS_EXTRAPOLATION_MAX_LAYERS int32 counters (256 bytes):
+ * allocated by the first step that runs a layer, released by ps_set_velocity_extrapolation(ctx, 0) (the layer and count arrays go with them).
+ * PS_INVALID (reason "layers outside 0..64" in ps_last_error, the previous setting kept): layers < 0 or > PS_EXTRAPOLATION_MAX_LAYERS.
+ * Arrays: "velocityExtrapolation" (int32, 1: the layers the last step ran; 0 when off, ignored, or the velocity was not written),
+ * "extrapolationLayerX" / "extrapolationLayerY" / "extrapolationLayerZ" (int8, one per face: L) and "extrapolationCounts" (int32, one per
+ * sweep: the faces it assigned, the three axes together); the last four only when the last step ran at least one layer. */
+#define PS_EXTRAPOLATION_MAX_LAYERS 64
+int32_t ps_set_velocity_extrapolation(ps_context* ctx, int32_t layers);   /* 0 = off (default) ... PS_EXTRAPOLATION_MAX_LAYERS */
+
 /* solveGasSubclass equivalent on host buffers: upload + step + download (HDK_PolyStokes.C:222-609). */
 int32_t polystokes_step(ps_context* ctx, const ps_params* p, const ps_fields_in* in,
                         ps_fields_out* out, ps_stats* stats);

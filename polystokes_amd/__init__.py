@@ -28,7 +28,7 @@ EXPORTED_SYMBOLS = [
     "ps_set_warm_start", "ps_download_solution_fields", "ps_upload_density_field", "ps_set_surface_tension",
     "ps_set_solid_boundary", "ps_set_rheology", "ps_set_solve_precision",
     "ps_upload_fields_device", "ps_upload_density_field_device", "ps_download_fields_device", "ps_download_solution_fields_device",
-    "ps_step_device_fields",
+    "ps_step_device_fields", "ps_set_velocity_extrapolation",
 ]
 
 
@@ -124,6 +124,8 @@ def lib():
         L.ps_set_rheology.restype = C.c_int32
         L.ps_set_solve_precision.argtypes = [C.c_void_p, C.c_int32]
         L.ps_set_solve_precision.restype = C.c_int32
+        L.ps_set_velocity_extrapolation.argtypes = [C.c_void_p, C.c_int32]
+        L.ps_set_velocity_extrapolation.restype = C.c_int32
         L.ps_upload_fields_device.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(FieldsIn), C.c_int32, C.c_void_p]
         L.ps_upload_fields_device.restype = C.c_int32
         L.ps_upload_density_field_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
@@ -225,7 +227,8 @@ def _kind(name):
         return "i"
     if name in ("valuesCoded", "columns16", "diagonalsCoded", "fusedStep", "streamRuns", "rowPerLane", "chebInner32", "warmStartUsed", "densityField", "launchWalk",
                 "surfaceTensionReducedFaces", "solidBoundary", "solidSlipEdges", "rheologyModel", "rheologyIterations",
-                "solvePrecisionUsed", "solvePassIterations"):
+                "solvePrecisionUsed", "solvePassIterations",
+                "velocityExtrapolation", "extrapolationLayerX", "extrapolationLayerY", "extrapolationLayerZ", "extrapolationCounts"):
         return "i"
     if name in ("ownedX", "ownedY", "ownedZ"):
         return "f"
@@ -307,6 +310,13 @@ class Solver:
         the ps_result: INVALID for another mode (the previous setting kept).  Arrays "solvePrecisionUsed", "solvePassIterations",
         "solveTrueResidual" say what the last solve did."""
         return self._check(self.L.ps_set_solve_precision(self.h, int(mode)), allow=(1, -2))
+
+    def set_velocity_extrapolation(self, layers):
+        """ps_set_velocity_extrapolation: 0 (the default) is off; n = 1 .. EXTRAPOLATION_MAX_LAYERS carries the written velocity n faces deep
+        into the invalid faces after the write-back of every later single-domain step of this context, across uploads.  Returns the
+        ps_result: INVALID for a value outside 0..64 (the previous setting kept).  Arrays "velocityExtrapolation",
+        "extrapolationLayerX" / Y / Z, "extrapolationCounts" say what the last step did."""
+        return self._check(self.L.ps_set_velocity_extrapolation(self.h, int(layers)), allow=(1, -2))
 
     def solution_fields(self):
         """ps_download_solution_fields: the last solve's [p; tau] as dense fp32 grids (x fastest), keyed pressure, txx, tyy, tzz, tyz, txz, txy;
@@ -622,6 +632,11 @@ class Group:
     def set_solve_precision(self, mode):
         """ps_set_solve_precision on every rank (a decomposition solves in fp64 whatever the setting: "solvePrecisionUsed" reads 0)."""
         rc = [r.set_solve_precision(mode) for r in self.ranks]
+        return rc[0]
+
+    def set_velocity_extrapolation(self, layers):
+        """ps_set_velocity_extrapolation on every rank (a decomposition ignores the setting: "velocityExtrapolation" reads 0)."""
+        rc = [r.set_velocity_extrapolation(layers) for r in self.ranks]
         return rc[0]
 
     def set_rheology(self, *args, **kw):

@@ -71,6 +71,7 @@ RHEOLOGY_NEWTONIAN, RHEOLOGY_HERSCHEL_BULKLEY = 0, 1
 PRECISION_FP64, PRECISION_MIXED = 0, 1
 # ps_field_layout (the ps_*_device calls): i + d0*(j + d1*k), or k + d2*(j + d1*i) — a C-contiguous array indexed [i, j, k]
 LAYOUT_X_FASTEST, LAYOUT_Z_FASTEST = 0, 1
+EXTRAPOLATION_MAX_LAYERS = 64      # PS_EXTRAPOLATION_MAX_LAYERS (ps_set_velocity_extrapolation)
 
 
 class Rheology(C.Structure):

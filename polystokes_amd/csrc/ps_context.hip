@@ -215,6 +215,7 @@ void ps_context::setupPhase(int phase) {
         setupPhaseDone = -1;
         warmUsedHost = 0; warmX0Valid = false;
         solvePrecisionUsedHost = 0; passIters.clear();
+        extrapUsedHost = 0;
         arrays.clear();
         if (rheoPass == 0) rheoIters.clear();   // (ps_set_rheology: one entry per solve of the step)
         // Picard passes need the halo of the last pass's output velocity: a decomposition refuses them on every rank (ps_dist.hpp: distStep)
@@ -304,6 +305,7 @@ int ps_context::solveStage(ps_stats* stats) {
     HIP_CHECK(hipSetDevice(device));
     StageTimer T(stream);
     int result = PS_INCOMPLETE;
+    extrapUsedHost = 0;
     const std::clock_t c0 = std::clock();
     const auto w0 = std::chrono::high_resolution_clock::now();
     T.mark(0);
@@ -327,6 +329,9 @@ int ps_context::solveStage(ps_stats* stats) {
         recoverVelocityFromPressureStress();
         T.mark(2);
         applySolutionToVelocity();
+        // ps_set_velocity_extrapolation: the written velocity into the faces around the valid ones (single domain only; a Picard pass that
+        // follows reads used faces alone, which no sweep changes)
+        if (extrapSet > 0 && !slabEnabled) extrapolateVelocity(extrapSet);
         // warm start: a kept PCG step (SUCCESS, or NOCONVERGE with keepNonConvergedResults; after the BiCGStab fallback too) carries its x
         // (also to the next Picard pass of the step: ps_set_rheology)
         if ((warmMode == PS_WARM_PREVIOUS_STEP || rheoCarry) && P.doSolve && P.solverType == PS_PCG_MATRIX_VECTOR_PRODUCTS && !slabEnabled) carryWarmStart();
@@ -411,6 +416,12 @@ void ps_context::registerArrays() {
         reg("rheologyStrainRate", rheoRate.p, g.count(0), 4);
         reg("rheologyViscosity", rheoMu.p, g.count(0), 4);
         regHost("rheologyIterations", rheoIters.data(), (int64_t)rheoIters.size(), 4);   // PCG iterations of each solve of the last step
+    }
+    regHost("velocityExtrapolation", &extrapUsedHost, 1, 4);   // layers the last step ran (ps_set_velocity_extrapolation)
+    if (extrapUsedHost > 0) {
+        static const char* axn[3] = {"X", "Y", "Z"};
+        for (int a = 0; a < 3; ++a) reg(std::string("extrapolationLayer") + axn[a], extrapLayer[a].p, g.count(1 + a), 1);
+        reg("extrapolationCounts", extrapCounts.p, extrapUsedHost, 4);   // faces assigned by each sweep, the three axes together
     }
     if (P.preconditioner == PS_PRE_DIAGONAL) regp("dinv", dinv.p, nSystem, permSys.p, 0);
     if (isSolved) {
@@ -756,6 +767,24 @@ int32_t ps_set_solve_precision(ps_context* c, int32_t mode) {
             HIP_CHECK(hipSetDevice(c->device));
             HIP_CHECK(hipStreamSynchronize(c->stream));
             c->dropMixedBuffers();
+            c->drainDeferred(true);
+        }
+        return PS_SUCCESS;
+    })
+}
+int32_t ps_set_velocity_extrapolation(ps_context* c, int32_t layers) {
+    if (!c) return PS_FAILED;
+    PS_TRY(c, {
+        if (layers < 0 || layers > PS_EXTRAPOLATION_MAX_LAYERS) {
+            c->err = "ps_set_velocity_extrapolation: layers outside 0.." + std::to_string(PS_EXTRAPOLATION_MAX_LAYERS);
+            return PS_INVALID;
+        }
+        c->extrapSet = layers;   // read by every later step that writes the velocity (solveStage)
+        if (layers == 0 && c->extrapCounts.p) {   // the layer buffers go with the setting (and their arrays): dropped and, with the stream idle, released here
+            HIP_CHECK(hipSetDevice(c->device));
+            HIP_CHECK(hipStreamSynchronize(c->stream));
+            for (const char* n : {"extrapolationLayerX", "extrapolationLayerY", "extrapolationLayerZ", "extrapolationCounts"}) c->arrays.erase(n);
+            c->dropExtrapolationBuffers();
             c->drainDeferred(true);
         }
         return PS_SUCCESS;

@@ -337,6 +337,15 @@ struct ps_context {
     std::vector<int32_t> passIters;
     double trueResidualHost = 0;
     void dropMixedBuffers() { d32.free(); p32.free(); r32.free(); ts32.free(); Ap32.free(); }
+    // Velocity extrapolation (ps_set_velocity_extrapolation, extension; ps_extrapolate.hip): extrapSet is the context setting, extrapUsedHost the
+    // layers the last step ran (array "velocityExtrapolation": 0 when off, on a decomposition, or when the velocity was not written).
+    // extrapLayer: the layer of every face, 1 B each (arrays "extrapolationLayerX" / Y / Z); extrapCounts: faces assigned per sweep (array
+    // "extrapolationCounts").  Allocated by the first step that runs a layer, dropped when the setting returns to 0.
+    int32_t extrapSet = 0, extrapUsedHost = 0;
+    ps::DevBuf<int8_t> extrapLayer[3];
+    ps::DevBuf<int32_t> extrapCounts;
+    void extrapolateVelocity(int layers);               // ps_extrapolate.hip: after the write-back of a step whose velocity is written
+    void dropExtrapolationBuffers() { for (auto& b : extrapLayer) b.free(); extrapCounts.free(); }
     int64_t solutionGridCount(int q) const { return g.count(q < 4 ? 0 : q); }   // grid q of the store: 0..3 cell grid, 4..6 edge grids
     void scatterSolution(float* dst, int q0, int nq);   // ps_solve.hip: grids q0 .. q0+nq-1 of x, back to back in dst
     void carryWarmStart();                              // ps_solve.hip: x -> warmStore (after a kept step)

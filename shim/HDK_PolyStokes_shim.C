@@ -85,6 +85,7 @@ const ParmRow theRows[] = {
     {'F', "minViscosity",               "Min Viscosity",                    nullptr,            1e-3},
     {'F', "maxViscosity",               "Max Viscosity",                    nullptr,            1e6},
     {'I', "rheologyPasses",             "Rheology Passes",                  nullptr,            0},
+    {'I', "extrapolateLayers",          "Velocity Extrapolation Layers",    nullptr,            0},
 };
 constexpr int theRowCount = (int)(sizeof(theRows) / sizeof(theRows[0]));
 }  // namespace
@@ -232,6 +233,11 @@ bool HDK_PolyStokes::solveGasSubclass(SIM_Engine& engine, SIM_Object* obj, SIM_T
         rh.minViscosity = (double)getMinViscosity();    rh.maxViscosity = (double)getMaxViscosity();
         if (ps_set_rheology(myCtx, &rh) != PS_SUCCESS) return fail(ps_last_error(myCtx), UT_ERROR_ABORT);
     }
+
+    // shim-only: extrapolate the written velocity into the invalid faces on the device (ps_set_velocity_extrapolation, a context setting;
+    // host-side only, so it is set every step).  0, the default, is off: Houdini's network extrapolates after the node.  A refused value
+    // aborts with the library's reason.
+    if (ps_set_velocity_extrapolation(myCtx, (int32_t)getExtrapolateLayers()) != PS_SUCCESS) return fail(ps_last_error(myCtx), UT_ERROR_ABORT);
 
     const fpreal dt = timestep;
     const fpreal dx = velocityField->getVoxelSize(0).maxComponent();
