@@ -892,8 +892,8 @@ struct Dist {
         for (ps_context* c : R) {
             const size_t nl = (size_t)std::max<int64_t>(c->nSystem, 1);
             c->tmp1.alloc(nl); c->tmp2.alloc(nl); c->tmp3.alloc(nl);
-            c->chebPartials.alloc((size_t)std::max<int64_t>(3 * VGRID, gridFor(std::max<int64_t>(c->nSystem, 1), BS)) + 16);
-            c->dotPartials.alloc((size_t)std::max<int64_t>(3 * VGRID, gridFor(std::max<int64_t>(c->nSystem, 1), BS)) + 16);
+            c->chebPartials.alloc(partialsSize(c->nSystem));
+            c->dotPartials.alloc(partialsSize(c->nSystem));
             hipLaunchKernelGGL(k_fill_f64, dim3(dotBlocks((int64_t)nl)), dim3(BS), 0, c->stream, c->tmp1.p, 1., (int64_t)nl);
             HIP_CHECK(hipMemsetAsync(c->tmp2.p, 0, nl * 8, c->stream));
         }
@@ -1084,7 +1084,7 @@ struct Dist {
             for (ps_context* c : R) {
                 const size_t nl = (size_t)std::max<int64_t>(c->nSystem, 1);
                 c->tmp1.alloc(nl); c->tmp2.alloc(nl); c->tmp5.alloc(nl);
-                c->chebPartials.alloc((size_t)std::max<int64_t>(3 * VGRID, gridFor((int64_t)nl, BS)) + 16);
+                c->chebPartials.alloc(partialsSize((int64_t)nl));
                 HIP_CHECK(hipMemsetAsync(c->scal.p, 0, sizeof(CGScalars), c->stream));   // `done` must read 0 inside the polynomial's kernels
                 HIP_CHECK(hipMemsetAsync(c->tmp1.p, 0, nl * 8, c->stream));
                 HIP_CHECK(hipMemsetAsync(c->tmp2.p, 0, nl * 8, c->stream));
@@ -1194,8 +1194,7 @@ struct Dist {
         for (size_t q = 0; q < R.size(); ++q) {
             ps_context* c = R[q];
             RankSolve& f = rs[q];
-            FusedR fr{f.sc, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, it, c->r.p, jac ? c->dinvF.p : (const diag_t*)nullptr, f.fR, nullptr, 0., nullptr,
-                      (const double*)c->redbuf.p, (int)c->ownLo, (int)c->ownHi, c->Ap.p, f.stBF};
+            FusedR fr = fusedSlab(f.sc, it, c->r.p, f.fR, FusedZ::jacobi(jac ? c->dinvF.p : nullptr), c->redbuf.p, (int)c->ownLo, (int)c->ownHi, c->Ap.p, f.stBF);
             if (split) {
                 f.L.stList = c->distList[2].p; f.L.nStList = c->nDistList[2];
                 f.L.spmvSt(3, c->ts.p, c->pvec.p, nullptr, nullptr, nullptr, nullptr, &fr);
@@ -1240,12 +1239,9 @@ struct Dist {
             l.L.spmvS(0, c->pvec.p, c->ts.p);
             l.L.tiles(0, c->ts.p);
             l.L.spmvSt(0, c->ts.p, c->pvec.p, nullptr, c->Ap.p, c->dotPartials.p);
-            if (l.stBlocks <= 8192) {
-                hipLaunchKernelGGL(k_sumq, dim3(1), dim3(BS), 0, c->stream, (const CGScalars*)l.sc, c->dotPartials.p, l.stBlocks, 0, 1, c->redbuf.p);
-            } else {
-                hipLaunchKernelGGL(k_reduce_partials, dim3(RED_BLOCKS), dim3(BS), 0, c->stream, l.sc, c->dotPartials.p, l.stBlocks, c->dotPartials2.p);
-                hipLaunchKernelGGL(k_sumq, dim3(1), dim3(BS), 0, c->stream, (const CGScalars*)l.sc, c->dotPartials2.p, RED_BLOCKS, 0, 1, c->redbuf.p);
-            }
+            int cnt;
+            const double* part = reducedPartials(c, l.sc, c->dotPartials.p, l.stBlocks, c->dotPartials2.p, cnt);
+            hipLaunchKernelGGL(k_sumq, dim3(1), dim3(BS), 0, c->stream, (const CGScalars*)l.sc, part, cnt, 0, 1, c->redbuf.p);
             // ||x||^2 of the x updated last iteration rides along (stop test of the previous iteration, see k_cg_update_r)
             hipLaunchKernelGGL(k_sumq, dim3(1), dim3(BS), 0, c->stream, (const CGScalars*)l.sc, c->dotPartials3.p, l.vb, 0, 1, c->redbuf.p + 1);
         }

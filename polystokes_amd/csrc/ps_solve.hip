@@ -23,7 +23,10 @@
 //                          and k_cg_init_pass / k_cg_scal0_pass / k_cg_check_pass / k_cg_end_pass run the passes of the mixed-precision solve
 //                          (ps_set_solve_precision: fp32 d, p, r, A p, t around the fp64 x; ps_context::solve).
 //   this file            : the launch dispatch (Launch: planS / planSt choose the kernel and grid of a product, one launcher per kernel family runs it),
-//                          ps_context::applyOperator / assemble / solve / recover.
+//                          ps_context::applyOperator / assemble / solve / recover.  The solve runs in stages (DomainSolve, as Dist's in ps_dist.hpp):
+//                          solveStart, chooseStepForm, fusedStart, [mixedPasses: passStart + batches of the fp32 steps], pcgStart, batches of
+//                          fourKernelStep / fiveKernelStep (one body for fp64 and fp32 vectors) or their ...ChebStep forms, bicgstabFallback; runBatches
+//                          is the one batch driver (stop test, scalar read-back, interrupt), fusedSingle / fusedSlab + FusedZ build every FusedR.
 //   ps_dist.hpp          : the z-slab distributed solve (RCCL or in-process ranks) and its C ABI.
 //   ps_import.hpp        : MatrixMarket import + general CSR PCG (ps_solve_exported_system).
 #include <algorithm>
@@ -62,6 +65,8 @@ template <class F> auto withPipe(bool packed, int pol, F&& f) {
     if (!packed) f(std::true_type{}, std::integral_constant<int, 3>{}); else withPolicy(pol, [&](auto POL) { f(std::false_type{}, POL); });
 }
 template <class T> struct Type { using type = T; };
+// the element type of the Chebyshev polynomial's vectors z_j (fp32: PS_PRE_CHEBYSHEV_F32 where it runs, ps_context::chebInner32; fp64 otherwise)
+template <class F> auto withZ(bool f32, F&& f) { if (f32) f(Type<float>{}); else f(Type<double>{}); }
 
 // The kernel of one S or St product (ps_kernels_spmv.hpp).  CSR: k_spmv_S / k_spmv_St (one-shot); PIPE: k_spmv_S_pipe / k_spmv_St_pipe
 // (persistent, compressed or fp64-value stream); ELL: k_spmv_S_ell / k_spmv_St_ell (FX), row-per-lane on the coded stream; two units in flight
@@ -80,7 +85,7 @@ struct Launch {
     ps_context* c;
     const int* done;
     int rowsS, rowsSt, nA, nP;
-    // fused residual update (solve(): FusedR): where the S and tile kernels leave their shares of p.Ap (null: not asked for)
+    // fused residual update (DomainSolve::fusedStart: FusedR): where the S and tile kernels leave their shares of p.Ap (null: not asked for)
     double* sPart = nullptr;
     double* wvPart = nullptr;
     // chunk lists (row-per-lane kernels only; null: every chunk): ps_dist.hpp launches the chunks next to a cut and the others separately
@@ -366,7 +371,7 @@ struct Launch {
         else if (p.kernel == ELL2C) stEll2c(p, t, xin, out, partial, ca);
         else if (p.kernel == ELL2Z) {
             auto z = [&](auto TZ) { withPolicy(p.pol, [&](auto POL) { withBool(c->uCoded, [&](auto UC) { ell2(POL, T{}, F{}, F{}, TZ, F{}, UC); }); }); };
-            if (cz32) z(Type<float>{}); else z(Type<double>{});
+            withZ(cz32, z);
         }
         else if (p.kernel == ELL2) withBool(c->uCoded, [&](auto UC) { withPolicy(p.pol, [&](auto POL) { ell2(POL, F{}, F{}, F{}, Type<double>{}, F{}, UC); }); });
         else if (p.kernel == ELL && p.fx == 3) withPolicy(p.pol, [&](auto POL) { withBool(stList, [&](auto LIST) { ell(M3{}, POL, M3{}, LIST); }); });
@@ -457,15 +462,80 @@ Launch mk(ps_context* c, const int* done) {
     L.walk = c->walkRecord ? c->launchWalkHost : nullptr;
     return L;
 }
-constexpr int64_t FUSED_STEP_MIN_ROWS = 1200000;   // see solve() (r05: 2 M -> 1.2 M: the coil 128^3 of BASELINE config 2, 1.49 M rows, solves 3 % faster in four kernels — 10.55 against 10.86 ms,
+constexpr int64_t FUSED_STEP_MIN_ROWS = 1200000;   // see DomainSolve::chooseStepForm (r05: 2 M -> 1.2 M: the coil 128^3 of BASELINE config 2, 1.49 M rows, solves 3 % faster in four kernels — 10.55 against 10.86 ms,
                                                     // two rounds on one box; the 64^3 cavity, 0.8 M rows, stays faster in five: 57.3 against 58.8 us per iteration)
 constexpr int64_t NT_LEVEL1_MIN_ROWS = 4000000, NT_LEVEL2_MIN_ROWS = 10000000;   // see ps_context::ntLevel
 int dotBlocks(int64_t n) { return (int)std::min<int64_t>(VGRID, std::max<int64_t>(1, (n + BS - 1) / BS)); }
+// entries of a partial-sums buffer over n DOFs (dotPartials, chebPartials): three sets of vector-kernel partials or one value per 256-row chunk, and the sums' slots
+size_t partialsSize(int64_t n) { return (size_t)std::max<int64_t>(3 * VGRID, gridFor(std::max<int64_t>(n, 1), BS)) + 16; }
 constexpr int CG_BATCH = 25;   // PCG iterations between two stop tests on the host (ps_context::solve, Dist::solve)
 // The mixed-precision solve (ps_context::solve): a pass ends at the latest when r.r has fallen to MIXED_PASS_REDUCTION^2 of the true r.r it
 // started from (fp32 carries 2^-24: about three digits are left for drift; profiles/mixed_precision.md), and there are at most MIXED_MAX_PASSES
 constexpr double MIXED_PASS_REDUCTION = 1e-4;
 constexpr int MIXED_MAX_PASSES = 8;
+
+// More than 8192 partial sums (a one-shot kernel's: one per 256 rows) are first reduced to RED_BLOCKS sums in `red`.  Returns the sums to read, their count in cnt.
+const double* reducedPartials(ps_context* c, const CGScalars* sc, const double* src, int count, double* red, int& cnt) {
+    if (count > 8192) hipLaunchKernelGGL(k_reduce_partials, dim3(RED_BLOCKS), dim3(BS), 0, c->stream, sc, src, count, red);
+    cnt = count > 8192 ? RED_BLOCKS : count;
+    return count > 8192 ? red : src;
+}
+// a . b over n DOFs on the host: one scalar read-back per product (the BiCGStab fallback, Eigen's CG)
+double hostDot(ps_context* c, const double* a, const double* b, int64_t n) {
+    double out, *sum = c->dotPartials.p + 3 * VGRID;
+    hipLaunchKernelGGL(k_dot, dim3(dotBlocks(n)), dim3(BS), 0, c->stream, a, b, n, c->dotPartials.p);
+    hipLaunchKernelGGL(k_sum1, dim3(1), dim3(BS), 0, c->stream, c->dotPartials.p, dotBlocks(n), sum);
+    HIP_CHECK(hipMemcpyAsync(&out, sum, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_CHECK(hipStreamSynchronize(c->stream));
+    return out;
+}
+// the polynomial's result z (fp32 or fp64 values: chebInner32) as the fp64 vector dst — widened (dst is then another buffer), or copied unless it is there already
+void zToF64(ps_context* c, double* dst, const double* z, int64_t n) {
+    withZ(c->chebInner32, [&](auto TZ) {
+        if constexpr (std::is_same<typename decltype(TZ)::type, float>::value) hipLaunchKernelGGL(k_widen_f32, dim3(dotBlocks(n)), dim3(BS), 0, c->stream, dst, (const float*)z, n);
+        else if (dst != z) HIP_CHECK(hipMemcpyAsync(dst, z, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    });
+}
+// ---- FusedR (ps_kernels_spmv.hpp: the argument of the St kernel that carries the residual update) by what a site sets; the rest is null / zero.
+// What forms the step's r.z: the stored Jacobi diagonal (null: the identity) OR the polynomial's first term, z_1 = dinvC r invTheta -> cz.  The
+// builders below take ONE FusedZ, made by one of its two functions: no FusedR holds both.
+struct FusedZ {
+    const diag_t *dinvF = nullptr, *dinvC = nullptr; double invTheta = 0.; double* cz = nullptr;
+    static FusedZ jacobi(const diag_t* dinvF) { FusedZ z; z.dinvF = dinvF; return z; }
+    static FusedZ chebFirst(const diag_t* dinvC, double invTheta, double* cz) { FusedZ z; z.dinvC = dinvC; z.invTheta = invTheta; z.cz = cz; return z; }
+};
+// where the four producers of p.Ap and ||x||^2 left their partials: the S kernel, the tile kernel, uInv p^2 and x.x of the last x, p update
+struct FusedPartials { const double* s; int sCount; const double* t; int tCount; const double* u; int uCount; const double* xx; int xxCount; };
+// the single-domain step: the producers' partials; every row in [0, rows) is this domain's DOF
+FusedR fusedSingle(CGScalars* sc, const FusedPartials& p, int it, double* r, double* rPart, int rows, const FusedZ& z) {
+    FusedR f{};
+    f.sc = sc; f.it = it; f.r = r; f.rPart = rPart; f.dinvF = z.dinvF; f.dinvC = z.dinvC; f.invTheta = z.invTheta; f.cz = z.cz;
+    f.sPart = p.s; f.sCount = p.sCount; f.tPart = p.t; f.tCount = p.tCount; f.uPart = p.u; f.uCount = p.uCount; f.xxPart = p.xx; f.xxCount = p.xxCount; f.ownHi = rows;
+    return f;
+}
+// a slab rank's step: red = the sums over the ranks instead of partials, its DOFs [ownLo, ownHi) of the rows, the halo rows' y -> yOut, the stride
+// between the r.r and r.z partials of a step that runs as two launches
+FusedR fusedSlab(CGScalars* sc, int it, double* r, double* rPart, const FusedZ& z, const double* red, int ownLo, int ownHi, double* yOut, int rStride) {
+    FusedR f = fusedSingle(sc, FusedPartials{}, it, r, rPart, ownHi, z);
+    f.red = red; f.ownLo = ownLo; f.yOut = yOut; f.rStride = rStride;
+    return f;
+}
+// The batches of a PCG loop: iterations it .. min(budget, it + CG_BATCH) - 1 through step(it), then check(it - 1) — the stop test of the batch's last
+// iteration — and the scalars read back; until they say done, the budget is used up or the interrupt callback asks (between batches only: sets
+// ps_context::interrupted).  h0: the scalars as the caller holds them (returned as they are when the budget is empty).
+struct BatchRun { int it; CGScalars h; bool interrupted; };
+template <class Step, class Check> BatchRun runBatches(ps_context* c, CGScalars* sc, int budget, const CGScalars& h0, Step step, Check check) {
+    BatchRun b{0, h0, false};
+    for (bool finished = false; b.it < budget && !finished; ) {
+        for (const int upto = std::min(budget, b.it + CG_BATCH); b.it < upto; ++b.it) step(b.it);
+        check(b.it - 1);
+        HIP_CHECK(hipMemcpyAsync(&b.h, sc, sizeof(b.h), hipMemcpyDeviceToHost, c->stream));
+        HIP_CHECK(hipStreamSynchronize(c->stream));
+        finished = b.h.done != 0;
+        if (!finished && c->interruptCb && c->interruptCb(c->interruptUser)) { c->interrupted = b.interrupted = true; break; }
+    }
+    return b;
+}
 
 double chebRatio() { static const double r = PS_ENV("PS_CHEB_RATIO") ? atof(PS_ENV("PS_CHEB_RATIO")) : PS_CHEB_INTERVAL_RATIO; return r; }   // lmax / lmin (PS_CHEB_RATIO: experiments only — the oracle uses the constant)
 // The Chebyshev iteration on [lmax / chebRatio(), lmax] (ps_context::chebyshevApply, Dist::chebyshevDist): z_1 = D^-1 r / theta, then
@@ -551,7 +621,7 @@ void ps_context::assembleSystemPressureStressFactored() {
     vreg.alloc((size_t)std::max<int64_t>(1, regionCount) * PS_RD);
     wreg.alloc((size_t)std::max<int64_t>(1, nRChunks) * PS_RD);
     b.alloc((size_t)n); x.alloc((size_t)n); r.alloc((size_t)n); pvec.alloc((size_t)n); Ap.alloc((size_t)n);
-    dotPartials.alloc((size_t)std::max<int64_t>(3 * VGRID, gridFor(std::max<int64_t>(n, 1), BS)) + 16);
+    dotPartials.alloc(partialsSize(n));
     scal.alloc(1);
     dotPartials2.alloc(RED_BLOCKS);
     dotPartials3.alloc(VGRID);
@@ -611,7 +681,7 @@ void ps_context::estimateLambdaMax() {
     const int vb = dotBlocks(n);
     tmp1.alloc((size_t)n); tmp2.alloc((size_t)n); tmp3.alloc((size_t)n);
     double* v = tmp1.p; double* w = tmp2.p; double* Av = tmp3.p;
-    chebPartials.alloc((size_t)std::max<int64_t>(3 * VGRID, gridFor(n, BS)) + 16);
+    chebPartials.alloc(partialsSize(n));
     hipLaunchKernelGGL(k_fill_f64, dim3(vb), dim3(BS), 0, stream, v, 1., n);
     chebLmax = powerLambdaMax([&] {
         applyOperator(v, Av, dotPartials.p);
@@ -642,10 +712,10 @@ int ps_context::chebyshevApply(const double* rvec, double* zA, double* zB, doubl
     Launch L = mk(this, done);
     // PS_PRE_CHEBYSHEV_F32 (chebInner32): the same recurrence with z_j (zA / zB) and the face-row vector of the inner applies (the first half
     // of ts) STORED as fp32; r, the diagonal, every product and sum fp64.  The two-units-per-wave kernels only (Launch::cheb32Ok decided chebInner32).
-    if (!firstDone) {
-        if (chebInner32) hipLaunchKernelGGL(k_cheb_first<float>, dim3(vb), dim3(BS), 0, stream, sc, rvec, (const diag_t*)dinvF.p, 1. / cr.theta, (float*)zA, n, rzPartial);
-        else hipLaunchKernelGGL(k_cheb_first<double>, dim3(vb), dim3(BS), 0, stream, sc, rvec, (const diag_t*)dinvF.p, 1. / cr.theta, zA, n, rzPartial);
-    }
+    if (!firstDone) withZ(chebInner32, [&](auto TZ) {
+        using T = typename decltype(TZ)::type;
+        hipLaunchKernelGGL(k_cheb_first<T>, dim3(vb), dim3(BS), 0, stream, sc, rvec, (const diag_t*)dinvF.p, 1. / cr.theta, (T*)zA, n, rzPartial);
+    });
     int count = firstDone ? 0 : vb;
     double* cur = zA; double* other = zB;    // z_j, and the buffer of z_{j-1} that receives z_{j+1}
     for (int j = 1; j < k; ++j) {
@@ -682,17 +752,16 @@ void ps_context::applyPreconditionerDevice(const double* rvec, double* z, double
     if (n == 0) return;
     const int vb = dotBlocks(n);
     if (P.preconditioner == PS_PRE_CHEBYSHEV) {
-        chebPartials.alloc((size_t)std::max<int64_t>(3 * VGRID, gridFor(n, BS)) + 16);
+        chebPartials.alloc(partialsSize(n));
         double* zfin = z;
         chebInner32 = chebInner32Req && mk(this, nullptr).cheb32Ok();
         chebInner32Host = chebInner32 ? 1 : 0;   // (array "chebInner32")
         chebyshevApply(rvec, z, scratch, chebPartials.p, nullptr, false, &zfin);
         if (chebInner32) {      // the result is an fp32 vector in one of the two buffers: widen it through a third
             tmp5.alloc((size_t)n);
-            hipLaunchKernelGGL(k_widen_f32, dim3(vb), dim3(BS), 0, stream, tmp5.p, (const float*)zfin, n);
+            zToF64(this, tmp5.p, zfin, n);
             HIP_CHECK(hipMemcpyAsync(z, tmp5.p, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, stream));
-        } else
-        if (zfin != z) HIP_CHECK(hipMemcpyAsync(z, zfin, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, stream));
+        } else zToF64(this, z, zfin, n);
     } else if (P.preconditioner == PS_PRE_DIAGONAL) {
         hipLaunchKernelGGL(k_mul_diag, dim3(vb), dim3(BS), 0, stream, z, (const diag_t*)dinvF.p, rvec, n);   // the diagonal as the PCG kernels read it
     } else {
@@ -700,254 +769,241 @@ void ps_context::applyPreconditionerDevice(const double* rvec, double* z, double
     }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// The single-domain PCG solve in stages, named after Dist's (ps_dist.hpp: RankSolve, solveStart, chooseStepForm, fusedStart, the steps,
+// bicgstabDist) where the job is the same; ps_context::solve below runs them in order.
+namespace {
+// The Krylov vectors of a Jacobi / identity step — the fp64 solve's x, p, r, A p and face-row vector, or a pass's fp32 ones with its correction d
+// in x's place (ps_set_solve_precision; A p: the five-kernel step only) — and the vector kernels of their element type
+template <class T> struct StepVecs { T *x, *p, *r, *Ap, *ts; };
+template <class T> struct StepKernels { static constexpr auto updateR = k_cg_update_r; static constexpr auto updateXp = k_cg_update_xp; static constexpr auto updateXpU = k_cg_update_xp_u; };
+template <> struct StepKernels<float> { static constexpr auto updateR = k_cg_update_r_f32; static constexpr auto updateXp = k_cg_update_xp_f32; static constexpr auto updateXpU = k_cg_update_xp_u_f32; };
+// How the fp32 passes ended: the stop rule holds on the fp64 residual; a pass no longer halved it or the passes are used up (fp64 PCG goes on
+// from this x); the iteration budget is used up (-> BiCGStab); the interrupt callback asked
+enum class Passes { Converged, Stagnated, BudgetUsed, Interrupted };
+
+struct DomainSolve {
+    ps_context* c = nullptr;
+    int64_t n = 0; double tol = 0.; int maxit = 0;
+    int vb = 0, stBlocks = 0, stBF = 0, sBlocks = 0;              // workgroups: the vector kernels, St plain / with the residual update, S (four-kernel step)
+    const diag_t* dv = nullptr; const uint8_t* ucode = nullptr;   // Jacobi: the stored diagonal; the stress diagonal's codes
+    CGScalars *sc = nullptr, h{};                                 // the scalars on the device, and as last read back
+    Launch L;
+    bool cheb = false, fused = false, recording = false;
+    double *fS = nullptr, *fT = nullptr, *fU = nullptr, *fR = nullptr;   // the four-kernel step's partials in fusedPart (fusedStart)
+    double *zvec = nullptr, *dvec = nullptr, *rzPart = nullptr;   // the polynomial's two buffers and the r.z partials of its last term
+    int itBase = 0;                                               // iterations the fp32 passes took: the fp64 loop gets the rest of the budget
+    ~DomainSolve() { if (recording) c->walkRecord = false; }
+    template <class K, class... A> void run(K kernel, int grid, A... a) const { hipLaunchKernelGGL(kernel, dim3(grid), dim3(BS), 0, c->stream, a...); }
+
+    // Resets; false: there is nothing to iterate and rc is the solve's result (Eigen's CG ran, an unsupported solver, an empty system).
+    // Otherwise the walks are being recorded, the launch dispatch stands and the polynomial has its buffers.
+    bool solveStart(ps_context* ctx, int& rc) {
+        c = ctx; n = c->nSystem; maxit = c->P.maxSolverIterations; tol = c->P.tolerance;
+        c->usedBiCGStab = 0; c->interrupted = false; c->solvePrecisionUsedHost = 0; c->passIters.clear();
+        if (c->P.solverType == PS_EIGEN) { rc = c->solveEigenCG(); return false; }
+        if (c->P.solverType != PS_PCG_MATRIX_VECTOR_PRODUCTS) { c->err = "Unsupported Solver."; rc = PS_UNSUPPORTED_SOLVER; return false; }
+        std::fill(std::begin(c->launchWalkHost), std::end(c->launchWalkHost), 0);
+        if (n == 0) { c->solveIterations = 0; c->solveError = 0; rc = PS_SUCCESS; return false; }
+        c->walkRecord = recording = true;
+        cheb = c->P.preconditioner == PS_PRE_CHEBYSHEV;
+        dv = (c->P.preconditioner == PS_PRE_DIAGONAL) ? c->dinvF.p : nullptr;
+        vb = dotBlocks(n); sc = c->scal.p; ucode = c->uCoded ? c->uCode.p : nullptr;
+        L = mk(c, &sc->done);
+        stBlocks = L.stBlocks(0); stBF = L.stBlocks(3);
+        L.cz32 = c->chebInner32 = cheb && c->chebInner32Req && L.cheb32Ok();     // PS_PRE_CHEBYSHEV_F32 where the two-unit kernels run; fp64 inner vectors otherwise
+        if (cheb) {
+            c->tmp1.alloc((size_t)n); c->tmp2.alloc((size_t)n); c->chebPartials.alloc(partialsSize(n)); c->chebPartials2.alloc(RED_BLOCKS);
+            zvec = c->tmp1.p; dvec = c->tmp2.p; rzPart = c->chebPartials.p;
+        }
+        return true;
+    }
+    // Fused step (default on the coded stream): p.Ap = -(sum_active s.t + sum_tiles w.v + 1/2 sum uInv p^2) is complete before the St kernel
+    // starts, so that kernel forms alpha and updates r in its epilogue — A p is neither written nor read back (16 B per row less) and the step is
+    // four launches (FusedR, ps_kernels_spmv.hpp).  Every St workgroup sums the partials of three producers in its prologue: a fixed cost per
+    // iteration, which pays from 1.2 M rows (FUSED_STEP_MIN_ROWS; the figures and the rejected ticket reduction: docs/history.md).  PS_FUSED_R =
+    // 0 / 1 forces it off / on (on only where the kernels exist).
+    void chooseStepForm() {
+        static const int fusedEnv = envInt(PS_ENV("PS_FUSED_R"), -1);
+        fused = fusedEnv != 0 && (fusedEnv > 0 || n >= FUSED_STEP_MIN_ROWS) && L.fusedOk();
+        c->fusedStepHost = fused ? 1 : 0;
+    }
+    void fusedStart() {   // the partials of the four-kernel step
+        sBlocks = L.sBlocks();
+        c->fusedPart.alloc((size_t)sBlocks + (size_t)c->regionCount + VGRID + 2 * (size_t)stBF + 16);
+        L.sPart = fS = c->fusedPart.p; L.wvPart = fT = fS + sBlocks; fU = fT + c->regionCount; fR = fU + VGRID;
+    }
+    // r = b - A x (warm: x is the carried solution, pcg.h:284) or r = b, x = 0; z = M^-1 r, p = z, rsold = r.z; with the four-kernel step the first
+    // direction's share of p.Ap on the diagonal
+    void pcgStart(bool warm) {
+        if (warm) {
+            c->applyOperator(c->x.p, c->Ap.p, c->dotPartials.p);
+            run(k_cg_init_warm, vb, c->b.p, c->Ap.p, dv, c->r.p, c->pvec.p, n, c->dotPartials.p);
+        } else
+            run(k_cg_init_f, vb, c->b.p, dv, c->x.p, c->r.p, c->pvec.p, n, c->dotPartials.p);
+        if (cheb) {
+            HIP_CHECK(hipMemsetAsync(sc, 0, sizeof(CGScalars), c->stream));   // `done` must read 0 inside the polynomial's kernels
+            double* z0 = zvec;
+            const int zCount = c->chebyshevApply(c->r.p, zvec, dvec, rzPart, nullptr, false, &z0);
+            zToF64(c, c->pvec.p, z0, n);
+            run(k_sum_to, 1, rzPart, zCount, c->dotPartials.p);
+        }
+        run(k_cg_scal0, 1, sc, c->dotPartials.p, cheb ? 1 : vb, tol, maxit, c->ntLevel() >= 2 ? 1 : 0);
+        if (fused) run(k_uinv_pp, vb, c->pvec.p, ucode, c->uDict.p, c->uInv.p, n, fU);
+    }
+
+    // ---- the steps.  (r of either element type goes through FusedR's double*.)
+    StepVecs<double> v64() const { return {c->x.p, c->pvec.p, c->r.p, c->Ap.p, c->ts.p}; }
+    FusedR fusedArgs(int it, void* r, const FusedZ& z) const {
+        return fusedSingle(sc, {fS, sBlocks, fT, (int)c->regionCount, fU, vb, c->dotPartials3.p, vb}, it, (double*)r, fR, (int)n, z);
+    }
+    template <class T> auto faceRows(const StepVecs<T>& v) const {   // ts = S p, the tiles' rows rewritten in place
+        if constexpr (std::is_same<T, float>::value) { L.spmvS32(v.p, v.ts); L.tiles32(v.ts); }
+        else { L.spmvS(0, v.p, v.ts); L.tiles(0, v.ts); }
+    }
+    // Four kernels: S, tiles, St with r -= alpha A p in its epilogue, then x, p (and the new p's share of p.Ap on the diagonal)
+    template <class T> auto fourKernelStep(int it, const StepVecs<T>& v) const {
+        faceRows(v);
+        const FusedR fr = fusedArgs(it, v.r, FusedZ::jacobi(dv));
+        if constexpr (std::is_same<T, float>::value) L.spmvSt32(false, v.ts, v.p, fr);
+        else L.spmvSt(3, v.ts, v.p, nullptr, nullptr, nullptr, nullptr, &fr);
+        run(StepKernels<T>::updateXpU, vb, sc, nullptr, fR, stBF, dv ? 1 : 0, it, v.r, dv, v.x, v.p, n, c->dotPartials3.p, ucode, c->uDict.p, c->uInv.p, fU);
+    }
+    // ... with the polynomial: the St kernel also forms its first term on the new r; then terms 2..k; then x, p
+    void fourKernelChebStep(int it) {
+        const StepVecs<double> v = v64();
+        faceRows(v);
+        const FusedR fr = fusedArgs(it, v.r, FusedZ::chebFirst(c->dinvF.p, 1. / c->chebTheta(), zvec));
+        L.spmvSt(3, v.ts, v.p, nullptr, nullptr, nullptr, nullptr, &fr);
+        double* zfin = zvec;
+        const int zCount = c->chebyshevApply(v.r, zvec, dvec, rzPart, sc, true, &zfin);
+        int cnt = stBF; const double* part = fR + stBF;         // a one-term polynomial: the St kernel's own r.z partials
+        if (zCount > 0) part = reducedPartials(c, sc, rzPart, zCount, c->chebPartials2.p, cnt);
+        withZ(c->chebInner32, [&](auto TZ) {
+            using Z = typename decltype(TZ)::type;
+            run(k_cg_update_xp_z_u<Z>, vb, sc, fR, stBF, part, cnt, it, (const Z*)zfin, v.x, v.p, n, c->dotPartials3.p, ucode, c->uDict.p, c->uInv.p, fU);
+        });
+    }
+    // The first four kernels of the five-kernel step: A p (S, tiles, St with the partials of p.Ap), then r -= alpha A p
+    template <class T> auto residualUpdate(int it, const StepVecs<T>& v) const {
+        faceRows(v);
+        int cnt = stBlocks;
+        if constexpr (std::is_same<T, float>::value) {
+            FusedR fr{}; fr.r = (double*)v.Ap; fr.rPart = c->dotPartials.p;
+            cnt = L.spmvSt32(true, v.ts, v.p, fr);
+        } else
+            L.spmvSt(0, v.ts, v.p, nullptr, v.Ap, c->dotPartials.p);
+        const double* part = reducedPartials(c, sc, c->dotPartials.p, cnt, c->dotPartials2.p, cnt);   // (the one-shot St kernel: a partial per 256 rows)
+        run(StepKernels<T>::updateR, vb, sc, nullptr, part, cnt, c->dotPartials3.p, vb, it, v.Ap, dv, v.r, n, c->dotPartialsR.p);
+    }
+    template <class T> auto fiveKernelStep(int it, const StepVecs<T>& v) const {
+        residualUpdate(it, v);
+        run(StepKernels<T>::updateXp, vb, sc, nullptr, c->dotPartialsR.p, vb, dv ? 1 : 0, it, v.r, dv, v.x, v.p, n, c->dotPartials3.p);
+    }
+    void fiveKernelChebStep(int it) {   // ... with the polynomial: z = M^-1 r between the residual update and x, p
+        const StepVecs<double> v = v64();
+        residualUpdate(it, v);
+        double* zfin = zvec;
+        const int zCount = c->chebyshevApply(v.r, zvec, dvec, rzPart, sc, false, &zfin);
+        int cnt;
+        const double* part = reducedPartials(c, sc, rzPart, zCount, c->chebPartials2.p, cnt);
+        withZ(c->chebInner32, [&](auto TZ) {
+            using Z = typename decltype(TZ)::type;
+            run(k_cg_update_xp_z<Z>, vb, sc, c->dotPartialsR.p, vb, part, cnt, it, (const Z*)zfin, v.x, v.p, n, c->dotPartials3.p);
+        });
+    }
+    void step(int it) {   // one fp64 iteration
+        if (cheb) { if (fused) fourKernelChebStep(it); else fiveKernelChebStep(it); }
+        else if (fused) fourKernelStep(it, v64());
+        else fiveKernelStep(it, v64());
+    }
+
+    // ---- mixed precision (ps_set_solve_precision; include/polystokes.h, DESIGN.md "Mixed-precision PCG"): x stays fp64; a pass runs the Jacobi /
+    // identity step on fp32 vectors (d32 in x's place) for A d = b - A x, then x += d, and the stop rule is evaluated on the fp64 b - A x
+    bool mixedAsked() const { return c->solvePrecisionSet == PS_PRECISION_MIXED && !cheb && !c->slabEnabled && L.mixedOk(); }
+    // The true residual of the current x (fp64 operator, as k_cg_init_warm; haveX false: x = 0) rounded into the pass's r, p = z; its r.r and x.x —
+    // the evaluation of the stop rule — into h
+    void passStart(bool haveX) {
+        if (haveX) c->applyOperator(c->x.p, c->Ap.p, c->dotPartials.p);
+        run(k_cg_init_pass, vb, c->b.p, haveX ? c->Ap.p : nullptr, c->x.p, dv, c->d32.p, c->r32.p, c->p32.p, n, c->dotPartials.p);
+        run(k_cg_scal0_pass, 1, sc, c->dotPartials.p, vb, tol, maxit, c->ntLevel() >= 2 ? 1 : 0, MIXED_PASS_REDUCTION * MIXED_PASS_REDUCTION, haveX ? 1 : 0);
+        if (fused) run(k_uinv_pp_f32, vb, c->p32.p, ucode, c->uDict.p, c->uInv.p, n, fU);
+        HIP_CHECK(hipMemcpyAsync(&h, sc, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+        HIP_CHECK(hipStreamSynchronize(c->stream));
+    }
+    // The passes.  solveError / trueResidualHost hold the last evaluation, solveIterations and itBase the iterations so far, passIters each pass's.
+    Passes mixedPasses(bool warm) {
+        c->solvePrecisionUsedHost = 1;
+        c->d32.alloc((size_t)n); c->p32.alloc((size_t)n); c->r32.alloc((size_t)n); c->ts32.alloc((size_t)c->nRows + 1);
+        if (!fused) c->Ap32.alloc((size_t)n);
+        L.v32 = true;
+        const StepVecs<float> v{c->d32.p, c->p32.p, c->r32.p, c->Ap32.p, c->ts32.p};
+        auto toFp64 = [&](Passes how) { L.v32 = false; HIP_CHECK(hipMemsetAsync(c->dotPartials3.p, 0, VGRID * sizeof(double), c->stream)); return how; };   // the fp64 kernels take over
+        double rrStart = 0.;
+        for (int pass = 0; ; ++pass) {
+            const bool haveX = warm || pass > 0;
+            passStart(haveX);
+            const double trueRR = h.rr;
+            c->solveError = c->trueResidualHost = std::sqrt(h.rre);
+            c->solveIterations = itBase;
+            if (pass > 0 && h.rre < tol * tol) return Passes::Converged;
+            if (h.done) {   // r = 0 exactly (b == 0: as the fp64 solve, x = 0)
+                if (!haveX) HIP_CHECK(hipMemsetAsync(c->x.p, 0, (size_t)n * sizeof(double), c->stream));
+                return Passes::Converged;
+            }
+            // stagnation: the pass did not halve the true ||r|| (the floor of fp32), or the passes are used up
+            if (pass > 0 && (!(trueRR < 0.25 * rrStart) || pass == MIXED_MAX_PASSES)) return toFp64(Passes::Stagnated);
+            if (itBase >= maxit) return toFp64(Passes::BudgetUsed);
+            rrStart = trueRR;
+            const BatchRun b = runBatches(c, sc, maxit - itBase, h, [&](int it) { if (fused) fourKernelStep(it, v); else fiveKernelStep(it, v); },
+                                          [&](int last) { run(k_cg_check_pass, 1, sc, c->dotPartials3.p, vb, last); });
+            h = b.h;
+            c->passIters.push_back(h.done ? h.iter + 1 : b.it);   // the iterations whose update d holds
+            c->solveIterations = itBase += c->passIters.back();
+            if (b.interrupted) return Passes::Interrupted;
+            run(k_cg_end_pass, vb, c->d32.p, c->x.p, n, haveX ? 0 : 1);
+            if (!h.done) return toFp64(Passes::BudgetUsed);      // the budget ran out inside the pass
+        }
+    }
+    int bicgstabFallback() {   // bicgstab (above), restarted from zero, on the factored operator: the solve's result
+        c->usedBiCGStab = 1;
+        c->tmp1.alloc((size_t)n); c->tmp2.alloc((size_t)n); c->tmp3.alloc((size_t)n); c->tmp4.alloc((size_t)n); c->tmp5.alloc((size_t)n);
+        c->solveIterations = bicgstab(BiCGVecs<double*>{c->x.p, c->r.p, c->pvec.p, c->b.p, c->Ap.p, c->tmp1.p, c->tmp2.p, c->tmp3.p, c->tmp4.p, c->tmp5.p}, maxit, tol, c->solveError,
+            [&](double* in, double* out) { c->applyOperator(in, out, c->dotPartials.p); },
+            [&](const double* a, const double* bb) { return hostDot(c, a, bb, n); },
+            [&](double* out, double ca, const double* a, double cb, const double* bb, double cc, const double* c3) { run(k_lin, vb, out, ca, a, cb, bb, cc, c3, n); },
+            [&](double* v) { HIP_CHECK(hipMemsetAsync(v, 0, (size_t)n * sizeof(double), c->stream)); });
+        return c->solveIterations == maxit ? PS_NOCONVERGE : PS_SUCCESS;
+    }
+};
+}  // namespace
+
 // Solver.cpp:734-812 solveSPDwithMatrixVectorPCG -> pcg_external_matrix_A (pcg.h:268-340), BiCGStab fallback (pcg.h:134-200)
 int ps_context::solve() {
-    const int64_t n = nSystem;
-    const int maxit = P.maxSolverIterations;
-    const double tol = P.tolerance;
-    usedBiCGStab = 0;
-    interrupted = false;
-    solvePrecisionUsedHost = 0;
-    passIters.clear();
-    if (P.solverType == PS_EIGEN) return solveEigenCG();
-    if (P.solverType != PS_PCG_MATRIX_VECTOR_PRODUCTS) { err = "Unsupported Solver."; return PS_UNSUPPORTED_SOLVER; }
-    std::fill(std::begin(launchWalkHost), std::end(launchWalkHost), 0);
-    if (n == 0) { solveIterations = 0; solveError = 0; return PS_SUCCESS; }
-    struct WalkRecord { bool& on; explicit WalkRecord(bool& f) : on(f) { on = true; } ~WalkRecord() { on = false; } } walkRecording(walkRecord);
-    const bool cheb = P.preconditioner == PS_PRE_CHEBYSHEV;
-    const diag_t* dv = (P.preconditioner == PS_PRE_DIAGONAL) ? dinvF.p : nullptr;
-    const int vb = dotBlocks(n);
-    CGScalars* sc = scal.p;
-    const int* done = &sc->done;
-    Launch L = mk(this, done);
-    const int stBlocks = L.stBlocks(0), stBF = L.stBlocks(3);   // workgroups of the St kernel: plain / with the residual update
-    double* zvec = nullptr; double* dvec = nullptr; double* rzPart = nullptr;
-    chebInner32 = cheb && chebInner32Req && L.cheb32Ok();     // PS_PRE_CHEBYSHEV_F32 where the two-unit kernels run; fp64 inner vectors otherwise
-    L.cz32 = chebInner32;
-    if (cheb) {
-        tmp1.alloc((size_t)n); tmp2.alloc((size_t)n);
-        zvec = tmp1.p; dvec = tmp2.p;
-        chebPartials.alloc((size_t)std::max<int64_t>(3 * VGRID, gridFor(n, BS)) + 16);
-        chebPartials2.alloc(RED_BLOCKS);
-        rzPart = chebPartials.p;
-    }
-    // r.z partials of the polynomial's last term, reduced to <= RED_BLOCKS values when there is one per 256-row chunk
-    auto rzReduce = [&](const double* src, int count, const double*& part, int& cnt) {
-        part = src; cnt = count;
-        if (count > 8192) {
-            hipLaunchKernelGGL(k_reduce_partials, dim3(RED_BLOCKS), dim3(BS), 0, stream, sc, src, count, chebPartials2.p);
-            part = chebPartials2.p; cnt = RED_BLOCKS;
-        }
-    };
-
-    // Fused step (default on the coded stream; PS_FUSED_R=0 keeps the five-kernel step): p.Ap = -(sum_active s.t + sum_tiles w.v
-    // + 1/2 sum uInv p^2) is complete before the St kernel starts, so that kernel forms alpha and updates r in its epilogue —
-    // A p is neither written nor read back (16 B per row less) and the step is four launches (FusedR, ps_kernels_spmv.hpp).
-    // Every St workgroup sums the partials of three producers in its prologue (up to 4096 + regions + 1024 + 1024 values, from
-    // L2): a fixed cost per iteration, against 16 B per row saved.  Measured us per iteration, four / five kernels (St on 1536
-    // workgroups, shared runs): 64^3 (0.8 M rows) 58.8 / 57.3, 96^3 (2.6 M) 93.2 / 95.6, 128^3 (5.9 M) 164.8 / 175.5, 160^3 (11.4 M)
-    // 285.9 / 309.3, 192^3 (19.4 M) 466.7 / 506.5, 256^3 (45 M) 1147 / 1248 (before shared runs) -> on from 1.2 M rows (FUSED_STEP_MIN_ROWS).  (Folding the
-    // partials 64 to 1 in the producers with a ticket per group costs more than it saves: one device-scope atomic per workgroup,
-    // +30 us per iteration with write-through stores and no fence, +650 us with __threadfence(), which flushes the XCD's L2.)
-    // PS_FUSED_R = 0 / 1 forces it off / on (on only where the kernels exist).
-    static const int fusedEnv = envInt(PS_ENV("PS_FUSED_R"), -1);
-    const bool fused = fusedEnv != 0 && (fusedEnv > 0 || n >= FUSED_STEP_MIN_ROWS) && L.fusedOk();
-    fusedStepHost = fused ? 1 : 0;
-    const int sBlocks = fused ? L.sBlocks() : 0;
-    double *fS = nullptr, *fT = nullptr, *fU = nullptr, *fR = nullptr;
-    const uint8_t* ucode = uCoded ? uCode.p : nullptr;
-    if (fused) {
-        fusedPart.alloc((size_t)sBlocks + (size_t)regionCount + VGRID + 2 * (size_t)stBF + 16);
-        fS = fusedPart.p; fT = fS + sBlocks; fU = fT + regionCount; fR = fU + VGRID;
-        L.sPart = fS; L.wvPart = fT;
-    }
-
+    DomainSolve s; int rc;
+    if (!s.solveStart(this, rc)) return rc;
+    s.chooseStepForm();
+    if (s.fused) s.fusedStart();
     HIP_CHECK(hipMemsetAsync(dotPartials3.p, 0, VGRID * sizeof(double), stream));
     // warm start (ps_set_warm_start): x0 = the carried solution, r0 = b - A x0 (pcg.h:284); from here on the PCG is the same
     // (a Picard pass of ps_set_rheology starts from the last pass's solution the same way)
     bool warm = (warmMode == PS_WARM_PREVIOUS_STEP || rheoPass > 0) && gatherWarmStart();
     warmUsedHost = warm ? 1 : 0;
-    CGScalars h{};
-    int itBase = 0;           // iterations the fp32 passes took: the fp64 loop below gets the rest of the budget
-    bool pcg64 = true;        // false: the passes used the budget up (-> BiCGStab)
-
-    // ---- mixed precision (ps_set_solve_precision; include/polystokes.h, DESIGN.md "Mixed-precision PCG"): x stays fp64; a pass runs the step
-    // below on fp32 vectors (d32 in x's place) for A d = b - A x, then x += d, and the stop rule is evaluated on the fp64 b - A x
-    if (solvePrecisionSet == PS_PRECISION_MIXED && !cheb && !slabEnabled && L.mixedOk()) {
-        solvePrecisionUsedHost = 1;
-        d32.alloc((size_t)n); p32.alloc((size_t)n); r32.alloc((size_t)n); ts32.alloc((size_t)nRows + 1);
-        if (!fused) Ap32.alloc((size_t)n);
-        L.v32 = true;
-        const int vecNT = ntLevel() >= 2 ? 1 : 0;
-        double rrStart = 0.;
-        bool resume64 = false;
-        for (int pass = 0; ; ++pass) {
-            // the true residual of the current x (fp64 operator, as k_cg_init_warm), rounded into the pass's r; its r.r and x.x: the evaluation
-            const bool haveX = warm || pass > 0;
-            if (haveX) applyOperator(x.p, Ap.p, dotPartials.p);
-            hipLaunchKernelGGL(k_cg_init_pass, dim3(vb), dim3(BS), 0, stream, (const double*)b.p, haveX ? (const double*)Ap.p : (const double*)nullptr, (const double*)x.p, dv,
-                               d32.p, r32.p, p32.p, n, dotPartials.p);
-            hipLaunchKernelGGL(k_cg_scal0_pass, dim3(1), dim3(BS), 0, stream, sc, (const double*)dotPartials.p, vb, tol, maxit, vecNT, MIXED_PASS_REDUCTION * MIXED_PASS_REDUCTION, haveX ? 1 : 0);
-            if (fused) hipLaunchKernelGGL(k_uinv_pp_f32, dim3(vb), dim3(BS), 0, stream, (const float*)p32.p, ucode, (const double*)uDict.p, (const double*)uInv.p, n, fU);
-            HIP_CHECK(hipMemcpyAsync(&h, sc, sizeof(h), hipMemcpyDeviceToHost, stream));
-            HIP_CHECK(hipStreamSynchronize(stream));
-            const double trueRR = h.rr;
-            solveError = std::sqrt(h.rre);
-            trueResidualHost = solveError;
-            if (pass > 0 && h.rre < tol * tol) { solveIterations = itBase; return PS_SUCCESS; }
-            if (h.done) {   // r = 0 exactly (b == 0: as the fp64 solve, x = 0)
-                if (!haveX) HIP_CHECK(hipMemsetAsync(x.p, 0, (size_t)n * sizeof(double), stream));
-                solveIterations = itBase;
-                return PS_SUCCESS;
-            }
-            // stagnation: the pass did not halve the true ||r|| (the floor of fp32), or the passes are used up -> fp64 PCG from this x
-            if (pass > 0 && (!(trueRR < 0.25 * rrStart) || pass == MIXED_MAX_PASSES)) { resume64 = true; break; }
-            if (itBase >= maxit) { pcg64 = false; break; }
-            rrStart = trueRR;
-            const int budget = maxit - itBase;
-            int it = 0;
-            bool finished = false;
-            while (it < budget && !finished) {
-                const int upto = std::min(budget, it + CG_BATCH);
-                for (; it < upto; ++it) {
-                    L.spmvS32(p32.p, ts32.p);
-                    L.tiles32(ts32.p);
-                    if (fused) {
-                        const FusedR fr{sc, fS, sBlocks, fT, (int)regionCount, fU, vb, dotPartials3.p, vb, it, (double*)r32.p, dv, fR, nullptr, 0., nullptr, nullptr, 0, (int)n, nullptr};
-                        L.spmvSt32(false, ts32.p, p32.p, fr);
-                        hipLaunchKernelGGL(k_cg_update_xp_u_f32, dim3(vb), dim3(BS), 0, stream, sc, (const double*)nullptr, (const double*)fR, stBF, dv ? 1 : 0, it, (const float*)r32.p, dv, d32.p,
-                                           p32.p, n, dotPartials3.p, ucode, (const double*)uDict.p, (const double*)uInv.p, fU);
-                        continue;
-                    }
-                    FusedR fr{};
-                    fr.r = (double*)Ap32.p; fr.rPart = dotPartials.p;
-                    const int pApCount = L.spmvSt32(true, ts32.p, p32.p, fr);
-                    hipLaunchKernelGGL(k_cg_update_r_f32, dim3(vb), dim3(BS), 0, stream, sc, (const double*)nullptr, (const double*)dotPartials.p, pApCount, (const double*)dotPartials3.p, vb, it,
-                                       (const float*)Ap32.p, dv, r32.p, n, dotPartialsR.p);
-                    hipLaunchKernelGGL(k_cg_update_xp_f32, dim3(vb), dim3(BS), 0, stream, sc, (const double*)nullptr, (const double*)dotPartialsR.p, vb, dv ? 1 : 0, it, (const float*)r32.p, dv,
-                                       d32.p, p32.p, n, dotPartials3.p);
-                }
-                hipLaunchKernelGGL(k_cg_check_pass, dim3(1), dim3(BS), 0, stream, sc, (const double*)dotPartials3.p, vb, it - 1);
-                HIP_CHECK(hipMemcpyAsync(&h, sc, sizeof(h), hipMemcpyDeviceToHost, stream));
-                HIP_CHECK(hipStreamSynchronize(stream));
-                if (h.done) finished = true;
-                if (!finished && interruptCb && interruptCb(interruptUser)) { interrupted = true; break; }
-            }
-            const int ran = h.done ? h.iter + 1 : it;   // the iterations whose update d holds
-            passIters.push_back(ran);
-            itBase += ran;
-            if (interrupted) { solveIterations = itBase; return PS_INCOMPLETE; }
-            hipLaunchKernelGGL(k_cg_end_pass, dim3(vb), dim3(BS), 0, stream, (const float*)d32.p, x.p, n, haveX ? 0 : 1);
-            if (!h.done) { pcg64 = false; break; }      // the budget ran out inside the pass
+    if (s.mixedAsked())
+        switch (s.mixedPasses(warm)) {
+        case Passes::Converged: return PS_SUCCESS;
+        case Passes::Interrupted: return PS_INCOMPLETE;
+        case Passes::BudgetUsed: return s.bicgstabFallback();
+        case Passes::Stagnated: solvePrecisionUsedHost = 2; warm = true;   // fp64 PCG from the passes' x, on the rest of the budget
         }
-        L.v32 = false;
-        if (resume64) { solvePrecisionUsedHost = 2; warm = true; }
-        HIP_CHECK(hipMemsetAsync(dotPartials3.p, 0, VGRID * sizeof(double), stream));
-    }
-    const int budget = maxit - itBase;
-    if (!pcg64) { h = CGScalars{}; }
-    else {
-    if (warm) {
-        applyOperator(x.p, Ap.p, dotPartials.p);
-        hipLaunchKernelGGL(k_cg_init_warm, dim3(vb), dim3(BS), 0, stream, (const double*)b.p, (const double*)Ap.p, dv, r.p, pvec.p, n, dotPartials.p);
-    } else
-    hipLaunchKernelGGL(k_cg_init_f, dim3(vb), dim3(BS), 0, stream, b.p, dv, x.p, r.p, pvec.p, n, dotPartials.p);
-    if (cheb) {   // z = M^-1 r, p = z, rsold = r.z
-        HIP_CHECK(hipMemsetAsync(sc, 0, sizeof(CGScalars), stream));   // `done` must read 0 inside the polynomial's kernels
-        double* z0 = zvec;
-        const int cnt0 = chebyshevApply(r.p, zvec, dvec, rzPart, nullptr, false, &z0);
-        if (chebInner32) hipLaunchKernelGGL(k_widen_f32, dim3(vb), dim3(BS), 0, stream, pvec.p, (const float*)z0, n);
-        else
-        HIP_CHECK(hipMemcpyAsync(pvec.p, z0, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, stream));
-        hipLaunchKernelGGL(k_sum_to, dim3(1), dim3(BS), 0, stream, rzPart, cnt0, dotPartials.p);
-        hipLaunchKernelGGL(k_cg_scal0, dim3(1), dim3(BS), 0, stream, sc, dotPartials.p, 1, tol, maxit, ntLevel() >= 2 ? 1 : 0);
-    } else
-    hipLaunchKernelGGL(k_cg_scal0, dim3(1), dim3(BS), 0, stream, sc, dotPartials.p, vb, tol, maxit, ntLevel() >= 2 ? 1 : 0);
-    // the first direction's share of p.Ap on the diagonal
-    if (fused) hipLaunchKernelGGL(k_uinv_pp, dim3(vb), dim3(BS), 0, stream, (const double*)pvec.p, ucode, (const double*)uDict.p, (const double*)uInv.p, n, fU);
-    int it = 0;
-    bool finished = false;
-    while (it < budget && !finished) {
-        const int upto = std::min(budget, it + CG_BATCH);
-        for (; it < upto; ++it) {
-            L.spmvS(0, pvec.p, ts.p);
-            L.tiles(0, ts.p);
-            if (fused && cheb) {   // St kernel: r -= alpha A p and the polynomial's first term on the new r; then terms 2..k; then x, p
-                const FusedR fr{sc, fS, sBlocks, fT, (int)regionCount, fU, vb, dotPartials3.p, vb, it, r.p, nullptr, fR, dinvF.p, 1. / chebTheta(), zvec, nullptr, 0, (int)n, nullptr};
-                L.spmvSt(3, ts.p, pvec.p, nullptr, nullptr, nullptr, nullptr, &fr);
-                double* zfin = zvec;
-                const int c2 = chebyshevApply(r.p, zvec, dvec, rzPart, sc, true, &zfin);
-                const double* part; int cnt;
-                if (c2 > 0) rzReduce(rzPart, c2, part, cnt); else { part = fR + stBF; cnt = stBF; }
-                if (chebInner32)
-                hipLaunchKernelGGL(k_cg_update_xp_z_u<float>, dim3(vb), dim3(BS), 0, stream, sc, (const double*)fR, stBF, part, cnt, it, (const float*)zfin,
-                                   x.p, pvec.p, n, dotPartials3.p, ucode, (const double*)uDict.p, (const double*)uInv.p, fU);
-                else
-                hipLaunchKernelGGL(k_cg_update_xp_z_u<double>, dim3(vb), dim3(BS), 0, stream, sc, (const double*)fR, stBF, part, cnt, it, (const double*)zfin,
-                                   x.p, pvec.p, n, dotPartials3.p, ucode, (const double*)uDict.p, (const double*)uInv.p, fU);
-                continue;
-            }
-            if (fused) {
-                const FusedR fr{sc, fS, sBlocks, fT, (int)regionCount, fU, vb, dotPartials3.p, vb, it, r.p, dv, fR, nullptr, 0., nullptr, nullptr, 0, (int)n, nullptr};
-                L.spmvSt(3, ts.p, pvec.p, nullptr, nullptr, nullptr, nullptr, &fr);
-                hipLaunchKernelGGL(k_cg_update_xp_u, dim3(vb), dim3(BS), 0, stream, sc, (const double*)nullptr, (const double*)fR, stBF, dv ? 1 : 0, it, (const double*)r.p, dv, x.p,
-                                   pvec.p, n, dotPartials3.p, ucode, (const double*)uDict.p, (const double*)uInv.p, fU);
-                continue;
-            }
-            L.spmvSt(0, ts.p, pvec.p, nullptr, Ap.p, dotPartials.p);
-            const double* pApPart = dotPartials.p;
-            int pApCount = stBlocks;
-            if (stBlocks > 8192) {   // one-shot St kernel: one partial per 256 rows, reduced in two stages
-                hipLaunchKernelGGL(k_reduce_partials, dim3(RED_BLOCKS), dim3(BS), 0, stream, sc, dotPartials.p, stBlocks, dotPartials2.p);
-                pApPart = dotPartials2.p; pApCount = RED_BLOCKS;
-            }
-            hipLaunchKernelGGL(k_cg_update_r, dim3(vb), dim3(BS), 0, stream, sc, (const double*)nullptr, pApPart, pApCount, dotPartials3.p, vb, it, Ap.p, dv,
-                               r.p, n, dotPartialsR.p);
-            if (cheb) {
-                const double* part; int cnt;
-                double* zfin = zvec;
-                rzReduce(rzPart, chebyshevApply(r.p, zvec, dvec, rzPart, sc, false, &zfin), part, cnt);
-                if (chebInner32)
-                hipLaunchKernelGGL(k_cg_update_xp_z<float>, dim3(vb), dim3(BS), 0, stream, sc, (const double*)dotPartialsR.p, vb, part, cnt, it, (const float*)zfin,
-                                   x.p, pvec.p, n, dotPartials3.p);
-                else
-                hipLaunchKernelGGL(k_cg_update_xp_z<double>, dim3(vb), dim3(BS), 0, stream, sc, (const double*)dotPartialsR.p, vb, part, cnt, it, (const double*)zfin,
-                                   x.p, pvec.p, n, dotPartials3.p);
-            } else
-            hipLaunchKernelGGL(k_cg_update_xp, dim3(vb), dim3(BS), 0, stream, sc, (const double*)nullptr, dotPartialsR.p, vb, dv ? 1 : 0, it, r.p, dv, x.p,
-                               pvec.p, n, dotPartials3.p);
-        }
-        hipLaunchKernelGGL(k_cg_check, dim3(1), dim3(BS), 0, stream, sc, (const double*)nullptr, dotPartials3.p, vb, it - 1);
-        HIP_CHECK(hipMemcpyAsync(&h, sc, sizeof(h), hipMemcpyDeviceToHost, stream));
-        HIP_CHECK(hipStreamSynchronize(stream));
-        if (h.done) finished = true;
-        if (!finished && interruptCb && interruptCb(interruptUser)) { interrupted = true; break; }
-    }
-    if (interrupted) { solveIterations = itBase + it; solveError = std::sqrt(h.rre); return PS_INCOMPLETE; }
-    }
-    solveIterations = h.done ? itBase + h.iter : maxit;
-    if (pcg64) solveError = std::sqrt(h.rre);
+    s.pcgStart(warm);
+    const BatchRun b = runBatches(this, s.sc, s.maxit - s.itBase, s.h, [&](int it) { s.step(it); },
+                                  [&](int last) { s.run(k_cg_check, 1, s.sc, nullptr, dotPartials3.p, s.vb, last); });
+    solveError = std::sqrt(b.h.rre);
+    if (b.interrupted) { solveIterations = s.itBase + b.it; return PS_INCOMPLETE; }
+    solveIterations = b.h.done ? s.itBase + b.h.iter : s.maxit;
     if (solvePrecisionUsedHost == 2) trueResidualHost = solveError;   // (the fp64 recurrence's value, as any fp64 solve reports)
-
-    if (solveIterations == maxit) {
-        usedBiCGStab = 1;          // the BiCGStab fallback
-        tmp1.alloc((size_t)n); tmp2.alloc((size_t)n); tmp3.alloc((size_t)n); tmp4.alloc((size_t)n); tmp5.alloc((size_t)n);
-        solveIterations = bicgstab(BiCGVecs<double*>{x.p, r.p, pvec.p, b.p, Ap.p, tmp1.p, tmp2.p, tmp3.p, tmp4.p, tmp5.p}, maxit, tol, solveError,
-            [&](double* in, double* out) { applyOperator(in, out, dotPartials.p); },
-            [&](const double* a, const double* bb) {
-                hipLaunchKernelGGL(k_dot, dim3(vb), dim3(BS), 0, stream, a, bb, n, dotPartials.p);
-                hipLaunchKernelGGL(k_sum1, dim3(1), dim3(BS), 0, stream, dotPartials.p, vb, dotPartials.p + 3 * VGRID);
-                double out;
-                HIP_CHECK(hipMemcpyAsync(&out, dotPartials.p + 3 * VGRID, sizeof(double), hipMemcpyDeviceToHost, stream));
-                HIP_CHECK(hipStreamSynchronize(stream));
-                return out;
-            },
-            [&](double* out, double ca, const double* a, double cb, const double* bb, double cc, const double* c3) {
-                hipLaunchKernelGGL(k_lin, dim3(vb), dim3(BS), 0, stream, out, ca, a, cb, bb, cc, c3, n);
-            },
-            [&](double* v) { HIP_CHECK(hipMemsetAsync(v, 0, (size_t)n * sizeof(double), stream)); });
-    }
-    return solveIterations == maxit ? PS_NOCONVERGE : PS_SUCCESS;
+    return solveIterations == s.maxit ? s.bicgstabFallback() : PS_SUCCESS;
 }
 
 // ---- warm start (ps_set_warm_start; DESIGN.md "Warm start") ----
@@ -1043,14 +1099,7 @@ int ps_context::solveEigenCG() {
     const int vb = dotBlocks(n);
     tmp1.alloc((size_t)n);
     double* z = tmp1.p;
-    auto dotH = [&](const double* a, const double* bb) {
-        hipLaunchKernelGGL(k_dot, dim3(vb), dim3(BS), 0, stream, a, bb, n, dotPartials.p);
-        hipLaunchKernelGGL(k_sum1, dim3(1), dim3(BS), 0, stream, dotPartials.p, vb, dotPartials.p + 3 * VGRID);
-        double out;
-        HIP_CHECK(hipMemcpyAsync(&out, dotPartials.p + 3 * VGRID, sizeof(double), hipMemcpyDeviceToHost, stream));
-        HIP_CHECK(hipStreamSynchronize(stream));
-        return out;
-    };
+    auto dotH = [&](const double* a, const double* bb) { return hostDot(this, a, bb, n); };
     auto lin = [&](double* out, double ca, const double* a, double cb, const double* bb) {
         hipLaunchKernelGGL(k_lin, dim3(vb), dim3(BS), 0, stream, out, ca, a, cb, bb, 0., (const double*)nullptr, n);
     };
@@ -1160,7 +1209,7 @@ void ps_bench_launch(ps_context* c, const std::string& k, const double* x, doubl
         const uint8_t* ucode = c->uCoded ? c->uCode.p : nullptr;
         if (base == "spmv_St_r") {   // the St kernel of the four-kernel step: r (scratch) -= 0 * A x in the epilogue
             if (!L.fusedOk()) throw Error("no fused step on this system");
-            const FusedR fr{scratch.p, ones.p, VGRID, zeros.p, 0, zeros.p, 0, ones.p, 0, 0, c->tmp5.p, dvf, c->dotPartials.p, nullptr, 0., nullptr, nullptr, 0, (int)n, nullptr};
+            const FusedR fr = fusedSingle(scratch.p, {ones.p, VGRID, zeros.p, 0, zeros.p, 0, ones.p, 0}, 0, c->tmp5.p, c->dotPartials.p, (int)n, FusedZ::jacobi(dvf));
             L.spmvSt(3, c->ts.p, x, nullptr, nullptr, nullptr, nullptr, &fr);
         }
         else if (base == "cg_update_xp_u")
