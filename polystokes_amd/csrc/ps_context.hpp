@@ -373,17 +373,23 @@ struct ps_context {
     // both.  Only one kind of sample crosses a diagonal: the edge stress that lives on both cut planes (XY / XZ / YZ edges on the corner line), which
     // the skin rows of a tile that ends at both planes touch (a tile's rows belong to the tile's owner whatever plane they lie on) — so a diagonal
     // link has an upper halo list and a lower own list, the other two are empty.
+    // One table: cut[l][side], side 0 = the neighbour below, side 1 = the one above.  Only buildHaloLists writes a list's n and hash.
     static constexpr int NLINK = 6;
-    ps::DevBuf<int32_t> listLowHalo[NLINK], listLowOwn[NLINK], listUpHalo[NLINK], listUpOwn[NLINK];
-    int64_t nLowHalo[NLINK] = {0, 0, 0, 0, 0, 0}, nLowOwn[NLINK] = {0, 0, 0, 0, 0, 0}, nUpHalo[NLINK] = {0, 0, 0, 0, 0, 0}, nUpOwn[NLINK] = {0, 0, 0, 0, 0, 0};
-    ps::DevBuf<double> sendLo[NLINK], sendUp[NLINK], recvLo[NLINK], recvUp[NLINK], redbuf;
+    struct CutList { ps::DevBuf<int32_t> idx; int64_t n = 0; uint64_t hash = 0; };   // hash: order-sensitive, of the list's global keys
+    struct Cut {
+        CutList own, halo;
+        ps::DevBuf<double> send, recv;
+        std::vector<int32_t> hostOwn;       // host copy of own.idx: Dist::buildFixup merges them per DOF
+        const CutList& list(bool ownKind) const { return ownKind ? own : halo; }
+    };
+    Cut cut[NLINK][2];
+    ps::DevBuf<double> redbuf;
+    void ensureBuffers(int l, size_t doubles) { for (Cut& k : cut[l]) k.send.alloc(doubles); for (Cut& k : cut[l]) k.recv.alloc(doubles); }
     static void linkAxes(int l, int& a, int& b) { a = l < 3 ? l : (l == 5 ? 1 : 0); b = l < 3 ? -1 : (l == 3 ? 1 : 2); }
     int axisStride(int a) const { return a == 0 ? 1 : (a == 1 ? brick.dims[0] : brick.dims[0] * brick.dims[1]); }
-    bool linkLower(int l) const { int a, b; linkAxes(l, a, b); return brick.hasLower[a] && (b < 0 || brick.hasLower[b]); }
-    bool linkUpper(int l) const { int a, b; linkAxes(l, a, b); return brick.hasUpper[a] && (b < 0 || brick.hasUpper[b]); }
-    int nbrLo(int l) const { int a, b; linkAxes(l, a, b); return linkLower(l) ? brick.rank - axisStride(a) - (b >= 0 ? axisStride(b) : 0) : -1; }
-    int nbrUp(int l) const { int a, b; linkAxes(l, a, b); return linkUpper(l) ? brick.rank + axisStride(a) + (b >= 0 ? axisStride(b) : 0) : -1; }
-    int64_t exchangeEntries() const { int64_t n = 0; for (int a = 0; a < NLINK; ++a) n += nLowOwn[a] + nUpOwn[a] + nLowHalo[a] + nUpHalo[a]; return n; }
+    bool linked(int l, int side) const { int a, b; linkAxes(l, a, b); const int32_t* has = side ? brick.hasUpper : brick.hasLower; return has[a] && (b < 0 || has[b]); }
+    int nbr(int l, int side) const { int a, b; linkAxes(l, a, b); return linked(l, side) ? brick.rank + (side ? 1 : -1) * (axisStride(a) + (b >= 0 ? axisStride(b) : 0)) : -1; }
+    int64_t exchangeEntries() const { int64_t n = 0; for (const auto& l : cut) for (const Cut& k : l) n += k.own.n + k.halo.n; return n; }
     // Overlap of the halo exchanges with the rows that do not need them (ps_dist.hpp: Dist::solve).  Chunk lists of the row-per-lane
     // kernels: [0] S chunks without a halo column, [1] S chunks with one; [2] St chunks holding halo rows with entries (their A p goes
     // to the neighbour), [3] St chunks of owned rows only.  St chunks of halo rows without entries are in neither: never launched.
@@ -395,7 +401,6 @@ struct ps_context {
     // what one distributed solve did (ps_dist_stats): bytes per iteration over the cuts, sampled transport / all-reduce times
     double distStats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     ps::DevBuf<int32_t> labelFlags;          // Dist::exchangeLabels: labels changed, REDUCED cells without a component
-    std::vector<int32_t> hostOwnList[2 * NLINK];   // host copies of listLowOwn / listUpOwn (index 2 l / 2 l + 1): Dist::buildFixup merges them per DOF
     ps::DevBuf<int32_t> fixDof, fixSrc;      // the merged fix-up of the fused step (k_dist_fixup_merged): DOFs that receive contributions, their sources
     ps::DevBuf<const double*> fixBufs;       // ... and the table of the twelve receive buffers
     int64_t nFix = 0;
@@ -411,7 +416,6 @@ struct ps_context {
     int64_t haloLabelChanges = 0;            // halo cells whose label the owners' exchange changed in the last setup (both passes)
     void* rcclComm = nullptr;                // ncclComm_t when one process per GPU
     void* hostComm = nullptr;                // host-staged TCP transport (ps_comm_init_tcp): same algorithm without RCCL
-    uint64_t hashLowHalo[NLINK] = {0, 0, 0, 0, 0, 0}, hashLowOwn[NLINK] = {0, 0, 0, 0, 0, 0}, hashUpHalo[NLINK] = {0, 0, 0, 0, 0, 0}, hashUpOwn[NLINK] = {0, 0, 0, 0, 0, 0};   // order-sensitive hashes of the lists' global keys
     ps::DevBuf<ps::CGScalars> benchScal;     // scratch of ps_bench_kernel
     ps::DevBuf<double> benchOnes, benchZeros;
     bool ownsStream = true;

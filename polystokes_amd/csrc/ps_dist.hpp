@@ -289,15 +289,15 @@ struct HostComm {
     int rank = 0, world = 1;
     int fdListen = -1, fdRoot = -1;
     static constexpr int NL = ps_context::NLINK;
-    int fdLo[NL] = {-1, -1, -1, -1, -1, -1}, fdUp[NL] = {-1, -1, -1, -1, -1, -1};   // the neighbour below / above of every link (faces 0..2, diagonals 3..5; connected once the brick is known)
-    int nbrLo[NL] = {-1, -1, -1, -1, -1, -1}, nbrUp[NL] = {-1, -1, -1, -1, -1, -1};
+    int fd[NL][2], nbr[NL][2];          // the neighbour below / above of every link (faces 0..2, diagonals 3..5; connected once the brick is known)
+    HostComm() { for (int l = 0; l < NL; ++l) for (int s = 0; s < 2; ++s) fd[l][s] = nbr[l][s] = -1; }
     std::string host; int basePort = 0;
     std::vector<int> fdLeaf;            // rank 0: connection of every other rank (index = rank)
     std::vector<std::array<int, 3>> pending;   // accepted connections nobody has asked for yet: (fd, rank, kind)
     std::vector<double> hs[2 * NL], hr[2 * NL];
     ~HostComm() {
         for (int fd : {fdListen, fdRoot}) if (fd >= 0) ::close(fd);
-        for (int a = 0; a < NL; ++a) { if (fdLo[a] >= 0) ::close(fdLo[a]); if (fdUp[a] >= 0) ::close(fdUp[a]); }
+        for (auto& l : fd) for (int f : l) if (f >= 0) ::close(f);
         for (int fd : fdLeaf) if (fd >= 0) ::close(fd);
         for (auto& q : pending) ::close(q[0]);
     }
@@ -368,24 +368,24 @@ struct HostComm {
         if (r > 0) fdRoot = connectTo(host.c_str(), basePort, r, 1);
         else for (int q = 1; q < w; ++q) fdLeaf[(size_t)q] = acceptFrom(q, 1);
     }
-    // links to the face neighbours (lo[a] / up[a]: their ranks, -1 = none): a rank connects to its lower neighbours and accepts its upper ones
-    void connectNeighbours(const int* lo, const int* up) {
-        bool same = true;
-        for (int a = 0; a < NL; ++a) same = same && lo[a] == nbrLo[a] && up[a] == nbrUp[a];
-        if (same) return;
-        for (int a = 0; a < NL; ++a) {
-            if (fdLo[a] >= 0) { ::close(fdLo[a]); fdLo[a] = -1; }
-            if (fdUp[a] >= 0) { ::close(fdUp[a]); fdUp[a] = -1; }
-            nbrLo[a] = lo[a]; nbrUp[a] = up[a];
-        }
-        for (int a = 0; a < NL; ++a) if (lo[a] >= 0) fdLo[a] = connectTo(host.c_str(), basePort + lo[a], rank, 10 + a);
-        for (int a = 0; a < NL; ++a) if (up[a] >= 0) fdUp[a] = acceptFrom(up[a], 10 + a);
+    // links to the neighbours (nb[l][side]: their ranks, -1 = none): a rank connects to its lower neighbours and accepts its upper ones
+    void connectNeighbours(const int (*nb)[2]) {
+        if (std::memcmp(nb, nbr, sizeof(nbr)) == 0) return;
+        for (int l = 0; l < NL; ++l)
+            for (int s = 0; s < 2; ++s) {
+                if (fd[l][s] >= 0) { ::close(fd[l][s]); fd[l][s] = -1; }
+                nbr[l][s] = nb[l][s];
+            }
+        for (int l = 0; l < NL; ++l) if (nbr[l][0] >= 0) fd[l][0] = connectTo(host.c_str(), basePort + nbr[l][0], rank, 10 + l);
+        for (int l = 0; l < NL; ++l) if (nbr[l][1] >= 0) fd[l][1] = acceptFrom(nbr[l][1], 10 + l);
     }
-    // neighbour exchange along one axis, ordered so that the chain of ranks along it cannot deadlock: with the lower neighbour receive
-    // first, with the upper send first
-    void exchange(int a, const double* sLo, size_t nsLo, double* rLo, size_t nrLo, const double* sUp, size_t nsUp, double* rUp, size_t nrUp) {
-        if (fdLo[a] >= 0) { if (nrLo) recvAll(fdLo[a], rLo, nrLo * 8); if (nsLo) sendAll(fdLo[a], sLo, nsLo * 8); }
-        if (fdUp[a] >= 0) { if (nsUp) sendAll(fdUp[a], sUp, nsUp * 8); if (nrUp) recvAll(fdUp[a], rUp, nrUp * 8); }
+    // neighbour exchange over one link (hs / hr[2 l + side], ns / nr[side] doubles), ordered so that the chain of ranks along it cannot
+    // deadlock: with the lower neighbour receive first, with the upper send first
+    void exchange(int l, const int64_t* ns, const int64_t* nr) {
+        auto snd = [&](int s) { if (ns[s]) sendAll(fd[l][s], hs[2 * l + s].data(), (size_t)ns[s] * 8); };
+        auto rcv = [&](int s) { if (nr[s]) recvAll(fd[l][s], hr[2 * l + s].data(), (size_t)nr[s] * 8); };
+        if (fd[l][0] >= 0) { rcv(0); snd(0); }
+        if (fd[l][1] >= 0) { snd(1); rcv(1); }
     }
     void allreduceSum(double* v, int count) {
         if (world == 1) return;
@@ -432,89 +432,94 @@ struct Dist {
         HIP_CHECK(hipEventRecord(c->distEv[ev], from));
         HIP_CHECK(hipStreamWaitEvent(to, c->distEv[ev], 0));
     }
-    // sizes: kind 0 = x exchange (send own layers, receive halo), kind 1 = y exchange (send halo contributions, receive for own); every
-    // axis with a neighbour, all of them in ONE group of sends and receives (each face neighbour is its own xGMI link)
-    static int64_t nSendLo(const ps_context* c, int kind, int a) { return c->linkLower(a) ? (kind == 0 ? c->nLowOwn[a] : c->nLowHalo[a]) : 0; }
-    static int64_t nSendUp(const ps_context* c, int kind, int a) { return c->linkUpper(a) ? (kind == 0 ? c->nUpOwn[a] : c->nUpHalo[a]) : 0; }
-    static int64_t nRecvLo(const ps_context* c, int kind, int a) { return c->linkLower(a) ? (kind == 0 ? c->nLowHalo[a] : c->nLowOwn[a]) : 0; }
-    static int64_t nRecvUp(const ps_context* c, int kind, int a) { return c->linkUpper(a) ? (kind == 0 ? c->nUpHalo[a] : c->nUpOwn[a]) : 0; }
-    void transport(int kind, bool onComm = false, int only = -1) {   // only >= 0: that axis alone
+    static constexpr int NL = ps_context::NLINK;
+    // f(l, side) over both sides of every link, or of the link `only` alone (only >= 0), in the order 2 * l + side
+    template <class F>
+    static void eachSide(int only, F&& f) { for (int l = 0; l < NL; ++l) if (only < 0 || l == only) for (int s = 0; s < 2; ++s) f(l, s); }
+    // What one transport moves, in doubles per side of every link (0 for a side without a neighbour).  The exchanges of the solve take
+    // it from the lists (every axis with a neighbour, all of them in ONE group of sends and receives: each face neighbour is its own xGMI
+    // link); the setup's handshakes ship a few doubles of their own through the same buffers.
+    struct Msg { int64_t send[NL][2] = {}, recv[NL][2] = {}; };
+    static Msg listsMsg(const ps_context* c, bool sendOwn) {
+        Msg m;
+        eachSide(-1, [&](int l, int s) { if (c->linked(l, s)) { m.send[l][s] = c->cut[l][s].list(sendOwn).n; m.recv[l][s] = c->cut[l][s].list(!sendOwn).n; } });
+        return m;
+    }
+    static Msg valuesMsg(const ps_context* c) { return listsMsg(c, true); }     // x exchange: send own layers, receive halo
+    static Msg contribMsg(const ps_context* c) { return listsMsg(c, false); }   // y exchange: send halo contributions, receive for own
+    static Msg evenMsg(const ps_context* c, int64_t n) {                        // n doubles each way across every cut
+        Msg m;
+        eachSide(-1, [&](int l, int s) { if (c->linked(l, s)) m.send[l][s] = m.recv[l][s] = n; });
+        return m;
+    }
+    // send buffers -> the neighbours' receive buffers; msgOf(rank) = that rank's Msg (in-process: every rank's from its own table)
+    template <class MsgOf>
+    void transport(MsgOf&& msgOf, bool onComm = false, int only = -1) {   // only >= 0: that link alone
         if (useRccl) {
             ps_context* c = R[0];
+            const Msg m = msgOf(c);
             hipStream_t st = cs(c, onComm);
             Rccl& L = rccl();
             ncclCheck(L.GroupStart(), "ncclGroupStart");
-            for (int a = 0; a < ps_context::NLINK; ++a) {
-                if (only >= 0 && a != only) continue;
-                const int64_t sLo = nSendLo(c, kind, a), sUp = nSendUp(c, kind, a), rLo = nRecvLo(c, kind, a), rUp = nRecvUp(c, kind, a);
-                if (sLo) ncclCheck(L.Send(c->sendLo[a].p, (size_t)sLo, NCCL_DOUBLE, c->nbrLo(a), c->rcclComm, st), "ncclSend");
-                if (rLo) ncclCheck(L.Recv(c->recvLo[a].p, (size_t)rLo, NCCL_DOUBLE, c->nbrLo(a), c->rcclComm, st), "ncclRecv");
-                if (sUp) ncclCheck(L.Send(c->sendUp[a].p, (size_t)sUp, NCCL_DOUBLE, c->nbrUp(a), c->rcclComm, st), "ncclSend");
-                if (rUp) ncclCheck(L.Recv(c->recvUp[a].p, (size_t)rUp, NCCL_DOUBLE, c->nbrUp(a), c->rcclComm, st), "ncclRecv");
-            }
+            eachSide(only, [&](int l, int s) {   // per link: send lower, receive lower, send upper, receive upper
+                const ps_context::Cut& k = c->cut[l][s];
+                if (m.send[l][s]) ncclCheck(L.Send(k.send.p, (size_t)m.send[l][s], NCCL_DOUBLE, c->nbr(l, s), c->rcclComm, st), "ncclSend");
+                if (m.recv[l][s]) ncclCheck(L.Recv(k.recv.p, (size_t)m.recv[l][s], NCCL_DOUBLE, c->nbr(l, s), c->rcclComm, st), "ncclRecv");
+            });
             ncclCheck(L.GroupEnd(), "ncclGroupEnd");
             return;
         }
         if (useTcp) {
             ps_context* c = R[0];
+            const Msg m = msgOf(c);
             HostComm& H = *hc();
             hipStream_t st = cs(c, onComm);
-            for (int a = 0; a < ps_context::NLINK; ++a) {
-                if (only >= 0 && a != only) continue;
-                const size_t sLo = (size_t)nSendLo(c, kind, a), sUp = (size_t)nSendUp(c, kind, a);
-                H.hs[2 * a].resize(sLo + 1); H.hs[2 * a + 1].resize(sUp + 1);
-                H.hr[2 * a].resize((size_t)nRecvLo(c, kind, a) + 1); H.hr[2 * a + 1].resize((size_t)nRecvUp(c, kind, a) + 1);
-                if (sLo) HIP_CHECK(hipMemcpyAsync(H.hs[2 * a].data(), c->sendLo[a].p, sLo * 8, hipMemcpyDeviceToHost, st));
-                if (sUp) HIP_CHECK(hipMemcpyAsync(H.hs[2 * a + 1].data(), c->sendUp[a].p, sUp * 8, hipMemcpyDeviceToHost, st));
-            }
+            eachSide(only, [&](int l, int s) {
+                H.hs[2 * l + s].resize((size_t)m.send[l][s] + 1); H.hr[2 * l + s].resize((size_t)m.recv[l][s] + 1);
+                if (m.send[l][s]) HIP_CHECK(hipMemcpyAsync(H.hs[2 * l + s].data(), c->cut[l][s].send.p, (size_t)m.send[l][s] * 8, hipMemcpyDeviceToHost, st));
+            });
             HIP_CHECK(hipStreamSynchronize(st));
-            for (int a = 0; a < ps_context::NLINK; ++a)
-                if (only < 0 || a == only) H.exchange(a, H.hs[2 * a].data(), (size_t)nSendLo(c, kind, a), H.hr[2 * a].data(), (size_t)nRecvLo(c, kind, a), H.hs[2 * a + 1].data(),
-                           (size_t)nSendUp(c, kind, a), H.hr[2 * a + 1].data(), (size_t)nRecvUp(c, kind, a));
-            for (int a = 0; a < ps_context::NLINK; ++a) {
-                if (only >= 0 && a != only) continue;
-                const size_t rLo = (size_t)nRecvLo(c, kind, a), rUp = (size_t)nRecvUp(c, kind, a);
-                if (rLo) HIP_CHECK(hipMemcpyAsync(c->recvLo[a].p, H.hr[2 * a].data(), rLo * 8, hipMemcpyHostToDevice, st));
-                if (rUp) HIP_CHECK(hipMemcpyAsync(c->recvUp[a].p, H.hr[2 * a + 1].data(), rUp * 8, hipMemcpyHostToDevice, st));
-            }
+            for (int l = 0; l < NL; ++l) if (only < 0 || l == only) H.exchange(l, m.send[l], m.recv[l]);
+            eachSide(only, [&](int l, int s) {
+                if (m.recv[l][s]) HIP_CHECK(hipMemcpyAsync(c->cut[l][s].recv.p, H.hr[2 * l + s].data(), (size_t)m.recv[l][s] * 8, hipMemcpyHostToDevice, st));
+            });
             HIP_CHECK(hipStreamSynchronize(st));   // the host buffers are reused by the next exchange
             return;
         }
-        for (size_t q = 0; q < R.size(); ++q) {   // in-process ranks share one stream: plain device copies
-            ps_context* c = R[q];
-            for (int a = 0; a < ps_context::NLINK; ++a) {
-                if (only >= 0 && a != only) continue;
-                const int64_t sLo = nSendLo(c, kind, a), sUp = nSendUp(c, kind, a);
-                if (sLo) HIP_CHECK(hipMemcpyAsync(R[(size_t)c->nbrLo(a)]->recvUp[a].p, c->sendLo[a].p, (size_t)sLo * 8, hipMemcpyDeviceToDevice, c->stream));
-                if (sUp) HIP_CHECK(hipMemcpyAsync(R[(size_t)c->nbrUp(a)]->recvLo[a].p, c->sendUp[a].p, (size_t)sUp * 8, hipMemcpyDeviceToDevice, c->stream));
-            }
+        for (ps_context* c : R) {   // in-process ranks share one stream: plain device copies, into the neighbour's opposite side
+            const Msg m = msgOf(c);
+            eachSide(only, [&](int l, int s) {
+                if (m.send[l][s]) HIP_CHECK(hipMemcpyAsync(R[(size_t)c->nbr(l, s)]->cut[l][1 - s].recv.p, c->cut[l][s].send.p, (size_t)m.send[l][s] * 8, hipMemcpyDeviceToDevice, c->stream));
+            });
         }
     }
     // pack / unpack of one rank's lists along axis a (the two cuts of an axis in one launch: their lists are disjoint — a brick is at
     // least one 16-cell block thick).  own = true: the layers of mine the neighbours' rows touch; false: theirs my rows touch.
+    // (the kernels that take both sides of a link: A = side 0, below; B = side 1, above)
     void pack(ps_context* c, bool own, const double* v, hipStream_t st, int a) {
-        const int64_t nA = own ? c->nLowOwn[a] : c->nLowHalo[a], nB = own ? c->nUpOwn[a] : c->nUpHalo[a];
+        const ps_context::Cut &A = c->cut[a][0], &B = c->cut[a][1];
+        const int64_t nA = A.list(own).n, nB = B.list(own).n;
         if (nA + nB > 0)
-            hipLaunchKernelGGL(k_pack2, dim3(gridFor(nA + nB, BS)), dim3(BS), 0, st, (own ? c->listLowOwn[a] : c->listLowHalo[a]).p, nA, c->sendLo[a].p,
-                               (own ? c->listUpOwn[a] : c->listUpHalo[a]).p, nB, c->sendUp[a].p, v);
+            hipLaunchKernelGGL(k_pack2, dim3(gridFor(nA + nB, BS)), dim3(BS), 0, st, A.list(own).idx.p, nA, A.send.p, B.list(own).idx.p, nB, B.send.p, v);
     }
     template <bool ADD>
     void unpack(ps_context* c, bool own, double* v, hipStream_t st, int a) {
-        const int64_t nA = own ? c->nLowOwn[a] : c->nLowHalo[a], nB = own ? c->nUpOwn[a] : c->nUpHalo[a];
+        const ps_context::Cut &A = c->cut[a][0], &B = c->cut[a][1];
+        const int64_t nA = A.list(own).n, nB = B.list(own).n;
         if (nA + nB > 0)
-            hipLaunchKernelGGL(k_unpack2<ADD>, dim3(gridFor(nA + nB, BS)), dim3(BS), 0, st, (own ? c->listLowOwn[a] : c->listLowHalo[a]).p, nA, c->recvLo[a].p,
-                               (own ? c->listUpOwn[a] : c->listUpHalo[a]).p, nB, c->recvUp[a].p, v);
+            hipLaunchKernelGGL(k_unpack2<ADD>, dim3(gridFor(nA + nB, BS)), dim3(BS), 0, st, A.list(own).idx.p, nA, A.recv.p, B.list(own).idx.p, nB, B.recv.p, v);
     }
+    static int64_t nOwn(const ps_context* c, int l) { return c->cut[l][0].own.n + c->cut[l][1].own.n; }   // the own entries of a link, both sides
     // all axes of one rank at once (the one-round mode): own = true: my cut layers -> send buffers (pack) / false: my halo samples
     Lists6 lists6(ps_context* c, bool own, bool send) const {
         Lists6 L;
         int64_t run = 0;
-        for (int a = 0; a < ps_context::NLINK; ++a) {
-            L.list[2 * a] = (own ? c->listLowOwn[a] : c->listLowHalo[a]).p; L.list[2 * a + 1] = (own ? c->listUpOwn[a] : c->listUpHalo[a]).p;
-            L.buf[2 * a] = send ? c->sendLo[a].p : c->recvLo[a].p; L.buf[2 * a + 1] = send ? c->sendUp[a].p : c->recvUp[a].p;
-            run += own ? c->nLowOwn[a] : c->nLowHalo[a]; L.end[2 * a] = run;
-            run += own ? c->nUpOwn[a] : c->nUpHalo[a]; L.end[2 * a + 1] = run;
-        }
+        eachSide(-1, [&](int l, int s) {
+            const ps_context::Cut& k = c->cut[l][s];
+            L.list[2 * l + s] = k.list(own).idx.p;
+            L.buf[2 * l + s] = send ? k.send.p : k.recv.p;
+            run += k.list(own).n; L.end[2 * l + s] = run;
+        });
         return L;
     }
     void packAll(ps_context* c, bool own, const double* v, hipStream_t st) {
@@ -525,7 +530,7 @@ struct Dist {
         const Lists6 L = lists6(c, false, false);
         if (L.end[NLIST - 1] > 0) hipLaunchKernelGGL(k_unpack6, dim3(gridFor(L.end[NLIST - 1], BS)), dim3(BS), 0, st, L, v);
     }
-    bool axisUsed(int a) const { for (const ps_context* c : R) if (c->linkLower(a) || c->linkUpper(a)) return true; return false; }   // (a: a link, 0 .. NLINK - 1)
+    bool axisUsed(int a) const { for (const ps_context* c : R) if (c->linked(a, 0) || c->linked(a, 1)) return true; return false; }   // (a: a link, 0 .. NLINK - 1)
     // The exchanges run axis after axis, each one forwarding what the previous ones brought (ps_grid.hip: buildHaloLists): values x, y, z;
     // contributions z, y, x.  With cuts along one axis only (slabs) that is one pack / transport / unpack, as before.
     // values of the cut layers -> the neighbours' halo copies, on the stream `onComm` selects
@@ -540,7 +545,7 @@ struct Dist {
     void buildDirectExchange() {
         ps_context* c0 = R[0];
         c0->nXseg[0] = c0->nXseg[1] = 0;
-        if (!inProcess() || forwarding() || R.size() * 2 * ps_context::NLINK > (size_t)BS) return;
+        if (!inProcess() || forwarding() || R.size() * 2 * NL > (size_t)BS) return;
         for (int kind = 0; kind < 2; ++kind) {
             std::vector<XSeg> segs;
             int blk = 0;
@@ -549,19 +554,14 @@ struct Dist {
                 segs.push_back(XSeg{src, sl, dst, dl, (int32_t)n, blk});
                 blk += gridFor(n, BS);
             };
-            for (ps_context* c : R)
-                for (int a = 0; a < ps_context::NLINK; ++a) {
-                    if (c->linkLower(a)) {
-                        ps_context* nb = R[(size_t)c->nbrLo(a)];
-                        if (kind == 0) add(c->pvec.p, c->listLowOwn[a].p, nb->pvec.p, nb->listUpHalo[a].p, c->nLowOwn[a]);
-                        else add(c->Ap.p, c->listLowHalo[a].p, nb->recvUp[a].p, nullptr, c->nLowHalo[a]);
-                    }
-                    if (c->linkUpper(a)) {
-                        ps_context* nb = R[(size_t)c->nbrUp(a)];
-                        if (kind == 0) add(c->pvec.p, c->listUpOwn[a].p, nb->pvec.p, nb->listLowHalo[a].p, c->nUpOwn[a]);
-                        else add(c->Ap.p, c->listUpHalo[a].p, nb->recvLo[a].p, nullptr, c->nUpHalo[a]);
-                    }
-                }
+            for (ps_context* c : R)   // (segments by rank, link, lower before upper: the block numbering of k_xchg_direct follows them)
+                eachSide(-1, [&](int l, int s) {
+                    if (!c->linked(l, s)) return;
+                    ps_context* nb = R[(size_t)c->nbr(l, s)];
+                    const ps_context::Cut &mine = c->cut[l][s], &theirs = nb->cut[l][1 - s];   // (the neighbour's opposite side)
+                    if (kind == 0) add(c->pvec.p, mine.own.idx.p, nb->pvec.p, theirs.halo.idx.p, mine.own.n);
+                    else add(c->Ap.p, mine.halo.idx.p, theirs.recv.p, nullptr, mine.halo.n);
+                });
             if (segs.empty() || segs.size() > (size_t)BS) continue;
             c0->xsegTab[kind].alloc(segs.size() * sizeof(XSeg));
             HIP_CHECK(hipMemcpyAsync(c0->xsegTab[kind].p, segs.data(), segs.size() * sizeof(XSeg), hipMemcpyHostToDevice, c0->stream));
@@ -579,14 +579,14 @@ struct Dist {
         if (!forwarding()) {
             if (inProcess() && vec == &ps_context::pvec && directExchange(0)) return;
             for (ps_context* c : R) packAll(c, true, (c->*vec).p, cs(c, onComm));
-            transport(0, onComm);
+            transport(valuesMsg, onComm);
             for (ps_context* c : R) unpackAllValues(c, (c->*vec).p, cs(c, onComm));
             return;
         }
         for (int a = 0; a < 3; ++a) {
             if (!axisUsed(a)) continue;
             for (ps_context* c : R) pack(c, true, (c->*vec).p, cs(c, onComm), a);
-            transport(0, onComm, a);
+            transport(valuesMsg, onComm, a);
             for (ps_context* c : R) unpack<false>(c, false, (c->*vec).p, cs(c, onComm), a);
         }
     }
@@ -596,7 +596,7 @@ struct Dist {
         if (!forwarding()) {   // one round: what arrives is for DOFs of this rank's own (added here in the order z, y, x of the forwarding rounds: the same sums)
             if (inProcess() && !addOwned && vec == &ps_context::Ap && directExchange(1)) return;
             for (ps_context* c : R) packAll(c, false, (c->*vec).p, cs(c, onComm));
-            transport(1, onComm);
+            transport(contribMsg, onComm);
             if (addOwned)
                 for (int a = ps_context::NLINK - 1; a >= 0; --a) if (axisUsed(a)) for (ps_context* c : R) unpack<true>(c, true, (c->*vec).p, cs(c, onComm), a);   // (diagonals first, then z, y, x)
             return;
@@ -604,12 +604,14 @@ struct Dist {
         for (int a = 2; a >= 0; --a) {
             if (!axisUsed(a)) continue;
             for (ps_context* c : R) pack(c, false, (c->*vec).p, cs(c, onComm), a);
-            transport(1, onComm, a);
+            transport(contribMsg, onComm, a);
             for (ps_context* c : R) {
                 if (addOwned) unpack<true>(c, true, (c->*vec).p, cs(c, onComm), a);
-                else if (c->nLowOwn[a] + c->nUpOwn[a] > 0)
-                    hipLaunchKernelGGL(k_relay2, dim3(gridFor(c->nLowOwn[a] + c->nUpOwn[a], BS)), dim3(BS), 0, cs(c, onComm), (const int32_t*)c->listLowOwn[a].p, c->nLowOwn[a],
-                                       (const double*)c->recvLo[a].p, (const int32_t*)c->listUpOwn[a].p, c->nUpOwn[a], (const double*)c->recvUp[a].p, (c->*vec).p, (int)c->ownHi);
+                else if (nOwn(c, a) > 0) {
+                    const ps_context::Cut &A = c->cut[a][0], &B = c->cut[a][1];
+                    hipLaunchKernelGGL(k_relay2, dim3(gridFor(nOwn(c, a), BS)), dim3(BS), 0, cs(c, onComm), (const int32_t*)A.own.idx.p, A.own.n, (const double*)A.recv.p,
+                                       (const int32_t*)B.own.idx.p, B.own.n, (const double*)B.recv.p, (c->*vec).p, (int)c->ownHi);
+                }
             }
         }
     }
@@ -623,7 +625,7 @@ struct Dist {
         std::vector<std::pair<int32_t, int32_t>> ent;                       // (DOF, (list index << 4) | buffer), in link order
         for (int a = 0; a < ps_context::NLINK; ++a)
             for (int side = 0; side < 2; ++side) {
-                const std::vector<int32_t>& L = c->hostOwnList[2 * a + side];
+                const std::vector<int32_t>& L = c->cut[a][side].hostOwn;
                 if (L.size() >= (size_t)(1 << 27)) return;                  // (would not fit the encoding: the per-link launches stay)
                 for (size_t i = 0; i < L.size(); ++i) if (L[i] < (int32_t)c->ownHi) ent.push_back({L[i], (int32_t)((i << 4) | (size_t)(2 * a + side))});
             }
@@ -637,7 +639,7 @@ struct Dist {
         size_t e = 0;
         for (size_t i = 0; i < n; ++i) for (int32_t k = 0; k < cnt[i]; ++k) src[(size_t)k * n + i] = ent[e++].second;
         std::vector<const double*> bufs(12);
-        for (int a = 0; a < ps_context::NLINK; ++a) { bufs[(size_t)2 * a] = c->recvLo[a].p; bufs[(size_t)2 * a + 1] = c->recvUp[a].p; }
+        eachSide(-1, [&](int l, int side) { bufs[(size_t)(2 * l + side)] = c->cut[l][side].recv.p; });
         c->fixDof.alloc(n); c->fixSrc.alloc(src.size()); c->fixBufs.alloc(12);
         HIP_CHECK(hipMemcpyAsync(c->fixDof.p, dof.data(), n * 4, hipMemcpyHostToDevice, c->stream));
         HIP_CHECK(hipMemcpyAsync(c->fixSrc.p, src.data(), src.size() * 4, hipMemcpyHostToDevice, c->stream));
@@ -653,9 +655,10 @@ struct Dist {
         }
         for (int a = 0; a < ps_context::NLINK; ++a) {
             double* part = fX + (size_t)a * 2 * (size_t)gFix;
-            if (c->nLowOwn[a] + c->nUpOwn[a] > 0)
-                hipLaunchKernelGGL(k_dist_fixup, dim3(gFix), dim3(BS), 0, c->stream, sc, (const int32_t*)c->listLowOwn[a].p, c->nLowOwn[a], (const double*)c->recvLo[a].p,
-                                   (const int32_t*)c->listUpOwn[a].p, c->nUpOwn[a], (const double*)c->recvUp[a].p, c->r.p,
+            const ps_context::Cut &A = c->cut[a][0], &B = c->cut[a][1];
+            if (nOwn(c, a) > 0)
+                hipLaunchKernelGGL(k_dist_fixup, dim3(gFix), dim3(BS), 0, c->stream, sc, (const int32_t*)A.own.idx.p, A.own.n, (const double*)A.recv.p,
+                                   (const int32_t*)B.own.idx.p, B.own.n, (const double*)B.recv.p, c->r.p,
                                    jac ? (const diag_t*)c->dinvF.p : (const diag_t*)nullptr, part, (int)c->ownHi);
         }
     }
@@ -727,46 +730,60 @@ struct Dist {
         const int b = a == 0 ? d.y : d.x, e = a == 2 ? d.y : d.z;
         return (((double)b * 4096. + (double)e) * 64. + (double)layers) * 64. + (double)c->P.tileSize;      // < 2^42
     }
+    // A few host doubles across the cuts: rank q's mine[q].v[l][side][0 .. n) go through the send buffers and the transport to the neighbour on
+    // that side; returned: what came from each side (zeros where there is no neighbour).  viaMain: staged on the solver stream, ordered
+    // against the comm stream by the events of an exchange; else on the comm stream itself.
+    struct CutVals { double v[NL][2][8] = {}; };
+    std::vector<CutVals> swapCutVals(const std::vector<CutVals>& mine, int n, bool viaMain, int only = -1) {
+        std::vector<CutVals> got(R.size());
+        auto stage = [&](ps_context* c) { return viaMain ? c->stream : cs(c, true); };
+        for (size_t q = 0; q < R.size(); ++q) {
+            ps_context* c = R[q];
+            eachSide(only, [&](int l, int s) { HIP_CHECK(hipMemcpyAsync(c->cut[l][s].send.p, mine[q].v[l][s], (size_t)n * 8, hipMemcpyHostToDevice, stage(c))); });
+            if (viaMain) order(c, 0, true);
+        }
+        transport([n](const ps_context* c) { return evenMsg(c, n); }, true, only);
+        for (size_t q = 0; q < R.size(); ++q) {
+            ps_context* c = R[q];
+            if (viaMain) order(c, 1, false);
+            eachSide(only, [&](int l, int s) { if (c->linked(l, s)) HIP_CHECK(hipMemcpyAsync(got[q].v[l][s], c->cut[l][s].recv.p, (size_t)n * 8, hipMemcpyDeviceToHost, stage(c))); });
+            HIP_CHECK(hipStreamSynchronize(stage(c)));
+        }
+        return got;
+    }
     void handshakeCuts() {
         bool bad = false;
         for (int a = 0; a < 3; ++a) {
             if (!axisUsed(a)) continue;
-            std::vector<int64_t> keep(R.size() * 4);
-            std::vector<double> want(R.size() * 2);
+            std::vector<CutVals> want(R.size());
             for (size_t q = 0; q < R.size(); ++q) {
                 ps_context* c = R[q];
                 const int3 d = c->g.dims(0);
                 const int da = a == 0 ? d.x : (a == 1 ? d.y : d.z);
-                c->sendLo[a].alloc(8); c->sendUp[a].alloc(8); c->recvLo[a].alloc(8); c->recvUp[a].alloc(8);
-                want[2 * q] = c->brick.hasLower[a] ? cutKey(c, a, c->brick.lo[a]) : 0.;
-                want[2 * q + 1] = c->brick.hasUpper[a] ? cutKey(c, a, da - c->brick.hi[a]) : 0.;
-                HIP_CHECK(hipMemcpyAsync(c->sendLo[a].p, &want[2 * q], 8, hipMemcpyHostToDevice, cs(c, true)));
-                HIP_CHECK(hipMemcpyAsync(c->sendUp[a].p, &want[2 * q + 1], 8, hipMemcpyHostToDevice, cs(c, true)));
-                keep[4 * q] = c->nLowOwn[a]; keep[4 * q + 1] = c->nLowHalo[a]; keep[4 * q + 2] = c->nUpOwn[a]; keep[4 * q + 3] = c->nUpHalo[a];
-                c->nLowOwn[a] = c->nLowHalo[a] = c->nUpOwn[a] = c->nUpHalo[a] = 1;
+                c->ensureBuffers(a, 8);
+                if (c->brick.hasLower[a]) want[q].v[a][0][0] = cutKey(c, a, c->brick.lo[a]);
+                if (c->brick.hasUpper[a]) want[q].v[a][1][0] = cutKey(c, a, da - c->brick.hi[a]);
             }
-            auto restore = [&]() { for (size_t q = 0; q < R.size(); ++q) { ps_context* c = R[q]; c->nLowOwn[a] = keep[4 * q]; c->nLowHalo[a] = keep[4 * q + 1]; c->nUpOwn[a] = keep[4 * q + 2]; c->nUpHalo[a] = keep[4 * q + 3]; } };
-            try { transport(0, true, a); } catch (...) { restore(); throw; }
-            restore();
-            for (size_t q = 0; q < R.size(); ++q) {
-                ps_context* c = R[q];
-                double got[2] = {0., 0.};
-                if (c->brick.hasLower[a]) HIP_CHECK(hipMemcpyAsync(&got[0], c->recvLo[a].p, 8, hipMemcpyDeviceToHost, cs(c, true)));
-                if (c->brick.hasUpper[a]) HIP_CHECK(hipMemcpyAsync(&got[1], c->recvUp[a].p, 8, hipMemcpyDeviceToHost, cs(c, true)));
-                HIP_CHECK(hipStreamSynchronize(cs(c, true)));
-                bad = bad || (c->brick.hasLower[a] && got[0] != want[2 * q]) || (c->brick.hasUpper[a] && got[1] != want[2 * q + 1]);
-            }
+            const std::vector<CutVals> got = swapCutVals(want, 1, false, a);
+            for (size_t q = 0; q < R.size(); ++q)
+                for (int s = 0; s < 2; ++s) bad = bad || (R[q]->linked(a, s) && got[q].v[a][s][0] != want[q].v[a][s][0]);
         }
         if (sumFlag(bad ? 1. : 0.) > 0.)
             throw Error(bad ? "the rank across a cut was configured differently (cross-section, halo layers or tileSize of the two bricks disagree): refusing to exchange labels"
                             : "another pair of ranks disagrees about the cut between their bricks (cross-section, halo layers or tileSize)");
     }
     static int nbrMask(const ps_context* c) { int m = 0; for (int b = 0; b < 3; ++b) m |= (c->brick.hasLower[b] ? 1 : 0) << (2 * b) | (c->brick.hasUpper[b] ? 2 : 0) << (2 * b); return m; }
+    void connectCuts() {   // TCP: the sockets to this rank's neighbours (kept while the neighbours stay the same)
+        if (!useTcp) return;
+        int nb[NL][2];
+        eachSide(-1, [&](int l, int s) { nb[l][s] = R[0]->nbr(l, s); });
+        hc()->connectNeighbours(nb);
+    }
     void exchangeLabels(int pass) {
         bool any = false;
         for (int a = 0; a < 3; ++a) any = any || axisUsed(a);
         if (!any) return;
-        if (useTcp) { ps_context* c = R[0]; int lo[ps_context::NLINK], up[ps_context::NLINK]; for (int a = 0; a < ps_context::NLINK; ++a) { lo[a] = c->nbrLo(a); up[a] = c->nbrUp(a); } hc()->connectNeighbours(lo, up); }
+        connectCuts();
         for (ps_context* c : R) {
             c->labelFlags.alloc(4);
             HIP_CHECK(hipMemsetAsync(c->labelFlags.p, 0, 4 * sizeof(int32_t), c->stream));
@@ -775,36 +792,38 @@ struct Dist {
         if (pass == 0) handshakeCuts();
         for (int a = 0; a < 3; ++a) {
             if (!axisUsed(a)) continue;
-            struct Geo { int3 d; int hLo, hUp; int64_t nLo, nUp, keep[4]; };
-            std::vector<Geo> G(R.size());
-            for (size_t q = 0; q < R.size(); ++q) {
-                ps_context* c = R[q];
-                Geo& z = G[q];
+            struct Geo { int3 d; int hLo, hUp; int64_t nLo, nUp; };   // the halo blocks of a rank along a: layers and cells below / above
+            auto geo = [a](const ps_context* c) {
+                Geo z;
                 z.d = c->g.dims(0);
                 const int da = a == 0 ? z.d.x : (a == 1 ? z.d.y : z.d.z);
                 const int64_t cross = (int64_t)z.d.x * z.d.y * z.d.z / da;
                 z.hLo = c->brick.hasLower[a] ? c->brick.lo[a] : 0;
                 z.hUp = c->brick.hasUpper[a] ? da - c->brick.hi[a] : 0;
                 z.nLo = (int64_t)z.hLo * cross; z.nUp = (int64_t)z.hUp * cross;
-                z.keep[0] = c->nLowOwn[a]; z.keep[1] = c->nLowHalo[a]; z.keep[2] = c->nUpOwn[a]; z.keep[3] = c->nUpHalo[a];
-                const size_t mx = (size_t)(std::max(z.nLo, z.nUp) + 1) / 2 + 8;   // int32 labels in the double buffers of the exchanges
-                c->sendLo[a].alloc(mx); c->sendUp[a].alloc(mx); c->recvLo[a].alloc(mx); c->recvUp[a].alloc(mx);
-                c->nLowOwn[a] = c->nLowHalo[a] = (z.nLo + 1) / 2; c->nUpOwn[a] = c->nUpHalo[a] = (z.nUp + 1) / 2;
+                return z;
+            };
+            for (ps_context* c : R) {
+                const Geo z = geo(c);
+                c->ensureBuffers(a, (size_t)(std::max(z.nLo, z.nUp) + 1) / 2 + 8);   // int32 labels in the double buffers of the exchanges
                 // what goes down: my first hLo owned layers (the lower rank's upper halo block); up: my last hUp owned layers
                 if (z.nLo + z.nUp > 0)
                     hipLaunchKernelGGL(k_labels_pack, dim3(gridFor(z.nLo + z.nUp, BS)), dim3(BS), 0, cs(c, true), (const int32_t*)c->labels[0].p, z.d, a, c->brick.lo[a], z.nLo,
-                                       (int32_t*)c->sendLo[a].p, c->brick.hi[a] - z.hUp, z.nUp, (int32_t*)c->sendUp[a].p);
+                                       (int32_t*)c->cut[a][0].send.p, c->brick.hi[a] - z.hUp, z.nUp, (int32_t*)c->cut[a][1].send.p);
             }
-            auto restore = [&]() { for (size_t q = 0; q < R.size(); ++q) { ps_context* c = R[q]; c->nLowOwn[a] = G[q].keep[0]; c->nLowHalo[a] = G[q].keep[1]; c->nUpOwn[a] = G[q].keep[2]; c->nUpHalo[a] = G[q].keep[3]; } };
-            try { transport(0, true, a); } catch (...) { restore(); throw; }
-            restore();
-            for (size_t q = 0; q < R.size(); ++q) {
-                ps_context* c = R[q];
-                const Geo& z = G[q];
+            transport([&](const ps_context* c) {   // both ways across a cut: the halo block's labels, two to a double
+                const Geo z = geo(c);
+                Msg m;
+                if (c->linked(a, 0)) m.send[a][0] = m.recv[a][0] = (z.nLo + 1) / 2;
+                if (c->linked(a, 1)) m.send[a][1] = m.recv[a][1] = (z.nUp + 1) / 2;
+                return m;
+            }, true, a);
+            for (ps_context* c : R) {
+                const Geo z = geo(c);
                 if (z.nLo + z.nUp > 0)
                     hipLaunchKernelGGL(k_labels_unpack, dim3(gridFor(z.nLo + z.nUp, BS)), dim3(BS), 0, cs(c, true), c->labels[0].p, pass ? c->reducedIdx[0].p : (int32_t*)nullptr,
-                                       (const int32_t*)c->cellScratch[2].p, z.d, a, 0, z.nLo, (const int32_t*)c->recvLo[a].p, c->brick.hi[a], z.nUp,
-                                       (const int32_t*)c->recvUp[a].p, c->labelFlags.p, nbrMask(c),
+                                       (const int32_t*)c->cellScratch[2].p, z.d, a, 0, z.nLo, (const int32_t*)c->cut[a][0].recv.p, c->brick.hi[a], z.nUp,
+                                       (const int32_t*)c->cut[a][1].recv.p, c->labelFlags.p, nbrMask(c),
                                        c->P.activeLiquidBoundaryLayerSize + c->P.activeSolidBoundaryLayerSize + c->P.tilePadding + 2);   // (ps_set_brick: <= 16)
             }
         }
@@ -827,47 +846,30 @@ struct Dist {
     // neighbours must agree on the exchange lists: same lengths AND the same keys (position in the cut's cross-section, kind) in the
     // same order (ps_context::buildHaloLists hashes them) — equal counts of different DOF sets would otherwise pair the wrong entries.
     void checkLists() {
-        constexpr int NL = ps_context::NLINK;   // the three face links and the three diagonal links alike
-        auto enc = [](int64_t n, uint64_t h, double* o) { o[0] = (double)n; o[1] = (double)(h & 0xffffffu); o[2] = (double)((h >> 24) & 0xffffffu); o[3] = (double)((h >> 48) & 0xffffu); };
-        auto same = [](const double* a, const double* b) { return a[0] == b[0] && a[1] == b[1] && a[2] == b[2] && a[3] == b[3]; };
-        if (!useRccl && !useTcp) {
-            for (size_t q = 0; q < R.size(); ++q)
-                for (int a = 0; a < NL; ++a) {
-                    const ps_context* lo = R[q];
-                    if (!lo->linkUpper(a)) continue;
-                    const ps_context* up = R[(size_t)lo->nbrUp(a)];
-                    if (lo->nUpHalo[a] != up->nLowOwn[a] || lo->nUpOwn[a] != up->nLowHalo[a] || lo->hashUpHalo[a] != up->hashLowOwn[a] || lo->hashUpOwn[a] != up->hashLowHalo[a])
+        auto agrees = [](const ps_context::CutList& x, const ps_context::CutList& y) { return x.n == y.n && x.hash == y.hash; };
+        if (!useRccl && !useTcp) {   // my side-1 lists against the neighbour's side-0 lists, own against halo
+            for (const ps_context* lo : R)
+                for (int l = 0; l < NL; ++l) {
+                    if (!lo->linked(l, 1)) continue;
+                    const ps_context* up = R[(size_t)lo->nbr(l, 1)];
+                    if (!agrees(lo->cut[l][1].halo, up->cut[l][0].own) || !agrees(lo->cut[l][1].own, up->cut[l][0].halo))
                         throw Error("exchange lists disagree across the cut between ranks " + std::to_string(lo->brick.rank) + " and " + std::to_string(up->brick.rank));
                 }
             return;
         }
+        // across processes: 8 doubles per side, (n, hash in three exact pieces) of my own list, then of my halo list
         ps_context* c = R[0];
-        if (useTcp) { int lo[NL], up[NL]; for (int a = 0; a < NL; ++a) { lo[a] = c->nbrLo(a); up[a] = c->nbrUp(a); } hc()->connectNeighbours(lo, up); }
-        double mineLo[NL][8], mineUp[NL][8];
-        int64_t keep[NL][4];
-        for (int a = 0; a < NL; ++a) {
-            enc(c->nLowOwn[a], c->hashLowOwn[a], mineLo[a]); enc(c->nLowHalo[a], c->hashLowHalo[a], mineLo[a] + 4);   // what I send down
-            enc(c->nUpOwn[a], c->hashUpOwn[a], mineUp[a]); enc(c->nUpHalo[a], c->hashUpHalo[a], mineUp[a] + 4);       // what I send up
-            HIP_CHECK(hipMemcpyAsync(c->sendLo[a].p, mineLo[a], 64, hipMemcpyHostToDevice, c->stream));
-            HIP_CHECK(hipMemcpyAsync(c->sendUp[a].p, mineUp[a], 64, hipMemcpyHostToDevice, c->stream));
-            keep[a][0] = c->nLowOwn[a]; keep[a][1] = c->nLowHalo[a]; keep[a][2] = c->nUpOwn[a]; keep[a][3] = c->nUpHalo[a];
-            c->nLowOwn[a] = c->nLowHalo[a] = c->linkLower(a) ? 8 : 0; c->nUpOwn[a] = c->nUpHalo[a] = c->linkUpper(a) ? 8 : 0;   // ship 8 doubles each way through the x-exchange path
-        }
-        auto restore = [&]() { for (int a = 0; a < NL; ++a) { c->nLowOwn[a] = keep[a][0]; c->nLowHalo[a] = keep[a][1]; c->nUpOwn[a] = keep[a][2]; c->nUpHalo[a] = keep[a][3]; } };
-        order(c, 0, true);
-        try { transport(0, true); order(c, 1, false); } catch (...) { restore(); throw; }
-        restore();
-        // the lower rank's (UpHalo, UpOwn) must equal my (LowOwn, LowHalo); the upper rank's (LowHalo, LowOwn) my (UpOwn, UpHalo):
-        // received from below: its (UpOwn, UpHalo); from above: its (LowOwn, LowHalo)
+        connectCuts();
+        auto enc = [](const ps_context::CutList& L, double* o) { o[0] = (double)L.n; o[1] = (double)(L.hash & 0xffffffu); o[2] = (double)((L.hash >> 24) & 0xffffffu); o[3] = (double)((L.hash >> 48) & 0xffffu); };
+        std::vector<CutVals> mine(1);
+        eachSide(-1, [&](int l, int s) { enc(c->cut[l][s].own, mine[0].v[l][s]); enc(c->cut[l][s].halo, mine[0].v[l][s] + 4); });
+        const CutVals got = swapCutVals(mine, 8, true)[0];
+        // what came from side s is the neighbour's (own, halo) and must equal my (halo, own) of side s
         bool bad = false;
-        for (int a = 0; a < NL; ++a) {
-            double lo[8] = {0}, up[8] = {0};
-            if (c->linkLower(a)) HIP_CHECK(hipMemcpyAsync(lo, c->recvLo[a].p, 64, hipMemcpyDeviceToHost, c->stream));
-            if (c->linkUpper(a)) HIP_CHECK(hipMemcpyAsync(up, c->recvUp[a].p, 64, hipMemcpyDeviceToHost, c->stream));
-            HIP_CHECK(hipStreamSynchronize(c->stream));
-            if (c->linkLower(a) && !(same(lo, mineLo[a] + 4) && same(lo + 4, mineLo[a]))) bad = true;
-            if (c->linkUpper(a) && !(same(up, mineUp[a] + 4) && same(up + 4, mineUp[a]))) bad = true;
-        }
+        eachSide(-1, [&](int l, int s) {
+            const double *m = mine[0].v[l][s], *g = got.v[l][s];
+            if (c->linked(l, s) && !(std::equal(g, g + 4, m + 4) && std::equal(g + 4, g + 8, m))) bad = true;
+        });
         if (sumFlag(bad ? 1. : 0.) > 0.) throw Error(bad ? "exchange lists disagree with a neighbour (labels differ across the cut: halo too thin for the layer sizes?)"
                                                           : "another rank found its exchange lists in disagreement");
     }
@@ -971,9 +973,9 @@ struct Dist {
             hipLaunchKernelGGL(k_chunk_flags_St, dim3(gridFor(nT, BS)), dim3(BS), 0, c->stream, (const int32_t*)c->St.ptr.p, (const int4*)c->St.chunkInfo.p, nT,
                                (int)c->ownLo, (int)c->ownHi, flags.p);
             for (int a = 0; a < 3; ++a)
-                if (forwarding() && c->nLowOwn[a] + c->nUpOwn[a] > 0)
-                    hipLaunchKernelGGL(k_chunk_flags_relay, dim3(gridFor(c->nLowOwn[a] + c->nUpOwn[a], BS)), dim3(BS), 0, c->stream, (const int32_t*)c->listLowOwn[a].p, c->nLowOwn[a],
-                                       (const int32_t*)c->listUpOwn[a].p, c->nUpOwn[a], (int)c->ownHi, (const int4*)c->St.chunkInfo.p, nT, flags.p);
+                if (forwarding() && nOwn(c, a) > 0)
+                    hipLaunchKernelGGL(k_chunk_flags_relay, dim3(gridFor(nOwn(c, a), BS)), dim3(BS), 0, c->stream, (const int32_t*)c->cut[a][0].own.idx.p, c->cut[a][0].own.n,
+                                       (const int32_t*)c->cut[a][1].own.idx.p, c->cut[a][1].own.n, (int)c->ownHi, (const int4*)c->St.chunkInfo.p, nT, flags.p);
             HIP_CHECK(hipMemcpyAsync(h.data(), flags.p, (size_t)nT * 4, hipMemcpyDeviceToHost, c->stream));
             HIP_CHECK(hipStreamSynchronize(c->stream));
             for (int i = 0; i < nT; ++i) { if (h[(size_t)i] == 2) lists[2].push_back(i); else if (h[(size_t)i] == 1) lists[3].push_back(i); if (h[(size_t)i] != 0) lists[4].push_back(i); }
@@ -999,10 +1001,9 @@ struct Dist {
             mark.alloc((size_t)c->nSystem);
             HIP_CHECK(hipMemsetAsync(mark.p, 0, (size_t)c->nSystem, c->stream));
             HIP_CHECK(hipMemsetAsync(c->counters.p + CTR_HALO_UNMARKED, 0, sizeof(int32_t), c->stream));
-            for (int a = 0; a < ps_context::NLINK; ++a) {
-                if (c->nLowHalo[a] > 0) hipLaunchKernelGGL(k_mark_list, dim3(gridFor(c->nLowHalo[a], BS)), dim3(BS), 0, c->stream, (const int32_t*)c->listLowHalo[a].p, c->nLowHalo[a], mark.p);
-                if (c->nUpHalo[a] > 0) hipLaunchKernelGGL(k_mark_list, dim3(gridFor(c->nUpHalo[a], BS)), dim3(BS), 0, c->stream, (const int32_t*)c->listUpHalo[a].p, c->nUpHalo[a], mark.p);
-            }
+            for (const auto& l : c->cut)
+                for (const ps_context::Cut& k : l)
+                    if (k.halo.n > 0) hipLaunchKernelGGL(k_mark_list, dim3(gridFor(k.halo.n, BS)), dim3(BS), 0, c->stream, (const int32_t*)k.halo.idx.p, k.halo.n, mark.p);
             hipLaunchKernelGGL(k_count_unmarked_halo, dim3(gridFor(c->S.nnz, BS)), dim3(BS), 0, c->stream, (const int32_t*)c->S.col.p, (int64_t)c->S.nnz, (int)c->ownLo, (int)c->ownHi,
                                (const unsigned char*)mark.p, c->counters.p + CTR_HALO_UNMARKED);
             if (c->readCounter(CTR_HALO_UNMARKED) != 0) need = true;
@@ -1145,7 +1146,7 @@ struct Dist {
                 f.tB = f.L.stBlocksFor(c->nDistList[2], 3); f.stBF = f.tB + f.L.stBlocksFor(c->nDistList[3], 3);
             }
             int64_t mostOwn = 1;
-            for (int a = 0; a < ps_context::NLINK; ++a) mostOwn = std::max(mostOwn, c->nLowOwn[a] + c->nUpOwn[a]);
+            for (int a = 0; a < ps_context::NLINK; ++a) mostOwn = std::max(mostOwn, nOwn(c, a));
             if (c->nFix > 0) mostOwn = std::max<int64_t>(mostOwn, c->nFix);             // the merged fix-up: one thread per receiving DOF, up to 1024 workgroups
             f.gFix = (int)std::min<int64_t>(c->nFix > 0 ? 1024 : 256, (mostOwn + BS - 1) / BS);   // workgroups of one axis's k_dist_fixup; its partials: [axis][2][gFix]
             c->fusedPart.alloc((size_t)f.sBlocks + (size_t)c->regionCount + VGRID + 2 * (size_t)f.stBF + 2 * ps_context::NLINK * (size_t)f.gFix + 16);
@@ -1569,19 +1570,19 @@ int32_t ps_comm_selftest(ps_context* c) {
     try {
         if (!c->rcclComm) throw Error("no communicator");
         HIP_CHECK(hipSetDevice(c->device));
-        c->redbuf.alloc(8); c->sendLo[2].alloc(8); c->recvLo[2].alloc(8);
+        c->redbuf.alloc(8); c->cut[2][0].send.alloc(8); c->cut[2][0].recv.alloc(8);
         const double v[4] = {1.5, -2.0, 3.25, 4.0};
         HIP_CHECK(hipMemcpyAsync(c->redbuf.p, v, 32, hipMemcpyHostToDevice, c->stream));
-        HIP_CHECK(hipMemcpyAsync(c->sendLo[2].p, v, 32, hipMemcpyHostToDevice, c->stream));
+        HIP_CHECK(hipMemcpyAsync(c->cut[2][0].send.p, v, 32, hipMemcpyHostToDevice, c->stream));
         Rccl& L = rccl();
         ncclCheck(L.AllReduce(c->redbuf.p, c->redbuf.p, 3, NCCL_DOUBLE, NCCL_SUM, c->rcclComm, c->stream), "ncclAllReduce");
         ncclCheck(L.GroupStart(), "ncclGroupStart");
-        ncclCheck(L.Send(c->sendLo[2].p, 4, NCCL_DOUBLE, c->slab.rank, c->rcclComm, c->stream), "ncclSend");
-        ncclCheck(L.Recv(c->recvLo[2].p, 4, NCCL_DOUBLE, c->slab.rank, c->rcclComm, c->stream), "ncclRecv");
+        ncclCheck(L.Send(c->cut[2][0].send.p, 4, NCCL_DOUBLE, c->slab.rank, c->rcclComm, c->stream), "ncclSend");
+        ncclCheck(L.Recv(c->cut[2][0].recv.p, 4, NCCL_DOUBLE, c->slab.rank, c->rcclComm, c->stream), "ncclRecv");
         ncclCheck(L.GroupEnd(), "ncclGroupEnd");
         double a[4], b[4];
         HIP_CHECK(hipMemcpyAsync(a, c->redbuf.p, 32, hipMemcpyDeviceToHost, c->stream));
-        HIP_CHECK(hipMemcpyAsync(b, c->recvLo[2].p, 32, hipMemcpyDeviceToHost, c->stream));
+        HIP_CHECK(hipMemcpyAsync(b, c->cut[2][0].recv.p, 32, hipMemcpyDeviceToHost, c->stream));
         HIP_CHECK(hipStreamSynchronize(c->stream));
         for (int i = 0; i < 4; ++i) if (b[i] != v[i]) throw Error("send/recv self-test mismatch");
         if (a[3] != v[3]) throw Error("all-reduce touched elements beyond count");
@@ -1590,13 +1591,13 @@ int32_t ps_comm_selftest(ps_context* c) {
         if (c->slabEnabled && world > 1) {
             if (a[0] != world * v[0] || a[1] != world * v[1] || a[2] != world * v[2]) throw Error("all-reduce self-test: wrong sum over the ranks");
             const double mine[4] = {(double)rank, 100. + rank, -1. - rank, 0.5 * rank};
-            HIP_CHECK(hipMemcpyAsync(c->sendLo[2].p, mine, 32, hipMemcpyHostToDevice, c->stream));
+            HIP_CHECK(hipMemcpyAsync(c->cut[2][0].send.p, mine, 32, hipMemcpyHostToDevice, c->stream));
             const int up = (rank + 1) % world, down = (rank + world - 1) % world;
             ncclCheck(L.GroupStart(), "ncclGroupStart");
-            ncclCheck(L.Send(c->sendLo[2].p, 4, NCCL_DOUBLE, up, c->rcclComm, c->stream), "ncclSend");
-            ncclCheck(L.Recv(c->recvLo[2].p, 4, NCCL_DOUBLE, down, c->rcclComm, c->stream), "ncclRecv");
+            ncclCheck(L.Send(c->cut[2][0].send.p, 4, NCCL_DOUBLE, up, c->rcclComm, c->stream), "ncclSend");
+            ncclCheck(L.Recv(c->cut[2][0].recv.p, 4, NCCL_DOUBLE, down, c->rcclComm, c->stream), "ncclRecv");
             ncclCheck(L.GroupEnd(), "ncclGroupEnd");
-            HIP_CHECK(hipMemcpyAsync(b, c->recvLo[2].p, 32, hipMemcpyDeviceToHost, c->stream));
+            HIP_CHECK(hipMemcpyAsync(b, c->cut[2][0].recv.p, 32, hipMemcpyDeviceToHost, c->stream));
             HIP_CHECK(hipStreamSynchronize(c->stream));
             if (b[0] != (double)down || b[1] != 100. + down || b[2] != -1. - down || b[3] != 0.5 * down) throw Error("neighbour send/recv self-test mismatch");
         }

@@ -1292,8 +1292,7 @@ __global__ void k_slice(const int32_t* __restrict__ src, int3 d, int axis, int l
 }
 }  // namespace
 void ps_context::buildHaloLists() {
-    for (int a = 0; a < NLINK; ++a) { nLowHalo[a] = nLowOwn[a] = nUpHalo[a] = nUpOwn[a] = 0; hashLowHalo[a] = hashLowOwn[a] = hashUpHalo[a] = hashUpOwn[a] = 0; }
-    for (auto& v : hostOwnList) v.clear();
+    for (auto& l : cut) for (Cut& k : l) { k.own.n = k.halo.n = 0; k.own.hash = k.halo.hash = 0; k.hostOwn.clear(); }
     if (!slabEnabled) return;
     DevBuf<int32_t>& scr = scrSlice;
     // the slice of sample grid s perpendicular to `axis` at `layer`, over the positions this rank owns along the two other axes (the
@@ -1334,28 +1333,37 @@ void ps_context::buildHaloLists() {
             for (size_t q = 0; q < sl.size(); ++q) { const int32_t b = sl[q]; if (b >= 0) { list.push_back(b); mix(h, (uint64_t)q * 8 + (uint64_t)s); } }
         }
     };
-    auto up = [&](const std::vector<int32_t>& h, DevBuf<int32_t>& d, int64_t& n) {
-        n = (int64_t)h.size();
-        d.alloc(h.size());
-        if (n) HIP_CHECK(hipMemcpyAsync(d.p, h.data(), h.size() * 4, hipMemcpyHostToDevice, stream));
+    auto put = [&](Cut& k, bool ownKind, const std::vector<int32_t>& h) {
+        CutList& L = ownKind ? k.own : k.halo;
+        L.n = (int64_t)h.size();
+        L.idx.alloc(h.size());
+        if (L.n) HIP_CHECK(hipMemcpyAsync(L.idx.p, h.data(), h.size() * 4, hipMemcpyHostToDevice, stream));
+        if (ownKind) k.hostOwn = h;
+    };
+    // the tail of a link: its four lists uploaded — (halo, own) below, then (halo, own) above — the host copies of the own lists kept, and
+    // buffers for the longest of them (+ 8: Dist::checkLists ships counts + hashes through these buffers)
+    auto finish = [&](int l, const std::vector<int32_t> (&halo)[2], const std::vector<int32_t> (&own)[2]) {
+        int64_t most = 0;
+        for (int side = 0; side < 2; ++side) {
+            put(cut[l][side], false, halo[side]); put(cut[l][side], true, own[side]);
+            most = std::max(most, std::max(cut[l][side].halo.n, cut[l][side].own.n));
+        }
+        ensureBuffers(l, (size_t)most + 8);
+        HIP_CHECK(hipStreamSynchronize(stream));                                           // (the host vectors go out of scope)
     };
     for (int a = 0; a < 3; ++a) {
         const int lo = brick.lo[a], hi = brick.hi[a];
-        std::vector<int32_t> lowHalo, lowOwn, upHalo, upOwn;
-        hashLowHalo[a] = hashLowOwn[a] = hashUpHalo[a] = hashUpOwn[a] = 0;
+        std::vector<int32_t> halo[2], own[2];
+        Cut &below = cut[a][0], &above = cut[a][1];
         if (brick.hasLower[a]) {
-            cellsOf(a, lo - 1, lowHalo, hashLowHalo[a]);                                   // their last layer, touched by my faces on the plane lo
-            cellsOf(a, lo, lowOwn, hashLowOwn[a]); edgesOf(a, lo, lowOwn, hashLowOwn[a]);   // mine, touched by their rows
+            cellsOf(a, lo - 1, halo[0], below.halo.hash);                                  // their last layer, touched by my faces on the plane lo
+            cellsOf(a, lo, own[0], below.own.hash); edgesOf(a, lo, own[0], below.own.hash);   // mine, touched by their rows
         }
         if (brick.hasUpper[a]) {
-            cellsOf(a, hi, upHalo, hashUpHalo[a]); edgesOf(a, hi, upHalo, hashUpHalo[a]);   // theirs, touched by my rows
-            cellsOf(a, hi - 1, upOwn, hashUpOwn[a]);                                      // mine, touched by their faces on the plane hi
+            cellsOf(a, hi, halo[1], above.halo.hash); edgesOf(a, hi, halo[1], above.halo.hash);   // theirs, touched by my rows
+            cellsOf(a, hi - 1, own[1], above.own.hash);                                    // mine, touched by their faces on the plane hi
         }
-        up(lowHalo, listLowHalo[a], nLowHalo[a]); up(lowOwn, listLowOwn[a], nLowOwn[a]); up(upHalo, listUpHalo[a], nUpHalo[a]); up(upOwn, listUpOwn[a], nUpOwn[a]);
-        hostOwnList[2 * a] = lowOwn; hostOwnList[2 * a + 1] = upOwn;
-        const size_t mx = (size_t)std::max<int64_t>(std::max(nLowHalo[a], nLowOwn[a]), std::max(nUpHalo[a], nUpOwn[a])) + 8;   // >= 8: Dist::checkLists ships counts + hashes through these buffers
-        sendLo[a].alloc(mx); sendUp[a].alloc(mx); recvLo[a].alloc(mx); recvUp[a].alloc(mx);
-        HIP_CHECK(hipStreamSynchronize(stream));                                           // (the host vectors go out of scope)
+        finish(a, halo, own);
     }
     // The diagonal links (one-round mode only; in the forwarding mode these samples travel as copies through two axis exchanges): the edge stresses
     // on the corner line of two cuts.  Link 3 + d, d = (x, y), (x, z), (y, z): the edge grid that lives on both planes (XY = 6, XZ = 5, YZ = 4), the third
@@ -1364,7 +1372,7 @@ void ps_context::buildHaloLists() {
     //   below: the line (plane lo_a, plane lo_b) is mine, touched by the rows of the brick one down along both.
     for (int d = 0; d < 3; ++d) {
         const int l = 3 + d, a = d == 2 ? 1 : 0, b = d == 0 ? 1 : 2, c = 3 - a - b, s = d == 0 ? 6 : (d == 1 ? 5 : 4);
-        std::vector<int32_t> upHalo, lowOwn;
+        std::vector<int32_t> halo[2], own[2];     // (a diagonal link: an upper halo list and a lower own list, the other two stay empty)
         auto lineOf = [&](int pa, int pb, std::vector<int32_t>& list, uint64_t& h) {
             const int3 dm = g.dims(s);
             if (pa < 0 || pa >= comp(dm, a) || pb < 0 || pb >= comp(dm, b)) return;
@@ -1383,14 +1391,9 @@ void ps_context::buildHaloLists() {
             HIP_CHECK(hipStreamSynchronize(stream));
             for (size_t q = 0; q < sl.size(); ++q) if (sl[q] >= 0) { list.push_back(sl[q]); mix(h, (uint64_t)q * 8 + (uint64_t)s); }
         };
-        if (!haloForward && linkUpper(l)) lineOf(brick.hi[a], brick.hi[b], upHalo, hashUpHalo[l]);
-        if (!haloForward && linkLower(l)) lineOf(brick.lo[a], brick.lo[b], lowOwn, hashLowOwn[l]);
-        std::vector<int32_t> none;
-        up(none, listLowHalo[l], nLowHalo[l]); up(lowOwn, listLowOwn[l], nLowOwn[l]); up(upHalo, listUpHalo[l], nUpHalo[l]); up(none, listUpOwn[l], nUpOwn[l]);
-        hostOwnList[2 * l] = lowOwn; hostOwnList[2 * l + 1].clear();
-        const size_t mx = (size_t)std::max(nLowOwn[l], nUpHalo[l]) + 8;
-        sendLo[l].alloc(mx); sendUp[l].alloc(mx); recvLo[l].alloc(mx); recvUp[l].alloc(mx);
-        HIP_CHECK(hipStreamSynchronize(stream));
+        if (!haloForward && linked(l, 1)) lineOf(brick.hi[a], brick.hi[b], halo[1], cut[l][1].halo.hash);
+        if (!haloForward && linked(l, 0)) lineOf(brick.lo[a], brick.lo[b], own[0], cut[l][0].own.hash);
+        finish(l, halo, own);
     }
 }
 

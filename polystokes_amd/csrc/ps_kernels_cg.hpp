@@ -567,7 +567,7 @@ __global__ void __launch_bounds__(1024) k_sum_rr(const CGScalars* __restrict__ s
 }
 // The fix-up of the fused step in ONE launch (r05): a thread owns a DOF that receives contributions — from up to MAXSRC links (a DOF next to two or
 // three cuts) — and applies them in link order, each to the r the previous one left: the arithmetic of the per-link launches of k_dist_fixup, DOF by
-// DOF, without the launches (3 - 6 per rank-iteration at ~6 us each).  src[k][i] = (list index << 4) | buffer (0 .. 11: recvLo / recvUp of the six
+// DOF, without the launches (3 - 6 per rank-iteration at ~6 us each).  src[k][i] = (list index << 4) | buffer (0 .. 11: 2 l + side, the receive buffers of the six
 // links, a pointer table in device memory), -1 = none; built once per setup (Dist::buildFixup).
 constexpr int FIX_MAXSRC = 4;
 __global__ void __launch_bounds__(BS) k_dist_fixup_merged(const CGScalars* __restrict__ sc, const int32_t* __restrict__ dof, const int32_t* __restrict__ src, int64_t n, const double* const* __restrict__ bufs,

@@ -26,7 +26,7 @@ def tall_coil(n, nz):
 
 def base_case(case):
     """the scene of a case without its variant suffix"""
-    return case.replace("_interrupt", "").replace("_failrank", "").replace("_f32first", "")
+    return case.replace("_interrupt", "").replace("_failrank", "").replace("_f32first", "").replace("_tilemismatch", "")
 
 
 def make(case):

@@ -67,6 +67,10 @@ def run_rank(case, world, rank, port, out, device, done):
         # this rank sees air in a patch of its own first layers: its labels on the cut differ from what rank 0 computes
         # from its halo copy: the owners' label exchange finds the two views of the same cells in disagreement
         loc.surface[sl.zLoOwned:sl.zLoOwned + 3, 5:12, 5:12] = 1.0
+    if case.endswith("_tilemismatch") and rank == 1:
+        # this rank is configured with another tile size than its slab was cut for: the cut (a multiple of both) and the halo block
+        # (lcm of 16 and either) pass ps_set_slab on both ranks, only the handshake across the cut can tell (Dist::handshakeCuts)
+        p.tileSize = 8
     res = {}
     if case.endswith("_f32first"):
         # the same context solved first on its own with the fp32 polynomial, then as a rank: the decomposition's fp64 polynomial

@@ -207,6 +207,17 @@ def test_multiprocess_list_mismatch_fails_every_rank(tmp_path):
     assert "different fields" in str(res[0]["err"])
 
 
+def test_multiprocess_tile_size_mismatch_fails_every_rank(tmp_path):
+    """Rank 1 runs with tileSize 8 on a slab cut for rank 0's 16: both pass ps_set_slab (the cut at z = 32 and the 16-cell halo block suit
+    either), cross-section and halo layers agree, so only the tile size in the key the ranks swap before the first label exchange differs
+    (Dist::handshakeCuts).  EVERY rank returns FAILED with the handshake's message; nobody waits in a receive sized for the other's labels."""
+    res = _run_ranks("cavity_w2_tilemismatch", 2, tmp_path)
+    errs = [str(r["err"]) for r in res]
+    assert [int(r["rc"]) for r in res] == [-1, -1], errs
+    assert all("configured differently" in e or "another pair of ranks" in e for e in errs), errs
+    assert any("configured differently" in e for e in errs), errs
+
+
 def test_bench_two_ranks_produces_one_line_whatever_the_transport(tmp_path):
     """`python bench.py --gpus 2 --full` without a launcher: spawns one process per rank, rendezvous over gloo, and prints ONE JSON
     line.  With two GPUs the ranks talk over RCCL; on a one-GPU box RCCL refuses the duplicate device, every rank agrees on that
