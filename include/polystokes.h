@@ -246,6 +246,38 @@ int32_t ps_download_solution_fields(ps_context* ctx, const ps_solution_out* out)
  * setup used; only with sigma > 0), "surfaceTensionReducedFaces" (int32: reduced faces that received an impulse; only with sigma > 0). */
 int32_t ps_set_surface_tension(ps_context* ctx, double sigma);
 
+/* Free-surface fields (extension): the ghost pressure on the non-liquid side of the free surface as a per-cell quantity
+ *   q_c = sigma_c * kappa_c + P_c
+ * instead of the one sigma of ps_set_surface_tension and an ambient pressure of 0.
+ * sigma: cell field of surface-tension coefficients, nx*ny*nz, x-fastest; NULL: the scalar of ps_set_surface_tension everywhere.
+ * pressure: cell field of the ambient (air-side) pressure, same grid; NULL: 0.
+ * The lifetime is the density field's: the fields belong to the grid of the last ps_upload_fields / ps_upload_fields_device; call after that
+ * upload and before ps_setup_device / ps_step_device (on a slab / brick rank: after that rank's own upload, with the rank's local grid);
+ * a call before any upload returns PS_INVALID; every field upload drops both fields.  A call replaces both members: a NULL member means
+ * "not present", not "keep"; f == NULL or both members NULL drops them.  polystokes_step and ps_step_device_fields carry no such fields
+ * (a caller uses upload + this call + ps_step_device + download); the Picard passes of ps_set_rheology re-run the setup without an upload
+ * in between, so the fields stay for every pass.
+ * Arithmetic (fp64 from the fp32 inputs): s_c = (double)sigma[c], or the scalar setting without a sigma field; kappa_c = the fp32 value of
+ * "surfaceCurvature" (ps_set_surface_tension), computed when the sigma field is present or the scalar is > 0 and absent from q otherwise;
+ * P_c = (double)pressure[c] or 0.  For a face f with wF != 0 the sum t starts at 0 and visits the lower cell (sign -1), then the upper
+ * (sign +1), cells inside the grid only: ghost = 1 - liquidW_c for a cell with an active label or PS_REDUCED, else 1; a cell with ghost == 0
+ * is skipped; t += sign * wF * ghost * invDx * q_c, left to right.  With t != 0 an active face gets rhsA[row] -= dt * t and a reduced face
+ * C_f^T (-dt * t) into its tile's rhs; b, the recovery, the exports, the EIGEN path and ps_solve_exported_system follow from those two
+ * vectors.  With no field present the setup runs exactly the kernels and arguments of ps_set_surface_tension alone.
+ * sigma is sampled at the cell, not at the closest interface point; a varying sigma adds no Marangoni (tangential) stress; there are no
+ * contact angles; P is the caller's (no bubble model derives it from pocket volumes).
+ * PS_INVALID (reason in ps_last_error, both fields dropped): "sigma: non-finite or negative value at cell N" (checked first; -0 is not
+ * negative), "pressure: non-finite value at cell N", N the smallest such index in x-fastest numbering.  While present the fields cost two fp32 cell grids and,
+ * from the next setup on, one fp64 cell grid; a drop releases them.
+ * Arrays: "surfaceFields" (int32, 1: bit 0 / 1 = the last setup used the sigma / pressure field), "surfaceGhostPressure" (fp64 cell grid:
+ * q_c; only when "surfaceFields" != 0), "surfaceCurvature" (also when only the sigma field asked for the curvature),
+ * "surfaceTensionReducedFaces" (also when "surfaceFields" != 0), "surfaceTension" (the scalar setting, as before). */
+typedef struct ps_surface_fields {
+    const float* sigma;      /* cell field nx*ny*nz, x-fastest; NULL: the scalar of ps_set_surface_tension */
+    const float* pressure;   /* cell field nx*ny*nz, x-fastest; NULL: 0 */
+} ps_surface_fields;
+int32_t ps_upload_surface_fields(ps_context* ctx, const ps_surface_fields* f);
+
 /* Solid boundary condition (extension; the reference node's colliders are all no-slip).  A context setting like ps_set_surface_tension: it
  * persists across ps_upload_fields and is read by every later setup.  PS_SOLID_NO_SLIP (the default) launches exactly the kernels of a
  * context that never made the call.  PS_SOLID_FREE_SLIP zeroes the shear stress tau_e of every active edge whose fluid weight is below 1
@@ -378,10 +410,12 @@ int32_t polystokes_step(ps_context* ctx, const ps_params* p, const ps_fields_in*
  * slab / brick ranks and ps_group_rank contexts take it like the host upload, ps_set_slab / ps_set_brick follow it.
  * ps_upload_density_field_device follows ps_upload_density_field: a non-finite value is PS_INVALID with "non-finite value at cell N", N the
  * smallest such index in x-fastest numbering whatever the layout; a constant field runs the scalar path at its clamped value; the same clamp
- * errors; NULL drops the field.  ps_step_device_fields is polystokes_step: upload, the step (with the Picard passes of ps_set_rheology),
- * download, the three export flags.  ps_download_solution_fields_device writes the grids of ps_download_solution_fields.
+ * errors; NULL drops the field.  ps_upload_surface_fields_device follows ps_upload_surface_fields the same way (both fields of a call in
+ * `layout`, N in x-fastest numbering whatever the layout).  ps_step_device_fields is polystokes_step: upload, the step (with the Picard
+ * passes of ps_set_rheology), download, the three export flags.  ps_download_solution_fields_device writes the grids of ps_download_solution_fields.
  *
- * Refusals: PS_INVALID with the reason in ps_last_error, nothing read through any pointer, the context unchanged and usable:
+ * Refusals: PS_INVALID with the reason in ps_last_error, nothing read through any pointer, the context unchanged and usable (one exception:
+ * a refused ps_upload_surface_fields_device drops both free-surface fields, as every refusal of that call does):
  *   - a layout other than 0 or 1;
  *   - a required field that is null (the messages of ps_upload_fields: "Surface field is missing." ...);
  *   - a pointer that is not 4-byte aligned;
@@ -391,6 +425,7 @@ int32_t polystokes_step(ps_context* ctx, const ps_params* p, const ps_fields_in*
 enum ps_field_layout { PS_LAYOUT_X_FASTEST = 0, PS_LAYOUT_Z_FASTEST = 1 };
 int32_t ps_upload_fields_device(ps_context* ctx, const ps_params* p, const ps_fields_in* in, int32_t layout, void* stream);
 int32_t ps_upload_density_field_device(ps_context* ctx, const float* density, int32_t layout, void* stream);
+int32_t ps_upload_surface_fields_device(ps_context* ctx, const ps_surface_fields* f, int32_t layout, void* stream);
 int32_t ps_download_fields_device(ps_context* ctx, const ps_fields_out* out, int32_t layout, void* stream);
 int32_t ps_download_solution_fields_device(ps_context* ctx, const ps_solution_out* out, int32_t layout, void* stream);
 int32_t ps_step_device_fields(ps_context* ctx, const ps_params* p, const ps_fields_in* in, const ps_fields_out* out,

@@ -29,6 +29,7 @@ EXPORTED_SYMBOLS = [
     "ps_set_solid_boundary", "ps_set_rheology", "ps_set_solve_precision",
     "ps_upload_fields_device", "ps_upload_density_field_device", "ps_download_fields_device", "ps_download_solution_fields_device",
     "ps_step_device_fields", "ps_set_velocity_extrapolation",
+    "ps_upload_surface_fields", "ps_upload_surface_fields_device",
 ]
 
 
@@ -137,6 +138,10 @@ def lib():
         L.ps_step_device_fields.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(FieldsIn), C.POINTER(FieldsOut), C.POINTER(Stats),
                                             C.c_int32, C.c_void_p]
         L.ps_step_device_fields.restype = C.c_int32
+        L.ps_upload_surface_fields.argtypes = [C.c_void_p, C.POINTER(_abi.SurfaceFields)]
+        L.ps_upload_surface_fields.restype = C.c_int32
+        L.ps_upload_surface_fields_device.argtypes = [C.c_void_p, C.POINTER(_abi.SurfaceFields), C.c_int32, C.c_void_p]
+        L.ps_upload_surface_fields_device.restype = C.c_int32
         _lib = L
     return _lib
 
@@ -192,6 +197,8 @@ class DeviceScene:
         self.surface, self.collision, self.viscosity = put(scene.surface), put(scene.collision), put(scene.viscosity)
         self.weights = None if scene.weights is None else [put(a) for a in scene.weights]
         self.density_field = None if scene.density_field is None else put(scene.density_field)
+        opt = lambda name: None if getattr(scene, name, None) is None else put(getattr(scene, name))
+        self.surface_sigma_field, self.surface_pressure_field = opt("surface_sigma_field"), opt("surface_pressure_field")
 
 
 def device_scene(scene, layout=_abi.LAYOUT_X_FASTEST, pad=0):
@@ -226,7 +233,7 @@ def _kind(name):
     if name.endswith(("Labels", "Indices", ".col", ".ptr", "Region", "Perm", ".chunkInfo", ".chunkRep", ".code")) or name.startswith("faceRow"):
         return "i"
     if name in ("valuesCoded", "columns16", "diagonalsCoded", "fusedStep", "streamRuns", "rowPerLane", "chebInner32", "warmStartUsed", "densityField", "launchWalk",
-                "surfaceTensionReducedFaces", "solidBoundary", "solidSlipEdges", "rheologyModel", "rheologyIterations",
+                "surfaceTensionReducedFaces", "surfaceFields", "solidBoundary", "solidSlipEdges", "rheologyModel", "rheologyIterations",
                 "solvePrecisionUsed", "solvePassIterations",
                 "velocityExtrapolation", "extrapolationLayerX", "extrapolationLayerY", "extrapolationLayerZ", "extrapolationCounts"):
         return "i"
@@ -244,6 +251,10 @@ def process_memory_stats():
     v = (C.c_int64 * 4)()
     lib().ps_memory_stats(None, v)
     return {"live_bytes": int(v[0]), "peak_bytes": int(v[1]), "contexts": int(v[3])}
+
+
+def _has_surface_fields(scene):
+    return getattr(scene, "surface_sigma_field", None) is not None or getattr(scene, "surface_pressure_field", None) is not None
 
 
 class PolyStokesError(RuntimeError):
@@ -387,6 +398,8 @@ class Solver:
         self._scene_surface_tension(scene)
         if getattr(scene, "density_field", None) is not None:
             self._check(self.upload_density_field(scene.density_field))
+        if _has_surface_fields(scene):
+            self._check(self.upload_surface_fields(scene.surface_sigma_field, scene.surface_pressure_field))
 
     def _scene_surface_tension(self, scene):
         """Scene.surface_tension (None: the context keeps its setting) -> ps_set_surface_tension; a refused value raises."""
@@ -406,6 +419,21 @@ class Solver:
         self._density_keep = f
         return self._check(self.L.ps_upload_density_field(self.h, f.ctypes.data), allow=(1, -2))
 
+    def upload_surface_fields(self, sigma=None, pressure=None):
+        """ps_upload_surface_fields: the free-surface cell fields for the grid of the last upload — the surface-tension coefficient (None:
+        the scalar of set_surface_tension) and the ambient pressure (None: 0); both None drops them.  Returns the ps_result (INVALID for a
+        refused field, the reason in last_error()); FAILED raises."""
+        sh = _abi.grid_shapes(self.scene.nx, self.scene.ny, self.scene.nz)["center"] if self.scene is not None else None
+
+        def host(field):
+            if field is None:
+                return None
+            f = np.ascontiguousarray(field, dtype=np.float32)
+            return f.reshape(sh) if sh is not None and f.shape != sh else f
+        keep = host(sigma), host(pressure)
+        sf = _abi.SurfaceFields(*[None if f is None else f.ctypes.data for f in keep])
+        return self._check(self.L.ps_upload_surface_fields(self.h, C.byref(sf)), allow=(1, -2))
+
     def last_error(self):
         return self.L.ps_last_error(self.h).decode()
 
@@ -424,6 +452,11 @@ class Solver:
         """ps_upload_density_field_device (None drops the field).  Returns the ps_result, INVALID for a refused field."""
         return self._check(self.L.ps_upload_density_field_device(self.h, device_address(field), int(layout), stream_handle(stream)),
                            allow=(1, -2))
+
+    def upload_surface_fields_device(self, sigma=None, pressure=None, layout=0, stream=None):
+        """ps_upload_surface_fields_device (both None drops the fields).  Returns the ps_result, INVALID for a refused field."""
+        sf = _abi.SurfaceFields(device_address(sigma), device_address(pressure))
+        return self._check(self.L.ps_upload_surface_fields_device(self.h, C.byref(sf), int(layout), stream_handle(stream)), allow=(1, -2))
 
     def _device_out(self, out):
         """(ps_fields_out, vel buffers, valid buffers): `out` = (vel[3], valid[3]) of device arrays (entries may be None), or None to allocate."""
@@ -479,7 +512,7 @@ class Solver:
 
     def step(self, scene, params):
         """solveGasSubclass equivalent on host buffers (HDK_PolyStokes.C:222-609)."""
-        if getattr(scene, "density_field", None) is not None:          # upload, density field, step, download: polystokes_step has no field
+        if getattr(scene, "density_field", None) is not None or _has_surface_fields(scene):   # upload, the fields, step, download: polystokes_step has no field
             self.upload(scene, params)
             rc = self.step_device()
             self.download()

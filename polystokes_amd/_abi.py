@@ -98,6 +98,11 @@ class SlabStruct(C.Structure):
                 ("hasLower", C.c_int32), ("hasUpper", C.c_int32), ("zGlobalOwned", C.c_int32)]
 
 
+class SurfaceFields(C.Structure):
+    """ps_surface_fields"""
+    _fields_ = [("sigma", C.c_void_p), ("pressure", C.c_void_p)]
+
+
 class BrickStruct(C.Structure):
     _fields_ = [("rank", C.c_int32), ("world", C.c_int32), ("dims", C.c_int32 * 3), ("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3),
                 ("hasLower", C.c_int32 * 3), ("hasUpper", C.c_int32 * 3), ("globalLo", C.c_int32 * 3)]
@@ -137,7 +142,8 @@ class Scene:
     """Host-side input bundle: numpy float32 arrays laid out as the C ABI expects."""
 
     def __init__(self, nx, ny, nz, dx, dt, density, vel, surface, collision, viscosity,
-                 collisionvel=None, weights=None, name="scene", density_field=None, surface_tension=None):
+                 collisionvel=None, weights=None, name="scene", density_field=None, surface_tension=None,
+                 surface_sigma_field=None, surface_pressure_field=None):
         self.nx, self.ny, self.nz, self.dx, self.dt, self.density = nx, ny, nz, float(dx), float(dt), float(density)
         sh = grid_shapes(nx, ny, nz)
         f32 = lambda a, s: np.array(np.broadcast_to(np.asarray(a, dtype=np.float32), s), dtype=np.float32, order="C", copy=True)
@@ -156,6 +162,10 @@ class Scene:
         self.density_field = None if density_field is None else f32(density_field, sh["center"])
         # optional surface tension coefficient sigma (ps_set_surface_tension, applied at upload / step); None: leave the context's setting
         self.surface_tension = None if surface_tension is None else float(surface_tension)
+        # optional free-surface cell fields (ps_upload_surface_fields): the surface-tension coefficient (None: the scalar) and the ambient
+        # pressure (None: 0)
+        self.surface_sigma_field = None if surface_sigma_field is None else f32(surface_sigma_field, sh["center"])
+        self.surface_pressure_field = None if surface_pressure_field is None else f32(surface_pressure_field, sh["center"])
 
     def fields_in(self):
         fi = FieldsIn()

@@ -101,6 +101,11 @@ void ps_context::uploadReset(const ps_params* p, const ps_fields_in* in) {
     dx = in->dx; invDx = 1. / dx; dt = in->dt; invDt = 1. / dt; rho = (double)in->density;
     rhoScalar = rho; densField = false;   // every upload drops a density field (ps_upload_density_field): it described the previous grid
     HIP_CHECK(hipSetDevice(device));
+    if (surfSigma.p || surfPressure.p || surfQ.p) {   // ... and the free-surface fields (ps_upload_surface_fields), released here
+        HIP_CHECK(hipStreamSynchronize(stream));
+        dropSurfaceFields();
+        drainDeferred(true);
+    }
 }
 
 void ps_context::ingestHost(const ps_fields_in* in) {
@@ -405,10 +410,10 @@ void ps_context::registerArrays() {
     densFieldHost = densField ? 1 : 0;   // 1: the last setup sampled a non-constant density field (ps_upload_density_field)
     regHost("densityField", &densFieldHost, 1, 4);
     regHost("surfaceTension", &sigmaUsed, 1, 8);   // the sigma of the last setup (ps_set_surface_tension)
-    if (sigmaUsed != 0.) {
-        reg("surfaceCurvature", kappaC.p, g.count(0), 4);
-        reg("surfaceTensionReducedFaces", stReduced.p, 1, 4);
-    }
+    regHost("surfaceFields", &surfFieldsUsed, 1, 4);   // bit 0 / 1: the last setup used a sigma / pressure field (ps_upload_surface_fields)
+    if (sigmaUsed != 0. || (surfFieldsUsed & 1)) reg("surfaceCurvature", kappaC.p, g.count(0), 4);
+    if (sigmaUsed != 0. || surfFieldsUsed != 0) reg("surfaceTensionReducedFaces", stReduced.p, 1, 4);
+    if (surfFieldsUsed != 0 && surfQ.p) reg("surfaceGhostPressure", surfQ.p, g.count(0), 8);   // q_c of the last setup (gone once the fields are dropped)
     regHost("solidBoundary", &solidBoundaryUsed, 1, 4);   // the mode of the last setup (ps_set_solid_boundary)
     if (solidBoundaryUsed == PS_SOLID_FREE_SLIP) reg("solidSlipEdges", slipEdges.p, 1, 4);
     regHost("rheologyModel", &rheoModelUsed, 1, 4);   // the model of the last setup (ps_set_rheology)
@@ -733,6 +738,15 @@ int32_t ps_upload_density_field(ps_context* c, const float* density) {
         return PS_SUCCESS;
     })
 }
+int32_t ps_upload_surface_fields(ps_context* c, const ps_surface_fields* f) {
+    if (!c) return PS_FAILED;
+    PS_TRY(c, {
+        if (!c->uploaded) { c->err = "ps_upload_surface_fields: call ps_upload_fields first"; return PS_INVALID; }
+        const std::string why = c->uploadSurfaceFields(f, false, 0, nullptr);
+        if (!why.empty()) { c->err = "ps_upload_surface_fields: " + why; return PS_INVALID; }
+        return PS_SUCCESS;
+    })
+}
 int32_t ps_set_surface_tension(ps_context* c, double sigma) {
     if (!c) return PS_FAILED;
     PS_TRY(c, {
@@ -889,6 +903,27 @@ int32_t ps_upload_density_field_device(ps_context* c, const float* density, int3
         if (!why.empty()) { c->err = "ps_upload_density_field_device: " + why; return PS_INVALID; }
         why = c->uploadDensityDevice(density, layout, (hipStream_t)stream);
         if (!why.empty()) { c->err = why; return PS_INVALID; }
+        return PS_SUCCESS;
+    })
+}
+int32_t ps_upload_surface_fields_device(ps_context* c, const ps_surface_fields* f, int32_t layout, void* stream) {
+    if (!c) return PS_FAILED;
+    PS_TRY(c, {
+        if (!c->uploaded) { c->err = "ps_upload_surface_fields: call ps_upload_fields first"; return PS_INVALID; }
+        HIP_CHECK(hipSetDevice(c->device));
+        std::string why;
+        if (const char* m = ps_context::layoutRefusal(layout)) why = m;
+        if (why.empty() && f && f->sigma) why = c->checkDeviceField(f->sigma, c->g.count(0), "sigma");
+        if (why.empty() && f && f->pressure) why = c->checkDeviceField(f->pressure, c->g.count(0), "pressure");
+        if (!why.empty()) {   // (a refused call drops both fields, like a refused value; nothing was read through a pointer)
+            HIP_CHECK(hipStreamSynchronize(c->stream));
+            c->dropSurfaceFields();
+            c->drainDeferred(true);
+            c->err = "ps_upload_surface_fields_device: " + why;
+            return PS_INVALID;
+        }
+        why = c->uploadSurfaceFields(f, true, layout, (hipStream_t)stream);
+        if (!why.empty()) { c->err = "ps_upload_surface_fields: " + why; return PS_INVALID; }
         return PS_SUCCESS;
     })
 }

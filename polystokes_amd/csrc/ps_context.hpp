@@ -126,8 +126,9 @@ struct FieldTable {
 };
 void launchFieldsCopy(const FieldTable& T, hipStream_t s);      // ps_fields.hip: dst = src, entry by entry
 void launchFieldsSwapXZ(const FieldTable& T, hipStream_t s);    // ... dst = src with the x and z axes exchanged
-enum ScanWord { SCAN_BAD = 0, SCAN_DIFFERS = 1, SCAN_FIRST = 2, SCAN_WORDS = 3 };   // k_field_scan: smallest non-finite index (~0: none), f[i] != f[0] somewhere, bits of f[0]
-void launchFieldScan(const float* f, int64_t n, bool nonFinite, uint32_t* out, hipStream_t s);
+enum ScanWord { SCAN_BAD = 0, SCAN_DIFFERS = 1, SCAN_FIRST = 2, SCAN_WORDS = 3 };   // k_field_scan: smallest bad index (~0: none), f[i] != f[0] somewhere, bits of f[0]
+enum ScanBad { SCAN_BAD_NONE = 0, SCAN_BAD_NON_FINITE = 1, SCAN_BAD_NON_FINITE_OR_NEGATIVE = 2 };   // which values count as bad
+void launchFieldScan(const float* f, int64_t n, int bad, uint32_t* out, hipStream_t s);
 
 struct CellField;     // ps_setup_util.hpp: what the setup kernels sample
 struct FaceDensity;
@@ -194,7 +195,7 @@ struct ps_context {
     void waitForCaller(hipStream_t caller);      // our stream waits for everything queued on the caller's so far
     void releaseToCaller(hipStream_t caller);    // the caller's stream waits for everything queued on ours so far
     void moveFields(const ps::FieldTable& T, int layout) { if (layout == 0) ps::launchFieldsCopy(T, stream); else ps::launchFieldsSwapXZ(T, stream); }
-    const uint32_t* scanField(const float* f, int64_t n, bool nonFinite);   // k_field_scan + fetch; synchronises the stream
+    const uint32_t* scanField(const float* f, int64_t n, int bad);   // k_field_scan (bad: ps::ScanBad) + fetch; synchronises the stream
     void upload(const ps_params* p, const ps_fields_in* in, int layout, hipStream_t caller);   // the device upload
     std::string uploadDensityDevice(const float* field, int layout, hipStream_t caller);
     void downloadDevice(const ps_fields_out* out, int layout, hipStream_t caller);
@@ -205,6 +206,16 @@ struct ps_context {
     ps::DevBuf<float> kappaRaw, kappaC;      // cell grids: kappa of the SDF, and kappa_c (sampled at the interface point, clamped)
     ps::DevBuf<int32_t> stReduced;           // reduced faces that received an impulse (array "surfaceTensionReducedFaces")
     void applySurfaceTension();              // ps_surface.hip: after the blocks and tile rhs, before b
+    // Free-surface fields (ps_upload_surface_fields): the sigma and ambient-pressure cell fields of the last call, for the grid of the last
+    // upload (every upload drops them).  With either present the setup forms q_c = sigma_c kappa_c + P_c in surfQ (array
+    // "surfaceGhostPressure") and the force kernels read it; surfFieldsUsed: bit 0 / 1 = the last setup used the sigma / pressure field
+    // (array "surfaceFields").  The three buffers exist only while a field is present.
+    ps::DevBuf<float> surfSigma, surfPressure;
+    ps::DevBuf<double> surfQ;
+    bool surfSigmaField = false, surfPressureField = false;
+    int32_t surfFieldsUsed = 0;
+    bool dropSurfaceFields();                // ps_fields.hip: false when there was nothing to drop
+    std::string uploadSurfaceFields(const ps_surface_fields* f, bool device, int layout, hipStream_t caller);   // ps_fields.hip
     // Solid boundary (ps_set_solid_boundary): solidBoundarySet is the context setting, solidBoundaryUsed the mode of the last setup (array
     // "solidBoundary"; constructMatrixBlocks copies it).  slipEdges: free-slip edges counted by the St count pass (array "solidSlipEdges").
     int32_t solidBoundarySet = PS_SOLID_NO_SLIP, solidBoundaryUsed = PS_SOLID_NO_SLIP;

@@ -62,16 +62,19 @@ __global__ __launch_bounds__(FBS) void k_fields_swap_xz(FieldTable T) {
     }
 }
 
-// out[SCAN_BAD] = min(out[SCAN_BAD], smallest i with f[i] not finite) (only with nonFinite != 0), out[SCAN_DIFFERS] |= some f[i] != f[0]
+// out[SCAN_BAD] = min(out[SCAN_BAD], smallest i with f[i] bad): not finite (badMode >= SCAN_BAD_NON_FINITE) or below 0
+// (SCAN_BAD_NON_FINITE_OR_NEGATIVE; -0 is not), out[SCAN_DIFFERS] |= some f[i] != f[0]
 // (the comparison of fieldIsUniform: -0 == 0, a NaN differs from everything), out[SCAN_FIRST] = the bits of f[0]
-__global__ __launch_bounds__(FBS) void k_field_scan(const float* __restrict__ f, int64_t n, int nonFinite, uint32_t* __restrict__ out) {
+__global__ __launch_bounds__(FBS) void k_field_scan(const float* __restrict__ f, int64_t n, int badMode, uint32_t* __restrict__ out) {
     const float v0 = f[0];
     bool differs = false;
     uint32_t bad = 0xffffffffu;
     for (int64_t i = (int64_t)blockIdx.x * FBS + threadIdx.x; i < n; i += (int64_t)gridDim.x * FBS) {
         const float v = f[i];
         differs |= v != v0;
-        if (nonFinite && (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u && (uint32_t)i < bad) bad = (uint32_t)i;
+        const bool isBad = (badMode >= SCAN_BAD_NON_FINITE && (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u) ||
+                           (badMode == SCAN_BAD_NON_FINITE_OR_NEGATIVE && v < 0.f);
+        if (isBad && (uint32_t)i < bad) bad = (uint32_t)i;
     }
     const bool any = __any(differs);
 #pragma unroll
@@ -106,11 +109,11 @@ void launchFieldsSwapXZ(const FieldTable& T, hipStream_t s) {
 }
 
 // out: SCAN_WORDS device words; they are reset here, on the same stream
-void launchFieldScan(const float* f, int64_t n, bool nonFinite, uint32_t* out, hipStream_t s) {
+void launchFieldScan(const float* f, int64_t n, int bad, uint32_t* out, hipStream_t s) {
     static_assert(SCAN_BAD == 0 && SCAN_DIFFERS == 1 && SCAN_FIRST == 2 && SCAN_WORDS == 3, "the two resets below follow this order");
     HIP_CHECK(hipMemsetAsync(out + SCAN_BAD, 0xff, sizeof(uint32_t), s));
     HIP_CHECK(hipMemsetAsync(out + SCAN_DIFFERS, 0, 2 * sizeof(uint32_t), s));
-    hipLaunchKernelGGL(k_field_scan, dim3((unsigned)std::min<int64_t>(1024, gridFor(n, FBS))), dim3(FBS), 0, s, f, n, nonFinite ? 1 : 0, out);
+    hipLaunchKernelGGL(k_field_scan, dim3((unsigned)std::min<int64_t>(1024, gridFor(n, FBS))), dim3(FBS), 0, s, f, n, bad, out);
 }
 
 }  // namespace ps
@@ -168,10 +171,10 @@ void ps_context::releaseToCaller(hipStream_t caller) {
     HIP_CHECK(hipStreamWaitEvent(caller, fieldEv[1], 0));
 }
 
-const uint32_t* ps_context::scanField(const float* f, int64_t n, bool nonFinite) {
+const uint32_t* ps_context::scanField(const float* f, int64_t n, int bad) {
     fieldScan.alloc(SCAN_WORDS);
     if (!pinnedScan) HIP_CHECK(hipHostMalloc((void**)&pinnedScan, SCAN_WORDS * sizeof(uint32_t), hipHostMallocDefault));
-    launchFieldScan(f, n, nonFinite, fieldScan.p, stream);
+    launchFieldScan(f, n, bad, fieldScan.p, stream);
     HIP_CHECK(hipMemcpyAsync(pinnedScan, fieldScan.p, SCAN_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     HIP_CHECK(hipStreamSynchronize(stream));
     return pinnedScan;
@@ -210,7 +213,7 @@ void ps_context::ingestDevice(const ps_fields_in* in, int layout, hipStream_t ca
     for (int q = 0; q < 3; ++q) cellScratch[q].alloc((size_t)nc);
     counters.alloc(CTR_COUNT);
     moveFields(T, layout);
-    const uint32_t* w = scanField(viscosity.p, nc, false);
+    const uint32_t* w = scanField(viscosity.p, nc, SCAN_BAD_NONE);
     std::memcpy(&viscUniformValue, &w[SCAN_FIRST], sizeof(float));
     viscUniform = !w[SCAN_DIFFERS] && std::isfinite(viscUniformValue);
 }
@@ -239,7 +242,7 @@ std::string ps_context::uploadDensityDevice(const float* field, int layout, hipS
     FieldTable T;
     T.add(field, density.p, g.dims(0), layout == 1);
     moveFields(T, layout);
-    const uint32_t* w = scanField(density.p, nc, true);
+    const uint32_t* w = scanField(density.p, nc, SCAN_BAD_NON_FINITE);
     if (w[SCAN_BAD] != 0xffffffffu) return "ps_upload_density_field: non-finite value at cell " + std::to_string(w[SCAN_BAD]);
     densMin = lo; densMax = hi;
     if (!w[SCAN_DIFFERS]) {
@@ -251,6 +254,53 @@ std::string ps_context::uploadDensityDevice(const float* field, int layout, hipS
     }
     densField = true;
     return {};
+}
+
+// ps_upload_surface_fields / _device.  Both fields of a call reach their x-fastest buffers first (host: two copies; device: one launch of
+// the ingest, which transposes a z-fastest source), then k_field_scan checks each image, sigma first, so the index of a refused value is
+// the x-fastest one in either layout.  A refusal drops both fields.  Ends with the stream idle and everything dropped released.
+bool ps_context::dropSurfaceFields() {
+    const bool had = surfSigma.p || surfPressure.p || surfQ.p;
+    surfSigmaField = surfPressureField = false;
+    surfSigma.free(); surfPressure.free(); surfQ.free();
+    arrays.erase("surfaceGhostPressure");   // (its buffer has gone; "surfaceFields" keeps what the last setup used)
+    return had;
+}
+std::string ps_context::uploadSurfaceFields(const ps_surface_fields* f, bool fromDevice, int layout, hipStream_t caller) {
+    HIP_CHECK(hipSetDevice(device));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    dropSurfaceFields();
+    std::string why;
+    if (f && (f->sigma || f->pressure)) {
+        const bool ownScan = !fieldScan.p;   // the scan words this call allocates go with it: the fields cost their own buffers and nothing else
+        const int64_t nc = g.count(0);
+        if (f->sigma) surfSigma.alloc((size_t)nc);
+        if (f->pressure) surfPressure.alloc((size_t)nc);
+        if (fromDevice) {
+            waitForCaller(caller);
+            FieldTable T;
+            if (f->sigma) T.add(f->sigma, surfSigma.p, g.dims(0), layout == 1);
+            if (f->pressure) T.add(f->pressure, surfPressure.p, g.dims(0), layout == 1);
+            moveFields(T, layout);
+        } else {
+            if (f->sigma) HIP_CHECK(hipMemcpyAsync(surfSigma.p, f->sigma, (size_t)nc * sizeof(float), hipMemcpyHostToDevice, stream));
+            if (f->pressure) HIP_CHECK(hipMemcpyAsync(surfPressure.p, f->pressure, (size_t)nc * sizeof(float), hipMemcpyHostToDevice, stream));
+        }
+        if (f->sigma) {
+            const uint32_t* w = scanField(surfSigma.p, nc, SCAN_BAD_NON_FINITE_OR_NEGATIVE);
+            if (w[SCAN_BAD] != 0xffffffffu) why = "sigma: non-finite or negative value at cell " + std::to_string(w[SCAN_BAD]);
+        }
+        if (why.empty() && f->pressure) {
+            const uint32_t* w = scanField(surfPressure.p, nc, SCAN_BAD_NON_FINITE);
+            if (w[SCAN_BAD] != 0xffffffffu) why = "pressure: non-finite value at cell " + std::to_string(w[SCAN_BAD]);
+        }
+        HIP_CHECK(hipStreamSynchronize(stream));   // (the host copies when nothing was scanned after them; the scans end synchronised)
+        if (why.empty()) { surfSigmaField = f->sigma != nullptr; surfPressureField = f->pressure != nullptr; }
+        else dropSurfaceFields();
+        if (ownScan) fieldScan.free();
+    }
+    drainDeferred(true);
+    return why;
 }
 
 // vel / valid into the caller's device arrays: queued on our stream behind whatever the caller's stream holds so far (its earlier readers

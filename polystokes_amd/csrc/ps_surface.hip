@@ -6,6 +6,9 @@
 // gradSign wF_f (1 - liquidW_c) / dx for a cell with a pressure DOF (or inside a reduced tile, whose pressure the basis carries) and
 // gradSign wF_f / dx for any other cell of the grid.  The impulse -dt sum_c g(f,c) sigma kappa_c goes into the active rhs of f, or through
 // C_f^T into the rhs of its tile: b, the recovery and the exports follow from those two vectors ("Surface tension").
+//
+// Free-surface fields (ps_upload_surface_fields): the ghost pressure becomes the per-cell q_c = sigma_c kappa_c + P_c (k_surface_ghost_pressure,
+// fp64), and the same two force kernels read q with scale = dt in the place of kappa_c with scale = dt sigma ("Free-surface fields").
 #include "ps_context.hpp"
 
 using namespace ps;
@@ -96,19 +99,20 @@ __global__ void k_surface_curvature_at_interface(Grid g, const float* __restrict
 
 struct SurfArgs {
     Grid g;
-    double invDx, scale;           // scale = dt * sigma
+    double invDx, scale;           // scale = dt * sigma with kappa_c as the cell value, dt with q_c
     const float* lwC;              // cell liquid weights
     const float* fwF[3];           // face fluid weights
     const int32_t* labC;           // cell labels
     const int32_t* labF[3];
     const int32_t* regF[3];
     const int32_t* faceRow[3];
-    const float* kappaC;
     int64_t nA;
 };
 
-// sum_c g(f,c) kappa_c of face (axis, f): the lower cell has gradSign -1, the upper +1, a cell outside the grid has no term
-__device__ inline double ghostSum(const SurfArgs& A, int axis, const int3 f) {
+// sum_c g(f,c) v_c of face (axis, f), v = cellVal (kappa_c in fp32, or the ghost pressure q_c in fp64): the lower cell has gradSign -1,
+// the upper +1, a cell outside the grid has no term
+template <class T>
+__device__ inline double ghostSum(const SurfArgs& A, const T* __restrict__ cellVal, int axis, const int3 f) {
     const int3 cd = A.g.dims(0), fd = A.g.dims(1 + axis);
     const double wF = (double)A.fwF[axis][lin3(fd, f.x, f.y, f.z)];
     double s = 0.;
@@ -123,26 +127,29 @@ __device__ inline double ghostSum(const SurfArgs& A, int axis, const int3 f) {
         const int l = A.labC[cl];
         const double ghost = (isActiveL(l) || l == PS_REDUCED) ? 1. - (double)A.lwC[cl] : 1.;
         if (ghost == 0.) continue;
-        s += sign * wF * ghost * A.invDx * (double)A.kappaC[cl];
+        s += sign * wF * ghost * A.invDx * (double)cellVal[cl];
     }
     return s;
 }
 
-// active face rows: rhsA[row] -= dt sigma sum_c g(f,c) kappa_c (internal row numbering, as k_S_fill wrote it)
-__global__ void k_surface_tension_force(SurfArgs A, int axis, double* __restrict__ rhsA) {
+// active face rows: rhsA[row] -= scale sum_c g(f,c) v_c (internal row numbering, as k_S_fill wrote it)
+template <class T>
+__global__ void k_surface_tension_force(SurfArgs A, const T* __restrict__ cellVal, int axis, double* __restrict__ rhsA) {
     const int3 d = A.g.dims(1 + axis);
     const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= (int64_t)d.x * d.y * d.z) return;
     const int row = A.faceRow[axis][c];
     if (row < 0 || row >= A.nA) return;
-    const double s = ghostSum(A, axis, unlin3(d, c));
+    const double s = ghostSum(A, cellVal, axis, unlin3(d, c));
     if (s != 0.) rhsA[row] -= A.scale * s;
 }
 
-// reduced faces: rhs_r += C_f^T (-dt sigma sum_c g(f,c) kappa_c), one block per region over the union of its three face boxes (as k_skin),
+// reduced faces: rhs_r += C_f^T (-scale sum_c g(f,c) v_c), one block per region over the union of its three face boxes (as k_skin),
 // a fixed summation tree (deterministic).  count += faces with a non-zero impulse.
-__global__ void __launch_bounds__(BS) k_surface_tension_tiles(SurfArgs A, const int32_t* __restrict__ bbox, const double* __restrict__ COM, double dx,
-                                                              int3 off, double* __restrict__ rhsR, int32_t* __restrict__ count) {
+template <class T>
+__global__ void __launch_bounds__(BS) k_surface_tension_tiles(SurfArgs A, const T* __restrict__ cellVal, const int32_t* __restrict__ bbox,
+                                                              const double* __restrict__ COM, double dx, int3 off, double* __restrict__ rhsR,
+                                                              int32_t* __restrict__ count) {
     const int r = blockIdx.x;
     const int bx0 = bbox[r * 6 + 0], by0 = bbox[r * 6 + 1], bz0 = bbox[r * 6 + 2];
     const int ex = bbox[r * 6 + 3] - bx0 + 2, ey = bbox[r * 6 + 4] - by0 + 2, ez = bbox[r * 6 + 5] - bz0 + 2;
@@ -158,7 +165,7 @@ __global__ void __launch_bounds__(BS) k_surface_tension_tiles(SurfArgs A, const 
             if (oob3(fd, i, j, k)) continue;
             const int64_t fl = lin3(fd, i, j, k);
             if (A.labF[a][fl] != PS_REDUCED || A.regF[a][fl] != r) continue;
-            const double s = ghostSum(A, a, make_int3(i, j, k));
+            const double s = ghostSum(A, cellVal, a, make_int3(i, j, k));
             if (s == 0.) continue;
             ++hits;
             const double imp = -A.scale * s;
@@ -197,32 +204,64 @@ __global__ void __launch_bounds__(BS) k_surface_tension_tiles(SurfArgs A, const 
     }
 }
 
+// q_c = s_c kappa_c + P_c in fp64 from the fp32 inputs: s_c the sigma field or (sigmaC null) the scalar, kappa_c null when neither asks for
+// the curvature (the term is then absent), P_c null for 0
+__global__ void k_surface_ghost_pressure(int64_t n, const float* __restrict__ sigmaC, double sigma, const float* __restrict__ kappaC,
+                                         const float* __restrict__ pressureC, double* __restrict__ q) {
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= n) return;
+    const double P = pressureC ? (double)pressureC[c] : 0.;
+    if (!kappaC) { q[c] = P; return; }
+    const double s = sigmaC ? (double)sigmaC[c] : sigma;
+    q[c] = s * (double)kappaC[c] + P;
+}
+
+// the impulse of the cell values v into rhsA and the tiles' rhs
+template <class T>
+void launchSurfaceForce(ps_context* c, const SurfArgs& A, const T* cellVal) {
+    if (c->nActiveVs > 0)
+        for (int a = 0; a < 3; ++a) {
+            const int64_t nf = c->g.count(1 + a);
+            hipLaunchKernelGGL(k_surface_tension_force<T>, dim3(gridFor(nf, BS)), dim3(BS), 0, c->stream, A, cellVal, a, c->rhsA.p);
+        }
+    if (c->regionCount > 0)
+        hipLaunchKernelGGL(k_surface_tension_tiles<T>, dim3((unsigned)c->regionCount), dim3(BS), 0, c->stream, A, cellVal, (const int32_t*)c->bbox.p,
+                           (const double*)c->COM.p, c->dx, make_int3(c->gOff[0], c->gOff[1], c->gOff[2]), c->rhsR.p, c->stReduced.p);
+}
+
 }  // namespace
 
-// After constructMatrixBlocks (rhsA) and assembleReducedBlocks (rhs_r = Mr c_fit), before b.  sigma = 0: the buffers are dropped (deferred
-// frees) and nothing is launched.
+// After constructMatrixBlocks (rhsA) and assembleReducedBlocks (rhs_r = Mr c_fit), before b.  sigma = 0 and no free-surface field: the
+// buffers are dropped (deferred frees) and nothing is launched.  With a field of ps_upload_surface_fields the cell value is q_c and the
+// scale dt; without one, kappa_c and dt sigma as before the fields existed.
 void ps_context::applySurfaceTension() {
     sigmaUsed = sigmaSet;
-    if (sigmaUsed == 0.) {
-        kappaRaw.free(); kappaC.free(); stReduced.free();
+    surfFieldsUsed = (surfSigmaField ? 1 : 0) | (surfPressureField ? 2 : 0);
+    const bool curvature = surfSigmaField || sigmaUsed != 0.;
+    if (!curvature) { kappaRaw.free(); kappaC.free(); }
+    if (!curvature && surfFieldsUsed == 0) {
+        stReduced.free();
         return;
     }
     const int64_t n = g.count(0);
-    kappaRaw.alloc((size_t)n); kappaC.alloc((size_t)n); stReduced.alloc(1);
+    if (curvature) { kappaRaw.alloc((size_t)n); kappaC.alloc((size_t)n); }
+    stReduced.alloc(1);
     HIP_CHECK(hipMemsetAsync(stReduced.p, 0, sizeof(int32_t), stream));
-    hipLaunchKernelGGL(k_surface_curvature, dim3(gridFor(n, BS)), dim3(BS), 0, stream, g, (const float*)surface.p, invDx, kappaRaw.p);
-    hipLaunchKernelGGL(k_surface_curvature_at_interface, dim3(gridFor(n, BS)), dim3(BS), 0, stream, g, (const float*)surface.p,
-                       (const float*)kappaRaw.p, invDx, kappaC.p);
+    if (curvature) {
+        hipLaunchKernelGGL(k_surface_curvature, dim3(gridFor(n, BS)), dim3(BS), 0, stream, g, (const float*)surface.p, invDx, kappaRaw.p);
+        hipLaunchKernelGGL(k_surface_curvature_at_interface, dim3(gridFor(n, BS)), dim3(BS), 0, stream, g, (const float*)surface.p,
+                           (const float*)kappaRaw.p, invDx, kappaC.p);
+    }
     SurfArgs A;
-    A.g = g; A.invDx = invDx; A.scale = dt * sigmaUsed;
-    A.lwC = liquidW[0].p; A.labC = labels[0].p; A.kappaC = kappaC.p; A.nA = nActiveVs;
+    A.g = g; A.invDx = invDx; A.scale = surfFieldsUsed ? dt : dt * sigmaUsed;
+    A.lwC = liquidW[0].p; A.labC = labels[0].p; A.nA = nActiveVs;
     for (int a = 0; a < 3; ++a) { A.fwF[a] = fluidW[1 + a].p; A.labF[a] = labels[1 + a].p; A.regF[a] = reducedIdx[1 + a].p; A.faceRow[a] = faceRow[a].p; }
-    if (nActiveVs > 0)
-        for (int a = 0; a < 3; ++a) {
-            const int64_t nf = g.count(1 + a);
-            hipLaunchKernelGGL(k_surface_tension_force, dim3(gridFor(nf, BS)), dim3(BS), 0, stream, A, a, rhsA.p);
-        }
-    if (regionCount > 0)
-        hipLaunchKernelGGL(k_surface_tension_tiles, dim3((unsigned)regionCount), dim3(BS), 0, stream, A, (const int32_t*)bbox.p, (const double*)COM.p, dx,
-                           make_int3(gOff[0], gOff[1], gOff[2]), rhsR.p, stReduced.p);
+    if (surfFieldsUsed == 0) {
+        launchSurfaceForce(this, A, (const float*)kappaC.p);
+        return;
+    }
+    surfQ.alloc((size_t)n);
+    hipLaunchKernelGGL(k_surface_ghost_pressure, dim3(gridFor(n, BS)), dim3(BS), 0, stream, n, surfSigmaField ? (const float*)surfSigma.p : nullptr,
+                       sigmaUsed, curvature ? (const float*)kappaC.p : nullptr, surfPressureField ? (const float*)surfPressure.p : nullptr, surfQ.p);
+    launchSurfaceForce(this, A, (const double*)surfQ.p);
 }

@@ -50,6 +50,12 @@ def make_slab(nz, world, rank, tile_size=16):
     return Slab(rank, world, z0, z1, al if rank > 0 else 0, al if rank < world - 1 else 0)
 
 
+def _cut_opt(scene, name, cut):
+    """an optional cell field of `scene` through the rank's `cut`, or None"""
+    f = getattr(scene, name, None)
+    return None if f is None else cut(f)
+
+
 def local_scene(scene, slab):
     """The slab (+halo) of `scene` as an ordinary Scene."""
     a, b = slab.g0, slab.g0 + slab.nz_local
@@ -59,8 +65,10 @@ def local_scene(scene, slab):
                cut(scene.surface), cut(scene.collision), cut(scene.viscosity),
                collisionvel=[cut(scene.collisionvel[0]), cut(scene.collisionvel[1]), cut(scene.collisionvel[2], 1)],
                name=f"{scene.name}.r{slab.rank}",
-               density_field=None if getattr(scene, "density_field", None) is None else cut(scene.density_field),
-               surface_tension=getattr(scene, "surface_tension", None))
+               density_field=_cut_opt(scene, "density_field", cut),
+               surface_tension=getattr(scene, "surface_tension", None),
+               surface_sigma_field=_cut_opt(scene, "surface_sigma_field", cut),
+               surface_pressure_field=_cut_opt(scene, "surface_pressure_field", cut))
     return sc
 
 
@@ -113,8 +121,10 @@ def local_scene_brick(scene, b):
     faces = lambda v: [cut(v[0], ex=1), cut(v[1], ey=1), cut(v[2], ez=1)]
     return Scene(nx, ny, nz, scene.dx, scene.dt, scene.density, faces(scene.vel), cut(scene.surface), cut(scene.collision), cut(scene.viscosity),
                  collisionvel=faces(scene.collisionvel), name=f"{scene.name}.b{b.rank}",
-                 density_field=None if getattr(scene, "density_field", None) is None else cut(scene.density_field),
-                 surface_tension=getattr(scene, "surface_tension", None))
+                 density_field=_cut_opt(scene, "density_field", cut),
+                 surface_tension=getattr(scene, "surface_tension", None),
+                 surface_sigma_field=_cut_opt(scene, "surface_sigma_field", cut),
+                 surface_pressure_field=_cut_opt(scene, "surface_pressure_field", cut))
 
 
 def merge_faces_brick(global_out, local_out, owned_mask, b, axis):

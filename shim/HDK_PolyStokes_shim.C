@@ -77,6 +77,8 @@ const ParmRow theRows[] = {
     {'T', "variableDensity",            "Variable Density",                 nullptr,            0},
     {'T', "enableSurfaceTension",       "Enable Surface Tension",           nullptr,            0},
     {'F', "surfaceTension",             "Surface Tension",                  nullptr,            0},
+    {'S', "surfaceSigmaField",          "Surface Tension Field",            "",                 0},
+    {'S', "surfacePressureField",       "Ambient Pressure Field",           "",                 0},
     {'T', "solidFreeSlip",              "Free-Slip Solids",                 nullptr,            0},
     {'T', "nonNewtonian",               "Non-Newtonian Viscosity",          nullptr,            0},
     {'F', "flowIndex",                  "Flow Index",                       nullptr,            1},
@@ -214,6 +216,20 @@ bool HDK_PolyStokes::solveGasSubclass(SIM_Engine& engine, SIM_Object* obj, SIM_T
     // launches nothing extra).  A refused sigma (negative or not finite) aborts with the library's reason.
     const double sigma = getEnableSurfaceTension() ? (double)getSurfaceTension() : 0.;
     if (ps_set_surface_tension(myCtx, sigma) != PS_SUCCESS) return fail(ps_last_error(myCtx), UT_ERROR_ABORT);
+    // shim-only: free-surface fields (ps_upload_surface_fields): two string rows that name optional scalar fields of the object, sigma per
+    // cell and the ambient pressure per cell (like every field row, the GAS helper is given the row and looks the field's name up from it);
+    // both empty (the default) keeps the scalar sigma and an ambient pressure of 0.  A named field must exist and align with the surface
+    // field.  The sigma field holds whatever enableSurfaceTension says.
+    UT_String sigmaFieldName, pressureFieldName;
+    getSurfaceSigmaField(sigmaFieldName);
+    getSurfacePressureField(pressureFieldName);
+    const SIM_ScalarField* sigmaField = sigmaFieldName.isstring() ? getScalarField(obj, "surfaceSigmaField") : nullptr;
+    const SIM_ScalarField* ambientField = pressureFieldName.isstring() ? getScalarField(obj, "surfacePressureField") : nullptr;
+    if (sigmaFieldName.isstring() && !sigmaField) return fail("Surface tension field is missing.", UT_ERROR_ABORT);
+    if (pressureFieldName.isstring() && !ambientField) return fail("Ambient pressure field is missing.", UT_ERROR_ABORT);
+    if ((sigmaField && !sigmaField->isAligned(surfaceField)) || (ambientField && !ambientField->isAligned(surfaceField)))
+        return fail("Free-surface fields must align with the surface field.", UT_ERROR_ABORT);
+    const bool surfaceFields = sigmaField || ambientField;
     // shim-only: free-slip colliders (ps_set_solid_boundary, a context setting: no shear stress on the edges a solid cuts), set when the
     // toggle changes.  Off keeps the reference's no-slip walls.
     const int32_t solidMode = getSolidFreeSlip() ? PS_SOLID_FREE_SLIP : PS_SOLID_NO_SLIP;
@@ -280,6 +296,9 @@ bool HDK_PolyStokes::solveGasSubclass(SIM_Engine& engine, SIM_Object* obj, SIM_T
     toDense(*viscosityField->getField(), visc);
     std::vector<float> dens;
     if (variableDensity) toDense(*densityField->getField(), dens);
+    std::vector<float> sigmaCells, ambientCells;
+    if (sigmaField) toDense(*sigmaField->getField(), sigmaCells);
+    if (ambientField) toDense(*ambientField->getField(), ambientCells);
 
     ps_fields_in in = {};
     {
@@ -316,10 +335,14 @@ bool HDK_PolyStokes::solveGasSubclass(SIM_Engine& engine, SIM_Object* obj, SIM_T
 
     ps_stats st;
     int result;                                                         // == HDK_PolyStokes::Solver::SolverResult (Solver.h:61-70)
-    if (!variableDensity) result = polystokes_step(myCtx, &p, &in, &out, &st);
-    else {                                                              // polystokes_step's sequence with the density field after the upload
+    if (!variableDensity && !surfaceFields) result = polystokes_step(myCtx, &p, &in, &out, &st);
+    else {                                                              // polystokes_step's sequence with the cell fields after the upload
         result = ps_upload_fields(myCtx, &p, &in);
-        if (result == PS_SUCCESS && ps_upload_density_field(myCtx, dens.data()) != PS_SUCCESS) result = PS_FAILED;   // (reason: ps_last_error)
+        if (result == PS_SUCCESS && variableDensity && ps_upload_density_field(myCtx, dens.data()) != PS_SUCCESS) result = PS_FAILED;   // (reason: ps_last_error)
+        if (result == PS_SUCCESS && surfaceFields) {
+            const ps_surface_fields sf = {sigmaField ? sigmaCells.data() : nullptr, ambientField ? ambientCells.data() : nullptr};
+            if (ps_upload_surface_fields(myCtx, &sf) != PS_SUCCESS) result = PS_FAILED;
+        }
         if (result == PS_SUCCESS) result = ps_setup_device(myCtx, nullptr);
         if (result == PS_SUCCESS) {
             result = ps_solve_device(myCtx, &st);
