@@ -170,16 +170,15 @@ __global__ void __launch_bounds__(BS) k_skin(BlockArgs A, const int32_t* __restr
         if (ASSIGN && threadIdx.x == 0) itemLong[item] = 0;
         return;
     }
-    const int bx0 = bbox[r * 6 + 0], by0 = bbox[r * 6 + 1], bz0 = bbox[r * 6 + 2];
-    const int ex = bbox[r * 6 + 3] - bx0 + 2, ey = bbox[r * 6 + 4] - by0 + 2, ez = bbox[r * 6 + 5] - bz0 + 2;   // union of the three face boxes
-    const int total = ex * ey * ez;
-    const int end = min(start + FB_CHUNK, total);
+    const RegionBox box = RegionBox::faceUnion(bbox, r);
+    const int end = min(start + FB_CHUNK, (int)box.total());
     // pass 1: classify every position; totals per (class, axis) category — category = (long ? 0 : 3) + axis
     unsigned long long mine = 0;
     for (int base = start; base < end; base += BS) {
         const int pos = base + threadIdx.x;
         if (pos < end) {
-            const int i = bx0 + pos % ex, j = by0 + (pos / ex) % ey, k = bz0 + pos / (ex * ey);
+            const int3 q = box.at(pos);
+            const int i = q.x, j = q.y, k = q.z;
             int code = 0;
 #pragma unroll
             for (int a = 0; a < 3; ++a) {
@@ -224,7 +223,8 @@ __global__ void __launch_bounds__(BS) k_skin(BlockArgs A, const int32_t* __restr
             unsigned long long bt;
             const unsigned long long off = blockScanExclPacked(v, &bt);
             if (code) {
-                const int i = bx0 + pos % ex, j = by0 + (pos / ex) % ey, k = bz0 + pos / (ex * ey);
+                const int3 at = box.at(pos);
+                const int i = at.x, j = at.y, k = at.z;
 #pragma unroll
                 for (int a = 0; a < 3; ++a) {
                     const int q = (code >> (2 * a)) & 3;

@@ -250,6 +250,20 @@ __host__ __device__ inline void basisAccum(const double ox, const double oy, con
 #endif
 }
 
+// o = the offset of face (axis; i, j, k) from its tile's centre of mass com3[0..2] — the argument of basisRow / basisDot / basisAccum, and the
+// one place it is formed.  off = the global index of the local cell (0, 0, 0) (ps_context::gOff; 0 without a decomposition): a rank forms the
+// position with GLOBAL indices, the same arithmetic on the same numbers as the single domain, so that a tile's matrices do not depend on the
+// decomposition.  Index, minus the half cell on the face's axis, times dx, minus the centre: in that order, unfused
+// (-ffp-contract=off) — every tile array follows the bits of these three numbers.
+// Three kernels of the solve keep this arithmetic written out, because their code changes when they call it: ps_kernels_tiles.hpp
+// faceMonomials and k_tile_expand (the half cell as a select, the centre in registers) and ps_kernels_cg.hpp k_writeback.  Change them with it.
+__host__ __device__ inline void faceOffset(const double* com3, double dx, const int3 off, int axis, int i, int j, int k, double* o) {
+    double p[3] = {(double)(i + off.x), (double)(j + off.y), (double)(k + off.z)};
+    p[axis] -= 0.5;
+    o[0] = p[0] * dx - com3[0];
+    o[1] = p[1] * dx - com3[1];
+    o[2] = p[2] * dx - com3[2];
+}
 
 // face position packed in 32 bits: 10 bits per coordinate + 2 bits axis (grids up to 1023^3)
 __host__ __device__ inline uint32_t packFace(int i, int j, int k, int axis) {

@@ -272,7 +272,7 @@ void ps_context::setupPhase(int phase) {
         computeReducedMassMatrices();
         computeReducedViscosityMatricesInteriorOnly();
     } else {
-        fbItems = 0;
+        fbItems.count = 0;
     }
     T.mark(5);
     constructMatrixBlocks();
@@ -571,10 +571,9 @@ void ps_context::buildExplicitA(std::vector<int64_t>& aptr, std::vector<int32_t>
             for (int64_t q = first[(size_t)r]; q < first[(size_t)r + 1]; ++q) {
                 int i, j, k, axis;
                 unpackFace(rface[(size_t)q], i, j, k, axis);
-                double pos[3] = {(double)(i + gOff[0]), (double)(j + gOff[1]), (double)(k + gOff[2])};
-                pos[axis] -= 0.5;
-                double cf[PS_RD];
-                basisRow(pos[0] * dx - com[(size_t)r * 3], pos[1] * dx - com[(size_t)r * 3 + 1], pos[2] * dx - com[(size_t)r * 3 + 2], axis, cf);
+                double o[3], cf[PS_RD];
+                faceOffset(&com[(size_t)r * 3], dx, make_int3(gOff[0], gOff[1], gOff[2]), axis, i, j, k, o);
+                basisRow(o[0], o[1], o[2], axis, cf);
                 for (int32_t p = sp[(size_t)(nA + q)]; p < sp[(size_t)(nA + q) + 1]; ++p) {
                     const size_t lc = (size_t)(std::lower_bound(cols.begin(), cols.end(), sc[(size_t)p]) - cols.begin());
                     for (int e = 0; e < PS_RD; ++e) JS[(size_t)e * m + lc] += cf[e] * sv[(size_t)p];
@@ -1213,11 +1212,9 @@ int32_t ps_export_component_matrices(ps_context* c, const char* prefix) {
                 int i, j, k, a;
                 unpackFace(rface[(size_t)rr], i, j, k, a);
                 const int reg = rreg[(size_t)rr];
-                double pnt[3] = {(double)(i + c->gOff[0]), (double)(j + c->gOff[1]), (double)(k + c->gOff[2])};
-                pnt[a] -= 0.5;
-                double C[PS_RD];
-                basisRow(pnt[0] * c->dx - com[(size_t)reg * 3 + 0], pnt[1] * c->dx - com[(size_t)reg * 3 + 1],
-                         pnt[2] * c->dx - com[(size_t)reg * 3 + 2], a, C);
+                double o[3], C[PS_RD];
+                faceOffset(&com[(size_t)reg * 3], c->dx, make_int3(c->gOff[0], c->gOff[1], c->gOff[2]), a, i, j, k, o);
+                basisRow(o[0], o[1], o[2], a, C);
                 const int64_t row = nA + rr;
                 for (int p = sp[(size_t)row]; p < sp[(size_t)row + 1]; ++p) {
                     const int32_t rc = invSys[(size_t)sc[(size_t)p]];
@@ -1260,8 +1257,7 @@ int32_t ps_export_component_matrices(ps_context* c, const char* prefix) {
         diagOut("Mat_McInv.mtx", refRows(c->McInv.p));
         diagOut("Mat_uInv.mtx", refSys(c->uInv.p, nP, nT));
         if (c->P.exportComponentMatrices) { diagOut("Mat_Mc.mtx", refRows(c->Mc.p)); diagOut("Mat_u.mtx", refSys(c->uDiag.p, nP, nT)); }
-        auto blockOut = [&](const char* name, const double* dptr) {
-            auto v = fetch(c, dptr, R * PS_RD * PS_RD);
+        auto blocksWrite = [&](const char* name, const std::vector<double>& v) {   // R dense PS_RD x PS_RD blocks on the diagonal
             std::vector<int64_t> ptr((size_t)R * PS_RD + 1);
             std::vector<int32_t> col((size_t)R * PS_RD * PS_RD);
             for (int64_t r = 0; r <= R * PS_RD; ++r) ptr[(size_t)r] = r * PS_RD;
@@ -1270,6 +1266,7 @@ int32_t ps_export_component_matrices(ps_context* c, const char* prefix) {
                     for (int n = 0; n < PS_RD; ++n) col[(size_t)((r * PS_RD + m) * PS_RD + n)] = (int32_t)(r * PS_RD + n);
             writeMarketSparse(pre + name, R * PS_RD, R * PS_RD, ptr, col, v);
         };
+        auto blockOut = [&](const char* name, const double* dptr) { blocksWrite(name, fetch(c, dptr, R * PS_RD * PS_RD)); };
         blockOut("Mat_Mr.mtx", c->Mr.p);
         blockOut("Mat_JDtuDJ.mtx", c->Kv.p);
         blockOut("Mat_Inv_Mr_plus_2JDtuDJ.mtx", c->Binv.p);
@@ -1277,13 +1274,7 @@ int32_t ps_export_component_matrices(ps_context* c, const char* prefix) {
             auto mr = fetch(c, c->Mr.p, R * PS_RD * PS_RD), kv = fetch(c, c->Kv.p, R * PS_RD * PS_RD);
             std::vector<double> bsum(mr.size());
             for (size_t i = 0; i < mr.size(); ++i) bsum[i] = mr[i] * c->invDt + 2. * kv[i];
-            std::vector<int64_t> ptr((size_t)R * PS_RD + 1);
-            std::vector<int32_t> col((size_t)R * PS_RD * PS_RD);
-            for (int64_t r = 0; r <= R * PS_RD; ++r) ptr[(size_t)r] = r * PS_RD;
-            for (int64_t r = 0; r < R; ++r)
-                for (int m = 0; m < PS_RD; ++m)
-                    for (int n = 0; n < PS_RD; ++n) col[(size_t)((r * PS_RD + m) * PS_RD + n)] = (int32_t)(r * PS_RD + n);
-            writeMarketSparse(pre + "Mat_Mr_plus_2JDtuDJ.mtx", R * PS_RD, R * PS_RD, ptr, col, bsum);
+            blocksWrite("Mat_Mr_plus_2JDtuDJ.mtx", bsum);
         }
         {   // a member the live path of the reference never fills but still writes: MrInv (assembleReducedMassBlockInverse is only
             // called from the unreachable Eq-14 preconditioner, Preconditioners.cpp:48) is a default 0x0 matrix.

@@ -270,14 +270,19 @@ struct ps_context {
     ps::DevBuf<int32_t> bbox;                // R*6: min xyz, max xyz (cells)
     std::vector<int32_t> hbbox;
     ps::DevBuf<double> COM, cfit, Mr, Kv, Binv, rhsR, regionScratch;
-    // work tables for per-region reductions over the region's face box (host built, small)
-    ps::DevBuf<int32_t> fbItemRegion, fbItemAxis, fbItemStart;   // one item = <=FB_CHUNK face-box positions
-    ps::DevBuf<int32_t> fbRegionItemPtr;                         // R+1
-    int64_t fbItems = 0;
+    // Work items of the per-region dense sums (host built, small): one item = <= FB_CHUNK positions of the face box of one axis of one listed
+    // region, the regions in list order, per region axis by axis, per axis by rising start; regionPtr[q] .. regionPtr[q + 1] = the items of the
+    // q-th listed region (ps_tiles.hip: buildFaceBoxItems)
+    struct FaceBoxItems {
+        ps::DevBuf<int32_t> region, axis, start, regionPtr;
+        int64_t count = 0;
+    };
+    FaceBoxItems fbItems;                                        // of every region
     // classes of identical tiles (ps_tiles.hip:buildTileClasses): tileRep[r] = the region whose Mr / K region r copies (itself: sums its own);
-    // the face-box items of the representatives alone
-    ps::DevBuf<unsigned long long> tileSig; ps::DevBuf<int32_t> tileUnique, tileRep, repItemRegion, repItemAxis, repItemStart, repRegionItemPtr, repList;
-    int64_t tileReps = 0, repItems = 0;
+    // repList = the tileReps representatives, repItems = their face-box items alone
+    ps::DevBuf<unsigned long long> tileSig; ps::DevBuf<int32_t> tileUnique, tileRep, repList;
+    FaceBoxItems repItems;
+    int64_t tileReps = 0;
     void buildTileClasses();
     // skin-row enumeration: items of <= FB_CHUNK positions of a region's UNION face box (ex+1)(ey+1)(ez+1); a position yields up
     // to three rows (its X, Y, Z face) — rows are ordered (region, position x-fastest, axis), so the faces hanging off one

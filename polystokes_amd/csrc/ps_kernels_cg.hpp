@@ -849,6 +849,7 @@ __global__ void k_writeback(Grid g, int axis, const int32_t* __restrict__ lab, c
         double v = 0.;
         if (r >= 0) {
             const int3 q = unlin3(d, c);
+            // ps_common.hpp: faceOffset, written out: calling it swaps the operands of two multiplies of this kernel (profiles/region_box.md, section 1)
             double p[3] = {(double)(q.x + off.x), (double)(q.y + off.y), (double)(q.z + off.z)};
             p[axis] -= 0.5;
             const double ox = p[0] * dx - COM[(int64_t)r * 3 + 0], oy = p[1] * dx - COM[(int64_t)r * 3 + 1], oz = p[2] * dx - COM[(int64_t)r * 3 + 2];

@@ -3,16 +3,11 @@
 #pragma once
 
 // ---- per-tile reduced apply -------------------------------------------------------------------------
-// off (everywhere a face position is formed): global index of the local cell (0, 0, 0) — a rank of a decomposition forms offsets with
-// global indices, the same arithmetic as the single domain, so that a tile's matrices do not depend on the decomposition (0 without one)
+// the offset of a packed skin-row face from its region's centre (ps_common.hpp: faceOffset, which also says what `off` is)
 __device__ inline void rowOffset(uint32_t packed, const double* __restrict__ COM, int region, double dx, int3 off, double* o, int* axis) {
     int i, j, k, a;
     unpackFace(packed, i, j, k, a);
-    double p[3] = {(double)(i + off.x), (double)(j + off.y), (double)(k + off.z)};
-    p[a] -= 0.5;
-    o[0] = p[0] * dx - COM[(int64_t)region * 3 + 0];
-    o[1] = p[1] * dx - COM[(int64_t)region * 3 + 1];
-    o[2] = p[2] * dx - COM[(int64_t)region * 3 + 2];
+    faceOffset(COM + (int64_t)region * 3, dx, off, a, i, j, k, o);
     *axis = a;
 }
 // ---- the basis row through moments ----------------------------------------------------------------------------------
@@ -25,6 +20,8 @@ __device__ inline void rowOffset(uint32_t packed, const double* __restrict__ COM
 __device__ inline void faceMonomials(uint32_t f, double dx, int3 off, double cx, double cy, double cz, double* mu, int* axis) {
     int i, j, k, a;
     unpackFace(f, i, j, k, a);
+    // ps_common.hpp: faceOffset, written out — the half cell as a select, the centre in registers.  Calling the shared function gives the
+    // same numbers (x - 0. is x) but other code for every k_tile_apply instantiation (profiles/region_box.md, section 1): this text stays.
     const double ox = ((double)(i + off.x) - (a == 0 ? 0.5 : 0.)) * dx - cx;
     const double oy = ((double)(j + off.y) - (a == 1 ? 0.5 : 0.)) * dx - cy;
     const double oz = ((double)(k + off.z) - (a == 2 ? 0.5 : 0.)) * dx - cz;
@@ -390,7 +387,7 @@ __global__ void __launch_bounds__(BS) k_tile_expand(const int32_t* __restrict__ 
         if (rr < e) {
             int i, j, k, axis;
             unpackFace(fq[q], i, j, k, axis);
-            const double ox = ((double)(i + off.x) - (axis == 0 ? 0.5 : 0.)) * dx - cx;
+            const double ox = ((double)(i + off.x) - (axis == 0 ? 0.5 : 0.)) * dx - cx;   // faceOffset, written out as in faceMonomials
             const double oy = ((double)(j + off.y) - (axis == 1 ? 0.5 : 0.)) * dx - cy;
             const double oz = ((double)(k + off.z) - (axis == 2 ? 0.5 : 0.)) * dx - cz;
             tred[rr] = basisDot(ox, oy, oz, axis, v);

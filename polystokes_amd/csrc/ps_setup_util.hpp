@@ -1,6 +1,6 @@
-// Device and host helpers shared by the setup translation units (ps_grid.hip, ps_blocks.hip, ps_tiles.hip, ps_context.hip): the cell-field
-// sampler and the two material-field descriptions built on it, the block scan, the 64-bit mixer and the representative insert of the two
-// hash tables.  Not included by ps_solve.hip: nothing here may reach the solver's device code.
+// Device and host helpers shared by the setup translation units (ps_grid.hip, ps_blocks.hip, ps_tiles.hip, ps_surface.hip, ps_context.hip): the
+// cell-field sampler and the two material-field descriptions built on it, the walk over a region's box (RegionBox), the block scan, the 64-bit
+// mixer and the representative insert of the two hash tables.  Not included by ps_solve.hip: nothing here may reach the solver's device code.
 #pragma once
 #include "ps_common.hpp"
 
@@ -63,6 +63,39 @@ inline bool fieldIsUniform(const float* f, int64_t n, float* value) {
     for (int64_t i = 1; i < n; ++i) if (f[i] != f[0]) return false;
     return true;
 }
+
+// The box of positions that a per-tile kernel, or the host loop that cuts its work items, walks for region r.  bbox[r * 6 ..] holds the
+// smallest and the largest cell index of the region per axis (ps_grid.hip: k_bbox); the four shapes in use grow that box.  Position
+// pos in [0, total()) is x-fastest.  total() is 64 bits wide: the host refuses a box of more than 0x7fffffff positions where it cuts the
+// items (ps_tiles.hip: buildFaceBoxItems), after which a walk may keep pos in an int.
+struct RegionBox {
+    int x0, y0, z0;   // the first position
+    int ex, ey, ez;   // positions per axis
+    // the positions from `below` before the region's first cell to `above` after its last one, on every axis
+    __host__ __device__ static RegionBox grown(const int32_t* __restrict__ bbox, int r, int below, int above) {
+        const int32_t* b = bbox + r * 6;
+        RegionBox B;
+        B.x0 = b[0] - below; B.y0 = b[1] - below; B.z0 = b[2] - below;
+        B.ex = b[3] - B.x0 + 1 + above; B.ey = b[4] - B.y0 + 1 + above; B.ez = b[5] - B.z0 + 1 + above;
+        return B;
+    }
+    __host__ __device__ static RegionBox cells(const int32_t* __restrict__ bbox, int r) { return grown(bbox, r, 0, 0); }
+    // the faces of one axis around the region's cells: one plane more along that axis
+    __host__ __device__ static RegionBox faces(const int32_t* __restrict__ bbox, int r, int axis) {
+        RegionBox B = grown(bbox, r, 0, 0);
+        if (axis == 0) B.ex++; else if (axis == 1) B.ey++; else B.ez++;
+        return B;
+    }
+    // the union of the three face boxes (one position more than the cells on every axis): a position stands for up to three faces
+    __host__ __device__ static RegionBox faceUnion(const int32_t* __restrict__ bbox, int r) { return grown(bbox, r, 0, 1); }
+    // the face union and one sample around it, i.e. cells first - 1 .. last + 2: what a tile's Mr and K read (ps_tiles.hip: k_tile_signature)
+    __host__ __device__ static RegionBox ringed(const int32_t* __restrict__ bbox, int r) { return grown(bbox, r, 1, 2); }
+
+    __host__ __device__ int64_t total() const { return (int64_t)ex * ey * ez; }
+    // position pos on the grid (I: int, or int64_t where the total is not known to fit an int)
+    template <class I>
+    __host__ __device__ int3 at(I pos) const { return make_int3(x0 + (int)(pos % ex), y0 + (int)((pos / ex) % ey), z0 + (int)(pos / ((I)ex * ey))); }
+};
 
 // Exclusive scan of one int per thread over a workgroup of SETUP_BS threads (all of them call it); *total = the workgroup's sum.
 constexpr int SETUP_BS = 256;

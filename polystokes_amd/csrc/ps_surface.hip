@@ -10,6 +10,7 @@
 // Free-surface fields (ps_upload_surface_fields): the ghost pressure becomes the per-cell q_c = sigma_c kappa_c + P_c (k_surface_ghost_pressure,
 // fp64), and the same two force kernels read q with scale = dt in the place of kappa_c with scale = dt sigma ("Free-surface fields").
 #include "ps_context.hpp"
+#include "ps_setup_util.hpp"
 
 using namespace ps;
 
@@ -151,15 +152,15 @@ __global__ void __launch_bounds__(BS) k_surface_tension_tiles(SurfArgs A, const 
                                                               const double* __restrict__ COM, double dx, int3 off, double* __restrict__ rhsR,
                                                               int32_t* __restrict__ count) {
     const int r = blockIdx.x;
-    const int bx0 = bbox[r * 6 + 0], by0 = bbox[r * 6 + 1], bz0 = bbox[r * 6 + 2];
-    const int ex = bbox[r * 6 + 3] - bx0 + 2, ey = bbox[r * 6 + 4] - by0 + 2, ez = bbox[r * 6 + 5] - bz0 + 2;
-    const int total = ex * ey * ez;
+    const RegionBox box = RegionBox::faceUnion(bbox, r);
+    const int total = (int)box.total();
     double acc[PS_RD];
 #pragma unroll
     for (int n = 0; n < PS_RD; ++n) acc[n] = 0.;
     int hits = 0;
     for (int pos = threadIdx.x; pos < total; pos += BS) {
-        const int i = bx0 + pos % ex, j = by0 + (pos / ex) % ey, k = bz0 + pos / (ex * ey);
+        const int3 at = box.at(pos);
+        const int i = at.x, j = at.y, k = at.z;
         for (int a = 0; a < 3; ++a) {
             const int3 fd = A.g.dims(1 + a);
             if (oob3(fd, i, j, k)) continue;
@@ -169,10 +170,9 @@ __global__ void __launch_bounds__(BS) k_surface_tension_tiles(SurfArgs A, const 
             if (s == 0.) continue;
             ++hits;
             const double imp = -A.scale * s;
-            double p[3] = {(double)(i + off.x), (double)(j + off.y), (double)(k + off.z)};   // global indices (ps_kernels_tiles.hpp: rowOffset)
-            p[a] -= 0.5;
-            double row[PS_RD];
-            basisRow(p[0] * dx - COM[(int64_t)r * 3 + 0], p[1] * dx - COM[(int64_t)r * 3 + 1], p[2] * dx - COM[(int64_t)r * 3 + 2], a, row);
+            double o[3], row[PS_RD];
+            faceOffset(COM + (int64_t)r * 3, dx, off, a, i, j, k, o);
+            basisRow(o[0], o[1], o[2], a, row);
 #pragma unroll
             for (int n = 0; n < PS_RD; ++n) acc[n] += imp * row[n];
         }

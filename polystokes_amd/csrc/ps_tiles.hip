@@ -33,7 +33,7 @@ struct TileArgs {
     FaceDensity dens;                   // ps_context::densSource
     const double* densFace[3];          // a density field's clamped face samples (k_face_density), read by the MODE_MASS_FIELD sums
     const double* COM;
-    int3 off;                       // global index of the local cell (0, 0, 0) (ps_kernels_tiles.hpp: rowOffset)
+    int3 off;                       // global index of the local cell (0, 0, 0) (ps_common.hpp: faceOffset)
     const int32_t* bbox;
     const int32_t* itemRegion;
     const int32_t* itemAxis;
@@ -45,14 +45,6 @@ __device__ inline int labAt(const TileArgs& A, int s, const int3 d, int i, int j
 }
 __device__ inline int regAt(const TileArgs& A, int s, const int3 d, int i, int j, int k) {
     return oob3(d, i, j, k) ? PS_UNASSIGNED : A.reg[s][lin3(d, i, j, k)];
-}
-
-__device__ inline void faceOffset(const TileArgs& A, int axis, int i, int j, int k, int region, double* o) {
-    double p[3] = {(double)(i + A.off.x), (double)(j + A.off.y), (double)(k + A.off.z)};   // global indices: ps_kernels_tiles.hpp, rowOffset
-    p[axis] -= 0.5;
-#pragma unroll
-    for (int q = 0; q < 3; ++q) { p[q] *= A.dx; p[q] -= A.COM[(int64_t)region * 3 + q]; }
-    o[0] = p[0]; o[1] = p[1]; o[2] = p[2];
 }
 
 // g = sum_i contribution_i * C(adjacent face_i): the row-vector side of the viscosity outer products
@@ -90,7 +82,7 @@ __device__ void viscosityRowT(const TileArgs& A, int i, int j, int k, double* gv
                 const int adj = regAt(A, 1 + FA, fd, af.x, af.y, af.z);
                 if (adj < 0) continue;
                 double o[3];
-                faceOffset(A, FA, af.x, af.y, af.z, adj, o);
+                faceOffset(A.COM + (int64_t)adj * 3, A.dx, A.off, FA, af.x, af.y, af.z, o);
                 basisAccum<FA>(o[0], o[1], o[2], contribution, gv);
             }
         }
@@ -125,7 +117,7 @@ __device__ void viscosityRowT(const TileArgs& A, int i, int j, int k, double* gv
                     const int adj = regAt(A, 1 + adjFaceAxis, ad, af.x, af.y, af.z);
                     if (adj < 0) continue;
                     double o[3];
-                    faceOffset(A, adjFaceAxis, af.x, af.y, af.z, adj, o);
+                    faceOffset(A.COM + (int64_t)adj * 3, A.dx, A.off, adjFaceAxis, af.x, af.y, af.z, o);
                     if (adjFaceAxis == 0) basisAccum<0>(o[0], o[1], o[2], contribution, gv);
                     else if (adjFaceAxis == 1) basisAccum<1>(o[0], o[1], o[2], contribution, gv);
                     else basisAccum<2>(o[0], o[1], o[2], contribution, gv);
@@ -140,6 +132,23 @@ __device__ void viscosityRow(const TileArgs& A, int faceAxis, int i, int j, int 
     else viscosityRowT<2>(A, i, j, k, gv, part);
 }
 
+// Does face (axis; i, j, k) enter region r's sum of this MODE?  It must be r's face; the mass sums then take the faces of r's reduced cells and
+// those between a reduced cell below and an active cell above, the least-squares fit the faces between r and its active surroundings, the
+// viscosity every face of r.
+template <int MODE>
+__device__ inline bool outerUsesFace(const TileArgs& A, int r, int axis, const int3 fd, const int3 cd, int i, int j, int k) {
+    bool use = false;
+    if (regAt(A, 1 + axis, fd, i, j, k) == r) {
+        int3 hi = make_int3(i, j, k), lo = hi;
+        addc(lo, axis, -1);
+        const int lhi = labAt(A, 0, cd, hi.x, hi.y, hi.z), llo = labAt(A, 0, cd, lo.x, lo.y, lo.z);
+        if (MODE == MODE_MASS || MODE == MODE_MASS_FIELD) use = (lhi == PS_REDUCED) || (llo == PS_REDUCED && isActiveL(lhi));
+        else if (MODE == MODE_LSQ) use = (lhi == PS_REDUCED && isActiveL(llo)) || (llo == PS_REDUCED && isActiveL(lhi));
+        else use = true;
+    }
+    return use;
+}
+
 template <int MODE>
 __global__ void __launch_bounds__(BS) k_region_outer(TileArgs A, double* __restrict__ partial) {
     constexpr bool DENS = MODE == MODE_MASS_FIELD, MASS = MODE == MODE_MASS || DENS;
@@ -149,11 +158,8 @@ __global__ void __launch_bounds__(BS) k_region_outer(TileArgs A, double* __restr
     __shared__ double sr[DENS ? FBATCH : 1];   // the density of each staged face
     const int item = blockIdx.x;
     const int r = A.itemRegion[item], axis = A.itemAxis[item], start = A.itemStart[item];
-    const int bx0 = A.bbox[r * 6 + 0], by0 = A.bbox[r * 6 + 1], bz0 = A.bbox[r * 6 + 2];
-    int ex = A.bbox[r * 6 + 3] - bx0 + 1, ey = A.bbox[r * 6 + 4] - by0 + 1, ez = A.bbox[r * 6 + 5] - bz0 + 1;
-    if (axis == 0) ex++; else if (axis == 1) ey++; else ez++;
-    const int total = ex * ey * ez;
-    const int end = min(start + FB_CHUNK, total);
+    const RegionBox box = RegionBox::faces(A.bbox, r, axis);
+    const int end = min(start + FB_CHUNK, (int)box.total());
     const int3 fd = A.g.dims(1 + axis), cd = A.g.dims(0);
 
     double acc[3] = {0., 0., 0.};
@@ -170,27 +176,20 @@ __global__ void __launch_bounds__(BS) k_region_outer(TileArgs A, double* __restr
             double a[PS_RD];
             double uval = 0., rf = 0.;
             if (pos < end) {
-                const int li = pos % ex, lj = (pos / ex) % ey, lk = pos / (ex * ey);
-                const int i = bx0 + li, j = by0 + lj, k = bz0 + lk;
-                if (regAt(A, 1 + axis, fd, i, j, k) == r) {
-                    int3 hi = make_int3(i, j, k), lo = hi;
-                    addc(lo, axis, -1);
-                    const int lhi = labAt(A, 0, cd, hi.x, hi.y, hi.z), llo = labAt(A, 0, cd, lo.x, lo.y, lo.z);
-                    if (MASS) use = (lhi == PS_REDUCED) || (llo == PS_REDUCED && isActiveL(lhi));
-                    else if (MODE == MODE_LSQ) use = (lhi == PS_REDUCED && isActiveL(llo)) || (llo == PS_REDUCED && isActiveL(lhi));
-                    else use = true;
-                    if (use) {
-                        double o[3];
-                        faceOffset(A, axis, i, j, k, r, o);
-                        basisRow(o[0], o[1], o[2], axis, a);
-                        if (MODE == MODE_LSQ) uval = (double)A.vel[axis][lin3(fd, i, j, k)];
-                        if (DENS) rf = A.densFace[axis][lin3(fd, i, j, k)];
-                        if (MODE == MODE_VISC) {
-                            double gv[PS_RD];
-                            viscosityRow(A, axis, i, j, k, gv);
+                const int3 q = box.at(pos);
+                const int i = q.x, j = q.y, k = q.z;
+                use = outerUsesFace<MODE>(A, r, axis, fd, cd, i, j, k);
+                if (use) {
+                    double o[3];
+                    faceOffset(A.COM + (int64_t)r * 3, A.dx, A.off, axis, i, j, k, o);
+                    basisRow(o[0], o[1], o[2], axis, a);
+                    if (MODE == MODE_LSQ) uval = (double)A.vel[axis][lin3(fd, i, j, k)];
+                    if (DENS) rf = A.densFace[axis][lin3(fd, i, j, k)];
+                    if (MODE == MODE_VISC) {
+                        double gv[PS_RD];
+                        viscosityRow(A, axis, i, j, k, gv);
 #pragma unroll
-                            for (int n = 0; n < PS_RD; ++n) sb[t][n] = gv[n];
-                        }
+                        for (int n = 0; n < PS_RD; ++n) sb[t][n] = gv[n];
                     }
                 }
             }
@@ -256,11 +255,8 @@ __global__ void __launch_bounds__(BS) k_region_outer_mfma(TileArgs A, double* __
     __shared__ double sb[FBATCH][MPAD + 1];
     const int item = blockIdx.x;
     const int r = A.itemRegion[item], axis = A.itemAxis[item], start = A.itemStart[item];
-    const int bx0 = A.bbox[r * 6 + 0], by0 = A.bbox[r * 6 + 1], bz0 = A.bbox[r * 6 + 2];
-    int ex = A.bbox[r * 6 + 3] - bx0 + 1, ey = A.bbox[r * 6 + 4] - by0 + 1, ez = A.bbox[r * 6 + 5] - bz0 + 1;
-    if (axis == 0) ex++; else if (axis == 1) ey++; else ez++;
-    const int total = ex * ey * ez;
-    const int end = min(start + FB_CHUNK, total);
+    const RegionBox box = RegionBox::faces(A.bbox, r, axis);
+    const int end = min(start + FB_CHUNK, (int)box.total());
     const int3 fd = A.g.dims(1 + axis), cd = A.g.dims(0);
     const int t = threadIdx.x;
     const int ft = t & (FBATCH - 1);      // staged face handled by this thread
@@ -294,16 +290,9 @@ __global__ void __launch_bounds__(BS) k_region_outer_mfma(TileArgs A, double* __
         bool use = false;
         int i = 0, j = 0, k = 0;
         if (pos < end) {
-            const int li = pos % ex, lj = (pos / ex) % ey, lk = pos / (ex * ey);
-            i = bx0 + li; j = by0 + lj; k = bz0 + lk;
-            if (regAt(A, 1 + axis, fd, i, j, k) == r) {
-                int3 hi = make_int3(i, j, k), lo = hi;
-                addc(lo, axis, -1);
-                const int lhi = labAt(A, 0, cd, hi.x, hi.y, hi.z), llo = labAt(A, 0, cd, lo.x, lo.y, lo.z);
-                if (MASS) use = (lhi == PS_REDUCED) || (llo == PS_REDUCED && isActiveL(lhi));
-                else if (MODE == MODE_LSQ) use = (lhi == PS_REDUCED && isActiveL(llo)) || (llo == PS_REDUCED && isActiveL(lhi));
-                else use = true;
-            }
+            const int3 q = box.at(pos);
+            i = q.x; j = q.y; k = q.z;
+            use = outerUsesFace<MODE>(A, r, axis, fd, cd, i, j, k);
         }
         double vec[MPAD];
 #pragma unroll
@@ -312,7 +301,7 @@ __global__ void __launch_bounds__(BS) k_region_outer_mfma(TileArgs A, double* __
         if (use) {
             if (!doB || MODE != MODE_VISC) {
                 double o[3];
-                faceOffset(A, axis, i, j, k, r, o);
+                faceOffset(A.COM + (int64_t)r * 3, A.dx, A.off, axis, i, j, k, o);
                 basisRow(o[0], o[1], o[2], axis, vec);
                 if (MASS && !doB) {
                     const double rf = DENS ? A.densFace[axis][lin3(fd, i, j, k)] : A.dens.rho;
@@ -437,14 +426,15 @@ __device__ inline TileWord tileWord(const TileArgs& A, int r, int i, int j, int 
 constexpr long long TILE_SIG_MAX_POS = 1 << 16;   // boxes beyond this (the single region of the non-tiled mode) are not compared
 __global__ void __launch_bounds__(BS) k_tile_signature(TileArgs A, unsigned long long* __restrict__ sig, int32_t* __restrict__ unique) {
     const int r = blockIdx.x;
-    const int bx0 = A.bbox[r * 6 + 0] - 1, by0 = A.bbox[r * 6 + 1] - 1, bz0 = A.bbox[r * 6 + 2] - 1;
-    const int ex = A.bbox[r * 6 + 3] - bx0 + 3, ey = A.bbox[r * 6 + 4] - by0 + 3, ez = A.bbox[r * 6 + 5] - bz0 + 3;   // cells -1 .. max + 2
-    const long long total = (long long)ex * ey * ez;
+    const RegionBox box = RegionBox::ringed(A.bbox, r);
+    const int ex = box.ex, ey = box.ey, ez = box.ez;
+    const long long total = box.total();
     unsigned long long h1 = 0, h2 = 0;
     bool foreign = total > TILE_SIG_MAX_POS;
     if (!foreign)
         for (int pos = threadIdx.x; pos < (int)total; pos += BS) {
-            const TileWord w = tileWord(A, r, bx0 + pos % ex, by0 + (pos / ex) % ey, bz0 + pos / (ex * ey));
+            const int3 q = box.at(pos);
+            const TileWord w = tileWord(A, r, q.x, q.y, q.z);
             foreign |= w.foreign;
             h1 += mix64(((unsigned long long)pos << 46) ^ w.geom);
             h2 += mix64((((unsigned long long)pos * 0x9e3779b97f4a7c15ull) ^ w.geom) + ((unsigned long long)w.visc << 17) + 0x632be59bd9b4e019ull);
@@ -485,14 +475,13 @@ __global__ void __launch_bounds__(BS) k_tile_rep_verify(TileArgs A, const unsign
     }
     bool same = cand != r && sig[2 * cand + 1] == sig[2 * r + 1];
     if (same) {
-        const int ax0 = A.bbox[r * 6 + 0] - 1, ay0 = A.bbox[r * 6 + 1] - 1, az0 = A.bbox[r * 6 + 2] - 1;
-        const int ex = A.bbox[r * 6 + 3] - ax0 + 3, ey = A.bbox[r * 6 + 4] - ay0 + 3, ez = A.bbox[r * 6 + 5] - az0 + 3;
-        const int cx0 = A.bbox[cand * 6 + 0] - 1, cy0 = A.bbox[cand * 6 + 1] - 1, cz0 = A.bbox[cand * 6 + 2] - 1;
-        same = ex == A.bbox[cand * 6 + 3] - cx0 + 3 && ey == A.bbox[cand * 6 + 4] - cy0 + 3 && ez == A.bbox[cand * 6 + 5] - cz0 + 3;
+        const RegionBox mine = RegionBox::ringed(A.bbox, r), its = RegionBox::ringed(A.bbox, cand);
+        same = mine.ex == its.ex && mine.ey == its.ey && mine.ez == its.ez;
+        const int sx = its.x0 - mine.x0, sy = its.y0 - mine.y0, sz = its.z0 - mine.z0;   // the same position of the candidate's box
         if (same)
-            for (int pos = threadIdx.x; pos < ex * ey * ez; pos += BS) {
-                const int li = pos % ex, lj = (pos / ex) % ey, lk = pos / (ex * ey);
-                const TileWord a = tileWord(A, r, ax0 + li, ay0 + lj, az0 + lk), b = tileWord(A, cand, cx0 + li, cy0 + lj, cz0 + lk);
+            for (int pos = threadIdx.x; pos < (int)mine.total(); pos += BS) {
+                const int3 q = mine.at(pos);
+                const TileWord a = tileWord(A, r, q.x, q.y, q.z), b = tileWord(A, cand, q.x + sx, q.y + sy, q.z + sz);
                 same = same && a.geom == b.geom && a.visc == b.visc && !a.foreign && !b.foreign;
             }
     }
@@ -528,12 +517,12 @@ __global__ void k_com(Grid g, double dx, int3 off, const int32_t* __restrict__ l
                       const int32_t* __restrict__ bbox, double* __restrict__ COM) {
     const int r = blockIdx.x;
     const int3 d = g.dims(0);
-    const int bx0 = bbox[r * 6 + 0], by0 = bbox[r * 6 + 1], bz0 = bbox[r * 6 + 2];
-    const int ex = bbox[r * 6 + 3] - bx0 + 1, ey = bbox[r * 6 + 4] - by0 + 1, ez = bbox[r * 6 + 5] - bz0 + 1;
-    const int64_t total = (int64_t)ex * ey * ez;
+    const RegionBox box = RegionBox::cells(bbox, r);
+    const int64_t total = box.total();
     unsigned long long sx = 0, sy = 0, sz = 0, cnt = 0;
     for (int64_t pos = threadIdx.x; pos < total; pos += blockDim.x) {
-        const int i = bx0 + (int)(pos % ex), j = by0 + (int)((pos / ex) % ey), k = bz0 + (int)(pos / ((int64_t)ex * ey));
+        const int3 q = box.at(pos);
+        const int i = q.x, j = q.y, k = q.z;
         const int64_t c = lin3(d, i, j, k);
         if (isReducedL(lab[c]) && reg[c] == r) { sx += i + off.x; sy += j + off.y; sz += k + off.z; cnt++; }
     }
@@ -683,16 +672,24 @@ TileArgs makeArgs(ps_context* c) {
     A.COM = c->COM.p;
     A.off = make_int3(c->gOff[0], c->gOff[1], c->gOff[2]);
     A.bbox = c->bbox.p;
-    A.itemRegion = c->fbItemRegion.p; A.itemAxis = c->fbItemAxis.p; A.itemStart = c->fbItemStart.p;
+    A.itemRegion = c->fbItems.region.p; A.itemAxis = c->fbItems.axis.p; A.itemStart = c->fbItems.start.p;
     return A;
+}
+
+// one block per item of `items`, the MFMA kernel unless PS_TILE_VALU asks for the plain one
+template <int MODE>
+void launchOuter(ps_context* c, TileArgs A, const ps_context::FaceBoxItems& items) {
+    static const bool useMfma = envInt(PS_ENV("PS_TILE_VALU"), 0) == 0;
+    A.itemRegion = items.region.p; A.itemAxis = items.axis.p; A.itemStart = items.start.p;
+    if (useMfma) hipLaunchKernelGGL(k_region_outer_mfma<MODE>, dim3((unsigned)items.count), dim3(BS), 0, c->stream, A, c->partials.p);
+    else hipLaunchKernelGGL(k_region_outer<MODE>, dim3((unsigned)items.count), dim3(BS), 0, c->stream, A, c->partials.p);
 }
 
 template <int MODE>
 void runOuter(ps_context* c, double* out676, double* out26) {
-    if (c->regionCount == 0 || c->fbItems == 0) return;
-    c->partials.alloc((size_t)c->fbItems * OUTW);
+    if (c->regionCount == 0 || c->fbItems.count == 0) return;
+    c->partials.alloc((size_t)c->fbItems.count * OUTW);
     TileArgs A = makeArgs(c);
-    static const bool useMfma = envInt(PS_ENV("PS_TILE_VALU"), 0) == 0;
     // Which blocks are shared (PS_TILE_CLASS_MASK; bit 0: Mr, bit 1: K).  Default: K only.  A copied block differs from the tile's own sums
     // by the rounding of `index * dx - COM` at the representative's position (Mr 3e-16, K 4e-14 relative to the oracle's either way).  On
     // the stiff 48^3 spheres at tol 1e-8 — where a 1e-15 change of B moves the velocities by 1e-5..1e-4, the AMP sensitivity of
@@ -703,10 +700,8 @@ void runOuter(ps_context* c, double* out676, double* out26) {
     // (a density field makes Mr a function of the tile's densities, which the class signature does not see: Mr then stays per tile)
     const bool shareable = MODE == MODE_VISC || (MODE == MODE_MASS && !c->densField);
     if (shareable && ((MODE == MODE_MASS ? 1 : 2) & clsMask) && c->tileReps > 0 && c->tileReps < c->regionCount) {   // one sum per class of identical tiles, copied to the others
-        A.itemRegion = c->repItemRegion.p; A.itemAxis = c->repItemAxis.p; A.itemStart = c->repItemStart.p;
-        if (useMfma) hipLaunchKernelGGL(k_region_outer_mfma<MODE>, dim3((unsigned)c->repItems), dim3(BS), 0, c->stream, A, c->partials.p);
-        else hipLaunchKernelGGL(k_region_outer<MODE>, dim3((unsigned)c->repItems), dim3(BS), 0, c->stream, A, c->partials.p);
-        hipLaunchKernelGGL(k_region_sum_list, dim3((unsigned)c->tileReps), dim3(BS), 0, c->stream, c->partials.p, c->repRegionItemPtr.p, c->repList.p, out676);
+        launchOuter<MODE>(c, A, c->repItems);
+        hipLaunchKernelGGL(k_region_sum_list, dim3((unsigned)c->tileReps), dim3(BS), 0, c->stream, c->partials.p, c->repItems.regionPtr.p, c->repList.p, out676);
         hipLaunchKernelGGL(k_tile_replicate, dim3((unsigned)c->regionCount), dim3(BS), 0, c->stream, (const int32_t*)c->tileRep.p, out676);
         return;
     }
@@ -717,11 +712,32 @@ void runOuter(ps_context* c, double* out676, double* out26) {
             A.densFace[a] = c->densFace[a].p;
             hipLaunchKernelGGL(k_face_density, dim3(gridFor(n, BS)), dim3(BS), 0, c->stream, A, a, c->densFace[a].p);
         }
-        if (useMfma) hipLaunchKernelGGL(k_region_outer_mfma<MODE_MASS_FIELD>, dim3((unsigned)c->fbItems), dim3(BS), 0, c->stream, A, c->partials.p);
-        else hipLaunchKernelGGL(k_region_outer<MODE_MASS_FIELD>, dim3((unsigned)c->fbItems), dim3(BS), 0, c->stream, A, c->partials.p);
-    } else if (useMfma) hipLaunchKernelGGL(k_region_outer_mfma<MODE>, dim3((unsigned)c->fbItems), dim3(BS), 0, c->stream, A, c->partials.p);
-    else hipLaunchKernelGGL(k_region_outer<MODE>, dim3((unsigned)c->fbItems), dim3(BS), 0, c->stream, A, c->partials.p);
-    hipLaunchKernelGGL(k_region_sum, dim3((unsigned)c->regionCount), dim3(BS), 0, c->stream, c->partials.p, c->fbRegionItemPtr.p, out676, out26);
+        launchOuter<MODE_MASS_FIELD>(c, A, c->fbItems);
+    } else launchOuter<MODE>(c, A, c->fbItems);
+    hipLaunchKernelGGL(k_region_sum, dim3((unsigned)c->regionCount), dim3(BS), 0, c->stream, c->partials.p, c->fbItems.regionPtr.p, out676, out26);
+}
+
+// The face-box items (ps_context::FaceBoxItems) of the n listed regions (list null: regions 0 .. n - 1), built in tab[0 .. 3] and uploaded.
+// tab: four of the context's hostTab vectors — they outlive the asynchronous copies, which therefore need no synchronisation.
+void buildFaceBoxItems(ps_context* c, ps_context::FaceBoxItems& items, std::vector<int32_t>* tab, const int32_t* list, int64_t n) {
+    std::vector<int32_t>& iR = tab[0]; std::vector<int32_t>& iA = tab[1]; std::vector<int32_t>& iS = tab[2]; std::vector<int32_t>& ptr = tab[3];
+    iR.clear(); iA.clear(); iS.clear(); ptr.assign((size_t)n + 1, 0);
+    for (int64_t q = 0; q < n; ++q) {
+        const int32_t r = list ? list[q] : (int32_t)q;
+        ptr[(size_t)q] = (int32_t)iR.size();
+        for (int a = 0; a < 3; ++a) {
+            const int64_t total = RegionBox::faces(c->hbbox.data(), r, a).total();
+            if (total > 0x7fffffff) throw Error("region face box too large");
+            for (int64_t st = 0; st < total; st += FB_CHUNK) { iR.push_back(r); iA.push_back(a); iS.push_back((int32_t)st); }
+        }
+    }
+    ptr[(size_t)n] = (int32_t)iR.size();
+    items.count = (int64_t)iR.size();
+    items.region.alloc(iR.size()); items.axis.alloc(iA.size()); items.start.alloc(iS.size()); items.regionPtr.alloc(ptr.size());
+    HIP_CHECK(hipMemcpyAsync(items.region.p, iR.data(), iR.size() * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_CHECK(hipMemcpyAsync(items.axis.p, iA.data(), iA.size() * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_CHECK(hipMemcpyAsync(items.start.p, iS.data(), iS.size() * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_CHECK(hipMemcpyAsync(items.regionPtr.p, ptr.data(), ptr.size() * 4, hipMemcpyHostToDevice, c->stream));
 }
 
 }  // namespace
@@ -734,7 +750,7 @@ void ps_context::computeCenterOfMasses() {
     Mr.alloc((size_t)R * PS_RD * PS_RD); Kv.alloc((size_t)R * PS_RD * PS_RD); Binv.alloc((size_t)R * PS_RD * PS_RD);
     rhsR.alloc((size_t)R * PS_RD);
     regionScratch.alloc((size_t)R * OUTW);
-    if (R == 0) { fbItems = 0; return; }
+    if (R == 0) { fbItems.count = 0; return; }
     if (slabEnabled) {   // a tile is owned iff all of its cells are in my box; cuts are tile aligned
         std::vector<int32_t> ro((size_t)R, 1);
         for (int64_t r = 0; r < R; ++r) {
@@ -751,31 +767,14 @@ void ps_context::computeCenterOfMasses() {
         HIP_CHECK(hipMemcpyAsync(regionOwned.p, ro.data(), (size_t)R * 4, hipMemcpyHostToDevice, stream));
         HIP_CHECK(hipStreamSynchronize(stream));
     }
-    // (host tables kept with the context — hostTab* — so that their uploads need no synchronisation: the vectors outlive the copies)
-    std::vector<int32_t>& iR = hostTab[0]; std::vector<int32_t>& iA = hostTab[1]; std::vector<int32_t>& iS = hostTab[2]; std::vector<int32_t>& ptr = hostTab[3];
-    iR.clear(); iA.clear(); iS.clear(); ptr.assign((size_t)R + 1, 0);
-    for (int64_t r = 0; r < R; ++r) {
-        ptr[(size_t)r] = (int32_t)iR.size();
-        for (int a = 0; a < 3; ++a) {
-            int64_t e[3];
-            for (int q = 0; q < 3; ++q) e[q] = (int64_t)hbbox[(size_t)r * 6 + 3 + q] - hbbox[(size_t)r * 6 + q] + 1;
-            e[a] += 1;
-            const int64_t total = e[0] * e[1] * e[2];
-            if (total > 0x7fffffff) throw Error("region face box too large");
-            for (int64_t st = 0; st < total; st += FB_CHUNK) { iR.push_back((int32_t)r); iA.push_back(a); iS.push_back((int32_t)st); }
-        }
-    }
-    ptr[(size_t)R] = (int32_t)iR.size();
-    fbItems = (int64_t)iR.size();
-    fbItemRegion.alloc(iR.size()); fbItemAxis.alloc(iR.size()); fbItemStart.alloc(iR.size()); fbRegionItemPtr.alloc(ptr.size());
-    {   // skin-row enumeration items: the union face box of each region, FB_CHUNK positions per item
+    buildFaceBoxItems(this, fbItems, &hostTab[0], nullptr, R);
+    {   // skin-row enumeration items: the union face box of each region, FB_CHUNK positions per item (hostTab: see buildFaceBoxItems)
         std::vector<int32_t>& sR = hostTab[4]; std::vector<int32_t>& sS = hostTab[5];
         sR.clear(); sS.clear();
         sbRegionItemPtrHost.assign((size_t)R + 1, 0);
         for (int64_t r = 0; r < R; ++r) {
             sbRegionItemPtrHost[(size_t)r] = (int32_t)sR.size();
-            int64_t total = 1;
-            for (int q = 0; q < 3; ++q) total *= (int64_t)hbbox[(size_t)r * 6 + 3 + q] - hbbox[(size_t)r * 6 + q] + 2;
+            const int64_t total = RegionBox::faceUnion(hbbox.data(), (int)r).total();
             if (total > 0x7fffffff) throw Error("region face box too large");
             for (int64_t st = 0; st < total; st += FB_CHUNK) { sR.push_back((int32_t)r); sS.push_back((int32_t)st); }
         }
@@ -785,17 +784,13 @@ void ps_context::computeCenterOfMasses() {
         HIP_CHECK(hipMemcpyAsync(sbItemRegion.p, sR.data(), sR.size() * 4, hipMemcpyHostToDevice, stream));
         HIP_CHECK(hipMemcpyAsync(sbItemStart.p, sS.data(), sS.size() * 4, hipMemcpyHostToDevice, stream));
     }
-    HIP_CHECK(hipMemcpyAsync(fbItemRegion.p, iR.data(), iR.size() * 4, hipMemcpyHostToDevice, stream));
-    HIP_CHECK(hipMemcpyAsync(fbItemAxis.p, iA.data(), iA.size() * 4, hipMemcpyHostToDevice, stream));
-    HIP_CHECK(hipMemcpyAsync(fbItemStart.p, iS.data(), iS.size() * 4, hipMemcpyHostToDevice, stream));
-    HIP_CHECK(hipMemcpyAsync(fbRegionItemPtr.p, ptr.data(), ptr.size() * 4, hipMemcpyHostToDevice, stream));
     hipLaunchKernelGGL(k_com, dim3((unsigned)R), dim3(BS), 0, stream, g, dx, make_int3(gOff[0], gOff[1], gOff[2]), labels[0].p, reducedIdx[0].p, bbox.p, COM.p);
     buildTileClasses();
 }
 
 // Classes of identical tiles (see k_tile_signature): tileRep[r], and the face-box items of the representatives alone.
 void ps_context::buildTileClasses() {
-    tileReps = 0; repItems = 0;
+    tileReps = 0; repItems.count = 0;
     const int64_t R = regionCount;
     static const bool off = envInt(PS_ENV("PS_NO_TILE_CLASSES"), 0) != 0;   // A/B: every tile sums its own blocks
     if (off || R < 2) return;
@@ -815,29 +810,14 @@ void ps_context::buildTileClasses() {
     rep.assign((size_t)R, 0);
     HIP_CHECK(hipMemcpyAsync(rep.data(), tileRep.p, (size_t)R * 4, hipMemcpyDeviceToHost, stream));
     HIP_CHECK(hipStreamSynchronize(stream));
-    std::vector<int32_t>& iR = hostTab[12]; std::vector<int32_t>& iA = hostTab[13]; std::vector<int32_t>& iS = hostTab[14];
-    std::vector<int32_t>& ptr = hostTab[15]; std::vector<int32_t>& list = hostTab[16];
-    iR.clear(); iA.clear(); iS.clear(); ptr.clear(); list.clear();
-    for (int64_t r = 0; r < R; ++r) {
-        if (rep[(size_t)r] != (int32_t)r) continue;
-        list.push_back((int32_t)r);
-        ptr.push_back((int32_t)iR.size());
-        for (int a = 0; a < 3; ++a) {                 // the same items, in the same order, as computeCenterOfMasses builds for every region
-            int64_t e[3];
-            for (int q = 0; q < 3; ++q) e[q] = (int64_t)hbbox[(size_t)r * 6 + 3 + q] - hbbox[(size_t)r * 6 + q] + 1;
-            e[a] += 1;
-            const int64_t total = e[0] * e[1] * e[2];
-            for (int64_t st = 0; st < total; st += FB_CHUNK) { iR.push_back((int32_t)r); iA.push_back(a); iS.push_back((int32_t)st); }
-        }
-    }
-    ptr.push_back((int32_t)iR.size());
+    std::vector<int32_t>& list = hostTab[16];
+    list.clear();
+    for (int64_t r = 0; r < R; ++r)
+        if (rep[(size_t)r] == (int32_t)r) list.push_back((int32_t)r);
     if ((int64_t)list.size() == R) return;            // nothing repeats: the plain path
-    tileReps = (int64_t)list.size(); repItems = (int64_t)iR.size();
-    repItemRegion.alloc(iR.size()); repItemAxis.alloc(iA.size()); repItemStart.alloc(iS.size()); repRegionItemPtr.alloc(ptr.size()); repList.alloc(list.size());
-    HIP_CHECK(hipMemcpyAsync(repItemRegion.p, iR.data(), iR.size() * 4, hipMemcpyHostToDevice, stream));
-    HIP_CHECK(hipMemcpyAsync(repItemAxis.p, iA.data(), iA.size() * 4, hipMemcpyHostToDevice, stream));
-    HIP_CHECK(hipMemcpyAsync(repItemStart.p, iS.data(), iS.size() * 4, hipMemcpyHostToDevice, stream));
-    HIP_CHECK(hipMemcpyAsync(repRegionItemPtr.p, ptr.data(), ptr.size() * 4, hipMemcpyHostToDevice, stream));
+    tileReps = (int64_t)list.size();
+    buildFaceBoxItems(this, repItems, &hostTab[12], list.data(), tileReps);
+    repList.alloc(list.size());
     HIP_CHECK(hipMemcpyAsync(repList.p, list.data(), list.size() * 4, hipMemcpyHostToDevice, stream));
     if (PS_ENV_VERBOSE()) std::fprintf(stderr, "[polystokes] tile classes: %lld of %lld tiles sum their own Mr / K\n", (long long)tileReps, (long long)R);
 }

@@ -408,3 +408,52 @@ def test_bricks_without_reduced_regions_match_single_domain(dims):
         assert np.abs(grp.vel[a] - single.vel[a]).max() <= 1e-6 * scale
     grp.close()
     single.close()
+
+
+@pytest.mark.parametrize("case", ["cavity32", "spheres32", "cavity64", "spheres64"])
+def test_owned_tiles_of_a_brick_carry_the_single_domains_tile_arrays(case):
+    """a rank forms every face offset with GLOBAL indices (ps_common.hpp: faceOffset), so the tiles it owns carry the
+    single domain's centre of mass, mass block, least-squares fit and reduced right-hand side BYTE FOR BYTE.  Regions are matched by the
+    bytes of their centre; a rank owns a region whose centre lies in its owned global box (cuts are tile aligned); every region of the single
+    domain must be matched exactly once over the eight ranks.  K is compared at 1e-12 of its largest entry only: a tile copies it from its
+    class representative, which may be another tile on a rank than in the whole domain (ps_tiles.hip: PS_TILE_CLASS_MASK).
+    cavity32 and spheres32 (tile 8, 2 x 2 x 2): the halo block of 16 cells makes every rank's view the whole 32^3 grid, so the global
+    offset is 0 there and the ranks differ from the single domain in their region numbering and ownership only; 64^3 (tile 8) is the
+    smallest cube whose upper ranks start at global cell 16 on every axis, where an offset formed with local indices would show.  The
+    cavity moves its lid only, so its tiles' fits and right-hand sides are zero (equal, but saying nothing): the spheres cases are the ones
+    that compare them, and there they must hold something.  Setup only (doSolve = 0): the arrays are complete before the solve."""
+    import polystokes_amd
+    sc, p = {"cavity32": lambda: scenes.cavity(32, tile=8), "spheres32": lambda: scenes.spheres(32, tile=8),
+             "cavity64": lambda: scenes.cavity(64, tile=8), "spheres64": lambda: scenes.spheres(64, tile=8)}[case]()
+    p.doSolve = 0
+    exact = ("reducedRegionCOM", "reducedMassMatrices", "reducedRegionBestFitVectors", "reducedRHSVector")
+    names = exact + ("reducedViscosityMatrices",)
+    single = polystokes_amd.Solver(0)
+    assert single.step(sc, p) == abi.INCOMPLETE
+    R = single.nRegions
+    assert R > 1
+    ref = {n: single.array(n).reshape(R, -1) for n in names}
+    for n in names:                                 # (the comparisons below are between arrays that hold something)
+        assert np.any(ref[n] != 0.) or (case.startswith("cavity") and n in ("reducedRegionBestFitVectors", "reducedRHSVector")), (case, n)
+    index = {ref["reducedRegionCOM"][r].tobytes(): r for r in range(R)}
+    assert len(index) == R
+    grp = polystokes_amd.Group(8, dims=(2, 2, 2))
+    assert grp.solve_scene(sc, p) == abi.INCOMPLETE
+    matched = np.zeros(R, np.int64)
+    for b, s in zip(grp.bricks, grp.ranks):
+        if case.endswith("64") and all(b.coord):
+            assert min(b.origin) > 0
+        com = s.array("reducedRegionCOM").reshape(-1, 3)
+        mine = {n: s.array(n).reshape(len(com), -1) for n in names}
+        lo, hi = np.array(b.g0) * sc.dx, np.array(b.g1) * sc.dx
+        for q in np.nonzero(((com >= lo) & (com < hi)).all(axis=1))[0]:
+            r = index.get(com[q].tobytes())
+            assert r is not None, (case, b.rank, q, com[q])
+            matched[r] += 1
+            for n in exact:
+                assert mine[n][q].tobytes() == ref[n][r].tobytes(), (case, b.rank, n, q, r, np.abs(mine[n][q] - ref[n][r]).max())
+            K, Kr = mine["reducedViscosityMatrices"][q], ref["reducedViscosityMatrices"][r]
+            assert np.abs(K - Kr).max() <= 1e-12 * np.abs(Kr).max(), (case, b.rank, q, r)
+    assert np.array_equal(matched, np.ones(R, np.int64)), (case, np.nonzero(matched != 1)[0][:10])
+    grp.close()
+    single.close()
