@@ -99,6 +99,11 @@ struct Oracle {
     int64_t nActiveVs = 0, nReducedVs = 0, nPressures = 0, nStresses = 0, nReducedStresses = 0;
     int64_t nTotalDOFs = 0, nSystemSize = 0;
     int64_t regionCount = 0;
+    // what the region fixes did (array "regionFixCounters"; tests/classification_cases.py): [0] sweeps of fixReducedRegionBoundaries, the last,
+    // idle one included, [1] fixes applied, [2] of them by a cell that was REDUCED when its sweep began, [3] regions the fix left without a
+    // cell, [4] / [5] regions before / after fixSmallReducedRegions
+    int64_t fixCounters[6] = {0, 0, 0, 0, 0, 0};
+    std::vector<int64_t> componentSizes;   // cells of every component as connectedComponents numbered it, before either fix ("componentSizeCounters")
 
     // per-region data
     std::vector<double> COM;        // R*3

@@ -68,7 +68,7 @@ _DT = {(4, "i"): np.int32, (4, "f"): np.float32, (8, "f"): np.float64, (8, "i"):
 def _kind(name):
     if name.endswith("Labels") or name.endswith("Indices") or name.endswith(".col"):
         return "i"
-    if name.endswith(".ptr"):
+    if name.endswith(".ptr") or name.endswith("Counters"):
         return "i"
     return "f"
 
@@ -116,6 +116,11 @@ class Oracle:
         ptr, col, val = self.array(name + ".ptr"), self.array(name + ".col"), self.array(name + ".val")
         ncols = {"G": self.nP, "JG": self.nP, "Dt": self.nT, "JDt": self.nT, "A": self.nP + self.nT}[name]
         return sp.csr_matrix((val, col, ptr), shape=(len(ptr) - 1, ncols))
+
+    def fix_counters(self):
+        """what fixReducedRegionBoundaries and fixSmallReducedRegions did in the last run (ps_oracle.hpp: fixCounters)"""
+        c = self.array("regionFixCounters")
+        return dict(zip(("sweeps", "fixes", "fixes_by_demoted", "regions_emptied", "regions_before", "regions_after"), (int(v) for v in c)))
 
     @property
     def nP(self):

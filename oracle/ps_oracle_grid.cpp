@@ -339,6 +339,8 @@ void Oracle::connectedComponents() {
         }
     });
     regionCount = count;
+    componentSizes.assign((size_t)count, 0);
+    for (const int32_t r : R.v) if (r >= 0) ++componentSizes[(size_t)r];
 }
 
 // Classifier.cpp:1073-1172 — serial, in-place, traversal-ordered fix point.
@@ -347,8 +349,11 @@ void Oracle::fixReducedRegionBoundaries() {
     Field<int32_t>& L = labels[0];
     Field<int32_t>& R = reducedIdx[0];
     bool done = false;
+    std::vector<int32_t> atSweepStart;   // (counters only: the labels are never read from it)
     while (!done) {
         done = true;
+        ++fixCounters[0];
+        atSweepStart = L.v;
         forEachOrdered(d, [&](int i, int j, int k) {
             if (L.at(i, j, k) != PS_ACTIVEFLUID) return;
             bool applyFix = false, isBoundaryCell = false;
@@ -367,6 +372,8 @@ void Oracle::fixReducedRegionBoundaries() {
                 }
             if (applyFix) {
                 done = false;
+                ++fixCounters[1];
+                if (atSweepStart[(size_t)d.lin(i, j, k)] == PS_REDUCED) ++fixCounters[2];
                 for (int axis = 0; axis < 3; ++axis)
                     for (int dir = 0; dir < 2; ++dir) {
                         int a[3] = {i, j, k};
@@ -400,6 +407,8 @@ void Oracle::fixSmallReducedRegions() {
                     bbmax[(size_t)r * 3 + a] = std::max<int64_t>(bbmax[(size_t)r * 3 + a], c[a]);
                 }
             }
+    fixCounters[4] = Rn;
+    for (int64_t r = 0; r < Rn; ++r) if (bbmax[(size_t)r * 3] < bbmin[(size_t)r * 3]) ++fixCounters[3];
     std::vector<char> doRemove((size_t)Rn, 0);
     for (int64_t r = 0; r < Rn; ++r)
         for (int a = 0; a < 3; ++a) {
@@ -413,6 +422,7 @@ void Oracle::fixSmallReducedRegions() {
     std::vector<int64_t> remap((size_t)Rn, -1);
     int64_t regionMap = 0;
     for (int64_t r = 0; r < Rn; ++r) if (!doRemove[(size_t)r]) remap[(size_t)r] = regionMap++;
+    fixCounters[5] = regionMap;
     if (Rn > regionMap) {
         regionCount = regionMap;
         for (size_t c = 0; c < L.v.size(); ++c) {   // remapInteriorRegions :1264-1313

@@ -502,6 +502,8 @@ int Oracle::load(const ps_params* p, const ps_fields_in* in) {
         reducedIdx[s].init(d, PS_UNASSIGNED);
     }
     regionCount = 0;
+    for (auto& c : fixCounters) c = 0;
+    componentSizes.clear();
     std::memset(&stats, 0, sizeof(stats));
     stats.result = PS_INCOMPLETE;
     return PS_SUCCESS;
@@ -593,6 +595,8 @@ void Oracle::registerArrays() {
         reg(std::string(sname[s]) + "ReducedIndices", reducedIdx[s].v.data(), (int64_t)reducedIdx[s].v.size(), 4);
     }
     auto regv = [&](const std::string& n, const std::vector<double>& v) { reg(n, v.data(), (int64_t)v.size(), 8); };
+    reg("regionFixCounters", fixCounters, 6, 8);
+    reg("componentSizeCounters", componentSizes.data(), (int64_t)componentSizes.size(), 8);
     regv("reducedRegionCOM", COM);
     regv("reducedRegionBestFitVectors", cfit);
     regv("reducedRegionBestFitSystems", fitN); regv("reducedRegionBestFitRHS", fitRhs);

@@ -10,7 +10,7 @@ import pytest
 from polystokes_amd import _abi as abi
 from polystokes_amd import scenes
 
-from helpers import materialise_blocks, relerr
+from helpers import check_rhs_and_operator, check_solve, check_stencil_blocks, check_tile_blocks, relerr
 
 pytestmark = pytest.mark.gpu
 
@@ -74,76 +74,19 @@ def test_setup_integer_state_is_bit_exact(pair):
 
 
 def test_tile_blocks_match(pair):
-    name, sc, p, o, g = pair
-    if o.nRegions == 0:
-        pytest.skip("no reduced regions")
-    assert np.array_equal(g.array("reducedRegionCOM"), o.array("reducedRegionCOM"))   # exact integer sums
-    tol = 1e-12
-    assert relerr(g.array("reducedMassMatrices"), o.array("reducedMassMatrices")) < tol
-    assert relerr(g.array("reducedViscosityMatrices"), o.array("reducedViscosityMatrices")) < tol
-    R = o.nRegions
-    # c_fit solves an ill-conditioned LSQ system and BInv inverts B: compare through what they feed
-    Mr = o.array("reducedMassMatrices").reshape(R, 26, 26)
-    K = o.array("reducedViscosityMatrices").reshape(R, 26, 26)
-    Bi = g.array("Inv_Mr_plus_2JDtuDJ").reshape(R, 26, 26)
-    Bo = o.array("Inv_Mr_plus_2JDtuDJ").reshape(R, 26, 26)
-    for r in range(R):
-        B = Mr[r] / sc.dt + 2 * K[r]
-        assert np.abs(Bi[r] @ B - np.eye(26)).max() < 1e-7
-        assert relerr(Bi[r], Bo[r]) < 1e-6
-    assert relerr(g.array("reducedRHSVector"), o.array("reducedRHSVector")) < 1e-8
+    check_tile_blocks(*pair)
 
 
 def test_stencil_blocks_match(pair):
-    name, sc, p, o, g = pair
-    for nm in ("McInv", "activeRHSVector", "uInv", "pressureRHSVector", "stressRHSVector"):
-        assert relerr(g.array(nm), o.array(nm)) < 1e-13, (name, nm)
-    G, Dt, JG, JDt = materialise_blocks(g)
-    for nm, M in (("G", G), ("Dt", Dt), ("JG", JG), ("JDt", JDt)):
-        Mo = o.csr(nm)
-        assert M.shape == Mo.shape, (name, nm, M.shape, Mo.shape)
-        d = abs(M - Mo)
-        scale = abs(Mo).max() if Mo.nnz else 1.0
-        assert (d.max() if d.nnz else 0.0) <= 1e-12 * scale, (name, nm)
-    # G and Dt have the same sparsity pattern, entry for entry
-    assert np.array_equal(G.indptr, o.csr("G").indptr) and np.array_equal(G.indices, o.csr("G").indices)
-    S, St = g.S_matrices()
-    assert abs(S.T - St).max() == 0.0 if S.nnz else True
+    check_stencil_blocks(*pair)
 
 
 def test_rhs_and_operator_match(pair):
-    name, sc, p, o, g = pair
-    n = o.nP + o.nT
-    if n == 0:
-        pytest.skip("empty system")
-    assert relerr(g.array("b"), o.array("b")) < 1e-9, name
-    rng = np.random.RandomState(7)
-    for _ in range(2):
-        x = rng.randn(n)
-        yo, yg = o.apply(x), g.apply(x)
-        assert relerr(yg, yo) < 1e-10, name
-    # symmetry / definiteness of the device operator itself
-    x, y = rng.randn(n), rng.randn(n)
-    Ax, Ay = g.apply(x), g.apply(y)
-    assert abs(x @ Ay - y @ Ax) < 1e-9 * abs(x @ Ay)
-    assert x @ Ax < 0
+    check_rhs_and_operator(*pair)
 
 
 def test_solve_matches(pair):
-    name, sc, p, o, g = pair
-    rc = g.solve()
-    assert rc == o.result, name
-    it_o, it_g = o.stats.solveData[1], g.stats.solveData[1]
-    assert abs(it_g - it_o) <= max(2, 0.02 * it_o), (name, it_g, it_o)   # CG is order sensitive: +-2 %
-    xo, xg = o.array("solutionVector"), g.array("solutionVector")
-    if np.linalg.norm(xo) > 0:
-        assert np.linalg.norm(xg - xo) <= 10 * p.tolerance * np.linalg.norm(xo), name   # SURVEY §8c tolerance
-    vel, valid = g.download()
-    for a in range(3):
-        assert np.array_equal(valid[a].ravel(), o.array("valid" + "XYZ"[a])), name
-        vo = o.array("vel" + "XYZ"[a])
-        scale = max(np.abs(vo).max(), 1e-30)
-        assert np.abs(vel[a].ravel() - vo).max() <= 20 * p.tolerance * scale, name
+    check_solve(*pair)
 
 
 @pytest.mark.parametrize("scene", ["spheres48", "spheres64", "coil48"])
