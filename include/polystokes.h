@@ -384,6 +384,67 @@ int32_t ps_set_solve_precision(ps_context* ctx, int32_t mode);
 #define PS_EXTRAPOLATION_MAX_LAYERS 64
 int32_t ps_set_velocity_extrapolation(ps_context* ctx, int32_t layers);   /* 0 = off (default) ... PS_EXTRAPOLATION_MAX_LAYERS */
 
+/* Collider loads (extension; the reference returns the liquid's velocity and nothing of what the liquid does to the solids): the force and
+ * the torque of the liquid on each collider, integrated on the device from the solve's own [p; tau] right after the write-back.
+ * A context setting like ps_set_velocity_extrapolation: it persists across ps_upload_fields and is read by every later step.  count = 0 (the
+ * default) is off and launches exactly the kernels of a context that never made the call.  count = n in 1..PS_COLLIDER_MAX computes the
+ * loads of colliders 0..n-1; pivots: 3 * count doubles (x y z per collider) copied by the call, the points the torques are taken about;
+ * NULL: ps_fields_in.orig of the step's upload for every collider.
+ * Definition.  P, Txx, Tyy, Tzz (cell grid) and Tyz, Txz, Txy (the YZ, XZ, XY edge grids) are the grids of ps_download_solution_fields: the
+ * solution entry rounded to fp32 and widened to double, 0 where the sample has no DOF — a caller can reproduce the loads from public
+ * outputs.  wF_a = the array "faceXFluidWeights" / Y / Z of axis a, wL = the "...LiquidWeights" array of the sample's own grid (fp32, widened).
+ * All arithmetic is fp64, unfused, in the order written; dx2 = dx * dx; e_a = one step along axis a.  Force on the solids along axis a:
+ *   cell c, pressure:        d = wF_a[c + e_a] - wF_a[c];  f = ((-dx2 * wL[c]) * P[c]) * d
+ *   cell c, normal stress:   same d;                       f = (( dx2 * wL[c]) * T_aa[c]) * d
+ *     both at the cell centre r = orig + (i + 0.5, j + 0.5, k + 0.5) * dx  (each coordinate orig_m + ((double)index + 0.5) * dx);
+ *   edge e of the ab edge grid (a != b), shear on axis a:  d = wF_a[e] - wF_a[e - e_b];  f = ((dx2 * wL[e]) * T_ab[e]) * d
+ *     at the edge's position: the coordinates of a and b on grid lines (orig_m + (double)index * dx), the third at index + 0.5; the term
+ *     is skipped when either face lies outside the a-face grid.  An edge gives up to two terms, one on axis a and one on axis b.
+ * A term whose solution value is 0 or whose d is 0 is no term (not counted).  This is sigma_ab d_b(chi_fluid) summed over the grid; with the
+ * wL factor it is the adjoint of the stencil coefficient wF * wL / dx of the system's blocks: the impulse the recovery u = u* - dt McInv C x
+ * takes from the liquid, -dt dx^3 C x, arrives at the solids.  A grid border that liquid reaches without a solid counts as whatever wF says
+ * there (wF differences across the outermost cells are terms like any other).
+ * Torque of a term about the pivot o: with arm = r - o, a1 = (a + 1) % 3, a2 = (a + 2) % 3:  T[a1] += arm[a2] * f,  T[a2] += -(arm[a1] * f).
+ * Attribution.  Without an id field every term belongs to collider 0.  With one (ps_upload_collider_ids: int32 per cell) a cell term takes
+ * id[c]; an edge term takes the id of that cell, among the up to four cells around the edge that lie inside the grid, whose
+ * "centerFluidWeights" is smallest, ties to the lowest x-fastest cell index.  An id < 0 or >= count drops the term; dropped terms are counted.
+ * Per collider k the step leaves F_k, T_k, the number of its terms, and the scales A_k[a] = the sum of |f| over its terms of axis a and
+ * B_k[m] = the sum of the absolute values of the addends of T_k[m] (|arm| |f|, component by component): any order of summation keeps
+ * |F - F_exact| <= (terms_k + 8) 2^-53 A_k and the same with B_k for the torque.  The sums are formed in a fixed order (no floating-point
+ * atomics): the result of a step is bitwise reproducible run to run and context to context.
+ * It runs after the write-back, before the extrapolation of ps_set_velocity_extrapolation (which touches nothing the loads read), of every
+ * step that solved and whose velocity is written — SUCCESS, NOCONVERGE with keepNonConvergedResults, after the BiCGStab fallback too — in
+ * ps_step_device, ps_solve_device, polystokes_step and ps_step_device_fields, with both solverTypes and mixed precision; with the Picard
+ * passes of ps_set_rheology after every pass (the last pass's values stand).  A step that leaves the velocity alone and a doSolve = 0 step
+ * compute nothing.  Single domain only: slab and brick ranks, in-process groups and TCP / RCCL ranks ignore the setting ("colliderLoads" = 0;
+ * loads there need a reduction over ranks and a rule for the halo blocks).  The loads read only: velocity, valid, stats and iterations of a
+ * step are those of a step without the setting.  The time is part of stage_ms[PS_STAGE_WRITEBACK].
+ * Memory: with W = 4 * min(1024, ceil(m / 256)) workgroups, m the samples of the largest of the four grids, W * (100 * count + 12) bytes
+ * of partial sums plus 172 * count + 4 bytes of results and pivots: allocated by the first step that computes loads, released by
+ * ps_set_collider_loads with count = 0 (the four result arrays go with them).  The id field costs one int32 cell grid while present.
+ * ps_set_collider_loads: PS_INVALID (reason in ps_last_error, the previous setting kept) for loads == NULL, "count outside 0..64", or a pivot
+ * that is not finite.  A successful call discards the loads of earlier steps (the getters then fail until the next step computes them).
+ * ps_upload_collider_ids: a cell field with the lifetime and call order of the density field: it belongs to the grid of the last
+ * ps_upload_fields / ps_upload_fields_device, follows that upload, and is dropped by every field upload; NULL drops it; a call before any
+ * upload returns PS_INVALID.  The Picard passes keep it.  ps_upload_collider_ids_device takes it from device memory in either layout and
+ * obeys the pointer refusals of the other ps_*_device calls (below); it returns with the input consumed.
+ * ps_get_collider_loads writes Fx Fy Fz Tx Ty Tz per collider into out (host memory, out_len doubles); PS_FAILED (reason in ps_last_error)
+ * when the last step computed no loads (none since the context was created, the setting was changed or fields were uploaded; a step that
+ * was interrupted, dropped its result or ran on a decomposition) and when out_len < 6 * count.  ps_get_collider_loads_device writes the
+ * same values into device memory of the context's device (8-byte aligned, len doubles), ordered against `stream` like a download, without
+ * synchronising the host; PS_INVALID for the pointer refusals, PS_FAILED as above.
+ * Arrays: "colliderLoads" (int32, 1: the count of the last step; 0 when off, ignored, or the step computed none), "colliderForce" and
+ * "colliderTorque" (fp64, 3 * count), "colliderLoadTerms" (int32, count + 1: terms per collider, then the dropped terms) and
+ * "colliderLoadScale" (fp64, 6 * count: A_k then B_k per collider); the last four only when the last step computed loads. */
+#define PS_COLLIDER_MAX 64
+typedef struct ps_collider_loads {
+    int32_t count;          /* 0: off (the default); 1..PS_COLLIDER_MAX colliders */
+    const double* pivots;   /* 3 * count doubles, copied by the call; NULL: ps_fields_in.orig for every collider */
+} ps_collider_loads;
+int32_t ps_set_collider_loads(ps_context* ctx, const ps_collider_loads* loads);
+int32_t ps_upload_collider_ids(ps_context* ctx, const int32_t* ids);      /* cell field nx*ny*nz, x-fastest; NULL drops it */
+int32_t ps_get_collider_loads(ps_context* ctx, double* out, int64_t out_len);
+
 /* solveGasSubclass equivalent on host buffers: upload + step + download (HDK_PolyStokes.C:222-609). */
 int32_t polystokes_step(ps_context* ctx, const ps_params* p, const ps_fields_in* in,
                         ps_fields_out* out, ps_stats* stats);
@@ -426,6 +487,8 @@ enum ps_field_layout { PS_LAYOUT_X_FASTEST = 0, PS_LAYOUT_Z_FASTEST = 1 };
 int32_t ps_upload_fields_device(ps_context* ctx, const ps_params* p, const ps_fields_in* in, int32_t layout, void* stream);
 int32_t ps_upload_density_field_device(ps_context* ctx, const float* density, int32_t layout, void* stream);
 int32_t ps_upload_surface_fields_device(ps_context* ctx, const ps_surface_fields* f, int32_t layout, void* stream);
+int32_t ps_upload_collider_ids_device(ps_context* ctx, const int32_t* ids, int32_t layout, void* stream);   /* ps_upload_collider_ids */
+int32_t ps_get_collider_loads_device(ps_context* ctx, double* dev, int64_t len, void* stream);              /* ps_get_collider_loads */
 int32_t ps_download_fields_device(ps_context* ctx, const ps_fields_out* out, int32_t layout, void* stream);
 int32_t ps_download_solution_fields_device(ps_context* ctx, const ps_solution_out* out, int32_t layout, void* stream);
 int32_t ps_step_device_fields(ps_context* ctx, const ps_params* p, const ps_fields_in* in, const ps_fields_out* out,

@@ -30,6 +30,7 @@ EXPORTED_SYMBOLS = [
     "ps_upload_fields_device", "ps_upload_density_field_device", "ps_download_fields_device", "ps_download_solution_fields_device",
     "ps_step_device_fields", "ps_set_velocity_extrapolation",
     "ps_upload_surface_fields", "ps_upload_surface_fields_device",
+    "ps_set_collider_loads", "ps_upload_collider_ids", "ps_upload_collider_ids_device", "ps_get_collider_loads", "ps_get_collider_loads_device",
 ]
 
 
@@ -142,6 +143,16 @@ def lib():
         L.ps_upload_surface_fields.restype = C.c_int32
         L.ps_upload_surface_fields_device.argtypes = [C.c_void_p, C.POINTER(_abi.SurfaceFields), C.c_int32, C.c_void_p]
         L.ps_upload_surface_fields_device.restype = C.c_int32
+        L.ps_set_collider_loads.argtypes = [C.c_void_p, C.POINTER(_abi.ColliderLoads)]
+        L.ps_set_collider_loads.restype = C.c_int32
+        L.ps_upload_collider_ids.argtypes = [C.c_void_p, C.c_void_p]
+        L.ps_upload_collider_ids.restype = C.c_int32
+        L.ps_upload_collider_ids_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+        L.ps_upload_collider_ids_device.restype = C.c_int32
+        L.ps_get_collider_loads.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+        L.ps_get_collider_loads.restype = C.c_int32
+        L.ps_get_collider_loads_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        L.ps_get_collider_loads_device.restype = C.c_int32
         _lib = L
     return _lib
 
@@ -192,6 +203,7 @@ class DeviceScene:
         self.layout, self.host = layout, scene
         for k in ("nx", "ny", "nz", "dx", "dt", "density", "name", "surface_tension"):
             setattr(self, k, getattr(scene, k))
+        self.orig = tuple(getattr(scene, "orig", (0.0, 0.0, 0.0)))
         self.vel = [put(a) for a in scene.vel]
         self.collisionvel = [put(a) for a in scene.collisionvel]
         self.surface, self.collision, self.viscosity = put(scene.surface), put(scene.collision), put(scene.viscosity)
@@ -212,7 +224,7 @@ def fields_in_device(fields):
     fi = FieldsIn()
     fi.nx, fi.ny, fi.nz = fields.nx, fields.ny, fields.nz
     fi.dx, fi.dt = fields.dx, fields.dt
-    fi.orig[0] = fi.orig[1] = fi.orig[2] = 0.0
+    fi.orig[0], fi.orig[1], fi.orig[2] = (float(v) for v in getattr(fields, "orig", (0.0, 0.0, 0.0)))
     fi.density = fields.density
     cv = getattr(fields, "collisionvel", None)
     for a in range(3):
@@ -235,7 +247,8 @@ def _kind(name):
     if name in ("valuesCoded", "columns16", "diagonalsCoded", "fusedStep", "streamRuns", "rowPerLane", "chebInner32", "warmStartUsed", "densityField", "launchWalk",
                 "surfaceTensionReducedFaces", "surfaceFields", "solidBoundary", "solidSlipEdges", "rheologyModel", "rheologyIterations",
                 "solvePrecisionUsed", "solvePassIterations",
-                "velocityExtrapolation", "extrapolationLayerX", "extrapolationLayerY", "extrapolationLayerZ", "extrapolationCounts"):
+                "velocityExtrapolation", "extrapolationLayerX", "extrapolationLayerY", "extrapolationLayerZ", "extrapolationCounts",
+                "colliderLoads", "colliderLoadTerms"):
         return "i"
     if name in ("ownedX", "ownedY", "ownedZ"):
         return "f"
@@ -328,6 +341,45 @@ class Solver:
         ps_result: INVALID for a value outside 0..64 (the previous setting kept).  Arrays "velocityExtrapolation",
         "extrapolationLayerX" / Y / Z, "extrapolationCounts" say what the last step did."""
         return self._check(self.L.ps_set_velocity_extrapolation(self.h, int(layers)), allow=(1, -2))
+
+    def set_collider_loads(self, count, pivots=None):
+        """ps_set_collider_loads: 0 (the default) is off; count = 1 .. COLLIDER_MAX makes every later single-domain step of this context that
+        solves and writes the velocity compute the force and torque of the liquid on colliders 0 .. count-1, across uploads.  pivots: (count, 3)
+        points the torques are taken about (None: the upload's orig).  Returns the ps_result: INVALID for a count outside 0..64 or a
+        non-finite pivot (the previous setting kept).  Arrays "colliderLoads", "colliderForce", "colliderTorque", "colliderLoadTerms",
+        "colliderLoadScale" and collider_loads() say what the last step computed."""
+        piv = None if pivots is None else np.ascontiguousarray(pivots, dtype=np.float64).ravel()
+        if piv is not None and 0 <= int(count) <= _abi.COLLIDER_MAX and piv.size != 3 * int(count):
+            raise ValueError("pivots must hold 3 values per collider")
+        cl = _abi.ColliderLoads(int(count), None if piv is None else piv.ctypes.data)
+        return self._check(self.L.ps_set_collider_loads(self.h, C.byref(cl)), allow=(1, -2))
+
+    def upload_collider_ids(self, ids):
+        """ps_upload_collider_ids: the collider of every cell (int32, shape (nz, ny, nx)) for the grid of the last upload; None drops the
+        field.  Returns the ps_result (INVALID before any upload); FAILED raises."""
+        if ids is None:
+            return self._check(self.L.ps_upload_collider_ids(self.h, None), allow=(1, -2))
+        f = np.ascontiguousarray(ids, dtype=np.int32)
+        if self.scene is not None and f.size != self.scene.nx * self.scene.ny * self.scene.nz:
+            raise ValueError("ids must hold one value per cell")
+        return self._check(self.L.ps_upload_collider_ids(self.h, f.ctypes.data), allow=(1, -2))
+
+    def upload_collider_ids_device(self, ids, layout=0, stream=None):
+        """ps_upload_collider_ids_device (None drops the field): `ids` is int32 device memory in `layout`.  Returns the ps_result, INVALID
+        for a refused call."""
+        return self._check(self.L.ps_upload_collider_ids_device(self.h, device_address(ids), int(layout), stream_handle(stream)), allow=(1, -2))
+
+    def collider_loads(self):
+        """ps_get_collider_loads: (count, 6) float64, Fx Fy Fz Tx Ty Tz per collider of the last step; raises when it computed none."""
+        n = int(self.array("colliderLoads")[0]) if self.L.ps_query_array(self.h, b"colliderLoads", None) >= 0 else 0
+        out = np.empty((max(n, 1), 6), np.float64)
+        self._check(self.L.ps_get_collider_loads(self.h, out.ctypes.data, 6 * n))
+        return out[:n]
+
+    def collider_loads_device(self, out, length, stream=None):
+        """ps_get_collider_loads_device into `out` (device memory of `length` doubles).  Returns the ps_result (INVALID: a refused pointer;
+        the host is NOT synchronised); raises when the last step computed no loads."""
+        return self._check(self.L.ps_get_collider_loads_device(self.h, device_address(out), int(length), stream_handle(stream)), allow=(1, -2))
 
     def solution_fields(self):
         """ps_download_solution_fields: the last solve's [p; tau] as dense fp32 grids (x fastest), keyed pressure, txx, tyy, tzz, tyz, txz, txy;
@@ -670,6 +722,11 @@ class Group:
     def set_velocity_extrapolation(self, layers):
         """ps_set_velocity_extrapolation on every rank (a decomposition ignores the setting: "velocityExtrapolation" reads 0)."""
         rc = [r.set_velocity_extrapolation(layers) for r in self.ranks]
+        return rc[0]
+
+    def set_collider_loads(self, count, pivots=None):
+        """ps_set_collider_loads on every rank (a decomposition ignores the setting: "colliderLoads" reads 0)."""
+        rc = [r.set_collider_loads(count, pivots) for r in self.ranks]
         return rc[0]
 
     def set_rheology(self, *args, **kw):

@@ -72,6 +72,12 @@ PRECISION_FP64, PRECISION_MIXED = 0, 1
 # ps_field_layout (the ps_*_device calls): i + d0*(j + d1*k), or k + d2*(j + d1*i) — a C-contiguous array indexed [i, j, k]
 LAYOUT_X_FASTEST, LAYOUT_Z_FASTEST = 0, 1
 EXTRAPOLATION_MAX_LAYERS = 64      # PS_EXTRAPOLATION_MAX_LAYERS (ps_set_velocity_extrapolation)
+COLLIDER_MAX = 64                  # PS_COLLIDER_MAX (ps_set_collider_loads)
+
+
+class ColliderLoads(C.Structure):
+    """ps_collider_loads (ps_set_collider_loads): how many colliders' loads every later step computes, and the torques' pivots"""
+    _fields_ = [("count", C.c_int32), ("pivots", C.c_void_p)]
 
 
 class Rheology(C.Structure):
@@ -171,7 +177,7 @@ class Scene:
         fi = FieldsIn()
         fi.nx, fi.ny, fi.nz = self.nx, self.ny, self.nz
         fi.dx, fi.dt = self.dx, self.dt
-        fi.orig[0] = fi.orig[1] = fi.orig[2] = 0.0
+        fi.orig[0], fi.orig[1], fi.orig[2] = (float(v) for v in getattr(self, "orig", (0.0, 0.0, 0.0)))   # (the default pivot of collider loads)
         fi.density = self.density
         for a in range(3):
             fi.vel[a] = self.vel[a].ctypes.data

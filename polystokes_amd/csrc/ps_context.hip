@@ -106,6 +106,13 @@ void ps_context::uploadReset(const ps_params* p, const ps_fields_in* in) {
         dropSurfaceFields();
         drainDeferred(true);
     }
+    for (int a = 0; a < 3; ++a) orig[a] = in->orig[a];   // (the default pivot of ps_set_collider_loads)
+    forgetLoads();                                        // the loads of an earlier step described the previous fields
+    if (colliderIds.p) {                                  // ... and so did the collider ids (ps_upload_collider_ids), released here
+        HIP_CHECK(hipStreamSynchronize(stream));
+        dropColliderIds();
+        drainDeferred(true);
+    }
 }
 
 void ps_context::ingestHost(const ps_fields_in* in) {
@@ -221,6 +228,7 @@ void ps_context::setupPhase(int phase) {
         warmUsedHost = 0; warmX0Valid = false;
         solvePrecisionUsedHost = 0; passIters.clear();
         extrapUsedHost = 0;
+        loadsUsedHost = 0;
         arrays.clear();
         if (rheoPass == 0) rheoIters.clear();   // (ps_set_rheology: one entry per solve of the step)
         // Picard passes need the halo of the last pass's output velocity: a decomposition refuses them on every rank (ps_dist.hpp: distStep)
@@ -311,6 +319,7 @@ int ps_context::solveStage(ps_stats* stats) {
     StageTimer T(stream);
     int result = PS_INCOMPLETE;
     extrapUsedHost = 0;
+    loadsUsedHost = 0;
     const std::clock_t c0 = std::clock();
     const auto w0 = std::chrono::high_resolution_clock::now();
     T.mark(0);
@@ -334,6 +343,9 @@ int ps_context::solveStage(ps_stats* stats) {
         recoverVelocityFromPressureStress();
         T.mark(2);
         applySolutionToVelocity();
+        // ps_set_collider_loads: the force and torque of the liquid on every collider from this solve's x (single domain only; reads x, the
+        // weights, the index maps and the ids, writes its own buffers: nothing a step or a later Picard pass reads)
+        if (loadsCount > 0 && P.doSolve && !slabEnabled) computeColliderLoads();
         // ps_set_velocity_extrapolation: the written velocity into the faces around the valid ones (single domain only; a Picard pass that
         // follows reads used faces alone, which no sweep changes)
         if (extrapSet > 0 && !slabEnabled) extrapolateVelocity(extrapSet);
@@ -427,6 +439,14 @@ void ps_context::registerArrays() {
         static const char* axn[3] = {"X", "Y", "Z"};
         for (int a = 0; a < 3; ++a) reg(std::string("extrapolationLayer") + axn[a], extrapLayer[a].p, g.count(1 + a), 1);
         reg("extrapolationCounts", extrapCounts.p, extrapUsedHost, 4);   // faces assigned by each sweep, the three axes together
+    }
+    regHost("colliderLoads", &loadsUsedHost, 1, 4);   // the count the last step computed loads for (ps_set_collider_loads)
+    if (loadsUsedHost > 0) {
+        const int64_t nc = loadsUsedHost;
+        reg("colliderForce", loadsOut.p, 3 * nc, 8);
+        reg("colliderTorque", loadsOut.p + 3 * nc, 3 * nc, 8);
+        reg("colliderLoadScale", loadsOut.p + 6 * nc, 6 * nc, 8);   // A_k, B_k per collider
+        reg("colliderLoadTerms", loadsTerms.p, nc + 1, 4);          // terms per collider, then the dropped terms
     }
     if (P.preconditioner == PS_PRE_DIAGONAL) regp("dinv", dinv.p, nSystem, permSys.p, 0);
     if (isSolved) {
@@ -803,6 +823,45 @@ int32_t ps_set_velocity_extrapolation(ps_context* c, int32_t layers) {
         return PS_SUCCESS;
     })
 }
+int32_t ps_set_collider_loads(ps_context* c, const ps_collider_loads* l) {
+    if (!c) return PS_FAILED;
+    PS_TRY(c, {
+        std::string why;
+        if (!l) why = "loads is null";
+        else if (l->count < 0 || l->count > PS_COLLIDER_MAX) why = "count outside 0.." + std::to_string(PS_COLLIDER_MAX);
+        else if (l->pivots)
+            for (int q = 0; q < 3 * l->count && why.empty(); ++q)
+                if (!std::isfinite(l->pivots[q])) why = "pivot " + std::to_string(q / 3) + " is not finite";
+        if (!why.empty()) { c->err = "ps_set_collider_loads: " + why; return PS_INVALID; }
+        c->loadsCount = l->count;   // read by every later step that solves and writes the velocity (solveStage)
+        if (l->pivots) c->loadsPivots.assign(l->pivots, l->pivots + 3 * l->count); else c->loadsPivots.clear();
+        c->forgetLoads();           // what an earlier step computed answered another setting
+        if (l->count == 0 && c->loadsOut.p) {   // the buffers go with the setting: dropped and, with the stream idle, released here
+            HIP_CHECK(hipSetDevice(c->device));
+            HIP_CHECK(hipStreamSynchronize(c->stream));
+            c->dropLoadBuffers();
+            c->drainDeferred(true);
+        }
+        return PS_SUCCESS;
+    })
+}
+int32_t ps_upload_collider_ids(ps_context* c, const int32_t* ids) {
+    if (!c) return PS_FAILED;
+    PS_TRY(c, {
+        if (!c->uploaded) { c->err = "ps_upload_collider_ids: call ps_upload_fields first"; return PS_INVALID; }
+        const std::string why = c->uploadColliderIds(ids, false, 0, nullptr);
+        if (!why.empty()) { c->err = "ps_upload_collider_ids: " + why; return PS_INVALID; }
+        return PS_SUCCESS;
+    })
+}
+int32_t ps_get_collider_loads(ps_context* c, double* out, int64_t out_len) {
+    if (!c) return PS_FAILED;
+    PS_TRY(c, {
+        if (!out) throw Error("ps_get_collider_loads: out is null");
+        c->copyColliderLoads(out, out_len, false, nullptr);
+        return PS_SUCCESS;
+    })
+}
 int32_t ps_set_rheology(ps_context* c, const ps_rheology* r) {
     if (!c) return PS_FAILED;
     PS_TRY(c, {
@@ -923,6 +982,34 @@ int32_t ps_upload_surface_fields_device(ps_context* c, const ps_surface_fields* 
         }
         why = c->uploadSurfaceFields(f, true, layout, (hipStream_t)stream);
         if (!why.empty()) { c->err = "ps_upload_surface_fields: " + why; return PS_INVALID; }
+        return PS_SUCCESS;
+    })
+}
+int32_t ps_upload_collider_ids_device(ps_context* c, const int32_t* ids, int32_t layout, void* stream) {
+    if (!c) return PS_FAILED;
+    PS_TRY(c, {
+        if (!c->uploaded) { c->err = "ps_upload_collider_ids: call ps_upload_fields first"; return PS_INVALID; }
+        HIP_CHECK(hipSetDevice(c->device));
+        std::string why;
+        if (const char* m = ps_context::layoutRefusal(layout)) why = m;
+        else if (ids) why = c->checkDeviceField(ids, c->g.count(0), "ids");
+        if (!why.empty()) { c->err = "ps_upload_collider_ids_device: " + why; return PS_INVALID; }
+        why = c->uploadColliderIds(ids, true, layout, (hipStream_t)stream);
+        if (!why.empty()) { c->err = "ps_upload_collider_ids: " + why; return PS_INVALID; }
+        return PS_SUCCESS;
+    })
+}
+int32_t ps_get_collider_loads_device(ps_context* c, double* dev, int64_t len, void* stream) {
+    if (!c) return PS_FAILED;
+    PS_TRY(c, {
+        if (c->loadsUsedHost <= 0) throw Error("ps_get_collider_loads: the last step computed no loads");
+        if (len < 6 * (int64_t)c->loadsUsedHost) throw Error("ps_get_collider_loads: the destination holds fewer than 6 * count doubles");
+        HIP_CHECK(hipSetDevice(c->device));
+        std::string why;
+        if (!dev || ((uintptr_t)dev & 7)) why = "out: the pointer is null or not 8-byte aligned";
+        else why = c->checkDeviceField(dev, 2 * 6 * (int64_t)c->loadsUsedHost, "out");
+        if (!why.empty()) { c->err = "ps_get_collider_loads_device: " + why; return PS_INVALID; }
+        c->copyColliderLoads(dev, len, true, (hipStream_t)stream);
         return PS_SUCCESS;
     })
 }

@@ -362,6 +362,26 @@ struct ps_context {
     ps::DevBuf<int32_t> extrapCounts;
     void extrapolateVelocity(int layers);               // ps_extrapolate.hip: after the write-back of a step whose velocity is written
     void dropExtrapolationBuffers() { for (auto& b : extrapLayer) b.free(); extrapCounts.free(); }
+    // Collider loads (ps_set_collider_loads, extension; ps_loads.hip): loadsCount / loadsPivots are the context setting (pivots empty: the
+    // upload's orig), loadsUsedHost the count the last step computed loads for (array "colliderLoads": 0 when off, on a decomposition, or
+    // when the step computed none; the getters need it > 0).  colliderIds: the id of every cell (ps_upload_collider_ids), for the grid of
+    // the last upload (every upload drops it).  loadsPartial / loadsPartialN / loadsOccurs: per workgroup of k_loads_partial the 12 sums and
+    // the term count of every collider that occurs in it, the dropped terms, and the bit mask of those colliders; loadsOut: force (3 count),
+    // torque (3 count), scale (6 count), then Fx Fy Fz Tx Ty Tz per collider (6 count: what the getters copy); loadsTerms: count + 1.
+    // Allocated by the first step that computes loads, dropped when the count returns to 0.
+    int32_t loadsCount = 0, loadsUsedHost = 0;
+    std::vector<double> loadsPivots;
+    double orig[3] = {0., 0., 0.};                       // ps_fields_in.orig of the last upload
+    ps::DevBuf<int32_t> colliderIds;
+    ps::DevBuf<double> loadsPartial, loadsOut, loadsPivotsDev;
+    ps::DevBuf<int32_t> loadsPartialN, loadsTerms;
+    ps::DevBuf<unsigned long long> loadsOccurs;
+    void computeColliderLoads();                         // ps_loads.hip: after the write-back of a step that solved and whose velocity is written
+    void dropLoadBuffers() { loadsPartial.free(); loadsOut.free(); loadsPivotsDev.free(); loadsPartialN.free(); loadsTerms.free(); loadsOccurs.free(); }
+    void forgetLoads();                                  // ps_loads.hip: the last step's loads no longer stand (their arrays go)
+    bool dropColliderIds();                              // ps_loads.hip: false when there was nothing to drop
+    std::string uploadColliderIds(const int32_t* ids, bool device, int layout, hipStream_t caller);   // ps_loads.hip
+    void copyColliderLoads(double* dst, int64_t len, bool device, hipStream_t caller);                 // ps_loads.hip: throws when there are none
     int64_t solutionGridCount(int q) const { return g.count(q < 4 ? 0 : q); }   // grid q of the store: 0..3 cell grid, 4..6 edge grids
     void scatterSolution(float* dst, int q0, int nq);   // ps_solve.hip: grids q0 .. q0+nq-1 of x, back to back in dst
     void carryWarmStart();                              // ps_solve.hip: x -> warmStore (after a kept step)

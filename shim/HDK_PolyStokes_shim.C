@@ -88,6 +88,7 @@ const ParmRow theRows[] = {
     {'F', "maxViscosity",               "Max Viscosity",                    nullptr,            1e6},
     {'I', "rheologyPasses",             "Rheology Passes",                  nullptr,            0},
     {'I', "extrapolateLayers",          "Velocity Extrapolation Layers",    nullptr,            0},
+    {'I', "colliderLoads",              "Collider Loads",                   nullptr,            0},
 };
 constexpr int theRowCount = (int)(sizeof(theRows) / sizeof(theRows[0]));
 }  // namespace
@@ -254,6 +255,17 @@ bool HDK_PolyStokes::solveGasSubclass(SIM_Engine& engine, SIM_Object* obj, SIM_T
     // host-side only, so it is set every step).  0, the default, is off: Houdini's network extrapolates after the node.  A refused value
     // aborts with the library's reason.
     if (ps_set_velocity_extrapolation(myCtx, (int32_t)getExtrapolateLayers()) != PS_SUCCESS) return fail(ps_last_error(myCtx), UT_ERROR_ABORT);
+
+    // shim-only: the force and torque of the liquid on the colliders (ps_set_collider_loads, a context setting; host-side only, so it is
+    // set every step, before the step whose loads it asks for).  0, the default, is off.  The node passes no id field and no pivots: every
+    // term belongs to collider 0 and the torque is taken about the grid's origin; ps_get_collider_loads returns them after the step.  A
+    // refused value aborts with the library's reason.
+    {
+        ps_collider_loads cl;
+        cl.count = (int32_t)getColliderLoads();
+        cl.pivots = nullptr;
+        if (ps_set_collider_loads(myCtx, &cl) != PS_SUCCESS) return fail(ps_last_error(myCtx), UT_ERROR_ABORT);
+    }
 
     const fpreal dt = timestep;
     const fpreal dx = velocityField->getVoxelSize(0).maxComponent();

@@ -59,6 +59,7 @@ public:
     GET_DATA_FUNC_F("maxViscosity",                     MaxViscosity);            // clamp of mu (1e6)
     GET_DATA_FUNC_I("rheologyPasses",                   RheologyPasses);          // Picard passes per step (0)
     GET_DATA_FUNC_I("extrapolateLayers",                ExtrapolateLayers);       // ps_set_velocity_extrapolation(layers) (0)
+    GET_DATA_FUNC_I("colliderLoads",                    ColliderLoads);           // ps_set_collider_loads(count) (0)
 
 protected:
     explicit HDK_PolyStokes(const SIM_DataFactory* factory);
