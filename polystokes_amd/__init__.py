@@ -244,7 +244,7 @@ _DT = {(1, "i"): np.int8, (4, "i"): np.int32, (4, "f"): np.float32, (8, "f"): np
 def _kind(name):
     if name.endswith(("Labels", "Indices", ".col", ".ptr", "Region", "Perm", ".chunkInfo", ".chunkRep", ".code")) or name.startswith("faceRow"):
         return "i"
-    if name in ("valuesCoded", "columns16", "diagonalsCoded", "fusedStep", "streamRuns", "rowPerLane", "chebInner32", "warmStartUsed", "densityField", "launchWalk",
+    if name in ("valuesCoded", "columns16", "diagonalsCoded", "fusedStep", "ownedRange", "streamRuns", "rowPerLane", "chebInner32", "warmStartUsed", "densityField", "launchWalk",
                 "surfaceTensionReducedFaces", "surfaceFields", "solidBoundary", "solidSlipEdges", "rheologyModel", "rheologyIterations",
                 "solvePrecisionUsed", "solvePassIterations",
                 "velocityExtrapolation", "extrapolationLayerX", "extrapolationLayerY", "extrapolationLayerZ", "extrapolationCounts",
@@ -628,10 +628,11 @@ class Solver:
         self._check(self.L.ps_export_matrices(self.h, prefix.encode()))
 
     def solve_exported_system(self, prefix, params, dt, n):
-        """PCG on a component set written by exportComponentMatrices (files <prefix>Mat_*.mtx, Vec_b.mtx)."""
+        """PCG on a component set written by exportComponentMatrices (files <prefix>Mat_*.mtx, Vec_b.mtx).  Returns (rc, x); rc is INCOMPLETE
+        when the interrupt callback stopped the solve at a batch end (x is then the iterate reached)."""
         x = np.zeros(n, np.float64)
         rc = self._check(self.L.ps_solve_exported_system(self.h, prefix.encode(), C.byref(params), dt, x.ctypes.data, n, C.byref(self.stats)),
-                         allow=(0, 1))
+                         allow=(0, 1, _abi.INCOMPLETE))
         return rc, x
 
     def export_stats(self, prefix):

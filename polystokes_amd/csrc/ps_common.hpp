@@ -291,6 +291,7 @@ __host__ __device__ inline diag_t diagStore(double v) {
     return (diag_t)((b + 0x7FFFu + ((b >> 16) & 1u)) >> 16);
 }
 #endif
+__host__ __device__ inline double diagValue(double v) { return v; }   // an fp64 diagonal through the same kernels (the exported system: ps_import.hpp)
 
 inline bool debugPoisonOn() {
     static const bool on = [] { const char* e = PS_ENV_LOUD("PS_DEBUG_POISON"); return e && atoi(e) != 0; }();

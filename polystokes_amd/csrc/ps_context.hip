@@ -459,6 +459,9 @@ void ps_context::registerArrays() {
     regHost("columns16", &columns16Host, 1, 4);
     // 1: the last PCG solve ran the four-kernel step (residual update inside the St kernel, ps_solve.hip)
     regHost("fusedStep", &fusedStepHost, 1, 4);
+    // [ownLo, ownHi): the DOFs this context owns, in the internal numbering (a rank's vector kernels run on x + ownLo; single domain: [0, nSystem))
+    ownedRangeHost[0] = (int32_t)ownLo; ownedRangeHost[1] = (int32_t)ownHi;
+    regHost("ownedRange", ownedRangeHost, 2, 4);
     // the walks of the persistent SpMV launches of the last single-domain PCG solve (5 records of 8: ps_context.hpp launchWalkHost)
     regHost("launchWalk", launchWalkHost, 5 * LAUNCH_WALK_FIELDS, 4);
     // 1: the last solve / preconditioner apply kept the Chebyshev polynomial's inner vectors in fp32 (PS_PRE_CHEBYSHEV_F32 where its kernels run)
@@ -1232,8 +1235,6 @@ int32_t ps_bench_kernel(ps_context* c, const char* kernel, int32_t iters, double
             else if (kb == "tiles") *algorithmic_bytes = (double)c->nReducedRows * (8. + 4. + 8. + 4.);   // s in, t out, packed face x2
             else if (kb == "cg_update_r") *algorithmic_bytes = (24. + dg) * rowsT;
             else if (kb == "cg_update_xp") *algorithmic_bytes = (40. + dg) * rowsT;
-            else if (kb == "cg_update_xr") *algorithmic_bytes = (c->P.preconditioner == PS_PRE_DIAGONAL ? 56. : 48.) * rowsT;
-            else if (kb == "cg_update_p") *algorithmic_bytes = (c->P.preconditioner == PS_PRE_DIAGONAL ? 32. : 24.) * rowsT;
             else *algorithmic_bytes = 0;
         }
         return PS_SUCCESS;

@@ -400,6 +400,7 @@ struct ps_context {
     ps_slab slab{};             // rank / world (and the z-range when ps_set_slab was used)
     ps_brick brick{};           // the owned box in local coordinates, neighbours, global position (ps_set_slab fills it too)
     int64_t ownLo = 0, ownHi = 0;            // owned DOF range in the internal numbering (contiguous: the owned lattice blocks come first)
+    int32_t ownedRangeHost[2] = {0, 0};      // the same for ps_query_array ("ownedRange")
     ps::DevBuf<int32_t> regionOwned;         // R flags
     ps::DevBuf<int32_t> blockMap;            // sequence position -> lattice block (owned blocks first); empty: lattice order
     int blockMapOwned = -1, blockMapFor = 0; // owned lattice blocks (-1: the map has to be rebuilt: ps_set_brick), blocks it was built for

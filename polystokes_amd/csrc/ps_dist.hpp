@@ -138,24 +138,7 @@ __global__ void k_chunk_flags_relay(const int32_t* __restrict__ listA, int64_t n
     const int4 ci = chunkInfo[lo];
     if (j >= ci.z && j < ci.z + (int)((unsigned)ci.y >> 16)) flag[lo] = 2;
 }
-// out[q] = sum of partial[q*stride .. q*stride+count)   (q < nq), one block
-__global__ void __launch_bounds__(BS) k_sumq(const CGScalars* __restrict__ sc, const double* __restrict__ partial, int count, int stride, int nq,
-                                             double* __restrict__ out) {
-    if (sc && sc->done) return;
-    for (int q = 0; q < nq; ++q) {
-        const double s = sumPartials(partial + (int64_t)q * stride, count);
-        if (threadIdx.x == 0) out[q] = s;
-        __syncthreads();
-    }
-}
-__global__ void k_dscal0(CGScalars* sc, const double* __restrict__ red, double tol, int maxit, int vecNT) {
-    const double s = red[0];
-    sc->rsold = s; sc->rsold2[0] = s; sc->rsold2[1] = 0.; sc->rre = 0.; sc->iter = maxit; sc->maxit = maxit; sc->tol2 = tol * tol;
-    sc->done = (s == 0.) ? 1 : 0;
-    if (s == 0.) sc->iter = 0;
-    sc->alpha = sc->beta = sc->pAp = sc->rr = sc->xx = sc->rz = 0.;
-    sc->pend = 0; sc->pendIter = 0; sc->vecNT = vecNT;
-}
+__global__ void k_dscal0(CGScalars* sc, const double* __restrict__ red, double tol, int maxit, int vecNT) { cgScalInit(sc, red[0], tol, maxit, vecNT); }   // rsold all-reduced (one thread)
 __global__ void k_invert_diag(double* __restrict__ d, int64_t n) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const double v = d[i];
@@ -1153,9 +1136,7 @@ struct Dist {
             f.fS = c->fusedPart.p; f.fT = f.fS + f.sBlocks; f.fU = f.fT + c->regionCount; f.fR = f.fU + VGRID; f.fX = f.fR + 2 * f.stBF;
             HIP_CHECK(hipMemsetAsync(f.fX, 0, 2 * ps_context::NLINK * (size_t)f.gFix * sizeof(double), c->stream));
             f.L.sPart = f.fS; f.L.wvPart = f.fT;
-            const uint8_t* ucode = c->uCoded ? c->uCode.p + f.lo : nullptr;
-            hipLaunchKernelGGL(k_uinv_pp, dim3(f.vb), dim3(BS), 0, c->stream, (const double*)c->pvec.p + f.lo, ucode, (const double*)c->uDict.p,
-                               (const double*)c->uInv.p + f.lo, f.n, f.fU);
+            runOn(c, k_uinv_pp, f.vb, c->pvec.p + f.lo, stressDiag(c, f.lo), f.n, f.fU);
         }
     }
     // One iteration of the four-kernel step.  split (the overlapped form): S and St run in two launches each, the chunks that need no halo
@@ -1225,10 +1206,8 @@ struct Dist {
         for (size_t q = 0; q < R.size(); ++q) {   // (4) x, p
             ps_context* c = R[q];
             RankSolve& f = rs[q];
-            const uint8_t* ucode = c->uCoded ? c->uCode.p + f.lo : nullptr;
-            hipLaunchKernelGGL(k_cg_update_xp_u, dim3(f.vb), dim3(BS), 0, c->stream, f.sc, (const double*)c->redbuf.p, (const double*)nullptr, 0, jac ? 1 : 0, it,
-                               (const double*)c->r.p + f.lo, f.dv, c->x.p + f.lo, c->pvec.p + f.lo, f.n, c->dotPartials3.p, ucode, (const double*)c->uDict.p,
-                               (const double*)c->uInv.p + f.lo, f.fU);
+            runOn(c, k_cg_update_xp_u, f.vb, f.sc, TwoSums::reduced(c->redbuf.p, jac), it, c->r.p + f.lo, f.dv, c->x.p + f.lo, c->pvec.p + f.lo, f.n,
+                  c->dotPartials3.p, stressDiag(c, f.lo), f.fU);
         }
     }
     // One iteration of the five-kernel step: A p (S, tiles, St), r; with the Chebyshev polynomial z = M^-1 r; then x, p
@@ -1251,8 +1230,7 @@ struct Dist {
         for (size_t q = 0; q < R.size(); ++q) {
             ps_context* c = R[q];
             const RankSolve& l = rs[q];
-            hipLaunchKernelGGL(k_cg_update_r, dim3(l.vb), dim3(BS), 0, c->stream, l.sc, (const double*)c->redbuf.p, (const double*)nullptr, 0,
-                               (const double*)nullptr, 0, it, c->Ap.p + l.lo, l.dv, c->r.p + l.lo, l.n, c->dotPartialsR.p);
+            runOn(c, k_cg_update_r, l.vb, l.sc, TwoSums::reduced(c->redbuf.p), it, c->Ap.p + l.lo, l.dv, c->r.p + l.lo, l.n, c->dotPartialsR.p);
             hipLaunchKernelGGL(k_sumq, dim3(1), dim3(BS), 0, c->stream, (const CGScalars*)l.sc, c->dotPartialsR.p, l.vb, l.vb, 2, c->redbuf.p);
         }
         if (cheb) {   // z = M^-1 r (k-1 distributed applies), then {r.r, r.z} and x, p with the vector z
@@ -1263,8 +1241,9 @@ struct Dist {
             for (size_t q = 0; q < R.size(); ++q) {
                 ps_context* c = R[q];
                 const RankSolve& l = rs[q];
-                hipLaunchKernelGGL(k_cg_update_xp_z<double>, dim3(l.vb), dim3(BS), 0, c->stream, l.sc, (const double*)c->redbuf.p, 1, (const double*)c->redbuf.p + 1, 1, it,
-                                   (const double*)(c->*zf).p + l.lo, c->x.p + l.lo, c->pvec.p + l.lo, l.n, c->dotPartials3.p);
+                // (the two all-reduced values as arrays of one partial each: summed like partials, as this call always did)
+                runOn(c, k_cg_update_xp_z<double>, l.vb, l.sc, TwoSums::partials(c->redbuf.p, 1, c->redbuf.p + 1, 1), it, (c->*zf).p + l.lo, c->x.p + l.lo,
+                      c->pvec.p + l.lo, l.n, c->dotPartials3.p);
             }
             return;
         }
@@ -1272,8 +1251,7 @@ struct Dist {
         for (size_t q = 0; q < R.size(); ++q) {
             ps_context* c = R[q];
             const RankSolve& l = rs[q];
-            hipLaunchKernelGGL(k_cg_update_xp, dim3(l.vb), dim3(BS), 0, c->stream, l.sc, (const double*)c->redbuf.p, (const double*)nullptr, 0,
-                               jac ? 1 : 0, it, c->r.p + l.lo, l.dv, c->x.p + l.lo, c->pvec.p + l.lo, l.n, c->dotPartials3.p);
+            runOn(c, k_cg_update_xp, l.vb, l.sc, TwoSums::reduced(c->redbuf.p, jac), it, c->r.p + l.lo, l.dv, c->x.p + l.lo, c->pvec.p + l.lo, l.n, c->dotPartials3.p);
         }
     }
     // The stop test of the batch's last iteration (it - 1), its scalars into h; the ranks' interrupt requests ride along in the same
@@ -1296,7 +1274,7 @@ struct Dist {
             c0->distStats[6] += 1.;
         }
         for (size_t q = 0; q < R.size(); ++q)
-            hipLaunchKernelGGL(k_cg_check, dim3(1), dim3(BS), 0, R[q]->stream, rs[q].sc, (const double*)R[q]->redbuf.p, (const double*)nullptr, 0, it - 1);
+            runOn(R[q], k_cg_check, 1, rs[q].sc, R[q]->redbuf.p, nullptr, 0, it - 1);
         double stopSum = 0.;
         HIP_CHECK(hipMemcpyAsync(&h, rs[0].sc, sizeof(h), hipMemcpyDeviceToHost, c0->stream));
         HIP_CHECK(hipMemcpyAsync(&stopSum, c0->redbuf.p + 1, 8, hipMemcpyDeviceToHost, c0->stream));
@@ -1322,7 +1300,7 @@ struct Dist {
                     ps_context* c = R[q];
                     const RankSolve& l = rs[q];
                     hipLaunchKernelGGL(k_dot, dim3(l.vb), dim3(BS), 0, c->stream, (c->*a).p + l.lo, (c->*bvec).p + l.lo, l.n, c->dotPartials.p);
-                    hipLaunchKernelGGL(k_sum1, dim3(1), dim3(BS), 0, c->stream, c->dotPartials.p, l.vb, c->redbuf.p);
+                    hipLaunchKernelGGL(k_sumq, dim3(1), dim3(BS), 0, c->stream, (const CGScalars*)nullptr, (const double*)c->dotPartials.p, l.vb, 0, 1, c->redbuf.p);
                 }
                 allreduce(1);
                 double out = 0.;

@@ -232,7 +232,7 @@ extern "C" int32_t ps_solve_exported_system(ps_context* c, const char* prefix, c
         up(dMc, mc); up(dUi, ui); up(dBi, bi); up(db, bh);
         dx.alloc((size_t)n); dr.alloc((size_t)n); dp.alloc((size_t)n); dAp.alloc((size_t)n);
         ds.alloc((size_t)nA + 1); dw.alloc((size_t)nR + 1); dv.alloc((size_t)nR + 1); dsc.alloc(1);
-        part.alloc(3 * VGRID + 16);
+        part.alloc(4 * VGRID + 16);
         const bool jac = params->preconditioner == PS_PRE_DIAGONAL;
         if (jac) {
             ddinv.alloc((size_t)n);
@@ -250,32 +250,26 @@ extern "C" int32_t ps_solve_exported_system(ps_context* c, const char* prefix, c
             if (nT > 0) hipLaunchKernelGGL(k_uinv_term, dim3(gridFor(nT, BS)), dim3(BS), 0, st, dUi.p, x, y, nP, nT);
         };
         const auto w0 = std::chrono::high_resolution_clock::now();
+        // The product's own PCG step (ps_kernels_cg.hpp) on the generic operator and an fp64 diagonal: A p, p.Ap (k_dot), k_cg_update_r,
+        // k_cg_update_xp.  Partials: p.Ap (and r.z of the start), x.x, then r.r and r.z — read by every block of the next kernel, so each has its own
         const int vb = dotBlocks(n);
         const double* dvp = jac ? ddinv.p : nullptr;
         const int maxit = params->maxSolverIterations;
-        hipLaunchKernelGGL(k_cg_init, dim3(vb), dim3(BS), 0, st, db.p, dvp, dx.p, dr.p, dp.p, n, part.p);
-        hipLaunchKernelGGL(k_cg_scal0, dim3(1), dim3(BS), 0, st, dsc.p, part.p, vb, params->tolerance, maxit, 1);
-        CGScalars h{};
-        int it = 0;
-        bool finished = false;
-        while (it < maxit && !finished) {
-            const int upto = std::min(maxit, it + 25);
-            for (; it < upto; ++it) {
-                apply(dp.p, dAp.p);
-                hipLaunchKernelGGL(k_dot, dim3(vb), dim3(BS), 0, st, dp.p, dAp.p, n, part.p);
-                hipLaunchKernelGGL(k_cg_scal1, dim3(1), dim3(BS), 0, st, dsc.p, part.p, vb);
-                hipLaunchKernelGGL(k_cg_update_xr, dim3(vb), dim3(BS), 0, st, dsc.p, dp.p, dAp.p, dvp, dx.p, dr.p, n, part.p);
-                hipLaunchKernelGGL(k_cg_scal2, dim3(1), dim3(BS), 0, st, dsc.p, part.p, vb, jac ? 1 : 0, it);
-                hipLaunchKernelGGL(k_cg_update_p, dim3(vb), dim3(BS), 0, st, dsc.p, dr.p, dvp, dp.p, n);
-            }
-            HIP_CHECK(hipMemcpyAsync(&h, dsc.p, sizeof(h), hipMemcpyDeviceToHost, st));
-            HIP_CHECK(hipStreamSynchronize(st));
-            if (h.done) finished = true;
-        }
-        const int iters = h.done ? h.iter : maxit;
+        double *pAp = part.p, *xx = part.p + VGRID, *rr = part.p + 2 * VGRID;
+        auto run = [&](auto kernel, int grid, auto... a) { runOn(c, kernel, grid, a...); };
+        run(k_cg_init_d64, vb, db.p, dvp, dx.p, dr.p, dp.p, n, pAp);
+        run(k_cg_scal0, 1, dsc.p, pAp, vb, params->tolerance, maxit, 1);
+        const BatchRun br = runBatches(c, dsc.p, maxit, CGScalars{}, [&](int it) {
+            apply(dp.p, dAp.p);
+            run(k_dot, vb, dp.p, dAp.p, n, pAp);
+            run(k_cg_update_r_d64, vb, dsc.p, TwoSums::partials(pAp, vb, xx, vb), it, dAp.p, dvp, dr.p, n, rr);
+            run(k_cg_update_xp_d64, vb, dsc.p, TwoSums::partials(rr, vb, jac ? rr + vb : nullptr, vb), it, dr.p, dvp, dx.p, dp.p, n, xx);
+        }, [&](int last) { run(k_cg_check, 1, dsc.p, nullptr, xx, vb, last); });
+        const CGScalars& h = br.h;
+        const int iters = h.done ? h.iter : br.interrupted ? br.it : maxit;
         if (x_out) { HIP_CHECK(hipMemcpyAsync(x_out, dx.p, (size_t)n * 8, hipMemcpyDeviceToHost, st)); HIP_CHECK(hipStreamSynchronize(st)); }
         const auto w1 = std::chrono::high_resolution_clock::now();
-        const int result = iters == maxit ? PS_NOCONVERGE : PS_SUCCESS;   // the BiCGStab fallback is not wired into this path
+        const int result = br.interrupted ? PS_INCOMPLETE : iters == maxit ? PS_NOCONVERGE : PS_SUCCESS;   // the BiCGStab fallback is not wired into this path
         if (stats) {
             std::memset(stats, 0, sizeof(*stats));
             stats->dimData[7] = (double)nA; stats->dimData[11] = (double)nR; stats->dimData[12] = (double)nP; stats->dimData[13] = (double)nT;

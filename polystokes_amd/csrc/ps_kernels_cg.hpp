@@ -30,13 +30,18 @@
 #ifndef PS_VEC_NT_D
 #define PS_VEC_NT_D 1      // the stored Jacobi diagonal (read by both step kernels, half an iteration apart)
 #endif
+// two consecutive floats as doubles; i2 = index of the pair (the fp32 form of the stored diagonal; z of the single-precision polynomial, whose x
+// and p are fp64: two values per 16 bytes of x, not Vec16<float>'s four)
+__device__ inline double2 ldF2(const float* __restrict__ f, int64_t i2, bool nt) {
+    typedef float psf2 __attribute__((ext_vector_type(2)));
+    const psf2* q = reinterpret_cast<const psf2*>(f) + i2;
+    const psf2 v = nt ? __builtin_nontemporal_load(q) : *q;
+    return make_double2((double)v.x, (double)v.y);
+}
 // two consecutive entries of the stored Jacobi diagonal (ps_common.hpp: diag_t) as doubles; i2 = index of the pair
 __device__ inline double2 ldDiag2(const diag_t* __restrict__ d, int64_t i2, bool nt) {
 #ifdef PS_DIAG_FP32
-    typedef float psf2 __attribute__((ext_vector_type(2)));
-    const psf2* q = reinterpret_cast<const psf2*>(d) + i2;
-    const psf2 v = nt ? __builtin_nontemporal_load(q) : *q;
-    return make_double2((double)v.x, (double)v.y);
+    return ldF2(d, i2, nt);
 #else
     const uint32_t* q = reinterpret_cast<const uint32_t*>(d) + i2;
     const uint32_t v = nt ? __builtin_nontemporal_load(q) : *q;
@@ -79,12 +84,13 @@ template <> struct Vec16<float> {
     }
     __device__ static inline double stored(double v) { return (double)(float)v; }
 };
-// the W entries of the stored Jacobi diagonal / of the fp64 stress diagonal / the W one-byte codes that go with group iv
+// the W entries of the stored Jacobi diagonal / of an fp64 diagonal (the exported system's Jacobi diagonal, the stress diagonal) / the W one-byte
+// codes that go with group iv
 template <int W> __device__ inline void ldDiagW(const diag_t* __restrict__ d, int64_t iv, bool nt, double (&o)[W]) {
 #pragma unroll
     for (int k = 0; k < W / 2; ++k) { const double2 q = ldDiag2(d, iv * (W / 2) + k, nt); o[2 * k] = q.x; o[2 * k + 1] = q.y; }
 }
-template <int W> __device__ inline void ldF64W(const double* __restrict__ u, int64_t iv, bool nt, double (&o)[W]) {
+template <int W> __device__ inline void ldDiagW(const double* __restrict__ u, int64_t iv, bool nt, double (&o)[W]) {
 #pragma unroll
     for (int k = 0; k < W / 2; ++k) { const double2 q = ldD2((const double2*)u + iv * (W / 2) + k, nt); o[2 * k] = q.x; o[2 * k + 1] = q.y; }
 }
@@ -92,68 +98,72 @@ template <int W> __device__ inline uint32_t ldCodesW(const uint8_t* __restrict__
     if constexpr (W == 2) return nt ? __builtin_nontemporal_load((const uint16_t*)c + iv) : ((const uint16_t*)c)[iv];
     else return nt ? __builtin_nontemporal_load((const uint32_t*)c + iv) : ((const uint32_t*)c)[iv];
 }
-__global__ void k_scale_rows(double* __restrict__ out, const double* __restrict__ a, const double* __restrict__ b, int64_t n) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) out[i] = a[i] * b[i];
-}
-// r = b; x = 0; z = pre(r); p = z; partial rsold = r.z
-__global__ void __launch_bounds__(BS) k_cg_init(const double* __restrict__ b, const double* __restrict__ dinv, double* __restrict__ x,
-                                                double* __restrict__ r, double* __restrict__ p, int64_t n, double* __restrict__ partial) {
-    double acc = 0.;
-    for (int64_t i = (int64_t)blockIdx.x * BS + threadIdx.x; i < n; i += (int64_t)gridDim.x * BS) {
-        const double rv = b[i];
-        const double z = dinv ? dinv[i] * rv : rv;
-        x[i] = 0.; r[i] = rv; p[i] = z;
-        acc += rv * z;
+// The stress diagonal uInv as the x, p update and k_uinv_pp read it: one-byte codes into a 256-entry table (ps_context.hpp: uCode / uDict; code
+// null: none) or the fp64 array.  By value at the launch sites.  fill: the table into the block's LDS, to be read after the caller's next barrier;
+// value: entry i; load: the W entries of group iv (nt: PS_VEC_NT_U on the codes)
+struct StressDiag {
+    const uint8_t* code; const double* dict; const double* inv;
+    __device__ inline const double* fill() const {
+        __shared__ double lds[256];
+        if (code) lds[threadIdx.x] = dict[threadIdx.x];
+        return lds;
     }
-    const double s = blockReduceSum(acc);
-    if (threadIdx.x == 0) partial[blockIdx.x] = s;
-}
-// r = b; x = 0; z = pre(r); p = z; partial rsold = r.z — with the stored Jacobi diagonal of the main PCG path (diag_t)
-__global__ void __launch_bounds__(BS) k_cg_init_f(const double* __restrict__ b, const diag_t* __restrict__ dinv, double* __restrict__ x,
-                                                  double* __restrict__ r, double* __restrict__ p, int64_t n, double* __restrict__ partial) {
-    double acc = 0.;
-    for (int64_t i = (int64_t)blockIdx.x * BS + threadIdx.x; i < n; i += (int64_t)gridDim.x * BS) {
-        const double rv = b[i];
-        const double z = dinv ? diagValue(dinv[i]) * rv : rv;
-        x[i] = 0.; r[i] = rv; p[i] = z;
-        acc += rv * z;
+    template <int W> __device__ inline bool aligned() const { return (((uintptr_t)code & (W - 1)) == 0) && (((uintptr_t)inv & 15) == 0); }
+    __device__ inline double value(const double* lds, int64_t i) const { return code ? lds[code[i]] : inv[i]; }
+    template <int W> __device__ inline void load(const double* lds, int64_t iv, bool nt, double (&u)[W]) const {
+        if (code) {
+            const uint32_t cc = ldCodesW<W>(code, iv, nt && PS_VEC_NT_U);
+#pragma unroll
+            for (int k = 0; k < W; ++k) u[k] = lds[(cc >> (8 * k)) & 255u];
+        } else ldDiagW<W>(inv, iv, nt, u);
     }
-    const double s = blockReduceSum(acc);
-    if (threadIdx.x == 0) partial[blockIdx.x] = s;
+};
+// out = a .* b   (TA: double, or the stored Jacobi diagonal as the PCG kernels read it)
+template <class TA> __global__ void k_mul(double* __restrict__ out, const TA* __restrict__ a, const double* __restrict__ b, int64_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) out[i] = diagValue(a[i]) * b[i];
 }
-// ---- warm start (ps_set_warm_start) ----------------------------------------------------------------
-// r = b - A x0 (Ax = A x0 from applyOperator); z = pre(r); p = z; partial rsold = r.z — k_cg_init_f on a carried x0, which stays in x
+// Start of a solve or of a pass: r = b, or (warm) b - A x with Ax = A x from applyOperator (a warm start, whose x0 stays in x); z = pre(r);
+// p = z; (clear) xd = 0 — x, or a pass's correction d; partial rsold = r.z.  warm and clear are constants at every wrapper but the pass's warm.
+// DT: the diagonal's element type (diag_t, or double: the exported system).  TV = float: a pass of the mixed-precision solve
+// (ps_set_solve_precision; ps_solve.hip: solve), which solves A d = r64 with r = fp32(r64), p = fp32(z).  Partials: r.z of the values as stored
+// at [block]; then of the TRUE r64 . r64 at [grid + block] and of x . x (x64; warm only) at [2 grid + block] — the fp64 evaluation of the stop
+// rule on b - A x (k_cg_scal0_pass)
+template <class TV, class DT>
+__device__ inline void cgInit(const double* __restrict__ b, const double* __restrict__ Ax, bool warm, const double* __restrict__ x64,
+                              const DT* __restrict__ dinv, TV* __restrict__ xd, bool clear, TV* __restrict__ r, TV* __restrict__ p, int64_t n,
+                              double* __restrict__ partial) {
+    constexpr bool PASS = !std::is_same<TV, double>::value;
+    double arz = 0., arr = 0., axx = 0.;
+    for (int64_t i = (int64_t)blockIdx.x * BS + threadIdx.x; i < n; i += (int64_t)gridDim.x * BS) {
+        const double r64 = warm ? b[i] - Ax[i] : b[i];
+        const TV rs = (TV)r64;                                                              // as stored (Vec16<TV>::stored)
+        const TV zs = (TV)(dinv ? diagValue(dinv[i]) * (double)rs : (double)rs);
+        if (clear) xd[i] = (TV)0;
+        r[i] = rs; p[i] = zs;
+        arz += (double)rs * (double)zs;
+        if (PASS) {
+            arr += r64 * r64;
+            if (warm) { const double xv = x64[i]; axx += xv * xv; }
+        }
+    }
+    const double s0 = blockReduceSum(arz), s1 = PASS ? blockReduceSum(arr) : 0., s2 = PASS ? blockReduceSum(axx) : 0.;
+    if (threadIdx.x != 0) return;
+    partial[blockIdx.x] = s0;
+    if (PASS) { partial[gridDim.x + blockIdx.x] = s1; partial[2 * gridDim.x + blockIdx.x] = s2; }
+}
+#define PS_CG_INIT_PARAMS(DT) const double* __restrict__ b, const DT* __restrict__ dinv, double* __restrict__ x, double* __restrict__ r, double* __restrict__ p, \
+                              int64_t n, double* __restrict__ partial
+__global__ void __launch_bounds__(BS) k_cg_init_f(PS_CG_INIT_PARAMS(diag_t)) { cgInit(b, nullptr, false, nullptr, dinv, x, true, r, p, n, partial); }
+__global__ void __launch_bounds__(BS) k_cg_init_d64(PS_CG_INIT_PARAMS(double)) { cgInit(b, nullptr, false, nullptr, dinv, x, true, r, p, n, partial); }
+#undef PS_CG_INIT_PARAMS
 __global__ void __launch_bounds__(BS) k_cg_init_warm(const double* __restrict__ b, const double* __restrict__ Ax, const diag_t* __restrict__ dinv,
                                                      double* __restrict__ r, double* __restrict__ p, int64_t n, double* __restrict__ partial) {
-    double acc = 0.;
-    for (int64_t i = (int64_t)blockIdx.x * BS + threadIdx.x; i < n; i += (int64_t)gridDim.x * BS) {
-        const double rv = b[i] - Ax[i];
-        const double z = dinv ? diagValue(dinv[i]) * rv : rv;
-        r[i] = rv; p[i] = z;
-        acc += rv * z;
-    }
-    const double s = blockReduceSum(acc);
-    if (threadIdx.x == 0) partial[blockIdx.x] = s;
+    cgInit(b, Ax, true, nullptr, dinv, (double*)nullptr, false, r, p, n, partial);
 }
-// ---- mixed-precision solve (ps_set_solve_precision; ps_solve.hip: solve) ----------------------------------------------------
-// Start of a pass, the fp32 form of k_cg_init_f (Ax null: x = 0, r = b) and k_cg_init_warm (Ax = A x): the pass solves A d = r64 with
-// d = 0, r = fp32(r64), z = pre(r), p = fp32(z).  Partials: r.z of the values as stored at [block]; of the TRUE r64 . r64 at [grid + block] and
-// of x . x at [2 grid + block] — the fp64 evaluation of the stop rule on b - A x (k_cg_scal0_pass)
 __global__ void __launch_bounds__(BS) k_cg_init_pass(const double* __restrict__ b, const double* __restrict__ Ax, const double* __restrict__ x,
                                                      const diag_t* __restrict__ dinv, float* __restrict__ d, float* __restrict__ r,
                                                      float* __restrict__ p, int64_t n, double* __restrict__ partial) {
-    double arz = 0., arr = 0., axx = 0.;
-    for (int64_t i = (int64_t)blockIdx.x * BS + threadIdx.x; i < n; i += (int64_t)gridDim.x * BS) {
-        const double r64 = Ax ? b[i] - Ax[i] : b[i];
-        const float rs = (float)r64;
-        const float zs = (float)(dinv ? diagValue(dinv[i]) * (double)rs : (double)rs);
-        d[i] = 0.f; r[i] = rs; p[i] = zs;
-        arz += (double)rs * (double)zs;
-        arr += r64 * r64;
-        if (Ax) { const double xv = x[i]; axx += xv * xv; }
-    }
-    const double s0 = blockReduceSum(arz), s1 = blockReduceSum(arr), s2 = blockReduceSum(axx);
-    if (threadIdx.x == 0) { partial[blockIdx.x] = s0; partial[gridDim.x + blockIdx.x] = s1; partial[2 * gridDim.x + blockIdx.x] = s2; }
+    cgInit(b, Ax, Ax != nullptr, x, dinv, d, true, r, p, n, partial);
 }
 // End of a pass: x += d in fp64 (cold: x = d, the first pass of a cold solve)
 __global__ void __launch_bounds__(BS) k_cg_end_pass(const float* __restrict__ d, double* __restrict__ x, int64_t n, int cold) {
@@ -199,6 +209,16 @@ __global__ void k_to_diag(const double* __restrict__ a, diag_t* __restrict__ out
 }
 // sum of `count` partials, valid in thread 0 (sumLocal, stopTest: ps_kernels_spmv.hpp, shared with the fused St epilogue)
 __device__ inline double sumPartials(const double* __restrict__ partial, int count) { return blockReduceSum(sumLocal(partial, count)); }
+// out[q] = sum of partial[q*stride .. q*stride+count)   (q < nq), one block, fixed order; sc given: nothing once the solve is done
+__global__ void __launch_bounds__(BS) k_sumq(const CGScalars* __restrict__ sc, const double* __restrict__ partial, int count, int stride, int nq,
+                                             double* __restrict__ out) {
+    if (sc && sc->done) return;
+    for (int q = 0; q < nq; ++q) {
+        const double s = sumPartials(partial + (int64_t)q * stride, count);
+        if (threadIdx.x == 0) out[q] = s;
+        __syncthreads();
+    }
+}
 __device__ inline void cgScalInit(CGScalars* sc, double s, double tol, int maxit, int vecNT) {   // (one thread)
     sc->rsold = s; sc->rsold2[0] = s; sc->rsold2[1] = 0.; sc->rre = 0.; sc->iter = maxit; sc->maxit = maxit; sc->tol2 = tol * tol;
     sc->done = (s == 0.) ? 1 : 0;      // deviation: b == 0 -> return at once (reference divides 0/0, pcg.h:314)
@@ -235,80 +255,6 @@ __global__ void __launch_bounds__(BS) k_reduce_partials(const CGScalars* __restr
     const double s = blockReduceSum(acc);
     if (threadIdx.x == 0) out[blockIdx.x] = s;
 }
-__global__ void __launch_bounds__(BS) k_cg_scal1(CGScalars* sc, const double* __restrict__ partial, int count) {
-    if (sc->done) return;
-    const double s = sumPartials(partial, count);
-    if (threadIdx.x == 0) { sc->pAp = s; sc->alpha = sc->rsold / s; }   // pcg.h:314
-}
-// x += alpha p ; r -= alpha Ap ; partials of r.r, x.x, r.z   (pcg.h:315-319,331).  16-byte (double2) accesses.
-__global__ void __launch_bounds__(BS) k_cg_update_xr(const CGScalars* __restrict__ sc, const double* __restrict__ p, const double* __restrict__ Ap,
-                                                     const double* __restrict__ dinv, double* __restrict__ x, double* __restrict__ r, int64_t n,
-                                                     double* __restrict__ partial) {
-    if (sc->done) return;
-    const double alpha = sc->alpha;
-    double arr = 0., axx = 0., arz = 0.;
-    const bool vec = ((((uintptr_t)p | (uintptr_t)Ap | (uintptr_t)x | (uintptr_t)r | (uintptr_t)dinv) & 15) == 0);
-    const int64_t n2 = vec ? n / 2 : 0;
-    const double2* p2 = (const double2*)p; const double2* A2 = (const double2*)Ap; const double2* d2 = (const double2*)dinv;
-    double2* x2 = (double2*)x; double2* r2 = (double2*)r;
-    for (int64_t i = (int64_t)blockIdx.x * BS + threadIdx.x; i < n2; i += (int64_t)gridDim.x * BS) {
-        const double2 pv = p2[i], av = A2[i];
-        double2 xv = x2[i], rv = r2[i];
-        xv.x = xv.x + alpha * pv.x; xv.y = xv.y + alpha * pv.y;
-        rv.x = rv.x - alpha * av.x; rv.y = rv.y - alpha * av.y;
-        x2[i] = xv; r2[i] = rv;
-        arr += rv.x * rv.x; arr += rv.y * rv.y;
-        axx += xv.x * xv.x; axx += xv.y * xv.y;
-        if (dinv) { const double2 dv = d2[i]; arz += rv.x * (dv.x * rv.x); arz += rv.y * (dv.y * rv.y); }
-    }
-    for (int64_t i = 2 * n2 + (int64_t)blockIdx.x * BS + threadIdx.x; i < n; i += (int64_t)gridDim.x * BS) {
-        const double xv = x[i] + alpha * p[i];
-        const double rv = r[i] - alpha * Ap[i];
-        x[i] = xv; r[i] = rv;
-        arr += rv * rv; axx += xv * xv;
-        if (dinv) arz += rv * (dinv[i] * rv);
-    }
-    const double s0 = blockReduceSum(arr), s1 = blockReduceSum(axx), s2 = dinv ? blockReduceSum(arz) : 0.;
-    if (threadIdx.x == 0) {
-        partial[blockIdx.x] = s0;
-        partial[gridDim.x + blockIdx.x] = s1;
-        partial[2 * gridDim.x + blockIdx.x] = s2;
-    }
-}
-__global__ void __launch_bounds__(BS) k_cg_scal2(CGScalars* sc, const double* __restrict__ partial, int count, int jacobi, int iterIndex) {
-    if (sc->done) return;
-    const double rr = sumPartials(partial, count);
-    const double xx = sumPartials(partial + count, count);
-    const double rz = jacobi ? sumPartials(partial + 2 * count, count) : rr;
-    if (threadIdx.x == 0) {
-        sc->rr = rr; sc->xx = xx; sc->rz = rz;
-        double rre = rr;                              // pcg.h:319-325
-        if (rr / xx < rre) rre = rr / xx;
-        sc->rre = rre;
-        if (rre < sc->tol2) { sc->done = 1; sc->iter = iterIndex; }
-        else { sc->beta = rz / sc->rsold; sc->rsold = rz; }   // pcg.h:331-335
-    }
-}
-__global__ void __launch_bounds__(BS) k_cg_update_p(const CGScalars* __restrict__ sc, const double* __restrict__ r, const double* __restrict__ dinv,
-                                                    double* __restrict__ p, int64_t n) {
-    if (sc->done) return;
-    const double beta = sc->beta;
-    const bool vec = ((((uintptr_t)p | (uintptr_t)r | (uintptr_t)dinv) & 15) == 0);
-    const int64_t n2 = vec ? n / 2 : 0;
-    const double2* r2 = (const double2*)r; const double2* d2 = (const double2*)dinv;
-    double2* p2 = (double2*)p;
-    for (int64_t i = (int64_t)blockIdx.x * BS + threadIdx.x; i < n2; i += (int64_t)gridDim.x * BS) {
-        double2 z = r2[i];
-        if (dinv) { const double2 dv = d2[i]; z.x = dv.x * z.x; z.y = dv.y * z.y; }
-        double2 pv = p2[i];
-        pv.x = z.x + beta * pv.x; pv.y = z.y + beta * pv.y;
-        p2[i] = pv;
-    }
-    for (int64_t i = 2 * n2 + (int64_t)blockIdx.x * BS + threadIdx.x; i < n; i += (int64_t)gridDim.x * BS) {
-        const double z = dinv ? dinv[i] * r[i] : r[i];
-        p[i] = z + beta * p[i];
-    }
-}
 
 // ---- PCG step: x update deferred into the p update, scalar reductions folded into the vector kernels ---------------
 // pcg.h:311-335 updates x and r together, tests min(rr, rr/xx) < tol^2, then forms beta and the new p: 11 vector passes
@@ -322,6 +268,18 @@ __global__ void __launch_bounds__(BS) k_cg_update_p(const CGScalars* __restrict_
 // the start of iteration k+1 (or by k_cg_check before the host polls); when it fires every later kernel is a no-op and
 // x already holds the iterate the reference returns.  Cost: one unused p update and one unused operator apply.
 // With `red` (distributed solve) the sums come all-reduced from the ranks: red = {p.Ap, x.x} resp. {r.r, r.z}.
+// One sum of a step kernel's prologue: `count` >= 0 partials that every block sums itself (none: 0), or (count = SUM_REDUCED) the value at p[0],
+// all-reduced by the ranks.
+// Two of them, by value at the launch sites: {p.Ap, x.x} of k_cg_update_r, {r.r, r.z} of the x, p update, where an absent second (p null) means
+// r.z = r.r (identity)
+constexpr int SUM_REDUCED = -1;
+struct SumSrc { const double* p; int count; };
+struct TwoSums {
+    SumSrc a, b;
+    static TwoSums partials(const double* a, int na, const double* b, int nb) { return {{a, na}, {b, nb}}; }
+    static TwoSums reduced(const double* red, bool second = true) { return {{red, SUM_REDUCED}, {second ? red + 1 : nullptr, SUM_REDUCED}}; }
+};
+__device__ inline double sumOf(const SumSrc& s) { return s.count != SUM_REDUCED ? blockSumAll(sumLocal(s.p, s.count)) : s.p[0]; }
 template <bool PASS>
 __device__ inline void cgCheck(CGScalars* sc, const double* __restrict__ red, const double* __restrict__ xxPartial, int vb, int lastIter) {
     if (sc->done) return;
@@ -334,28 +292,23 @@ __global__ void __launch_bounds__(BS) k_cg_check(CGScalars* sc, const double* __
 __global__ void __launch_bounds__(BS) k_cg_check_pass(CGScalars* sc, const double* __restrict__ xxPartial, int vb, int lastIter) {   // a pass of the mixed-precision solve
     cgCheck<true>(sc, nullptr, xxPartial, vb, lastIter);
 }
-// [stop test of iteration it-1] ; alpha ; r -= alpha Ap ; partials of r.r and r.z
+// [stop test of iteration it-1] ; alpha ; r -= alpha Ap ; partials of r.r and r.z.  s = {p.Ap, x.x}
 // TV: element type of Ap and r (float: a pass of the mixed-precision solve — k_cg_update_r_f32; r.r and r.z from r as stored, the pass's stop test)
-template <class TV>
-__device__ inline void cgUpdateR(CGScalars* sc, const double* __restrict__ red, const double* __restrict__ pApPartial, int pApCount,
-                                 const double* __restrict__ xxPartial, int xxCount, int it, const TV* __restrict__ Ap,
-                                 const diag_t* __restrict__ dinv, TV* __restrict__ r, int64_t n, double* __restrict__ partial) {
+// DT: element type of the Jacobi diagonal (diag_t; double: the exported system — k_cg_update_r_d64)
+template <class TV, class DT>
+__device__ inline void cgUpdateR(CGScalars* sc, const TwoSums& s, int it, const TV* __restrict__ Ap, const DT* __restrict__ dinv, TV* __restrict__ r,
+                                 int64_t n, double* __restrict__ partial) {
     if (sc->done) return;
     constexpr bool PASS = !std::is_same<TV, double>::value;
     constexpr int W = Vec16<TV>::W;
     const bool writer = blockIdx.x == 0 && threadIdx.x == 0;
-    double pAp, xx = 0.;
-    if (red) { pAp = red[0]; xx = red[1]; }
-    else {
-        if (it > 0) xx = blockSumAll(sumLocal(xxPartial, xxCount));
-        pAp = blockSumAll(sumLocal(pApPartial, pApCount));
-    }
+    const double xx = it > 0 ? sumOf(s.b) : 0., pAp = sumOf(s.a);
     if (it > 0 && stopTest<PASS>(sc, xx, it - 1, writer)) return;     // same verdict in every block
     const double alpha = sc->rsold2[it & 1] / pAp;                      // pcg.h:314
     if (writer) { sc->pAp = pAp; sc->alpha = alpha; }
     double arr = 0., arz = 0.;
     const bool nt = sc->vecNT != 0;
-    const bool vec = ((((uintptr_t)Ap | (uintptr_t)r) & 15) == 0) && (((uintptr_t)dinv & (W * sizeof(diag_t) - 1)) == 0);
+    const bool vec = ((((uintptr_t)Ap | (uintptr_t)r) & 15) == 0) && (((uintptr_t)dinv & (W * sizeof(DT) - 1)) == 0);
     const int64_t nv = vec ? n / W : 0;
     for (int64_t i = (int64_t)blockIdx.x * BS + threadIdx.x; i < nv; i += (int64_t)gridDim.x * BS) {
         double av[W], rv[W];
@@ -382,48 +335,68 @@ __device__ inline void cgUpdateR(CGScalars* sc, const double* __restrict__ red, 
     const double s0 = blockReduceSum(arr), s2 = dinv ? blockReduceSum(arz) : 0.;
     if (threadIdx.x == 0) { partial[blockIdx.x] = s0; partial[gridDim.x + blockIdx.x] = s2; }
 }
-#define PS_CG_UPDATE_R_PARAMS(TV) CGScalars* sc, const double* __restrict__ red, const double* __restrict__ pApPartial, int pApCount, const double* __restrict__ xxPartial, \
-                                  int xxCount, int it, const TV* __restrict__ Ap, const diag_t* __restrict__ dinv, TV* __restrict__ r, int64_t n, double* __restrict__ partial
-__global__ void __launch_bounds__(BS) k_cg_update_r(PS_CG_UPDATE_R_PARAMS(double)) { cgUpdateR<double>(sc, red, pApPartial, pApCount, xxPartial, xxCount, it, Ap, dinv, r, n, partial); }
-__global__ void __launch_bounds__(BS) k_cg_update_r_f32(PS_CG_UPDATE_R_PARAMS(float)) { cgUpdateR<float>(sc, red, pApPartial, pApCount, xxPartial, xxCount, it, Ap, dinv, r, n, partial); }
+#define PS_CG_UPDATE_R_PARAMS(TV, DT) CGScalars* sc, TwoSums s, int it, const TV* __restrict__ Ap, const DT* __restrict__ dinv, TV* __restrict__ r, int64_t n, double* __restrict__ partial
+__global__ void __launch_bounds__(BS) k_cg_update_r(PS_CG_UPDATE_R_PARAMS(double, diag_t)) { cgUpdateR(sc, s, it, Ap, dinv, r, n, partial); }
+__global__ void __launch_bounds__(BS) k_cg_update_r_f32(PS_CG_UPDATE_R_PARAMS(float, diag_t)) { cgUpdateR(sc, s, it, Ap, dinv, r, n, partial); }
+__global__ void __launch_bounds__(BS) k_cg_update_r_d64(PS_CG_UPDATE_R_PARAMS(double, double)) { cgUpdateR(sc, s, it, Ap, dinv, r, n, partial); }
 #undef PS_CG_UPDATE_R_PARAMS
-// beta ; x += alpha p ; p = z + beta p (z = D^-1 r) ; partials of x.x
-// UPP (fused residual update, FusedR in ps_kernels_spmv.hpp): also the partials of sum_j uInv_j p_j^2 of the NEW p — the diagonal
-// share of the next p . A p — from the coded diagonal (1 B per entry + 256-entry table in LDS) or the fp64 one.
-// TV: element type of r, x and p (float: a pass of the mixed-precision solve, where x is the pass's correction d — k_cg_update_xp_f32 / _u_f32;
-// x.x and the uInv p^2 partials are formed from the values as stored)
-template <bool UPP, class TV = double>
-__device__ inline void cgUpdateXp(CGScalars* sc, const double* __restrict__ red, const double* __restrict__ rPartial, int rCount, int jacobi,
-                                  int it, const TV* __restrict__ r, const diag_t* __restrict__ dinv, TV* __restrict__ x,
-                                  TV* __restrict__ p, int64_t n, double* __restrict__ partial,
-                                  const uint8_t* __restrict__ uCode, const double* __restrict__ uDict, const double* __restrict__ uInv, double* __restrict__ uPart) {
-    if (sc->done) return;
-    constexpr int W = Vec16<TV>::W;
-    __shared__ double dict[UPP ? 256 : 1];
-    if (UPP && uCode) dict[threadIdx.x] = uDict[threadIdx.x];   // visible after the barriers of blockSumAll below
-    double rr, rz;
-    if (red) { rr = red[0]; rz = jacobi ? red[1] : red[0]; }
-    else {
-        rr = blockSumAll(sumLocal(rPartial, rCount));
-        rz = jacobi ? blockSumAll(sumLocal(rPartial + rCount, rCount)) : rr;
+// Where z = M^-1 r of the x, p update comes from.  V: element type of x and p; W values per 16-byte group of x; aligned: the 16-byte loop may run;
+// load: the W values of group iv; at: entry i (the scalar tail).
+// ZJacobi: z = D^-1 r with the stored diagonal (null: z = r).  TV: element type of r, x and p; DT as in cgUpdateR
+template <class TV, class DT> struct ZJacobi {
+    typedef TV V;
+    static constexpr int W = Vec16<TV>::W;
+    const TV* r; const DT* dinv;
+    __device__ inline bool aligned() const { return (((uintptr_t)r & 15) == 0) && (((uintptr_t)dinv & (W * sizeof(DT) - 1)) == 0); }
+    __device__ inline void load(int64_t iv, bool nt, double (&z)[W]) const {
+        Vec16<TV>::load(r, iv, nt && PS_VEC_NT_RX, z);
+        if (dinv) {
+            double dv[W];
+            ldDiagW<W>(dinv, iv, nt && PS_VEC_NT_D, dv);
+#pragma unroll
+            for (int k = 0; k < W; ++k) z[k] = dv[k] * z[k];
+        }
     }
-    if (UPP && red) __syncthreads();
+    __device__ inline double at(int64_t i) const { return dinv ? diagValue(dinv[i]) * (double)r[i] : (double)r[i]; }
+};
+// ZVector: z is a VECTOR (the polynomial preconditioner), x and p are fp64.  TZ: element type of z (float: the single-precision Chebyshev
+// polynomial — still two values per group, of 8 bytes)
+template <class TZ> struct ZVector {
+    typedef double V;
+    static constexpr int W = 2;
+    const TZ* z;
+    __device__ inline bool aligned() const { return ((uintptr_t)z & 15) == 0; }
+    __device__ inline void load(int64_t iv, bool nt, double (&o)[2]) const {
+        double2 q;
+        if constexpr (std::is_same<TZ, float>::value) q = ldF2(z, iv, nt); else q = ldD2((const double2*)z + iv, nt);
+        o[0] = q.x; o[1] = q.y;
+    }
+    __device__ inline double at(int64_t i) const { return (double)z[i]; }
+};
+// beta = r.z / rsold ; x += alpha p ; p = z + beta p (z from ZS) ; partials of x.x.  s = {r.r, r.z}
+// UPP (fused residual update, FusedR in ps_kernels_spmv.hpp): also the partials of sum_j uInv_j p_j^2 of the NEW p — the diagonal
+// share of the next p . A p — from the coded diagonal (1 B per entry + 256-entry table in LDS) or the fp64 one (StressDiag).
+// ZS::V = float: a pass of the mixed-precision solve, where x is the pass's correction d — k_cg_update_xp_f32 / _u_f32; x.x and the uInv p^2
+// partials are formed from the values as stored
+template <bool UPP, class ZS>
+__device__ inline void cgUpdateXp(CGScalars* sc, const TwoSums& s, int it, const ZS& zs, typename ZS::V* __restrict__ x, typename ZS::V* __restrict__ p,
+                                  int64_t n, double* __restrict__ partial, const StressDiag& u, double* __restrict__ uPart) {
+    if (sc->done) return;
+    typedef typename ZS::V TV;
+    constexpr int W = ZS::W;
+    const double* dict = nullptr;
+    if constexpr (UPP) dict = u.fill();
+    const double rr = sumOf(s.a), rz = s.b.p ? sumOf(s.b) : rr;
+    if (UPP && s.a.count == SUM_REDUCED) __syncthreads();                              // the table: visible after the barriers of blockSumAll otherwise
     const double alpha = sc->alpha, beta = rz / sc->rsold2[it & 1];      // pcg.h:331-335
     const bool nt = sc->vecNT != 0;
     if (blockIdx.x == 0 && threadIdx.x == 0) { sc->rr = rr; sc->rz = rz; sc->beta = beta; sc->rsold2[(it + 1) & 1] = rz; sc->rsold = rz; }
     double axx = 0., aup = 0.;
-    const bool vec = ((((uintptr_t)p | (uintptr_t)r | (uintptr_t)x) & 15) == 0) && (((uintptr_t)dinv & (W * sizeof(diag_t) - 1)) == 0) &&
-                     (!UPP || ((((uintptr_t)uCode & (W - 1)) == 0) && (((uintptr_t)uInv & 15) == 0)));
+    const bool vec = ((((uintptr_t)p | (uintptr_t)x) & 15) == 0) && zs.aligned() && (!UPP || u.template aligned<W>());
     const int64_t nv = vec ? n / W : 0;
     for (int64_t i = (int64_t)blockIdx.x * BS + threadIdx.x; i < nv; i += (int64_t)gridDim.x * BS) {
         double z[W], pv[W], xv[W];
-        Vec16<TV>::load(r, i, nt && PS_VEC_NT_RX, z);
-        if (dinv) {
-            double dv[W];
-            ldDiagW<W>(dinv, i, nt && PS_VEC_NT_D, dv);
-#pragma unroll
-            for (int k = 0; k < W; ++k) z[k] = dv[k] * z[k];
-        }
+        zs.load(i, nt, z);
         Vec16<TV>::load(p, i, nt && PS_VEC_NT_PL, pv);
         Vec16<TV>::load(x, i, nt && PS_VEC_NT_X, xv);
 #pragma unroll
@@ -435,24 +408,20 @@ __device__ inline void cgUpdateXp(CGScalars* sc, const double* __restrict__ red,
 #pragma unroll
         for (int k = 0; k < W; ++k) axx += xv[k] * xv[k];
         if (UPP) {
-            double u[W];
-            if (uCode) {
-                const uint32_t cc = ldCodesW<W>(uCode, i, nt && PS_VEC_NT_U);
+            double uv[W];
+            u.template load<W>(dict, i, nt, uv);
 #pragma unroll
-                for (int k = 0; k < W; ++k) u[k] = dict[(cc >> (8 * k)) & 255u];
-            } else ldF64W<W>(uInv, i, nt, u);
-#pragma unroll
-            for (int k = 0; k < W; ++k) aup += u[k] * (pv[k] * pv[k]);
+            for (int k = 0; k < W; ++k) aup += uv[k] * (pv[k] * pv[k]);
         }
     }
     for (int64_t i = W * nv + (int64_t)blockIdx.x * BS + threadIdx.x; i < n; i += (int64_t)gridDim.x * BS) {
-        const double z = dinv ? diagValue(dinv[i]) * (double)r[i] : (double)r[i];
+        const double z = zs.at(i);
         const double pv = p[i];
         const double xv = Vec16<TV>::stored((double)x[i] + alpha * pv);
         const double pn = Vec16<TV>::stored(z + beta * pv);
         x[i] = (TV)xv; p[i] = (TV)pn;
         axx += xv * xv;
-        if (UPP) aup += (uCode ? dict[uCode[i]] : uInv[i]) * (pn * pn);
+        if (UPP) aup += u.value(dict, i) * (pn * pn);
     }
     const double s1 = blockReduceSum(axx);
     if (threadIdx.x == 0) partial[blockIdx.x] = s1;
@@ -461,68 +430,81 @@ __device__ inline void cgUpdateXp(CGScalars* sc, const double* __restrict__ red,
         if (threadIdx.x == 0) uPart[blockIdx.x] = s2;
     }
 }
-#define PS_CG_XP_PARAMS(TV) CGScalars* sc, const double* __restrict__ red, const double* __restrict__ rPartial, int rCount, int jacobi, int it, const TV* __restrict__ r, \
-                            const diag_t* __restrict__ dinv, TV* __restrict__ x, TV* __restrict__ p, int64_t n, double* __restrict__ partial
-#define PS_CG_XP_U_PARAMS const uint8_t* __restrict__ uCode, const double* __restrict__ uDict, const double* __restrict__ uInv, double* __restrict__ uPart
-__global__ void __launch_bounds__(BS) k_cg_update_xp(PS_CG_XP_PARAMS(double)) {
-    cgUpdateXp<false>(sc, red, rPartial, rCount, jacobi, it, r, dinv, x, p, n, partial, nullptr, nullptr, nullptr, nullptr);
+#define PS_CG_XP_PARAMS(TV, DT) CGScalars* sc, TwoSums s, int it, const TV* __restrict__ r, const DT* __restrict__ dinv, TV* __restrict__ x, TV* __restrict__ p, \
+                                int64_t n, double* __restrict__ partial
+#define PS_CG_XP_Z_PARAMS CGScalars* sc, TwoSums s, int it, const TZ* __restrict__ z, double* __restrict__ x, double* __restrict__ p, int64_t n, double* __restrict__ partial
+__global__ void __launch_bounds__(BS) k_cg_update_xp(PS_CG_XP_PARAMS(double, diag_t)) { cgUpdateXp<false>(sc, s, it, ZJacobi<double, diag_t>{r, dinv}, x, p, n, partial, StressDiag{}, nullptr); }
+__global__ void __launch_bounds__(BS) k_cg_update_xp_u(PS_CG_XP_PARAMS(double, diag_t), StressDiag u, double* __restrict__ uPart) {
+    cgUpdateXp<true>(sc, s, it, ZJacobi<double, diag_t>{r, dinv}, x, p, n, partial, u, uPart);
 }
-__global__ void __launch_bounds__(BS) k_cg_update_xp_u(PS_CG_XP_PARAMS(double), PS_CG_XP_U_PARAMS) {
-    cgUpdateXp<true>(sc, red, rPartial, rCount, jacobi, it, r, dinv, x, p, n, partial, uCode, uDict, uInv, uPart);
+__global__ void __launch_bounds__(BS) k_cg_update_xp_f32(PS_CG_XP_PARAMS(float, diag_t)) { cgUpdateXp<false>(sc, s, it, ZJacobi<float, diag_t>{r, dinv}, x, p, n, partial, StressDiag{}, nullptr); }
+__global__ void __launch_bounds__(BS) k_cg_update_xp_u_f32(PS_CG_XP_PARAMS(float, diag_t), StressDiag u, double* __restrict__ uPart) {
+    cgUpdateXp<true>(sc, s, it, ZJacobi<float, diag_t>{r, dinv}, x, p, n, partial, u, uPart);
 }
-__global__ void __launch_bounds__(BS) k_cg_update_xp_f32(PS_CG_XP_PARAMS(float)) {
-    cgUpdateXp<false, float>(sc, red, rPartial, rCount, jacobi, it, r, dinv, x, p, n, partial, nullptr, nullptr, nullptr, nullptr);
+__global__ void __launch_bounds__(BS) k_cg_update_xp_d64(PS_CG_XP_PARAMS(double, double)) { cgUpdateXp<false>(sc, s, it, ZJacobi<double, double>{r, dinv}, x, p, n, partial, StressDiag{}, nullptr); }
+template <class TZ> __global__ void __launch_bounds__(BS) k_cg_update_xp_z(PS_CG_XP_Z_PARAMS) { cgUpdateXp<false>(sc, s, it, ZVector<TZ>{z}, x, p, n, partial, StressDiag{}, nullptr); }
+template <class TZ> __global__ void __launch_bounds__(BS) k_cg_update_xp_z_u(PS_CG_XP_Z_PARAMS, StressDiag u, double* __restrict__ uPart) {
+    cgUpdateXp<true>(sc, s, it, ZVector<TZ>{z}, x, p, n, partial, u, uPart);
 }
-__global__ void __launch_bounds__(BS) k_cg_update_xp_u_f32(PS_CG_XP_PARAMS(float), PS_CG_XP_U_PARAMS) {
-    cgUpdateXp<true, float>(sc, red, rPartial, rCount, jacobi, it, r, dinv, x, p, n, partial, uCode, uDict, uInv, uPart);
-}
-#undef PS_CG_XP_U_PARAMS
+#undef PS_CG_XP_Z_PARAMS
 #undef PS_CG_XP_PARAMS
 // partials of sum_j uInv_j p_j^2 (the first search direction of a fused-step solve; TV = float: of a pass of the mixed-precision solve)
 template <class TV>
-__device__ inline void uinvPp(const TV* __restrict__ p, const uint8_t* __restrict__ uCode, const double* __restrict__ uDict,
-                              const double* __restrict__ uInv, int64_t n, double* __restrict__ uPart) {
-    __shared__ double dict[256];
-    if (uCode) dict[threadIdx.x] = uDict[threadIdx.x];
+__device__ inline void uinvPp(const TV* __restrict__ p, const StressDiag& u, int64_t n, double* __restrict__ uPart) {
+    const double* dict = u.fill();
     __syncthreads();
     double acc = 0.;
     for (int64_t i = (int64_t)blockIdx.x * BS + threadIdx.x; i < n; i += (int64_t)gridDim.x * BS) {
         const double pv = p[i];
-        acc += (uCode ? dict[uCode[i]] : uInv[i]) * (pv * pv);
+        acc += u.value(dict, i) * (pv * pv);
     }
     const double s = blockReduceSum(acc);
     if (threadIdx.x == 0) uPart[blockIdx.x] = s;
 }
-__global__ void __launch_bounds__(BS) k_uinv_pp(const double* __restrict__ p, const uint8_t* __restrict__ uCode, const double* __restrict__ uDict,
-                                                const double* __restrict__ uInv, int64_t n, double* __restrict__ uPart) { uinvPp(p, uCode, uDict, uInv, n, uPart); }
-__global__ void __launch_bounds__(BS) k_uinv_pp_f32(const float* __restrict__ p, const uint8_t* __restrict__ uCode, const double* __restrict__ uDict,
-                                                    const double* __restrict__ uInv, int64_t n, double* __restrict__ uPart) { uinvPp(p, uCode, uDict, uInv, n, uPart); }
+__global__ void __launch_bounds__(BS) k_uinv_pp(const double* __restrict__ p, StressDiag u, int64_t n, double* __restrict__ uPart) { uinvPp(p, u, n, uPart); }
+__global__ void __launch_bounds__(BS) k_uinv_pp_f32(const float* __restrict__ p, StressDiag u, int64_t n, double* __restrict__ uPart) { uinvPp(p, u, n, uPart); }
 
 // ---- four-kernel step across slabs (ps_dist.hpp) ---------------------------------------------------------------------------
+// t = the sums of four values over a 1024-thread block, valid in thread 0 (fixed order).  The two one-block kernels below sit on the critical
+// path of every rank-iteration: 1024 threads, every load of a thread issued before the sums, ONE round of wave reductions for the four values
+// (k_fused_local_sum: 21 us -> a few with 256 threads walking the four arrays one after the other; k_sum_rr, r06: 12 us -> a few with 256
+// threads and four block reductions in a row)
+__device__ inline void blockSum4(const double (&acc)[4], double (&t)[4]) {
+    __shared__ double red[4][16];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) { const double v = waveReduceSum(acc[q]); if (lane == 0) red[q][w] = v; }
+    __syncthreads();
+    if (threadIdx.x == 0)
+        for (int q = 0; q < 4; ++q) { double a = 0.; for (int i = 0; i < 16; ++i) a += red[q][i]; t[q] = a; }
+}
 // this rank's share of p.Ap in its factored form and of ||x||^2: out = {sum S + sum T + 1/2 sum U, sum xx}   (one block, fixed order)
-// (1024 threads, all loads of a thread issued before the sums: 21 us -> a few with 256 threads walking the four arrays one after the other)
 __global__ void __launch_bounds__(1024) k_fused_local_sum(const CGScalars* __restrict__ sc, const double* __restrict__ sPart, int sCount, const double* __restrict__ tPart, int tCount,
                                                          const double* __restrict__ uPart, int uCount, const double* __restrict__ xxPart, int xxCount, double* __restrict__ out) {
     if (sc && sc->done) return;
-    __shared__ double red[4][16];
-    double acc[4] = {0., 0., 0., 0.};
+    double acc[4] = {0., 0., 0., 0.}, t[4];
     const double* arr[4] = {sPart, tPart, uPart, xxPart};
     const int cnt[4] = {sCount, tCount, uCount, xxCount};
 #pragma unroll
     for (int q = 0; q < 4; ++q)
         for (int i = threadIdx.x; i < cnt[q]; i += 1024) acc[q] += arr[q][i];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) { const double v = waveReduceSum(acc[q]); if (lane == 0) red[q][w] = v; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t[4];
-        for (int q = 0; q < 4; ++q) { double a = 0.; for (int i = 0; i < 16; ++i) a += red[q][i]; t[q] = a; }
-        out[0] = t[0] + t[1] + 0.5 * t[2]; out[1] = t[3];
-    }
+    blockSum4(acc, t);
+    if (threadIdx.x == 0) { out[0] = t[0] + t[1] + 0.5 * t[2]; out[1] = t[3]; }
 }
-// The St kernel updated r on the owned DOFs with this rank's rows only.  The DOFs next to a cut also receive the neighbour's share
-// c of (A p)_j (its halo rows): r_j -= alpha c, and the partial sums of r.r / r.z are corrected by the change of r_j^2.
+// The St kernel updated r on the owned DOFs with this rank's rows only.  The DOFs next to a cut also receive the neighbours' shares
+// c of (A p)_j (their halo rows): r_j -= alpha c, and the partial sums of r.r / r.z are corrected by the change of r_j^2.
+// fixupRow: r_j = rn (it was ro), the corrections into a0, a1; fixupPartials: the block's corrections of r.r at [block], of r.z at [grid + block]
+__device__ inline void fixupRow(double* __restrict__ r, const diag_t* __restrict__ dinv, int j, double ro, double rn, double& a0, double& a1) {
+    r[j] = rn;
+    const double d = rn * rn - ro * ro;
+    a0 += d;
+    if (dinv) a1 += diagValue(dinv[j]) * d;
+}
+__device__ inline void fixupPartials(double a0, double a1, double* __restrict__ partial) {
+    const double s0 = blockReduceSum(a0), s1 = blockReduceSum(a1);
+    if (threadIdx.x == 0) { partial[blockIdx.x] = s0; partial[gridDim.x + blockIdx.x] = s1; }
+}
+// one link: the contributions of its two receive buffers
 __global__ void __launch_bounds__(BS) k_dist_fixup(const CGScalars* __restrict__ sc, const int32_t* __restrict__ listA, int64_t nA, const double* __restrict__ bufA,
                                                    const int32_t* __restrict__ listB, int64_t nB, const double* __restrict__ bufB, double* __restrict__ r,
                                                    const diag_t* __restrict__ dinv, double* __restrict__ partial, int ownHi) {
@@ -533,37 +515,23 @@ __global__ void __launch_bounds__(BS) k_dist_fixup(const CGScalars* __restrict__
         const int j = i < nA ? listA[i] : listB[i - nA];
         if (j >= ownHi) continue;                        // a copy on its way to another rank (Dist::contributionsBack), not a DOF of this one
         const double c = i < nA ? bufA[i] : bufB[i - nA];
-        const double ro = r[j], rn = ro - alpha * c;
-        r[j] = rn;
-        const double d = rn * rn - ro * ro;
-        a0 += d;
-        if (dinv) a1 += diagValue(dinv[j]) * d;
+        const double ro = r[j];
+        fixupRow(r, dinv, j, ro, ro - alpha * c, a0, a1);
     }
-    const double s0 = blockReduceSum(a0), s1 = blockReduceSum(a1);
-    if (threadIdx.x == 0) { partial[blockIdx.x] = s0; partial[gridDim.x + blockIdx.x] = s1; }
+    fixupPartials(a0, a1, partial);
 }
 // out = {r.r, r.z} of this rank: the St kernel's partials plus the corrections of the fix-up ([2][fixCount] per set; r05: ONE set — the merged
-// fix-up k_dist_fixup_merged — and the two corrections folded thread by thread before ONE reduction each: this one-block kernel sits on the
-// critical path of every rank-iteration and took 17 us with 2 + 2 x 6 block reductions)   (one block)
+// fix-up k_dist_fixup_merged — and the two corrections folded thread by thread before ONE reduction each: this one-block kernel took 17 us with
+// 2 + 2 x 6 block reductions)   (one block)
 __global__ void __launch_bounds__(1024) k_sum_rr(const CGScalars* __restrict__ sc, const double* __restrict__ rPart, int rCount, const double* __restrict__ fixPart, int fixCount,
                                                int fixSets, double* __restrict__ out) {
-    // (r06: 1024 threads, every load of a thread issued before the sums, ONE round of wave reductions for the four values — as k_fused_local_sum:
-    // 12 us -> a few with 256 threads and four block reductions in a row)
     if (sc->done) return;
-    __shared__ double red[4][16];
-    double acc[4] = {0., 0., 0., 0.};
+    double acc[4] = {0., 0., 0., 0.}, t[4];
     for (int i = threadIdx.x; i < rCount; i += 1024) { acc[0] += rPart[i]; acc[1] += rPart[rCount + i]; }
     for (int q = 0; q < fixSets; ++q)
         for (int i = threadIdx.x; i < fixCount; i += 1024) { acc[2] += fixPart[(size_t)q * 2 * fixCount + i]; acc[3] += fixPart[(size_t)q * 2 * fixCount + fixCount + i]; }
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) { const double v = waveReduceSum(acc[q]); if (lane == 0) red[q][w] = v; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t[4];
-        for (int q = 0; q < 4; ++q) { double a = 0.; for (int i = 0; i < 16; ++i) a += red[q][i]; t[q] = a; }
-        out[0] = t[0] + t[2]; out[1] = t[1] + t[3];
-    }
+    blockSum4(acc, t);
+    if (threadIdx.x == 0) { out[0] = t[0] + t[2]; out[1] = t[1] + t[3]; }
 }
 // The fix-up of the fused step in ONE launch (r05): a thread owns a DOF that receives contributions — from up to MAXSRC links (a DOF next to two or
 // three cuts) — and applies them in link order, each to the r the previous one left: the arithmetic of the per-link launches of k_dist_fixup, DOF by
@@ -591,13 +559,9 @@ __global__ void __launch_bounds__(BS) k_dist_fixup_merged(const CGScalars* __res
 #pragma unroll
         for (int k = 0; k < FIX_MAXSRC; ++k)
             if (e[k] >= 0) rn -= alpha * cv[k];
-        r[j] = rn;
-        const double d = rn * rn - ro * ro;
-        a0 += d;
-        if (dinv) a1 += diagValue(dinv[j]) * d;
+        fixupRow(r, dinv, j, ro, rn, a0, a1);
     }
-    const double s0 = blockReduceSum(a0), s1 = blockReduceSum(a1);
-    if (threadIdx.x == 0) { partial[blockIdx.x] = s0; partial[gridDim.x + blockIdx.x] = s1; }
+    fixupPartials(a0, a1, partial);
 }
 
 // ---- generic vector helpers (BiCGStab fallback, rare) -----------------------------------------------
@@ -606,10 +570,6 @@ __global__ void __launch_bounds__(BS) k_dot(const double* __restrict__ a, const 
     for (int64_t i = (int64_t)blockIdx.x * BS + threadIdx.x; i < n; i += (int64_t)gridDim.x * BS) acc += a[i] * b[i];
     const double s = blockReduceSum(acc);
     if (threadIdx.x == 0) partial[blockIdx.x] = s;
-}
-__global__ void __launch_bounds__(BS) k_sum1(const double* __restrict__ partial, int count, double* __restrict__ out) {
-    const double s = sumPartials(partial, count);
-    if (threadIdx.x == 0) *out = s;
 }
 // ---- Chebyshev-Jacobi polynomial preconditioner (PS_PRE_CHEBYSHEV) -------------------------------------------------
 // first term: z_1 = dinv r / theta ; partial of r.z (used when the polynomial has this one term only)
@@ -645,75 +605,6 @@ __global__ void __launch_bounds__(BS) k_cheb_step(const CGScalars* __restrict__ 
     const double s = blockReduceSum(acc);
     if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
-// beta = r.z / rsold ; x += alpha p ; p = z + beta p with z a VECTOR (polynomial preconditioner) ; partials of x.x
-// UPP: also the partials of sum uInv p^2 of the new p (four-kernel step, see cgUpdateXp)
-// TZ: element type of z (float: the single-precision Chebyshev polynomial)
-__device__ inline double2 ldZ2(const double* z, int64_t i2, bool nt) { return ldD2((const double2*)z + i2, nt); }
-__device__ inline double2 ldZ2(const float* z, int64_t i2, bool nt) {
-    typedef float psf2z __attribute__((ext_vector_type(2)));
-    const psf2z* q = reinterpret_cast<const psf2z*>(z) + i2;
-    const psf2z v = nt ? __builtin_nontemporal_load(q) : *q;
-    return make_double2((double)v.x, (double)v.y);
-}
-template <bool UPP, class TZ>
-__device__ inline void cgUpdateXpZ(CGScalars* sc, const double* __restrict__ rrPartial, int rrCount, const double* __restrict__ rzPartial,
-                                   int rzCount, int it, const TZ* __restrict__ z, double* __restrict__ x, double* __restrict__ p,
-                                   int64_t n, double* __restrict__ partial,
-                                   const uint8_t* __restrict__ uCode, const double* __restrict__ uDict, const double* __restrict__ uInv, double* __restrict__ uPart) {
-    if (sc->done) return;
-    __shared__ double dict[UPP ? 256 : 1];
-    if (UPP && uCode) dict[threadIdx.x] = uDict[threadIdx.x];   // visible after the barriers of blockSumAll below
-    const double rr = blockSumAll(sumLocal(rrPartial, rrCount));
-    const double rz = blockSumAll(sumLocal(rzPartial, rzCount));
-    const double alpha = sc->alpha, beta = rz / sc->rsold2[it & 1];      // pcg.h:331-335
-    const bool nt = sc->vecNT != 0;
-    if (blockIdx.x == 0 && threadIdx.x == 0) { sc->rr = rr; sc->rz = rz; sc->beta = beta; sc->rsold2[(it + 1) & 1] = rz; sc->rsold = rz; }
-    double axx = 0., aup = 0.;
-    const bool vec = ((((uintptr_t)p | (uintptr_t)z | (uintptr_t)x) & 15) == 0) && (!UPP || ((((uintptr_t)uCode & 1) == 0) && (((uintptr_t)uInv & 15) == 0)));
-    const int64_t n2 = vec ? n / 2 : 0;
-    double2* p2 = (double2*)p; double2* x2 = (double2*)x;
-    for (int64_t i = (int64_t)blockIdx.x * BS + threadIdx.x; i < n2; i += (int64_t)gridDim.x * BS) {
-        const double2 zv = ldZ2(z, i, nt);
-        double2 pv = ldD2(p2 + i, nt && PS_VEC_NT_PL), xv = ldD2(x2 + i, nt && PS_VEC_NT_X);
-        xv.x = xv.x + alpha * pv.x; xv.y = xv.y + alpha * pv.y;
-        pv.x = zv.x + beta * pv.x; pv.y = zv.y + beta * pv.y;
-        stD2(x2 + i, xv, nt && PS_VEC_NT_X); stD2(p2 + i, pv, nt && PS_VEC_NT_P);
-        axx += xv.x * xv.x; axx += xv.y * xv.y;
-        if (UPP) {
-            double u0, u1;
-            if (uCode) { const uint16_t cc = (nt && PS_VEC_NT_U) ? __builtin_nontemporal_load((const uint16_t*)uCode + i) : ((const uint16_t*)uCode)[i]; u0 = dict[cc & 255]; u1 = dict[cc >> 8]; }
-            else { const double2 uv = ldD2((const double2*)uInv + i, nt); u0 = uv.x; u1 = uv.y; }
-            aup += u0 * (pv.x * pv.x); aup += u1 * (pv.y * pv.y);
-        }
-    }
-    for (int64_t i = 2 * n2 + (int64_t)blockIdx.x * BS + threadIdx.x; i < n; i += (int64_t)gridDim.x * BS) {
-        const double pv = p[i];
-        const double xv = x[i] + alpha * pv;
-        const double pn = (double)z[i] + beta * pv;
-        x[i] = xv; p[i] = pn;
-        axx += xv * xv;
-        if (UPP) aup += (uCode ? dict[uCode[i]] : uInv[i]) * (pn * pn);
-    }
-    const double s1 = blockReduceSum(axx);
-    if (threadIdx.x == 0) partial[blockIdx.x] = s1;
-    if (UPP) {
-        const double s2 = blockReduceSum(aup);
-        if (threadIdx.x == 0) uPart[blockIdx.x] = s2;
-    }
-}
-template <class TZ>
-__global__ void __launch_bounds__(BS) k_cg_update_xp_z(CGScalars* sc, const double* __restrict__ rrPartial, int rrCount, const double* __restrict__ rzPartial,
-                                                       int rzCount, int it, const TZ* __restrict__ z, double* __restrict__ x, double* __restrict__ p,
-                                                       int64_t n, double* __restrict__ partial) {
-    cgUpdateXpZ<false, TZ>(sc, rrPartial, rrCount, rzPartial, rzCount, it, z, x, p, n, partial, nullptr, nullptr, nullptr, nullptr);
-}
-template <class TZ>
-__global__ void __launch_bounds__(BS) k_cg_update_xp_z_u(CGScalars* sc, const double* __restrict__ rrPartial, int rrCount, const double* __restrict__ rzPartial,
-                                                         int rzCount, int it, const TZ* __restrict__ z, double* __restrict__ x, double* __restrict__ p,
-                                                         int64_t n, double* __restrict__ partial,
-                                                         const uint8_t* __restrict__ uCode, const double* __restrict__ uDict, const double* __restrict__ uInv, double* __restrict__ uPart) {
-    cgUpdateXpZ<true, TZ>(sc, rrPartial, rrCount, rzPartial, rzCount, it, z, x, p, n, partial, uCode, uDict, uInv, uPart);
-}
 // one step of the power iteration on D^-1 A (ps_context::estimateLambdaMax): w = dinv .* Av ; partials of v.v and v.w
 __global__ void __launch_bounds__(BS) k_power_step(const double* __restrict__ v, const double* __restrict__ Av, const double* __restrict__ dinv,
                                                    double* __restrict__ w, int64_t n, double* __restrict__ partial) {
@@ -731,18 +622,6 @@ __global__ void k_widen_f32(double* __restrict__ out, const float* __restrict__ 
 }
 __global__ void k_fill_f64(double* __restrict__ a, double v, int64_t n) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) a[i] = v;
-}
-// out[0] = sum of partial[0..count)   (one block, fixed order)
-__global__ void __launch_bounds__(BS) k_sum_to(const double* __restrict__ partial, int count, double* __restrict__ out) {
-    const double s = sumPartials(partial, count);
-    if (threadIdx.x == 0) out[0] = s;
-}
-// out = a .* b
-__global__ void k_mul_diag(double* __restrict__ out, const diag_t* __restrict__ d, const double* __restrict__ b, int64_t n) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) out[i] = diagValue(d[i]) * b[i];
-}
-__global__ void k_mulv(double* __restrict__ out, const double* __restrict__ a, const double* __restrict__ b, int64_t n) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) out[i] = a[i] * b[i];
 }
 // constructGuessVectors (Solver.cpp:528-529): g holds -(S^T t) in the internal numbering; pressure entries stay, stress entries
 // become -2 uInv g.  Indexed by REFERENCE index (pressures first) through permSys: every internal index is visited once.

@@ -17,11 +17,12 @@
 //                          fusedRowFinish, and RowDiag (a diagonal as 1-byte codes into an LDS table or as the fp64 array).
 //   ps_kernels_tiles.hpp : k_tile_gather / k_tile_solve / k_tile_expand — per-tile J^T, 26x26 BInv, J.
 //   ps_kernels_cg.hpp    : k_cg_update_r / k_cg_update_xp (the PCG step of pcg_external_matrix_A, lib/include/pcg.h:268-340,
-//                          with the scalar reductions and the stop rule folded in; scalars stay on the device), the legacy
-//                          k_cg_update_xr / _p / scal* used by the exported-system path, BiCGStab helpers, Jacobi diagonal,
-//                          velocity recovery / write-back.  The step kernels' bodies take the element type of the Krylov vectors: their _f32 forms
-//                          and k_cg_init_pass / k_cg_scal0_pass / k_cg_check_pass / k_cg_end_pass run the passes of the mixed-precision solve
-//                          (ps_set_solve_precision: fp32 d, p, r, A p, t around the fp64 x; ps_context::solve).
+//                          with the scalar reductions and the stop rule folded in; scalars stay on the device), BiCGStab helpers, Jacobi
+//                          diagonal, velocity recovery / write-back.  One body each — cgInit, cgUpdateR, cgUpdateXp (z from ZJacobi or ZVector;
+//                          prologue sums as TwoSums, the stress diagonal as StressDiag) — takes the element type of the Krylov vectors and of the
+//                          diagonal: the _f32 forms and k_cg_init_pass / k_cg_scal0_pass / k_cg_check_pass / k_cg_end_pass run the passes of the
+//                          mixed-precision solve (ps_set_solve_precision: fp32 d, p, r, A p, t around the fp64 x; ps_context::solve), the _d64
+//                          forms the exported system's step on its fp64 diagonal (ps_import.hpp).
 //   this file            : the launch dispatch (Launch: planS / planSt choose the kernel and grid of a product, one launcher per kernel family runs it),
 //                          ps_context::applyOperator / assemble / solve / recover.  The solve runs in stages (DomainSolve, as Dist's in ps_dist.hpp):
 //                          solveStart, chooseStepForm, fusedStart, [mixedPasses: passStart + batches of the fp32 steps], pcgStart, batches of
@@ -480,11 +481,15 @@ const double* reducedPartials(ps_context* c, const CGScalars* sc, const double* 
     cnt = count > 8192 ? RED_BLOCKS : count;
     return count > 8192 ? red : src;
 }
+// A launch of BS-thread workgroups on the context's stream (DomainSolve::run and Dist), and the stress diagonal of the DOFs from `lo` on as the
+// x, p update and k_uinv_pp take it
+template <class K, class... A> void runOn(const ps_context* c, K kernel, int grid, A... a) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(BS), 0, c->stream, a...); }
+StressDiag stressDiag(const ps_context* c, int64_t lo) { return {c->uCoded ? c->uCode.p + lo : nullptr, c->uDict.p, c->uInv.p + lo}; }
 // a . b over n DOFs on the host: one scalar read-back per product (the BiCGStab fallback, Eigen's CG)
 double hostDot(ps_context* c, const double* a, const double* b, int64_t n) {
     double out, *sum = c->dotPartials.p + 3 * VGRID;
     hipLaunchKernelGGL(k_dot, dim3(dotBlocks(n)), dim3(BS), 0, c->stream, a, b, n, c->dotPartials.p);
-    hipLaunchKernelGGL(k_sum1, dim3(1), dim3(BS), 0, c->stream, c->dotPartials.p, dotBlocks(n), sum);
+    hipLaunchKernelGGL(k_sumq, dim3(1), dim3(BS), 0, c->stream, (const CGScalars*)nullptr, c->dotPartials.p, dotBlocks(n), 0, 1, sum);
     HIP_CHECK(hipMemcpyAsync(&out, sum, sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_CHECK(hipStreamSynchronize(c->stream));
     return out;
@@ -628,7 +633,7 @@ void ps_context::assembleSystemPressureStressFactored() {
     dotPartialsR.alloc(2 * VGRID);
     // t0 = McInv rhs_a on active rows, C (invDt BInv rhs_r) on reduced rows;  b = -S^T t0 + [rhs_p; rhs_tau]
     if (nActiveVs > 0)
-        hipLaunchKernelGGL(k_scale_rows, dim3(dotBlocks(nActiveVs)), dim3(BS), 0, stream, ts.p, McInv.p, rhsA.p, nActiveVs);
+        hipLaunchKernelGGL(k_mul<double>, dim3(dotBlocks(nActiveVs)), dim3(BS), 0, stream, ts.p, McInv.p, rhsA.p, nActiveVs);
     Launch L = mk(this, nullptr);
     L.tiles(2, ts.p);
     L.spmvSt(1, ts.p, nullptr, rhsPT.p, b.p, nullptr);
@@ -688,8 +693,8 @@ void ps_context::estimateLambdaMax() {
         hipLaunchKernelGGL(k_power_step, dim3(vb), dim3(BS), 0, stream, (const double*)v, (const double*)Av, (const double*)dinv.p, w, n, chebPartials.p);
         std::swap(v, w);
     }, [&](double* h) {
-        hipLaunchKernelGGL(k_sum1, dim3(1), dim3(BS), 0, stream, chebPartials.p, vb, chebPartials.p + 2 * vb);
-        hipLaunchKernelGGL(k_sum1, dim3(1), dim3(BS), 0, stream, chebPartials.p + vb, vb, chebPartials.p + 2 * vb + 1);
+        hipLaunchKernelGGL(k_sumq, dim3(1), dim3(BS), 0, stream, (const CGScalars*)nullptr, (const double*)chebPartials.p, vb, 0, 1, chebPartials.p + 2 * vb);
+        hipLaunchKernelGGL(k_sumq, dim3(1), dim3(BS), 0, stream, (const CGScalars*)nullptr, (const double*)chebPartials.p + vb, vb, 0, 1, chebPartials.p + 2 * vb + 1);
         HIP_CHECK(hipMemcpyAsync(h, chebPartials.p + 2 * vb, 2 * sizeof(double), hipMemcpyDeviceToHost, stream));
         HIP_CHECK(hipStreamSynchronize(stream));
     });
@@ -763,7 +768,7 @@ void ps_context::applyPreconditionerDevice(const double* rvec, double* z, double
             HIP_CHECK(hipMemcpyAsync(z, tmp5.p, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, stream));
         } else zToF64(this, z, zfin, n);
     } else if (P.preconditioner == PS_PRE_DIAGONAL) {
-        hipLaunchKernelGGL(k_mul_diag, dim3(vb), dim3(BS), 0, stream, z, (const diag_t*)dinvF.p, rvec, n);   // the diagonal as the PCG kernels read it
+        hipLaunchKernelGGL(k_mul<diag_t>, dim3(vb), dim3(BS), 0, stream, z, (const diag_t*)dinvF.p, rvec, n);   // the diagonal as the PCG kernels read it
     } else {
         HIP_CHECK(hipMemcpyAsync(z, rvec, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, stream));
     }
@@ -786,7 +791,7 @@ struct DomainSolve {
     ps_context* c = nullptr;
     int64_t n = 0; double tol = 0.; int maxit = 0;
     int vb = 0, stBlocks = 0, stBF = 0, sBlocks = 0;              // workgroups: the vector kernels, St plain / with the residual update, S (four-kernel step)
-    const diag_t* dv = nullptr; const uint8_t* ucode = nullptr;   // Jacobi: the stored diagonal; the stress diagonal's codes
+    const diag_t* dv = nullptr; StressDiag ud{};                  // Jacobi: the stored diagonal; the stress diagonal, coded or fp64
     CGScalars *sc = nullptr, h{};                                 // the scalars on the device, and as last read back
     Launch L;
     bool cheb = false, fused = false, recording = false;
@@ -794,7 +799,7 @@ struct DomainSolve {
     double *zvec = nullptr, *dvec = nullptr, *rzPart = nullptr;   // the polynomial's two buffers and the r.z partials of its last term
     int itBase = 0;                                               // iterations the fp32 passes took: the fp64 loop gets the rest of the budget
     ~DomainSolve() { if (recording) c->walkRecord = false; }
-    template <class K, class... A> void run(K kernel, int grid, A... a) const { hipLaunchKernelGGL(kernel, dim3(grid), dim3(BS), 0, c->stream, a...); }
+    template <class K, class... A> void run(K kernel, int grid, A... a) const { runOn(c, kernel, grid, a...); }
 
     // Resets; false: there is nothing to iterate and rc is the solve's result (Eigen's CG ran, an unsupported solver, an empty system).
     // Otherwise the walks are being recorded, the launch dispatch stands and the polynomial has its buffers.
@@ -808,7 +813,7 @@ struct DomainSolve {
         c->walkRecord = recording = true;
         cheb = c->P.preconditioner == PS_PRE_CHEBYSHEV;
         dv = (c->P.preconditioner == PS_PRE_DIAGONAL) ? c->dinvF.p : nullptr;
-        vb = dotBlocks(n); sc = c->scal.p; ucode = c->uCoded ? c->uCode.p : nullptr;
+        vb = dotBlocks(n); sc = c->scal.p; ud = stressDiag(c, 0);
         L = mk(c, &sc->done);
         stBlocks = L.stBlocks(0); stBF = L.stBlocks(3);
         L.cz32 = c->chebInner32 = cheb && c->chebInner32Req && L.cheb32Ok();     // PS_PRE_CHEBYSHEV_F32 where the two-unit kernels run; fp64 inner vectors otherwise
@@ -846,14 +851,15 @@ struct DomainSolve {
             double* z0 = zvec;
             const int zCount = c->chebyshevApply(c->r.p, zvec, dvec, rzPart, nullptr, false, &z0);
             zToF64(c, c->pvec.p, z0, n);
-            run(k_sum_to, 1, rzPart, zCount, c->dotPartials.p);
+            run(k_sumq, 1, nullptr, rzPart, zCount, 0, 1, c->dotPartials.p);
         }
         run(k_cg_scal0, 1, sc, c->dotPartials.p, cheb ? 1 : vb, tol, maxit, c->ntLevel() >= 2 ? 1 : 0);
-        if (fused) run(k_uinv_pp, vb, c->pvec.p, ucode, c->uDict.p, c->uInv.p, n, fU);
+        if (fused) run(k_uinv_pp, vb, c->pvec.p, ud, n, fU);
     }
 
     // ---- the steps.  (r of either element type goes through FusedR's double*.)
     StepVecs<double> v64() const { return {c->x.p, c->pvec.p, c->r.p, c->Ap.p, c->ts.p}; }
+    TwoSums rrRz(const double* part, int cnt) const { return TwoSums::partials(part, cnt, dv ? part + cnt : nullptr, cnt); }   // a residual update's partials: r.r, then r.z (Jacobi)
     FusedR fusedArgs(int it, void* r, const FusedZ& z) const {
         return fusedSingle(sc, {fS, sBlocks, fT, (int)c->regionCount, fU, vb, c->dotPartials3.p, vb}, it, (double*)r, fR, (int)n, z);
     }
@@ -867,7 +873,7 @@ struct DomainSolve {
         const FusedR fr = fusedArgs(it, v.r, FusedZ::jacobi(dv));
         if constexpr (std::is_same<T, float>::value) L.spmvSt32(false, v.ts, v.p, fr);
         else L.spmvSt(3, v.ts, v.p, nullptr, nullptr, nullptr, nullptr, &fr);
-        run(StepKernels<T>::updateXpU, vb, sc, nullptr, fR, stBF, dv ? 1 : 0, it, v.r, dv, v.x, v.p, n, c->dotPartials3.p, ucode, c->uDict.p, c->uInv.p, fU);
+        run(StepKernels<T>::updateXpU, vb, sc, rrRz(fR, stBF), it, v.r, dv, v.x, v.p, n, c->dotPartials3.p, ud, fU);
     }
     // ... with the polynomial: the St kernel also forms its first term on the new r; then terms 2..k; then x, p
     void fourKernelChebStep(int it) {
@@ -881,7 +887,7 @@ struct DomainSolve {
         if (zCount > 0) part = reducedPartials(c, sc, rzPart, zCount, c->chebPartials2.p, cnt);
         withZ(c->chebInner32, [&](auto TZ) {
             using Z = typename decltype(TZ)::type;
-            run(k_cg_update_xp_z_u<Z>, vb, sc, fR, stBF, part, cnt, it, (const Z*)zfin, v.x, v.p, n, c->dotPartials3.p, ucode, c->uDict.p, c->uInv.p, fU);
+            run(k_cg_update_xp_z_u<Z>, vb, sc, TwoSums::partials(fR, stBF, part, cnt), it, (const Z*)zfin, v.x, v.p, n, c->dotPartials3.p, ud, fU);
         });
     }
     // The first four kernels of the five-kernel step: A p (S, tiles, St with the partials of p.Ap), then r -= alpha A p
@@ -894,11 +900,11 @@ struct DomainSolve {
         } else
             L.spmvSt(0, v.ts, v.p, nullptr, v.Ap, c->dotPartials.p);
         const double* part = reducedPartials(c, sc, c->dotPartials.p, cnt, c->dotPartials2.p, cnt);   // (the one-shot St kernel: a partial per 256 rows)
-        run(StepKernels<T>::updateR, vb, sc, nullptr, part, cnt, c->dotPartials3.p, vb, it, v.Ap, dv, v.r, n, c->dotPartialsR.p);
+        run(StepKernels<T>::updateR, vb, sc, TwoSums::partials(part, cnt, c->dotPartials3.p, vb), it, v.Ap, dv, v.r, n, c->dotPartialsR.p);
     }
     template <class T> auto fiveKernelStep(int it, const StepVecs<T>& v) const {
         residualUpdate(it, v);
-        run(StepKernels<T>::updateXp, vb, sc, nullptr, c->dotPartialsR.p, vb, dv ? 1 : 0, it, v.r, dv, v.x, v.p, n, c->dotPartials3.p);
+        run(StepKernels<T>::updateXp, vb, sc, rrRz(c->dotPartialsR.p, vb), it, v.r, dv, v.x, v.p, n, c->dotPartials3.p);
     }
     void fiveKernelChebStep(int it) {   // ... with the polynomial: z = M^-1 r between the residual update and x, p
         const StepVecs<double> v = v64();
@@ -909,7 +915,7 @@ struct DomainSolve {
         const double* part = reducedPartials(c, sc, rzPart, zCount, c->chebPartials2.p, cnt);
         withZ(c->chebInner32, [&](auto TZ) {
             using Z = typename decltype(TZ)::type;
-            run(k_cg_update_xp_z<Z>, vb, sc, c->dotPartialsR.p, vb, part, cnt, it, (const Z*)zfin, v.x, v.p, n, c->dotPartials3.p);
+            run(k_cg_update_xp_z<Z>, vb, sc, TwoSums::partials(c->dotPartialsR.p, vb, part, cnt), it, (const Z*)zfin, v.x, v.p, n, c->dotPartials3.p);
         });
     }
     void step(int it) {   // one fp64 iteration
@@ -927,7 +933,7 @@ struct DomainSolve {
         if (haveX) c->applyOperator(c->x.p, c->Ap.p, c->dotPartials.p);
         run(k_cg_init_pass, vb, c->b.p, haveX ? c->Ap.p : nullptr, c->x.p, dv, c->d32.p, c->r32.p, c->p32.p, n, c->dotPartials.p);
         run(k_cg_scal0_pass, 1, sc, c->dotPartials.p, vb, tol, maxit, c->ntLevel() >= 2 ? 1 : 0, MIXED_PASS_REDUCTION * MIXED_PASS_REDUCTION, haveX ? 1 : 0);
-        if (fused) run(k_uinv_pp_f32, vb, c->p32.p, ucode, c->uDict.p, c->uInv.p, n, fU);
+        if (fused) run(k_uinv_pp_f32, vb, c->p32.p, ud, n, fU);
         HIP_CHECK(hipMemcpyAsync(&h, sc, sizeof(h), hipMemcpyDeviceToHost, c->stream));
         HIP_CHECK(hipStreamSynchronize(c->stream));
     }
@@ -1116,7 +1122,7 @@ int ps_context::solveEigenCG() {
     double residualNorm2 = dotH(r.p, r.p);
     int i = 0;
     if (residualNorm2 >= threshold) {
-        hipLaunchKernelGGL(k_mulv, dim3(vb), dim3(BS), 0, stream, pvec.p, dinv.p, r.p, n);   // p = precond.solve(residual)
+        hipLaunchKernelGGL(k_mul<double>, dim3(vb), dim3(BS), 0, stream, pvec.p, dinv.p, r.p, n);   // p = precond.solve(residual)
         double absNew = dotH(r.p, pvec.p);
         while (i < maxit) {
             applyOperator(pvec.p, Ap.p, dotPartials.p);
@@ -1125,7 +1131,7 @@ int ps_context::solveEigenCG() {
             lin(r.p, 1., r.p, -alpha, Ap.p);
             residualNorm2 = dotH(r.p, r.p);
             if (residualNorm2 < threshold) break;
-            hipLaunchKernelGGL(k_mulv, dim3(vb), dim3(BS), 0, stream, z, dinv.p, r.p, n);
+            hipLaunchKernelGGL(k_mul<double>, dim3(vb), dim3(BS), 0, stream, z, dinv.p, r.p, n);
             const double absOld = absNew;
             absNew = dotH(r.p, z);
             const double beta = absNew / absOld;
@@ -1182,7 +1188,7 @@ void ps_bench_launch(ps_context* c, const std::string& k, const double* x, doubl
     else if (base == "spmv_St") L.spmvSt(0, c->ts.p, x, nullptr, y, c->dotPartials.p);
     else if (base == "apply") c->applyOperator(x, y, c->dotPartials.p);
     else if (base == "tiles") L.tiles(0, c->ts.p);
-    else if (base == "cg_update_xr" || base == "cg_update_p" || base == "cg_update_r" || base == "cg_update_xp" || base == "cg_update_xp_u" || base == "spmv_St_r") {
+    else if (base == "cg_update_r" || base == "cg_update_xp" || base == "cg_update_xp_u" || base == "spmv_St_r") {
         // streaming vector kernels on scratch vectors (alpha = beta = 0 keeps them finite over many launches)
         ps::DevBuf<CGScalars>& scratch = c->benchScal;
         scratch.alloc(1);
@@ -1202,29 +1208,21 @@ void ps_bench_launch(ps_context* c, const std::string& k, const double* x, doubl
         if (zeros.n < (size_t)2 * VGRID) { zeros.alloc((size_t)2 * VGRID); HIP_CHECK(hipMemsetAsync(zeros.p, 0, (size_t)2 * VGRID * 8, c->stream)); }
         const int64_t n = c->nSystem;
         const int vb = dotBlocks(n);
-        const double* dv = c->P.preconditioner == PS_PRE_DIAGONAL ? c->dinv.p : nullptr;
         const diag_t* dvf = c->P.preconditioner == PS_PRE_DIAGONAL ? c->dinvF.p : nullptr;
         c->tmp4.alloc((size_t)n); c->tmp5.alloc((size_t)n);
         c->dotPartials.alloc((size_t)std::max(3 * std::max(vb, VGRID), 2 * L.stBlocks()) + 16);
-        const uint8_t* ucode = c->uCoded ? c->uCode.p : nullptr;
+        const TwoSums rrRz = TwoSums::partials(zeros.p, VGRID, dvf ? zeros.p + VGRID : nullptr, VGRID);
         if (base == "spmv_St_r") {   // the St kernel of the four-kernel step: r (scratch) -= 0 * A x in the epilogue
             if (!L.fusedOk()) throw Error("no fused step on this system");
             const FusedR fr = fusedSingle(scratch.p, {ones.p, VGRID, zeros.p, 0, zeros.p, 0, ones.p, 0}, 0, c->tmp5.p, c->dotPartials.p, (int)n, FusedZ::jacobi(dvf));
             L.spmvSt(3, c->ts.p, x, nullptr, nullptr, nullptr, nullptr, &fr);
         }
         else if (base == "cg_update_xp_u")
-            hipLaunchKernelGGL(k_cg_update_xp_u, dim3(vb), dim3(BS), 0, c->stream, scratch.p, (const double*)nullptr, (const double*)zeros.p, VGRID, dvf ? 1 : 0, 0, x, dvf,
-                               c->tmp4.p, c->tmp5.p, n, c->dotPartials.p, ucode, (const double*)c->uDict.p, (const double*)c->uInv.p, c->dotPartials.p + VGRID);
-        else if (base == "cg_update_xr")
-            hipLaunchKernelGGL(k_cg_update_xr, dim3(vb), dim3(BS), 0, c->stream, scratch.p, x, y, dv, c->tmp4.p, c->tmp5.p, n, c->dotPartials.p);
-        else if (base == "cg_update_p")
-            hipLaunchKernelGGL(k_cg_update_p, dim3(vb), dim3(BS), 0, c->stream, scratch.p, x, dv, c->tmp4.p, n);
+            runOn(c, k_cg_update_xp_u, vb, scratch.p, rrRz, 0, x, dvf, c->tmp4.p, c->tmp5.p, n, c->dotPartials.p, stressDiag(c, 0), c->dotPartials.p + VGRID);
         else if (base == "cg_update_r")
-            hipLaunchKernelGGL(k_cg_update_r, dim3(vb), dim3(BS), 0, c->stream, scratch.p, (const double*)nullptr, ones.p, VGRID, ones.p, 0, 0, y, dvf,
-                               c->tmp5.p, n, c->dotPartials.p);
+            runOn(c, k_cg_update_r, vb, scratch.p, TwoSums::partials(ones.p, VGRID, ones.p, 0), 0, y, dvf, c->tmp5.p, n, c->dotPartials.p);
         else
-            hipLaunchKernelGGL(k_cg_update_xp, dim3(vb), dim3(BS), 0, c->stream, scratch.p, (const double*)nullptr, zeros.p, VGRID, dvf ? 1 : 0, 0, x, dvf,
-                               c->tmp4.p, c->tmp5.p, n, c->dotPartials.p);
+            runOn(c, k_cg_update_xp, vb, scratch.p, rrRz, 0, x, dvf, c->tmp4.p, c->tmp5.p, n, c->dotPartials.p);
     }
     else throw Error("unknown kernel name: " + k);
 }

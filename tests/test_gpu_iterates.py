@@ -35,6 +35,11 @@ SCENES = {
     "cavity48": lambda: scenes.cavity(48, tile=8),
     "coil48": lambda: scenes.coil(48, tile=8),
     "spheres48": lambda: scenes.spheres(48, tile=8),
+    # the vector kernels' scalar tails (test_gpu_vector_tails.py): nSystem % 4 = 1, 2, 3 (viscosity fields: the fp64 stress diagonal) and 1 (the coded one)
+    "tail1": lambda: scenes.blob(20, 18, 22, seed=4, tile=8),
+    "tail2": lambda: scenes.blob(20, 18, 22, seed=1, tile=8),
+    "tail3": lambda: scenes.blob(20, 18, 22, seed=2, tile=8),
+    "tail1c": lambda: scenes.coil(30, tile=8),
 }
 PRECONDS = {"identity": (abi.PRE_IDENTITY, 0), "jacobi": (abi.PRE_DIAGONAL, 0), "cheb1": (abi.PRE_CHEBYSHEV, 1), "cheb2": (abi.PRE_CHEBYSHEV, 2),
             "cheb4": (abi.PRE_CHEBYSHEV, 4), "cheb10": (abi.PRE_CHEBYSHEV, 10), "cheb32": (abi.PRE_CHEBYSHEV_F32, 4)}

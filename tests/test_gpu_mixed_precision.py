@@ -42,8 +42,8 @@ def gpu():
     s.close()
 
 
-def _case(scene, pre, tol):
-    sc, p = SCENES[scene]() if isinstance(scene, str) else scene
+def _case(scene, pre, tol, make=None):
+    sc, p = make() if make else SCENES[scene]() if isinstance(scene, str) else scene
     p.preconditioner = PRECONDS[pre] if isinstance(pre, str) else pre
     p.tolerance = tol
     p.maxSolverIterations = MAXIT
@@ -93,10 +93,10 @@ def check_mixed_solve(s, p, it64, label=""):
 _xstar = {}
 
 
-def xstar(s, scene, pre):
+def xstar(s, scene, pre, make=None):
     """the mode-0 solve at tol 1e-12, once per system"""
     if (scene, pre) not in _xstar:
-        sc, p = _case(scene, pre, 1e-12)
+        sc, p = _case(scene, pre, 1e-12, make)
         assert _solve(s, sc, p, FP64) == abi.SUCCESS
         _xstar[(scene, pre)] = s.array("solutionVector").copy()
     return _xstar[(scene, pre)]
@@ -106,8 +106,13 @@ def xstar(s, scene, pre):
 @pytest.mark.parametrize("pre", list(PRECONDS))
 @pytest.mark.parametrize("scene", list(SCENES))
 def test_mixed_solve_meets_the_rule_and_the_caps(gpu, scene, pre, tol):
-    xs = xstar(gpu, scene, pre)
-    sc, p = _case(scene, pre, tol)
+    mixed_solve_meets_the_rule_and_the_caps(gpu, scene, pre, tol)
+
+
+def mixed_solve_meets_the_rule_and_the_caps(gpu, scene, pre, tol, make=None):
+    """scene: a name in SCENES, or any name with `make`, the function that builds (scene, params) (test_gpu_vector_tails.py)"""
+    xs = xstar(gpu, scene, pre, make)
+    sc, p = _case(scene, pre, tol, make)
     assert _solve(gpu, sc, p, FP64) == abi.SUCCESS
     assert _used(gpu) == 0
     with pytest.raises(KeyError):

@@ -57,8 +57,15 @@ def test_group_matches_single_domain(case):
     else:
         (sc, p), world = _tall_cavity(24, 64, tile=8), 4
     single = polystokes_amd.Solver(0)
-    rc1 = single.step(sc, p)
     grp = polystokes_amd.Group(world)
+    slabs_match_single_domain(single, grp, sc, p, case)
+    grp.close()
+    single.close()
+
+
+def slabs_match_single_domain(single, grp, sc, p, case):
+    """one step of `sc` on the single domain and on the z-slab group: results, iteration counts, owned labels, valid faces, merged velocities"""
+    rc1 = single.step(sc, p)
     rc2 = grp.solve_scene(sc, p)
     assert rc1 == rc2 == abi.SUCCESS
     it1, it2 = single.stats.solveData[1], grp.stats.solveData[1]
@@ -72,8 +79,6 @@ def test_group_matches_single_domain(case):
         assert np.array_equal(grp.valid[a], single.valid[a]), case
         scale = max(np.abs(single.vel[a]).max(), 1e-30)
         assert np.abs(grp.vel[a] - single.vel[a]).max() <= 20 * p.tolerance * scale, case
-    grp.close()
-    single.close()
 
 
 @pytest.mark.parametrize("case", ["cavity128_2x2x2_jacobi", "cavity64_2x2x2", "cavity64_2x1x2_jacobi", "cavity_1x2x1", "spheres64_2x2x2_jacobi", "coil64_2x2x1", "cavity48_tile8_3x2x2_chebyshev"])

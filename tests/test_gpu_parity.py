@@ -585,8 +585,44 @@ def test_exported_system_import_and_solve(gpu, tmp_path, precond):
     """ps_solve_exported_system: read back the .mtx component set (the reference's exportComponentMatrices file set,
     Solver.cpp:543-566) and run the same PCG on it with general CSR SpMVs.  Must agree with the in-memory solve: same
     iteration count (the operator is the same up to summation order) and the same solution."""
-    import scipy.io
+    _import_and_solve(gpu, tmp_path, precond, 9)
+
+
+@pytest.mark.parametrize("precond", [abi.PRE_IDENTITY, abi.PRE_DIAGONAL])
+def test_exported_system_import_and_solve_odd_size(gpu, tmp_path, precond):
+    """the same on a system with an odd number of DOFs (seed 4: 9169): the step kernels' 16-byte loop ends one DOF short and the scalar tail
+    takes it, with the fp64 diagonal too"""
+    from oracle import ps_oracle
+    o = ps_oracle.Oracle()
+    o.run(*scenes.blob(20, 18, 22, seed=4, tile=8), solve=False)
+    assert int(o.stats.dimData[21]) % 2 == 1
+    assert _import_and_solve(gpu, tmp_path, precond, 4) == int(o.stats.dimData[21])
+
+
+def test_exported_system_solve_can_be_interrupted(gpu, tmp_path):
+    """the import runs the product's batch driver: the interrupt callback is polled at a batch end (25 iterations), the solve reports
+    INCOMPLETE with the iterations done, and the same call succeeds once the callback is cleared"""
     sc, p = scenes.blob(20, 18, 22, seed=9, tile=8)
+    p.tolerance = 1e-8
+    p.maxSolverIterations = 20000
+    assert gpu.step(sc, p) == abi.SUCCESS
+    pre = str(tmp_path) + "/sys."
+    gpu.export_component_matrices(pre)
+    n = int(gpu.stats.dimData[21])
+    calls = []
+    gpu.set_interrupt(lambda: calls.append(1) or True)
+    try:
+        rc, _ = gpu.solve_exported_system(pre, p, sc.dt, n)
+    finally:
+        gpu.set_interrupt(None)
+    assert rc == abi.INCOMPLETE and len(calls) == 1 and int(gpu.stats.solveData[1]) == 25
+    rc, x = gpu.solve_exported_system(pre, p, sc.dt, n)
+    assert rc == abi.SUCCESS and int(gpu.stats.solveData[1]) > 25
+
+
+def _import_and_solve(gpu, tmp_path, precond, seed):
+    import scipy.io
+    sc, p = scenes.blob(20, 18, 22, seed=seed, tile=8)
     p.tolerance = 1e-8
     p.maxSolverIterations = 20000
     p.preconditioner = precond
@@ -602,6 +638,7 @@ def test_exported_system_import_and_solve(gpu, tmp_path, precond):
     assert abs(gpu.stats.solveData[1] - its) <= 2
     assert int(gpu.stats.dimData[21]) == n and int(gpu.stats.dimData[24]) > 0
     assert np.linalg.norm(x - x_mem) <= 1e-6 * np.linalg.norm(x_mem)
+    return n
 
 
 def test_exported_system_import_errors(gpu, tmp_path):
