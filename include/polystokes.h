@@ -445,6 +445,56 @@ int32_t ps_set_collider_loads(ps_context* ctx, const ps_collider_loads* loads);
 int32_t ps_upload_collider_ids(ps_context* ctx, const int32_t* ids);      /* cell field nx*ny*nz, x-fastest; NULL drops it */
 int32_t ps_get_collider_loads(ps_context* ctx, double* out, int64_t out_len);
 
+/* Air pockets (extension; the free-surface fields above take the air-side pressure P_c from the caller, and a device-resident caller has
+ * nothing that finds trapped air): the connected air regions of the uploaded grid, their volumes and whether they reach the grid's border,
+ * and a pressure per pocket painted into the pressure member of the free-surface fields.  The gas law and the tracking of a pocket from
+ * step to step stay with the caller (isothermal or adiabatic, what happens on a merge): with the ids, volumes and open flags of this step
+ * and the id grid of the last one they are a few lines of the caller's own code.
+ * Call order and lifetime.  ps_label_air_pockets follows ps_upload_fields / ps_upload_fields_device of a single domain; the result belongs to
+ * that upload's grid, like the density field and the collider ids: every field upload drops it, ps_set_slab / ps_set_brick drop it too, a
+ * setup, solve or step (the Picard passes of ps_set_rheology included) keeps it.  Before any upload the call returns PS_INVALID; on a context
+ * that has a slab or brick or belongs to a ps_group it returns PS_FAILED, "air pockets need a single domain".  The three getters and the
+ * pressure call return PS_FAILED with a reason when there are no labels.  polystokes_step and ps_step_device_fields upload and therefore
+ * never see pockets: a caller uses upload + ps_label_air_pockets + ps_set_air_pocket_pressures + ps_step_device + download.
+ * Inputs.  The weights the next setup will use: lw = "centerLiquidWeights", fw = "centerFluidWeights", fwF_a = "faceX/Y/ZFluidWeights" —
+ * sampled from the uploaded SDFs exactly as the setup samples them, or the uploaded weights[14] where the caller passed them.  The call runs
+ * that stage itself; a setup after the call produces what it produces without the call, bit for bit.
+ * Definition.  Cells in x-fastest numbering; directions in the order -x, +x, -y, +y, -z, +z.
+ *   core cell:  fw_c > 0 and lw_c <= 0.5;
+ *   link:       two core cells that are face neighbours inside the grid and whose common face has fwF > 0;
+ *   pocket:     a connected component of core cells under these links; pockets are numbered 0 .. K-1 by their smallest x-fastest cell
+ *               index, whatever indexOrder is;
+ *   skin cell:  a cell that is not core, has fw_c > 0 and lw_c < 1, and has at least one core face neighbour across a face with fwF > 0;
+ *               it takes the pocket of the neighbour with the smallest lw, ties to the first in direction order;
+ *   every other cell has id -1;
+ *   air content of a cell with an id:  u_c = llrint((double)fw_c * (1.0 - (double)lw_c) * 1048576.0);
+ *   per pocket k:  units_k = the sum of u_c over its core and skin cells (64-bit integer), cells_k = the number of its core cells,
+ *               open_k = 1 if a core cell of it lies in the outermost cell layer of the grid on any side, else 0,
+ *               volume_k = ((double)units_k * (1.0 / 1048576.0)) * (dx * dx * dx).
+ * The sums are integers: every output is independent of the order of summation and bitwise reproducible; with the library's own 2x2x2
+ * sampler every u_c is exact.  K = 0 is legal (no air); the K-sized arrays then have zero elements.
+ * ps_label_air_pockets writes K to *count (count may be NULL).  ps_get_air_pockets writes volume_k and open_k (host memory, either pointer
+ * may be NULL) and needs len >= K, PS_FAILED otherwise.  ps_download_air_pocket_ids writes the id of every cell (host memory, nx*ny*nz,
+ * x-fastest); ps_download_air_pocket_ids_device writes them into device memory of the context's device in either layout, ordered against
+ * `stream` like a download, without synchronising the host, and obeys the pointer refusals of the other ps_*_device calls (PS_INVALID).
+ * ps_set_air_pocket_pressures: len must equal K and every value must be finite as the fp32 the field stores, else PS_INVALID — "pressure of pocket N is not finite" for
+ * the smallest such N — and nothing changes.  On the device it writes the cell field (float)pressure[id_c] for id_c >= 0 and 0.f elsewhere
+ * and installs it as the `pressure` member of the free-surface fields, as ps_upload_surface_fields_device would install the same array,
+ * except that a sigma field that is present stays; a later ps_upload_surface_fields / _device replaces both members as before;
+ * pressure == NULL drops the pressure member alone.  From there the existing path runs unchanged: q_c = sigma_c kappa_c + P_c, the arrays
+ * "surfaceFields" and "surfaceGhostPressure", the Picard passes keeping the field.
+ * Memory: while labels exist one int32 cell grid (4 * nx*ny*nz bytes) plus 24 * K bytes of results; the labels and link bytes of the
+ * propagation live in the cell scratch the setup uses anyway, and the pressure call's table (8 * K bytes) is released before it returns:
+ * ps_memory_stats entry 2 is 0 after each of these calls.  A drop releases the grid and the results.
+ * Arrays: "airPockets" (int32, 1: K of the current labels; absent without labels), "airPocketIds" (int32 cell grid), "airPocketUnits"
+ * (int64, K), "airPocketCells" (int32, K), "airPocketOpen" (int32, K), "airPocketVolume" (fp64, K), "airPocketPasses" (int32, 1: the
+ * grid-wide propagation passes the call ran, one host round trip each; above 1 when a pocket winds through several 16^3 boxes). */
+int32_t ps_label_air_pockets(ps_context* ctx, int32_t* count);
+int32_t ps_get_air_pockets(ps_context* ctx, double* volume, int32_t* open, int64_t len);
+int32_t ps_download_air_pocket_ids(ps_context* ctx, int32_t* ids);
+int32_t ps_download_air_pocket_ids_device(ps_context* ctx, int32_t* ids, int32_t layout, void* stream);
+int32_t ps_set_air_pocket_pressures(ps_context* ctx, const double* pressure, int64_t len);
+
 /* solveGasSubclass equivalent on host buffers: upload + step + download (HDK_PolyStokes.C:222-609). */
 int32_t polystokes_step(ps_context* ctx, const ps_params* p, const ps_fields_in* in,
                         ps_fields_out* out, ps_stats* stats);

@@ -31,6 +31,7 @@ EXPORTED_SYMBOLS = [
     "ps_step_device_fields", "ps_set_velocity_extrapolation",
     "ps_upload_surface_fields", "ps_upload_surface_fields_device",
     "ps_set_collider_loads", "ps_upload_collider_ids", "ps_upload_collider_ids_device", "ps_get_collider_loads", "ps_get_collider_loads_device",
+    "ps_label_air_pockets", "ps_get_air_pockets", "ps_download_air_pocket_ids", "ps_download_air_pocket_ids_device", "ps_set_air_pocket_pressures",
 ]
 
 
@@ -153,6 +154,9 @@ def lib():
         L.ps_get_collider_loads.restype = C.c_int32
         L.ps_get_collider_loads_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         L.ps_get_collider_loads_device.restype = C.c_int32
+        for name, argtypes in _abi.AIR_POCKET_CALLS:
+            getattr(L, name).argtypes = list(argtypes)
+            getattr(L, name).restype = C.c_int32
         _lib = L
     return _lib
 
@@ -238,7 +242,7 @@ def fields_in_device(fields):
     return fi
 
 
-_DT = {(1, "i"): np.int8, (4, "i"): np.int32, (4, "f"): np.float32, (8, "f"): np.float64, (4, "u"): np.uint32}
+_DT = {(1, "i"): np.int8, (4, "i"): np.int32, (8, "i"): np.int64, (4, "f"): np.float32, (8, "f"): np.float64, (4, "u"): np.uint32}
 
 
 def _kind(name):
@@ -248,7 +252,8 @@ def _kind(name):
                 "surfaceTensionReducedFaces", "surfaceFields", "solidBoundary", "solidSlipEdges", "rheologyModel", "rheologyIterations",
                 "solvePrecisionUsed", "solvePassIterations",
                 "velocityExtrapolation", "extrapolationLayerX", "extrapolationLayerY", "extrapolationLayerZ", "extrapolationCounts",
-                "colliderLoads", "colliderLoadTerms"):
+                "colliderLoads", "colliderLoadTerms",
+                "airPockets", "airPocketIds", "airPocketUnits", "airPocketCells", "airPocketOpen", "airPocketPasses"):
         return "i"
     if name in ("ownedX", "ownedY", "ownedZ"):
         return "f"
@@ -380,6 +385,45 @@ class Solver:
         """ps_get_collider_loads_device into `out` (device memory of `length` doubles).  Returns the ps_result (INVALID: a refused pointer;
         the host is NOT synchronised); raises when the last step computed no loads."""
         return self._check(self.L.ps_get_collider_loads_device(self.h, device_address(out), int(length), stream_handle(stream)), allow=(1, -2))
+
+    def label_air_pockets(self):
+        """ps_label_air_pockets: labels the connected air regions of the grid of the last upload (single domain) and returns their number K.
+        The labels last until the next upload (or set_slab / set_brick); arrays "airPockets", "airPocketIds", "airPocketUnits",
+        "airPocketCells", "airPocketOpen", "airPocketVolume", "airPocketPasses" say what the call found."""
+        k = C.c_int32(-1)
+        self._check(self.L.ps_label_air_pockets(self.h, C.byref(k)))
+        return int(k.value)
+
+    def _air_pocket_count(self):
+        return int(self.array("airPockets")[0]) if self.L.ps_query_array(self.h, b"airPockets", None) >= 0 else 0
+
+    def air_pockets(self):
+        """ps_get_air_pockets: (volume float64[K], open int32[K]) of the current labels; raises without labels."""
+        n = self._air_pocket_count()
+        vol, opn = np.empty(max(n, 1), np.float64), np.empty(max(n, 1), np.int32)
+        self._check(self.L.ps_get_air_pockets(self.h, vol.ctypes.data, opn.ctypes.data, n))
+        return vol[:n], opn[:n]
+
+    def air_pocket_ids(self):
+        """ps_download_air_pocket_ids: the pocket of every cell (int32, shape (nz, ny, nx); -1: none); raises without labels."""
+        out = np.empty(_abi.grid_shapes(self.scene.nx, self.scene.ny, self.scene.nz)["center"], np.int32)
+        self._check(self.L.ps_download_air_pocket_ids(self.h, out.ctypes.data))
+        return out
+
+    def air_pocket_ids_device(self, out, layout=0, stream=None):
+        """ps_download_air_pocket_ids_device into `out` (int32 device memory, one value per cell, in `layout`).  Returns the ps_result
+        (INVALID: a refused pointer or layout; the host is NOT synchronised); raises without labels."""
+        return self._check(self.L.ps_download_air_pocket_ids_device(self.h, device_address(out), int(layout), stream_handle(stream)), allow=(1, -2))
+
+    def set_air_pocket_pressures(self, p):
+        """ps_set_air_pocket_pressures: one pressure per pocket (K float64 values) becomes the pressure member of the free-surface fields, a
+        sigma field staying; None drops the pressure member alone.  Returns the ps_result: INVALID for a length other than K or a value
+        that is not finite (nothing changed); raises without labels."""
+        if p is None:
+            return self._check(self.L.ps_set_air_pocket_pressures(self.h, None, 0), allow=(1, -2))
+        v = np.ascontiguousarray(p, dtype=np.float64).ravel()
+        buf = v if v.size else np.zeros(1, np.float64)      # (K = 0: a valid pointer with len 0; NULL means "drop")
+        return self._check(self.L.ps_set_air_pocket_pressures(self.h, buf.ctypes.data, v.size), allow=(1, -2))
 
     def solution_fields(self):
         """ps_download_solution_fields: the last solve's [p; tau] as dense fp32 grids (x fastest), keyed pressure, txx, tyy, tzz, tyz, txz, txy;

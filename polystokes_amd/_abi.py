@@ -80,6 +80,16 @@ class ColliderLoads(C.Structure):
     _fields_ = [("count", C.c_int32), ("pivots", C.c_void_p)]
 
 
+# the air pocket calls (ps_label_air_pockets ...): name -> argument types; every one returns int32
+AIR_POCKET_CALLS = (
+    ("ps_label_air_pockets", (C.c_void_p, C.POINTER(C.c_int32))),
+    ("ps_get_air_pockets", (C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64)),
+    ("ps_download_air_pocket_ids", (C.c_void_p, C.c_void_p)),
+    ("ps_download_air_pocket_ids_device", (C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p)),
+    ("ps_set_air_pocket_pressures", (C.c_void_p, C.c_void_p, C.c_int64)),
+)
+
+
 class Rheology(C.Structure):
     """ps_rheology (ps_set_rheology): the viscosity law of every later setup of a context"""
     _fields_ = [("model", C.c_int32), ("passes", C.c_int32), ("flowIndex", C.c_double), ("yieldStress", C.c_double),

@@ -113,6 +113,11 @@ void ps_context::uploadReset(const ps_params* p, const ps_fields_in* in) {
         dropColliderIds();
         drainDeferred(true);
     }
+    if (pocketsHave || pocketIds.p) {                     // ... and the air pocket labels (ps_label_air_pockets)
+        HIP_CHECK(hipStreamSynchronize(stream));
+        dropAirPockets();
+        drainDeferred(true);
+    }
 }
 
 void ps_context::ingestHost(const ps_fields_in* in) {
@@ -230,6 +235,7 @@ void ps_context::setupPhase(int phase) {
         extrapUsedHost = 0;
         loadsUsedHost = 0;
         arrays.clear();
+        registerPocketArrays();                 // (ps_label_air_pockets: a setup keeps the labels, also one that throws)
         if (rheoPass == 0) rheoIters.clear();   // (ps_set_rheology: one entry per solve of the step)
         // Picard passes need the halo of the last pass's output velocity: a decomposition refuses them on every rank (ps_dist.hpp: distStep)
         if (slabEnabled && rheoSet.model != PS_RHEOLOGY_NEWTONIAN && rheoSet.passes > 0) throw Error("rheology passes need a single domain");
@@ -493,6 +499,7 @@ void ps_context::registerArrays() {
         reg(std::string("faceRow") + ax[a], faceRow[a].p, g.count(1 + a), 4);
         if (slabEnabled && isSolved) reg(std::string("owned") + ax[a], ownedFace[a].p, g.count(1 + a), 4);
     }
+    registerPocketArrays();   // the labels of ps_label_air_pockets outlive a setup, solve or step
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -862,6 +869,49 @@ int32_t ps_get_collider_loads(ps_context* c, double* out, int64_t out_len) {
     PS_TRY(c, {
         if (!out) throw Error("ps_get_collider_loads: out is null");
         c->copyColliderLoads(out, out_len, false, nullptr);
+        return PS_SUCCESS;
+    })
+}
+int32_t ps_label_air_pockets(ps_context* c, int32_t* count) {
+    if (!c) return PS_FAILED;
+    PS_TRY(c, {
+        if (!c->uploaded) { c->err = "ps_label_air_pockets: call ps_upload_fields first"; return PS_INVALID; }
+        c->labelAirPockets();
+        if (count) *count = c->pocketCount;
+        return PS_SUCCESS;
+    })
+}
+int32_t ps_get_air_pockets(ps_context* c, double* volume, int32_t* open, int64_t len) {
+    if (!c) return PS_FAILED;
+    PS_TRY(c, { c->copyAirPockets(volume, open, len); return PS_SUCCESS; })
+}
+int32_t ps_download_air_pocket_ids(ps_context* c, int32_t* ids) {
+    if (!c) return PS_FAILED;
+    PS_TRY(c, {
+        if (!ids) throw Error("ps_download_air_pocket_ids: ids is null");
+        c->copyAirPocketIds(ids, false, 0, nullptr);
+        return PS_SUCCESS;
+    })
+}
+int32_t ps_download_air_pocket_ids_device(ps_context* c, int32_t* ids, int32_t layout, void* stream) {
+    if (!c) return PS_FAILED;
+    PS_TRY(c, {
+        if (!c->pocketsHave) throw Error("ps_download_air_pocket_ids: there are no air pocket labels (ps_label_air_pockets after the last upload)");
+        HIP_CHECK(hipSetDevice(c->device));
+        std::string why;
+        if (const char* m = ps_context::layoutRefusal(layout)) why = m;
+        else if (!ids) why = "ids: the pointer is null";
+        else why = c->checkDeviceField(ids, c->g.count(0), "ids");
+        if (!why.empty()) { c->err = "ps_download_air_pocket_ids_device: " + why; return PS_INVALID; }
+        c->copyAirPocketIds(ids, true, layout, (hipStream_t)stream);
+        return PS_SUCCESS;
+    })
+}
+int32_t ps_set_air_pocket_pressures(ps_context* c, const double* pressure, int64_t len) {
+    if (!c) return PS_FAILED;
+    PS_TRY(c, {
+        const std::string why = c->setAirPocketPressures(pressure, len);
+        if (!why.empty()) { c->err = "ps_set_air_pocket_pressures: " + why; return PS_INVALID; }
         return PS_SUCCESS;
     })
 }

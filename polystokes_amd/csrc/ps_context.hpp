@@ -382,6 +382,23 @@ struct ps_context {
     bool dropColliderIds();                              // ps_loads.hip: false when there was nothing to drop
     std::string uploadColliderIds(const int32_t* ids, bool device, int layout, hipStream_t caller);   // ps_loads.hip
     void copyColliderLoads(double* dst, int64_t len, bool device, hipStream_t caller);                 // ps_loads.hip: throws when there are none
+    // Air pockets (ps_label_air_pockets, extension; ps_pockets.hip): the connected air regions of the grid of the last upload (every upload and
+    // every ps_set_slab / ps_set_brick drops them; a setup, solve or step keeps them).  pocketsHave: labels exist; pocketCount: K;
+    // pocketPassesHost: the global propagation passes the last call ran (array "airPocketPasses").  pocketIds: the pocket of every cell (-1:
+    // none), the one cell grid held while labels exist; pocketUnits / pocketCells / pocketOpen / pocketVolume: K entries each.  The labels and
+    // link bytes of the propagation live in cellScratch, which only a setup uses.
+    bool inGroup = false;                                // a rank of a ps_group (ps_group_create)
+    bool pocketsHave = false;
+    int32_t pocketCount = 0, pocketPassesHost = 0;
+    ps::DevBuf<int32_t> pocketIds, pocketCells, pocketOpen;
+    ps::DevBuf<long long> pocketUnits;
+    ps::DevBuf<double> pocketVolume;
+    void labelAirPockets();                              // ps_pockets.hip: throws on a decomposition
+    bool dropAirPockets();                               // ps_pockets.hip: false when there was nothing to drop
+    void registerPocketArrays();                         // ps_pockets.hip: the arrays of the current labels (none without labels)
+    void copyAirPockets(double* volume, int32_t* open, int64_t len);                                      // ps_pockets.hip: throws without labels
+    void copyAirPocketIds(int32_t* dst, bool device, int layout, hipStream_t caller);                     // ps_pockets.hip: throws without labels
+    std::string setAirPocketPressures(const double* pressure, int64_t len);                               // ps_pockets.hip: the refusal, or empty
     int64_t solutionGridCount(int q) const { return g.count(q < 4 ? 0 : q); }   // grid q of the store: 0..3 cell grid, 4..6 edge grids
     void scatterSolution(float* dst, int q0, int nq);   // ps_solve.hip: grids q0 .. q0+nq-1 of x, back to back in dst
     void carryWarmStart();                              // ps_solve.hip: x -> warmStore (after a kept step)

@@ -1483,6 +1483,13 @@ int32_t ps_set_brick(ps_context* c, const ps_brick* bk) {
         for (int a = 0; a < 3; ++a) c->gOff[a] = c->slabEnabled ? bk->globalLo[a] - bk->lo[a] : 0;
         c->blockMapOwned = -1;
         c->isSetup = false;
+        if (c->pocketsHave || c->pocketIds.p) {   // the labels of ps_label_air_pockets belong to the whole grid as a single domain
+            ps::SinkScope sinkScope_(&c->deferred);
+            HIP_CHECK(hipSetDevice(c->device));
+            HIP_CHECK(hipStreamSynchronize(c->stream));
+            c->dropAirPockets();
+            c->drainDeferred(true);
+        }
         return PS_SUCCESS;
     } PS_CATCH_ALL(c)
 }
@@ -1589,6 +1596,7 @@ ps_group* ps_group_create(int32_t device, int32_t world) {
     for (int q = 0; q < world; ++q) {
         ps_context* c = ps_context_create(device);
         if (!c) { for (ps_context* d : g->ranks) ps_context_destroy(d); delete g; return nullptr; }
+        c->inGroup = true;
         if (q == 0) g->stream = c->stream;
         else { (void)hipStreamDestroy(c->stream); c->stream = g->stream; c->ownsStream = false; }   // one shared stream: launches are ordered
         g->ranks.push_back(c);
