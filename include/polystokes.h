@@ -264,8 +264,8 @@ int32_t ps_set_surface_tension(ps_context* ctx, double sigma);
  * is skipped; t += sign * wF * ghost * invDx * q_c, left to right.  With t != 0 an active face gets rhsA[row] -= dt * t and a reduced face
  * C_f^T (-dt * t) into its tile's rhs; b, the recovery, the exports, the EIGEN path and ps_solve_exported_system follow from those two
  * vectors.  With no field present the setup runs exactly the kernels and arguments of ps_set_surface_tension alone.
- * sigma is sampled at the cell, not at the closest interface point; a varying sigma adds no Marangoni (tangential) stress; there are no
- * contact angles; P is the caller's (no bubble model derives it from pocket volumes).
+ * sigma is sampled at the cell, not at the closest interface point; a varying sigma adds no Marangoni (tangential) stress; contact angles
+ * are ps_set_contact_angle's (below); P is the caller's (no bubble model derives it from pocket volumes).
  * PS_INVALID (reason in ps_last_error, both fields dropped): "sigma: non-finite or negative value at cell N" (checked first; -0 is not
  * negative), "pressure: non-finite value at cell N", N the smallest such index in x-fastest numbering.  While present the fields cost two fp32 cell grids and,
  * from the next setup on, one fp64 cell grid; a drop releases them.
@@ -277,6 +277,46 @@ typedef struct ps_surface_fields {
     const float* pressure;   /* cell field nx*ny*nz, x-fastest; NULL: 0 */
 } ps_surface_fields;
 int32_t ps_upload_surface_fields(ps_context* ctx, const ps_surface_fields* f);
+
+/* Contact angles (extension): before the curvature of ps_set_surface_tension is taken, the liquid SDF inside the solid is rewritten so
+ * that its slope along the wall normal is cos(theta); at the wall the level set then meets the solid at theta, and where the liquid's
+ * current angle differs the curvature at the contact line changes and drives the line towards equilibrium.  Only the curvature reads the
+ * rewritten field phi' ("surfaceWetted"): the stencil of kappa and the closest-point gradient of kappa_c read phi' wherever they read
+ * `surface` otherwise; weights, classification, numbering, the operator and every other output are untouched.
+ * ps_set_contact_angle is a context setting like ps_set_surface_tension: it persists across uploads and is read by every later setup.
+ * degrees < 0 (the default: -1) is off; 0..180 is theta, measured inside the liquid.  The cosine is computed once on the host as
+ * cos(degrees * (pi / 180)), and is exactly 0 for degrees == 90 (array "contactCosine").  PS_INVALID for a NaN, an infinity or a value
+ * above 180 (reason "contact angle outside 0..180", the previous setting kept).
+ * ps_upload_contact_cosine_field: one fp32 value per cell, nx*ny*nz, x-fastest: the cos(theta) of the solid that cell belongs to (painted
+ * into the solid cells, like collider ids).  The lifetime and call order are the density field's: after an upload and before the setup,
+ * dropped by every field upload, kept across the Picard passes, PS_INVALID before any upload; NULL drops it.  PS_INVALID with the field
+ * dropped: "contact cosine: value outside [-1, 1] at cell N" (a NaN counts), N the smallest such index in x-fastest numbering whatever
+ * the layout.  While present the field overrides the scalar cell by cell and turns the rule on when the scalar is off.  polystokes_step
+ * and ps_step_device_fields carry no such field: the scalar setting applies to them.
+ * The rule runs in a setup only when that setup computes the curvature (sigma > 0 or a sigma field) and the angle or the cosine field is
+ * set; otherwise nothing is launched and nothing is allocated, and a context that never made these calls launches what it always did.
+ * All arithmetic is fp64 from the fp32 inputs, unfused, in the order written:
+ *   D_c = -collision[c] with negateCollision = 1, +collision[c] with 0 (the solid depth, positive inside the solid); phi^0 = `surface`;
+ *   cos_c = (double)field[c], or the scalar's cosine without a field.
+ *   U = { c : D_c > 0 and (double)D_c <= 6.0 * dx };  G_a(c) = (D[c + e_a] - D[c - e_a]) * 0.5, indices clamped to the grid;
+ *   g(c) = sqrt(G_x*G_x + G_y*G_y + G_z*G_z), summed left to right.
+ *   Sweep m = 1 .. PS_CONTACT_ANGLE_SWEEPS (Jacobi: it reads only phi^(m-1)).  c outside U: phi^m_c = phi^(m-1)_c.  c in U: from N = 0,
+ *   W = 0 visit the axes x, y, z: the upwind cell is c - e_a for G_a > 0 and c + e_a for G_a < 0; an axis with G_a == 0, or whose upwind
+ *   cell lies outside the grid, contributes nothing; otherwise N += |G_a| * (double)phi^(m-1)[up], W += |G_a|.  W == 0: the cell keeps
+ *   its value; otherwise phi^m_c = (float)((N - (dx * cos_c) * g) / W).
+ *   phi' = phi^PS_CONTACT_ANGLE_SWEEPS.
+ * Slab and brick ranks run the rule on their own grid: a value that reaches an owned face depends on cells at most 7 + 6 + 1 layers
+ * away, inside the 16-layer halo block.  No hysteresis or dynamic angle; the weights near walls do not change.
+ * Memory: from the first setup that runs the rule the context holds two fp32 cell grids (phi' and the other Jacobi iterate), one flag byte
+ * per 16x4x4 block of cells and a counter, plus one fp32 cell grid for the cosine field while present.  A setup that does not run the rule
+ * drops them, and so does ps_set_contact_angle(ctx, -1) with no field present, which releases them at once; ps_memory_stats entry 2 is 0
+ * after each of the three calls.
+ * Arrays: "contactAngle" (fp64, 1: the degrees the last setup used; -1 when it used none or only the field) and, only when the last
+ * setup ran the rule, "contactCosine" (fp64, 1: the scalar's cosine; 0 with the scalar off), "contactField" (int32, 1: 1 if the field
+ * was used), "contactCells" (int32, 1: |U|), "surfaceWetted" (fp32 cell grid: phi'). */
+#define PS_CONTACT_ANGLE_SWEEPS 6
+int32_t ps_set_contact_angle(ps_context* ctx, double degrees);              /* < 0: off (default); 0..180 */
+int32_t ps_upload_contact_cosine_field(ps_context* ctx, const float* cosTheta);   /* cell field nx*ny*nz, x-fastest; NULL drops it */
 
 /* Solid boundary condition (extension; the reference node's colliders are all no-slip).  A context setting like ps_set_surface_tension: it
  * persists across ps_upload_fields and is read by every later setup.  PS_SOLID_NO_SLIP (the default) launches exactly the kernels of a
@@ -538,6 +578,7 @@ int32_t ps_upload_fields_device(ps_context* ctx, const ps_params* p, const ps_fi
 int32_t ps_upload_density_field_device(ps_context* ctx, const float* density, int32_t layout, void* stream);
 int32_t ps_upload_surface_fields_device(ps_context* ctx, const ps_surface_fields* f, int32_t layout, void* stream);
 int32_t ps_upload_collider_ids_device(ps_context* ctx, const int32_t* ids, int32_t layout, void* stream);   /* ps_upload_collider_ids */
+int32_t ps_upload_contact_cosine_field_device(ps_context* ctx, const float* cosTheta, int32_t layout, void* stream);   /* ps_upload_contact_cosine_field; a refused pointer or layout leaves the context unchanged */
 int32_t ps_get_collider_loads_device(ps_context* ctx, double* dev, int64_t len, void* stream);              /* ps_get_collider_loads */
 int32_t ps_download_fields_device(ps_context* ctx, const ps_fields_out* out, int32_t layout, void* stream);
 int32_t ps_download_solution_fields_device(ps_context* ctx, const ps_solution_out* out, int32_t layout, void* stream);

@@ -32,6 +32,7 @@ EXPORTED_SYMBOLS = [
     "ps_upload_surface_fields", "ps_upload_surface_fields_device",
     "ps_set_collider_loads", "ps_upload_collider_ids", "ps_upload_collider_ids_device", "ps_get_collider_loads", "ps_get_collider_loads_device",
     "ps_label_air_pockets", "ps_get_air_pockets", "ps_download_air_pocket_ids", "ps_download_air_pocket_ids_device", "ps_set_air_pocket_pressures",
+    "ps_set_contact_angle", "ps_upload_contact_cosine_field", "ps_upload_contact_cosine_field_device",
 ]
 
 
@@ -154,6 +155,12 @@ def lib():
         L.ps_get_collider_loads.restype = C.c_int32
         L.ps_get_collider_loads_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         L.ps_get_collider_loads_device.restype = C.c_int32
+        L.ps_set_contact_angle.argtypes = [C.c_void_p, C.c_double]
+        L.ps_set_contact_angle.restype = C.c_int32
+        L.ps_upload_contact_cosine_field.argtypes = [C.c_void_p, C.c_void_p]
+        L.ps_upload_contact_cosine_field.restype = C.c_int32
+        L.ps_upload_contact_cosine_field_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+        L.ps_upload_contact_cosine_field_device.restype = C.c_int32
         for name, argtypes in _abi.AIR_POCKET_CALLS:
             getattr(L, name).argtypes = list(argtypes)
             getattr(L, name).restype = C.c_int32
@@ -215,6 +222,7 @@ class DeviceScene:
         self.density_field = None if scene.density_field is None else put(scene.density_field)
         opt = lambda name: None if getattr(scene, name, None) is None else put(getattr(scene, name))
         self.surface_sigma_field, self.surface_pressure_field = opt("surface_sigma_field"), opt("surface_pressure_field")
+        self.contact_angle, self.contact_cosine_field = getattr(scene, "contact_angle", None), opt("contact_cosine_field")
 
 
 def device_scene(scene, layout=_abi.LAYOUT_X_FASTEST, pad=0):
@@ -253,7 +261,8 @@ def _kind(name):
                 "solvePrecisionUsed", "solvePassIterations",
                 "velocityExtrapolation", "extrapolationLayerX", "extrapolationLayerY", "extrapolationLayerZ", "extrapolationCounts",
                 "colliderLoads", "colliderLoadTerms",
-                "airPockets", "airPocketIds", "airPocketUnits", "airPocketCells", "airPocketOpen", "airPocketPasses"):
+                "airPockets", "airPocketIds", "airPocketUnits", "airPocketCells", "airPocketOpen", "airPocketPasses",
+                "contactField", "contactCells"):
         return "i"
     if name in ("ownedX", "ownedY", "ownedZ"):
         return "f"
@@ -322,6 +331,32 @@ class Solver:
         """ps_set_solid_boundary: SOLID_NO_SLIP (0, the default) or SOLID_FREE_SLIP (1: no shear stress on the edges a solid cuts) for every
         later setup of this context, across uploads.  Returns the ps_result: INVALID for another mode (the previous setting kept)."""
         return self._check(self.L.ps_set_solid_boundary(self.h, int(mode)), allow=(1, -2))
+
+    def set_contact_angle(self, degrees):
+        """ps_set_contact_angle: the angle (degrees, inside the liquid) at which the liquid surface meets every solid, for every later setup
+        of this context that computes the curvature, across uploads; a negative value (the default) is off.  Returns the ps_result: INVALID
+        for a NaN, an infinity or a value above 180 (the previous setting kept).  Arrays "contactAngle", "contactCosine", "contactField",
+        "contactCells", "surfaceWetted" say what the last setup did."""
+        return self._check(self.L.ps_set_contact_angle(self.h, float(degrees)), allow=(1, -2))
+
+    def upload_contact_cosine_field(self, field):
+        """ps_upload_contact_cosine_field: cos(theta) per cell, painted into the solid cells, for the grid of the last upload (None drops
+        it); `field` is a host array or a torch tensor on the host.  Returns the ps_result (INVALID for a value outside [-1, 1], the reason
+        in last_error()); FAILED raises."""
+        if field is None:
+            return self._check(self.L.ps_upload_contact_cosine_field(self.h, None), allow=(1, -2))
+        if getattr(field, "is_cuda", False):
+            raise TypeError("a device tensor goes through upload_contact_cosine_field_device")
+        f = np.ascontiguousarray(field.numpy() if hasattr(field, "data_ptr") else field, dtype=np.float32)
+        if self.scene is not None and f.size != self.scene.nx * self.scene.ny * self.scene.nz:
+            raise ValueError("the field must hold one value per cell")
+        return self._check(self.L.ps_upload_contact_cosine_field(self.h, f.ctypes.data), allow=(1, -2))
+
+    def upload_contact_cosine_field_device(self, field, layout=0, stream=None):
+        """ps_upload_contact_cosine_field_device (None drops the field): `field` is fp32 device memory in `layout` (a DeviceBuffer, a torch
+        tensor, an address).  Returns the ps_result, INVALID for a refused call."""
+        return self._check(self.L.ps_upload_contact_cosine_field_device(self.h, device_address(field), int(layout), stream_handle(stream)),
+                           allow=(1, -2))
 
     def set_rheology(self, model=_abi.RHEOLOGY_HERSCHEL_BULKLEY, flow_index=1.0, yield_stress=0.0, min_shear_rate=1e-3,
                      min_viscosity=1e-3, max_viscosity=1e6, passes=0):
@@ -496,12 +531,18 @@ class Solver:
             self._check(self.upload_density_field(scene.density_field))
         if _has_surface_fields(scene):
             self._check(self.upload_surface_fields(scene.surface_sigma_field, scene.surface_pressure_field))
+        if getattr(scene, "contact_cosine_field", None) is not None:
+            self._check(self.upload_contact_cosine_field(scene.contact_cosine_field))
 
     def _scene_surface_tension(self, scene):
-        """Scene.surface_tension (None: the context keeps its setting) -> ps_set_surface_tension; a refused value raises."""
+        """Scene.surface_tension and Scene.contact_angle (None: the context keeps its setting) -> ps_set_surface_tension,
+        ps_set_contact_angle; a refused value raises."""
         sigma = getattr(scene, "surface_tension", None)
         if sigma is not None:
             self._check(self.L.ps_set_surface_tension(self.h, float(sigma)))
+        angle = getattr(scene, "contact_angle", None)
+        if angle is not None:
+            self._check(self.L.ps_set_contact_angle(self.h, float(angle)))
 
     def upload_density_field(self, field):
         """ps_upload_density_field: a cell density field for the grid of the last upload (None drops it).  Returns the ps_result
@@ -608,7 +649,8 @@ class Solver:
 
     def step(self, scene, params):
         """solveGasSubclass equivalent on host buffers (HDK_PolyStokes.C:222-609)."""
-        if getattr(scene, "density_field", None) is not None or _has_surface_fields(scene):   # upload, the fields, step, download: polystokes_step has no field
+        if (getattr(scene, "density_field", None) is not None or _has_surface_fields(scene)
+                or getattr(scene, "contact_cosine_field", None) is not None):   # upload, the fields, step, download: polystokes_step has no field
             self.upload(scene, params)
             rc = self.step_device()
             self.download()
@@ -757,6 +799,11 @@ class Group:
     def set_solid_boundary(self, mode):
         """ps_set_solid_boundary on every rank (a context setting: it holds for every later step of the group)."""
         rc = [r.set_solid_boundary(mode) for r in self.ranks]
+        return rc[0]
+
+    def set_contact_angle(self, degrees):
+        """ps_set_contact_angle on every rank (a context setting; a rank rewrites the SDF on its own grid, the halo block covers the reach)."""
+        rc = [r.set_contact_angle(degrees) for r in self.ranks]
         return rc[0]
 
     def set_solve_precision(self, mode):

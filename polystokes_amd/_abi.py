@@ -73,6 +73,7 @@ PRECISION_FP64, PRECISION_MIXED = 0, 1
 LAYOUT_X_FASTEST, LAYOUT_Z_FASTEST = 0, 1
 EXTRAPOLATION_MAX_LAYERS = 64      # PS_EXTRAPOLATION_MAX_LAYERS (ps_set_velocity_extrapolation)
 COLLIDER_MAX = 64                  # PS_COLLIDER_MAX (ps_set_collider_loads)
+CONTACT_ANGLE_SWEEPS = 6           # PS_CONTACT_ANGLE_SWEEPS (ps_set_contact_angle)
 
 
 class ColliderLoads(C.Structure):
@@ -159,7 +160,7 @@ class Scene:
 
     def __init__(self, nx, ny, nz, dx, dt, density, vel, surface, collision, viscosity,
                  collisionvel=None, weights=None, name="scene", density_field=None, surface_tension=None,
-                 surface_sigma_field=None, surface_pressure_field=None):
+                 surface_sigma_field=None, surface_pressure_field=None, contact_angle=None, contact_cosine_field=None):
         self.nx, self.ny, self.nz, self.dx, self.dt, self.density = nx, ny, nz, float(dx), float(dt), float(density)
         sh = grid_shapes(nx, ny, nz)
         f32 = lambda a, s: np.array(np.broadcast_to(np.asarray(a, dtype=np.float32), s), dtype=np.float32, order="C", copy=True)
@@ -182,6 +183,10 @@ class Scene:
         # pressure (None: 0)
         self.surface_sigma_field = None if surface_sigma_field is None else f32(surface_sigma_field, sh["center"])
         self.surface_pressure_field = None if surface_pressure_field is None else f32(surface_pressure_field, sh["center"])
+        # optional contact angle in degrees (ps_set_contact_angle, applied at upload / step; < 0: off); None: leave the context's setting
+        self.contact_angle = None if contact_angle is None else float(contact_angle)
+        # optional cell field of cos(theta), painted into the solids (ps_upload_contact_cosine_field); None: the scalar angle
+        self.contact_cosine_field = None if contact_cosine_field is None else f32(contact_cosine_field, sh["center"])
 
     def fields_in(self):
         fi = FieldsIn()

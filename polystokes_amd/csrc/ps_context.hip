@@ -106,6 +106,11 @@ void ps_context::uploadReset(const ps_params* p, const ps_fields_in* in) {
         dropSurfaceFields();
         drainDeferred(true);
     }
+    if (contactCos.p) {                                   // ... and the contact cosine field (ps_upload_contact_cosine_field)
+        HIP_CHECK(hipStreamSynchronize(stream));
+        dropContactCosine();
+        drainDeferred(true);
+    }
     for (int a = 0; a < 3; ++a) orig[a] = in->orig[a];   // (the default pivot of ps_set_collider_loads)
     forgetLoads();                                        // the loads of an earlier step described the previous fields
     if (colliderIds.p) {                                  // ... and so did the collider ids (ps_upload_collider_ids), released here
@@ -432,6 +437,13 @@ void ps_context::registerArrays() {
     if (sigmaUsed != 0. || (surfFieldsUsed & 1)) reg("surfaceCurvature", kappaC.p, g.count(0), 4);
     if (sigmaUsed != 0. || surfFieldsUsed != 0) reg("surfaceTensionReducedFaces", stReduced.p, 1, 4);
     if (surfFieldsUsed != 0 && surfQ.p) reg("surfaceGhostPressure", surfQ.p, g.count(0), 8);   // q_c of the last setup (gone once the fields are dropped)
+    regHost("contactAngle", &contactDegUsed, 1, 8);   // the degrees the last setup used (ps_set_contact_angle): -1 for none or the field alone
+    if (contactRan && wetPhi[0].p) {                   // the last setup rewrote the SDF inside the solid (ps_wetting.hip)
+        regHost("contactCosine", &contactCosUsed, 1, 8);
+        regHost("contactField", &contactFieldUsed, 1, 4);
+        reg("contactCells", wetCount.p, 1, 4);
+        reg("surfaceWetted", wetPhi[0].p, g.count(0), 4);
+    }
     regHost("solidBoundary", &solidBoundaryUsed, 1, 4);   // the mode of the last setup (ps_set_solid_boundary)
     if (solidBoundaryUsed == PS_SOLID_FREE_SLIP) reg("solidSlipEdges", slipEdges.p, 1, 4);
     regHost("rheologyModel", &rheoModelUsed, 1, 4);   // the model of the last setup (ps_set_rheology)
@@ -787,6 +799,33 @@ int32_t ps_set_surface_tension(ps_context* c, double sigma) {
         return PS_SUCCESS;
     })
 }
+int32_t ps_set_contact_angle(ps_context* c, double degrees) {
+    if (!c) return PS_FAILED;
+    PS_TRY(c, {
+        if (std::isnan(degrees) || std::isinf(degrees) || degrees > 180.) {
+            c->err = "ps_set_contact_angle: contact angle outside 0..180";
+            return PS_INVALID;
+        }
+        c->contactDegSet = degrees < 0. ? -1. : degrees;   // read by the next setup that computes the curvature (applyContactAngle)
+        c->contactCosSet = degrees < 0. ? 0. : (degrees == 90. ? 0. : std::cos(degrees * (3.14159265358979323846 / 180.)));
+        if (degrees < 0. && !c->contactCosField && c->wetPhi[0].p) {   // the buffers go with the setting: dropped and, with the stream idle, released here
+            HIP_CHECK(hipSetDevice(c->device));
+            HIP_CHECK(hipStreamSynchronize(c->stream));
+            c->dropWetting();
+            c->drainDeferred(true);
+        }
+        return PS_SUCCESS;
+    })
+}
+int32_t ps_upload_contact_cosine_field(ps_context* c, const float* cosTheta) {
+    if (!c) return PS_FAILED;
+    PS_TRY(c, {
+        if (!c->uploaded) { c->err = "ps_upload_contact_cosine_field: call ps_upload_fields first"; return PS_INVALID; }
+        const std::string why = c->uploadContactCosine(cosTheta, false, 0, nullptr);
+        if (!why.empty()) { c->err = "ps_upload_contact_cosine_field: " + why; return PS_INVALID; }
+        return PS_SUCCESS;
+    })
+}
 int32_t ps_set_solid_boundary(ps_context* c, int32_t mode) {
     if (!c) return PS_FAILED;
     PS_TRY(c, {
@@ -1049,6 +1088,20 @@ int32_t ps_upload_collider_ids_device(ps_context* c, const int32_t* ids, int32_t
         if (!why.empty()) { c->err = "ps_upload_collider_ids_device: " + why; return PS_INVALID; }
         why = c->uploadColliderIds(ids, true, layout, (hipStream_t)stream);
         if (!why.empty()) { c->err = "ps_upload_collider_ids: " + why; return PS_INVALID; }
+        return PS_SUCCESS;
+    })
+}
+int32_t ps_upload_contact_cosine_field_device(ps_context* c, const float* cosTheta, int32_t layout, void* stream) {
+    if (!c) return PS_FAILED;
+    PS_TRY(c, {
+        if (!c->uploaded) { c->err = "ps_upload_contact_cosine_field: call ps_upload_fields first"; return PS_INVALID; }
+        HIP_CHECK(hipSetDevice(c->device));
+        std::string why;
+        if (const char* m = ps_context::layoutRefusal(layout)) why = m;
+        else if (cosTheta) why = c->checkDeviceField(cosTheta, c->g.count(0), "cosTheta");
+        if (!why.empty()) { c->err = "ps_upload_contact_cosine_field_device: " + why; return PS_INVALID; }
+        why = c->uploadContactCosine(cosTheta, true, layout, (hipStream_t)stream);
+        if (!why.empty()) { c->err = "ps_upload_contact_cosine_field: " + why; return PS_INVALID; }
         return PS_SUCCESS;
     })
 }

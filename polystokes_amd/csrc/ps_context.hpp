@@ -127,7 +127,7 @@ struct FieldTable {
 void launchFieldsCopy(const FieldTable& T, hipStream_t s);      // ps_fields.hip: dst = src, entry by entry
 void launchFieldsSwapXZ(const FieldTable& T, hipStream_t s);    // ... dst = src with the x and z axes exchanged
 enum ScanWord { SCAN_BAD = 0, SCAN_DIFFERS = 1, SCAN_FIRST = 2, SCAN_WORDS = 3 };   // k_field_scan: smallest bad index (~0: none), f[i] != f[0] somewhere, bits of f[0]
-enum ScanBad { SCAN_BAD_NONE = 0, SCAN_BAD_NON_FINITE = 1, SCAN_BAD_NON_FINITE_OR_NEGATIVE = 2 };   // which values count as bad
+enum ScanBad { SCAN_BAD_NONE = 0, SCAN_BAD_NON_FINITE = 1, SCAN_BAD_NON_FINITE_OR_NEGATIVE = 2, SCAN_BAD_OUTSIDE_UNIT = 3 };   // which values count as bad (3: outside [-1, 1], a NaN included)
 void launchFieldScan(const float* f, int64_t n, int bad, uint32_t* out, hipStream_t s);
 
 struct CellField;     // ps_setup_util.hpp: what the setup kernels sample
@@ -216,6 +216,23 @@ struct ps_context {
     int32_t surfFieldsUsed = 0;
     bool dropSurfaceFields();                // ps_fields.hip: false when there was nothing to drop
     std::string uploadSurfaceFields(const ps_surface_fields* f, bool device, int layout, hipStream_t caller);   // ps_fields.hip
+    // Contact angles (ps_set_contact_angle, ps_upload_contact_cosine_field; ps_wetting.hip): contactDegSet / contactCosSet are the context
+    // setting (degrees < 0: off) and its cosine, contactCos the cosine cell field of the last call, for the grid of the last upload (every
+    // upload drops it).  A setup that computes the curvature with either set rewrites the SDF inside the solid into wetPhi[0] (array
+    // "surfaceWetted"; wetPhi[1] is the other Jacobi iterate) and the curvature kernels read that; wetFlags: one byte per block of cells
+    // that holds a cell of the update set, wetCount: the set's size (array "contactCells").  contactDegUsed / contactCosUsed /
+    // contactFieldUsed / contactRan: what the last setup did (arrays "contactAngle", "contactCosine", "contactField").  The wet buffers
+    // exist from the first setup that runs the rule to the first that does not, or to ps_set_contact_angle(-1) with no field present.
+    double contactDegSet = -1., contactCosSet = 0., contactDegUsed = -1., contactCosUsed = 0.;
+    ps::DevBuf<float> contactCos, wetPhi[2];
+    ps::DevBuf<uint8_t> wetFlags;
+    ps::DevBuf<int32_t> wetCount;
+    bool contactCosField = false, contactRan = false;
+    int32_t contactFieldUsed = 0;
+    const float* applyContactAngle(bool curvature);   // ps_wetting.hip: the SDF the curvature reads (surface itself when the rule does not run)
+    bool dropWetting();                      // ps_wetting.hip: the wet buffers and their arrays; false when there was nothing to drop
+    bool dropContactCosine();                // ps_wetting.hip: false when there was nothing to drop
+    std::string uploadContactCosine(const float* cosTheta, bool device, int layout, hipStream_t caller);   // ps_wetting.hip
     // Solid boundary (ps_set_solid_boundary): solidBoundarySet is the context setting, solidBoundaryUsed the mode of the last setup (array
     // "solidBoundary"; constructMatrixBlocks copies it).  slipEdges: free-slip edges counted by the St count pass (array "solidSlipEdges").
     int32_t solidBoundarySet = PS_SOLID_NO_SLIP, solidBoundaryUsed = PS_SOLID_NO_SLIP;

@@ -63,7 +63,7 @@ __global__ __launch_bounds__(FBS) void k_fields_swap_xz(FieldTable T) {
 }
 
 // out[SCAN_BAD] = min(out[SCAN_BAD], smallest i with f[i] bad): not finite (badMode >= SCAN_BAD_NON_FINITE) or below 0
-// (SCAN_BAD_NON_FINITE_OR_NEGATIVE; -0 is not), out[SCAN_DIFFERS] |= some f[i] != f[0]
+// (SCAN_BAD_NON_FINITE_OR_NEGATIVE; -0 is not) or outside [-1, 1] (SCAN_BAD_OUTSIDE_UNIT), out[SCAN_DIFFERS] |= some f[i] != f[0]
 // (the comparison of fieldIsUniform: -0 == 0, a NaN differs from everything), out[SCAN_FIRST] = the bits of f[0]
 __global__ __launch_bounds__(FBS) void k_field_scan(const float* __restrict__ f, int64_t n, int badMode, uint32_t* __restrict__ out) {
     const float v0 = f[0];
@@ -73,7 +73,8 @@ __global__ __launch_bounds__(FBS) void k_field_scan(const float* __restrict__ f,
         const float v = f[i];
         differs |= v != v0;
         const bool isBad = (badMode >= SCAN_BAD_NON_FINITE && (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u) ||
-                           (badMode == SCAN_BAD_NON_FINITE_OR_NEGATIVE && v < 0.f);
+                           (badMode == SCAN_BAD_NON_FINITE_OR_NEGATIVE && v < 0.f) ||
+                           (badMode == SCAN_BAD_OUTSIDE_UNIT && !(v >= -1.f && v <= 1.f));
         if (isBad && (uint32_t)i < bad) bad = (uint32_t)i;
     }
     const bool any = __any(differs);

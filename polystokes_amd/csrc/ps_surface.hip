@@ -9,6 +9,9 @@
 //
 // Free-surface fields (ps_upload_surface_fields): the ghost pressure becomes the per-cell q_c = sigma_c kappa_c + P_c (k_surface_ghost_pressure,
 // fp64), and the same two force kernels read q with scale = dt in the place of kappa_c with scale = dt sigma ("Free-surface fields").
+//
+// Contact angles (ps_set_contact_angle): the two curvature kernels read the SDF that ps_wetting.hip rewrote inside the solid in the place of
+// the uploaded one; nothing else here changes ("Contact angles").
 #include "ps_context.hpp"
 #include "ps_setup_util.hpp"
 
@@ -239,6 +242,7 @@ void ps_context::applySurfaceTension() {
     surfFieldsUsed = (surfSigmaField ? 1 : 0) | (surfPressureField ? 2 : 0);
     const bool curvature = surfSigmaField || sigmaUsed != 0.;
     if (!curvature) { kappaRaw.free(); kappaC.free(); }
+    const float* phi = applyContactAngle(curvature);   // ps_wetting.hip: the SDF rewritten inside the solid, or surface.p (the angle off: nothing launched)
     if (!curvature && surfFieldsUsed == 0) {
         stReduced.free();
         return;
@@ -248,9 +252,8 @@ void ps_context::applySurfaceTension() {
     stReduced.alloc(1);
     HIP_CHECK(hipMemsetAsync(stReduced.p, 0, sizeof(int32_t), stream));
     if (curvature) {
-        hipLaunchKernelGGL(k_surface_curvature, dim3(gridFor(n, BS)), dim3(BS), 0, stream, g, (const float*)surface.p, invDx, kappaRaw.p);
-        hipLaunchKernelGGL(k_surface_curvature_at_interface, dim3(gridFor(n, BS)), dim3(BS), 0, stream, g, (const float*)surface.p,
-                           (const float*)kappaRaw.p, invDx, kappaC.p);
+        hipLaunchKernelGGL(k_surface_curvature, dim3(gridFor(n, BS)), dim3(BS), 0, stream, g, phi, invDx, kappaRaw.p);
+        hipLaunchKernelGGL(k_surface_curvature_at_interface, dim3(gridFor(n, BS)), dim3(BS), 0, stream, g, phi, (const float*)kappaRaw.p, invDx, kappaC.p);
     }
     SurfArgs A;
     A.g = g; A.invDx = invDx; A.scale = surfFieldsUsed ? dt : dt * sigmaUsed;

@@ -68,7 +68,9 @@ def local_scene(scene, slab):
                density_field=_cut_opt(scene, "density_field", cut),
                surface_tension=getattr(scene, "surface_tension", None),
                surface_sigma_field=_cut_opt(scene, "surface_sigma_field", cut),
-               surface_pressure_field=_cut_opt(scene, "surface_pressure_field", cut))
+               surface_pressure_field=_cut_opt(scene, "surface_pressure_field", cut),
+               contact_angle=getattr(scene, "contact_angle", None),
+               contact_cosine_field=_cut_opt(scene, "contact_cosine_field", cut))
     return sc
 
 
@@ -124,7 +126,9 @@ def local_scene_brick(scene, b):
                  density_field=_cut_opt(scene, "density_field", cut),
                  surface_tension=getattr(scene, "surface_tension", None),
                  surface_sigma_field=_cut_opt(scene, "surface_sigma_field", cut),
-                 surface_pressure_field=_cut_opt(scene, "surface_pressure_field", cut))
+                 surface_pressure_field=_cut_opt(scene, "surface_pressure_field", cut),
+                 contact_angle=getattr(scene, "contact_angle", None),
+                 contact_cosine_field=_cut_opt(scene, "contact_cosine_field", cut))
 
 
 def merge_faces_brick(global_out, local_out, owned_mask, b, axis):

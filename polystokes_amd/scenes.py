@@ -252,3 +252,17 @@ def moving_floor(n=32, V=1.0, viscosity=100.0, dt=1.0 / 24.0, tile=8, pad=2, flo
     """Liquid at rest on a solid floor whose collision velocity is u_x = V.  A free-slip floor leaves the liquid at rest; a no-slip
     one drags it along."""
     return _floor_box(n, floor, height, margin, 0.0, float(V), viscosity, dt, f"moving_floor{n}", tile, pad)
+
+
+def sessile_drop(n=32, radius=0.3, floor=4, sigma=None, contact_angle=None, tile=8, pad=2, viscosity=50.0):
+    """A liquid hemisphere resting on a solid floor, no gravity: the floor is solid below the face plane y = floor cells, the ball of
+    `radius` has its centre on that plane at x = z = 0.5, and its SDF continues into the floor, so the liquid meets the floor at 90
+    degrees.  Under surface tension (Scene.surface_tension = sigma) with a contact angle (Scene.contact_angle, ps_set_contact_angle)
+    below 90 degrees the foot spreads, above it retracts.  None leaves either setting unset."""
+    dx, dt = 1.0 / n, 1.0 / 24.0
+    x, y, z = _centers(n, n, n, dx)
+    surface = np.sqrt((x - 0.5) ** 2 + (y - floor * dx) ** 2 + (z - 0.5) ** 2) - radius
+    collision = y - floor * dx + 0.0 * x + 0.0 * z
+    sc = Scene(n, n, n, dx, dt, 1000.0, [0.0, 0.0, 0.0], surface, collision, viscosity, name=f"sessile_drop{n}", surface_tension=sigma,
+               contact_angle=contact_angle)
+    return sc, default_params(tileSize=tile, tilePadding=pad)

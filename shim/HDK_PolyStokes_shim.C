@@ -79,6 +79,7 @@ const ParmRow theRows[] = {
     {'F', "surfaceTension",             "Surface Tension",                  nullptr,            0},
     {'S', "surfaceSigmaField",          "Surface Tension Field",            "",                 0},
     {'S', "surfacePressureField",       "Ambient Pressure Field",           "",                 0},
+    {'F', "contactAngle",               "Contact Angle",                    nullptr,            -1},
     {'T', "solidFreeSlip",              "Free-Slip Solids",                 nullptr,            0},
     {'T', "nonNewtonian",               "Non-Newtonian Viscosity",          nullptr,            0},
     {'F', "flowIndex",                  "Flow Index",                       nullptr,            1},
@@ -231,6 +232,10 @@ bool HDK_PolyStokes::solveGasSubclass(SIM_Engine& engine, SIM_Object* obj, SIM_T
     if ((sigmaField && !sigmaField->isAligned(surfaceField)) || (ambientField && !ambientField->isAligned(surfaceField)))
         return fail("Free-surface fields must align with the surface field.", UT_ERROR_ABORT);
     const bool surfaceFields = sigmaField || ambientField;
+    // shim-only: the angle (degrees, inside the liquid) at which the surface meets the colliders (ps_set_contact_angle, a context setting
+    // read by the curvature of the surface tension: a negative value, the default, is off and launches nothing extra).  A refused angle
+    // (above 180 or not finite) aborts with the library's reason.
+    if (ps_set_contact_angle(myCtx, (double)getContactAngle()) != PS_SUCCESS) return fail(ps_last_error(myCtx), UT_ERROR_ABORT);
     // shim-only: free-slip colliders (ps_set_solid_boundary, a context setting: no shear stress on the edges a solid cuts), set when the
     // toggle changes.  Off keeps the reference's no-slip walls.
     const int32_t solidMode = getSolidFreeSlip() ? PS_SOLID_FREE_SLIP : PS_SOLID_NO_SLIP;

@@ -50,6 +50,7 @@ public:
     GET_DATA_FUNC_F("surfaceTension",                   SurfaceTension);          // sigma of the curvature pressure jump (0)
     GET_DATA_FUNC_S("surfaceSigmaField",                SurfaceSigmaField);       // scalar field of sigma per cell -> ps_upload_surface_fields ("")
     GET_DATA_FUNC_S("surfacePressureField",             SurfacePressureField);    // scalar field of the ambient pressure per cell ("")
+    GET_DATA_FUNC_F("contactAngle",                     ContactAngle);            // ps_set_contact_angle(degrees); negative: off (-1)
     GET_DATA_FUNC_B("solidFreeSlip",                    SolidFreeSlip);           // ps_set_solid_boundary(PS_SOLID_FREE_SLIP) (0)
     GET_DATA_FUNC_B("nonNewtonian",                     NonNewtonian);            // ps_set_rheology(PS_RHEOLOGY_HERSCHEL_BULKLEY) (0)
     GET_DATA_FUNC_F("flowIndex",                        FlowIndex);               // n of the law (1)
