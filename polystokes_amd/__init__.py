@@ -343,14 +343,10 @@ class Solver:
         """ps_upload_contact_cosine_field: cos(theta) per cell, painted into the solid cells, for the grid of the last upload (None drops
         it); `field` is a host array or a torch tensor on the host.  Returns the ps_result (INVALID for a value outside [-1, 1], the reason
         in last_error()); FAILED raises."""
-        if field is None:
-            return self._check(self.L.ps_upload_contact_cosine_field(self.h, None), allow=(1, -2))
         if getattr(field, "is_cuda", False):
             raise TypeError("a device tensor goes through upload_contact_cosine_field_device")
-        f = np.ascontiguousarray(field.numpy() if hasattr(field, "data_ptr") else field, dtype=np.float32)
-        if self.scene is not None and f.size != self.scene.nx * self.scene.ny * self.scene.nz:
-            raise ValueError("the field must hold one value per cell")
-        return self._check(self.L.ps_upload_contact_cosine_field(self.h, f.ctypes.data), allow=(1, -2))
+        f = self._host_cell_field(field.numpy() if hasattr(field, "data_ptr") else field, np.float32, "the field must hold one value per cell")
+        return self._check(self.L.ps_upload_contact_cosine_field(self.h, None if f is None else f.ctypes.data), allow=(1, -2))
 
     def upload_contact_cosine_field_device(self, field, layout=0, stream=None):
         """ps_upload_contact_cosine_field_device (None drops the field): `field` is fp32 device memory in `layout` (a DeviceBuffer, a torch
@@ -397,12 +393,8 @@ class Solver:
     def upload_collider_ids(self, ids):
         """ps_upload_collider_ids: the collider of every cell (int32, shape (nz, ny, nx)) for the grid of the last upload; None drops the
         field.  Returns the ps_result (INVALID before any upload); FAILED raises."""
-        if ids is None:
-            return self._check(self.L.ps_upload_collider_ids(self.h, None), allow=(1, -2))
-        f = np.ascontiguousarray(ids, dtype=np.int32)
-        if self.scene is not None and f.size != self.scene.nx * self.scene.ny * self.scene.nz:
-            raise ValueError("ids must hold one value per cell")
-        return self._check(self.L.ps_upload_collider_ids(self.h, f.ctypes.data), allow=(1, -2))
+        f = self._host_cell_field(ids, np.int32, "ids must hold one value per cell")
+        return self._check(self.L.ps_upload_collider_ids(self.h, None if f is None else f.ctypes.data), allow=(1, -2))
 
     def upload_collider_ids_device(self, ids, layout=0, stream=None):
         """ps_upload_collider_ids_device (None drops the field): `ids` is int32 device memory in `layout`.  Returns the ps_result, INVALID
@@ -534,6 +526,21 @@ class Solver:
         if getattr(scene, "contact_cosine_field", None) is not None:
             self._check(self.upload_contact_cosine_field(scene.contact_cosine_field))
 
+    def _host_cell_field(self, field, dtype, wrong_size=None):
+        """A host cell field as the ABI takes it: None, or a contiguous array of `dtype` with one value per cell of the last upload's grid.
+        Another size raises ValueError(wrong_size), or whatever reshaping to the cell grid raises when no message is given."""
+        if field is None:
+            return None
+        f = np.ascontiguousarray(field, dtype=dtype)
+        if self.scene is None:
+            return f
+        sh = _abi.grid_shapes(self.scene.nx, self.scene.ny, self.scene.nz)["center"]
+        if wrong_size is not None:
+            if f.size != sh[0] * sh[1] * sh[2]:
+                raise ValueError(wrong_size)
+            return f
+        return f if f.shape == sh else f.reshape(sh)
+
     def _scene_surface_tension(self, scene):
         """Scene.surface_tension and Scene.contact_angle (None: the context keeps its setting) -> ps_set_surface_tension,
         ps_set_contact_angle; a refused value raises."""
@@ -547,27 +554,16 @@ class Solver:
     def upload_density_field(self, field):
         """ps_upload_density_field: a cell density field for the grid of the last upload (None drops it).  Returns the ps_result
         (INVALID for a refused field, the reason in last_error()); FAILED raises."""
-        if field is None:
-            return self._check(self.L.ps_upload_density_field(self.h, None), allow=(1, -2))
-        sh = _abi.grid_shapes(self.scene.nx, self.scene.ny, self.scene.nz)["center"] if self.scene is not None else None
-        f = np.ascontiguousarray(field, dtype=np.float32)
-        if sh is not None and f.shape != sh:
-            f = f.reshape(sh)
-        self._density_keep = f
-        return self._check(self.L.ps_upload_density_field(self.h, f.ctypes.data), allow=(1, -2))
+        f = self._host_cell_field(field, np.float32)
+        if f is not None:
+            self._density_keep = f
+        return self._check(self.L.ps_upload_density_field(self.h, None if f is None else f.ctypes.data), allow=(1, -2))
 
     def upload_surface_fields(self, sigma=None, pressure=None):
         """ps_upload_surface_fields: the free-surface cell fields for the grid of the last upload — the surface-tension coefficient (None:
         the scalar of set_surface_tension) and the ambient pressure (None: 0); both None drops them.  Returns the ps_result (INVALID for a
         refused field, the reason in last_error()); FAILED raises."""
-        sh = _abi.grid_shapes(self.scene.nx, self.scene.ny, self.scene.nz)["center"] if self.scene is not None else None
-
-        def host(field):
-            if field is None:
-                return None
-            f = np.ascontiguousarray(field, dtype=np.float32)
-            return f.reshape(sh) if sh is not None and f.shape != sh else f
-        keep = host(sigma), host(pressure)
+        keep = self._host_cell_field(sigma, np.float32), self._host_cell_field(pressure, np.float32)
         sf = _abi.SurfaceFields(*[None if f is None else f.ctypes.data for f in keep])
         return self._check(self.L.ps_upload_surface_fields(self.h, C.byref(sf)), allow=(1, -2))
 
@@ -796,36 +792,6 @@ class Group:
             r.stats = self.stats
         return rc
 
-    def set_solid_boundary(self, mode):
-        """ps_set_solid_boundary on every rank (a context setting: it holds for every later step of the group)."""
-        rc = [r.set_solid_boundary(mode) for r in self.ranks]
-        return rc[0]
-
-    def set_contact_angle(self, degrees):
-        """ps_set_contact_angle on every rank (a context setting; a rank rewrites the SDF on its own grid, the halo block covers the reach)."""
-        rc = [r.set_contact_angle(degrees) for r in self.ranks]
-        return rc[0]
-
-    def set_solve_precision(self, mode):
-        """ps_set_solve_precision on every rank (a decomposition solves in fp64 whatever the setting: "solvePrecisionUsed" reads 0)."""
-        rc = [r.set_solve_precision(mode) for r in self.ranks]
-        return rc[0]
-
-    def set_velocity_extrapolation(self, layers):
-        """ps_set_velocity_extrapolation on every rank (a decomposition ignores the setting: "velocityExtrapolation" reads 0)."""
-        rc = [r.set_velocity_extrapolation(layers) for r in self.ranks]
-        return rc[0]
-
-    def set_collider_loads(self, count, pivots=None):
-        """ps_set_collider_loads on every rank (a decomposition ignores the setting: "colliderLoads" reads 0)."""
-        rc = [r.set_collider_loads(count, pivots) for r in self.ranks]
-        return rc[0]
-
-    def set_rheology(self, *args, **kw):
-        """ps_set_rheology on every rank (a context setting: it holds for every later step of the group)."""
-        rc = [r.set_rheology(*args, **kw) for r in self.ranks]
-        return rc[0]
-
     def solve_scene(self, scene, params):
         """Partition `scene` into slabs, run the distributed step, merge the owned faces into global arrays."""
         from . import partition
@@ -879,3 +845,19 @@ class Group:
             self.close()
         except Exception:
             pass
+
+
+def _forward_to_ranks(name, note):
+    def setter(self, *args, **kw):
+        return [getattr(r, name)(*args, **kw) for r in self.ranks][0]
+    setter.__name__, setter.__doc__ = name, "ps_%s on every rank (%s)." % (name, note)
+    return setter
+
+
+for _name, _note in (("set_solid_boundary", "a context setting: it holds for every later step of the group"),
+                     ("set_contact_angle", "a context setting; a rank rewrites the SDF on its own grid, the halo block covers the reach"),
+                     ("set_solve_precision", 'a decomposition solves in fp64 whatever the setting: "solvePrecisionUsed" reads 0'),
+                     ("set_velocity_extrapolation", 'a decomposition ignores the setting: "velocityExtrapolation" reads 0'),
+                     ("set_collider_loads", 'a decomposition ignores the setting: "colliderLoads" reads 0'),
+                     ("set_rheology", "a context setting: it holds for every later step of the group")):
+    setattr(Group, _name, _forward_to_ranks(_name, _note))

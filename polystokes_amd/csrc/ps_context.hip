@@ -101,28 +101,13 @@ void ps_context::uploadReset(const ps_params* p, const ps_fields_in* in) {
     dx = in->dx; invDx = 1. / dx; dt = in->dt; invDt = 1. / dt; rho = (double)in->density;
     rhoScalar = rho; densField = false;   // every upload drops a density field (ps_upload_density_field): it described the previous grid
     HIP_CHECK(hipSetDevice(device));
-    if (surfSigma.p || surfPressure.p || surfQ.p) {   // ... and the free-surface fields (ps_upload_surface_fields), released here
-        HIP_CHECK(hipStreamSynchronize(stream));
-        dropSurfaceFields();
-        drainDeferred(true);
-    }
-    if (contactCos.p) {                                   // ... and the contact cosine field (ps_upload_contact_cosine_field)
-        HIP_CHECK(hipStreamSynchronize(stream));
-        dropContactCosine();
-        drainDeferred(true);
-    }
+    bool dropped = dropSurfaceFields();                   // ... and the free-surface fields (ps_upload_surface_fields)
+    dropped |= dropContactCosine();                       // ... and the contact cosine field (ps_upload_contact_cosine_field)
     for (int a = 0; a < 3; ++a) orig[a] = in->orig[a];   // (the default pivot of ps_set_collider_loads)
     forgetLoads();                                        // the loads of an earlier step described the previous fields
-    if (colliderIds.p) {                                  // ... and so did the collider ids (ps_upload_collider_ids), released here
-        HIP_CHECK(hipStreamSynchronize(stream));
-        dropColliderIds();
-        drainDeferred(true);
-    }
-    if (pocketsHave || pocketIds.p) {                     // ... and the air pocket labels (ps_label_air_pockets)
-        HIP_CHECK(hipStreamSynchronize(stream));
-        dropAirPockets();
-        drainDeferred(true);
-    }
+    dropped |= dropColliderIds();                         // ... and so did the collider ids (ps_upload_collider_ids)
+    dropped |= dropAirPockets();                          // ... and the air pocket labels (ps_label_air_pockets)
+    releaseIdle(dropped);                                 // one synchronisation for whatever was present, none when nothing was
 }
 
 void ps_context::ingestHost(const ps_fields_in* in) {
@@ -171,31 +156,6 @@ void ps_context::upload(const ps_params* p, const ps_fields_in* in) {
     uploadReset(p, in);
     ingestHost(in);
     uploadTail();
-}
-
-// ps_upload_density_field.  A constant field (all values equal) runs the scalar path at its clamped value, as a constant viscosity skips
-// the sampling (viscUniform); any other field is uploaded and sampled per face by the setup kernels (ps_setup_util.hpp: FaceDensity, handed out by densSource).
-// Returns the reason an input is refused (the field is then dropped), or an empty string.
-std::string ps_context::uploadDensity(const float* field) {
-    densField = false;
-    densFieldHost = 0;
-    rho = rhoScalar;
-    if (!field) return {};
-    const double lo = P.mindensity, hi = P.maxdensity;
-    if (!std::isfinite(lo) || !std::isfinite(hi) || !(lo > 0.) || hi < lo)
-        return "ps_upload_density_field: mindensity must be positive and maxdensity at least mindensity, both finite";
-    const int64_t nc = g.count(0);
-    for (int64_t i = 0; i < nc; ++i)
-        if (!std::isfinite(field[i])) return "ps_upload_density_field: non-finite value at cell " + std::to_string(i);
-    float v0;
-    const bool same = fieldIsUniform(field, nc, &v0);
-    densMin = lo; densMax = hi;
-    if (same) { const double v = (double)v0; rho = v < lo ? lo : (v > hi ? hi : v); return {}; }
-    HIP_CHECK(hipSetDevice(device));
-    uploadField(density, field, nc, stream);
-    HIP_CHECK(hipStreamSynchronize(stream));
-    densField = true;
-    return {};
 }
 
 void ps_context::fillDimData(ps_stats* st) const {   // Solver.cpp:578-593
@@ -436,14 +396,9 @@ void ps_context::registerArrays() {
     regHost("surfaceFields", &surfFieldsUsed, 1, 4);   // bit 0 / 1: the last setup used a sigma / pressure field (ps_upload_surface_fields)
     if (sigmaUsed != 0. || (surfFieldsUsed & 1)) reg("surfaceCurvature", kappaC.p, g.count(0), 4);
     if (sigmaUsed != 0. || surfFieldsUsed != 0) reg("surfaceTensionReducedFaces", stReduced.p, 1, 4);
-    if (surfFieldsUsed != 0 && surfQ.p) reg("surfaceGhostPressure", surfQ.p, g.count(0), 8);   // q_c of the last setup (gone once the fields are dropped)
+    registerSurfaceFieldArrays();                      // q_c of the last setup (gone once the fields are dropped)
     regHost("contactAngle", &contactDegUsed, 1, 8);   // the degrees the last setup used (ps_set_contact_angle): -1 for none or the field alone
-    if (contactRan && wetPhi[0].p) {                   // the last setup rewrote the SDF inside the solid (ps_wetting.hip)
-        regHost("contactCosine", &contactCosUsed, 1, 8);
-        regHost("contactField", &contactFieldUsed, 1, 4);
-        reg("contactCells", wetCount.p, 1, 4);
-        reg("surfaceWetted", wetPhi[0].p, g.count(0), 4);
-    }
+    registerWettingArrays();                           // the last setup rewrote the SDF inside the solid (ps_wetting.hip)
     regHost("solidBoundary", &solidBoundaryUsed, 1, 4);   // the mode of the last setup (ps_set_solid_boundary)
     if (solidBoundaryUsed == PS_SOLID_FREE_SLIP) reg("solidSlipEdges", slipEdges.p, 1, 4);
     regHost("rheologyModel", &rheoModelUsed, 1, 4);   // the model of the last setup (ps_set_rheology)
@@ -453,19 +408,9 @@ void ps_context::registerArrays() {
         regHost("rheologyIterations", rheoIters.data(), (int64_t)rheoIters.size(), 4);   // PCG iterations of each solve of the last step
     }
     regHost("velocityExtrapolation", &extrapUsedHost, 1, 4);   // layers the last step ran (ps_set_velocity_extrapolation)
-    if (extrapUsedHost > 0) {
-        static const char* axn[3] = {"X", "Y", "Z"};
-        for (int a = 0; a < 3; ++a) reg(std::string("extrapolationLayer") + axn[a], extrapLayer[a].p, g.count(1 + a), 1);
-        reg("extrapolationCounts", extrapCounts.p, extrapUsedHost, 4);   // faces assigned by each sweep, the three axes together
-    }
+    registerExtrapolationArrays();
     regHost("colliderLoads", &loadsUsedHost, 1, 4);   // the count the last step computed loads for (ps_set_collider_loads)
-    if (loadsUsedHost > 0) {
-        const int64_t nc = loadsUsedHost;
-        reg("colliderForce", loadsOut.p, 3 * nc, 8);
-        reg("colliderTorque", loadsOut.p + 3 * nc, 3 * nc, 8);
-        reg("colliderLoadScale", loadsOut.p + 6 * nc, 6 * nc, 8);   // A_k, B_k per collider
-        reg("colliderLoadTerms", loadsTerms.p, nc + 1, 4);          // terms per collider, then the dropped terms
-    }
+    registerLoadArrays();
     if (P.preconditioner == PS_PRE_DIAGONAL) regp("dinv", dinv.p, nSystem, permSys.p, 0);
     if (isSolved) {
         regp("recoveredActiveVelocity", recovered.p, nActiveVs, permRow.p, 0);
@@ -530,6 +475,36 @@ void ps_context::registerArrays() {
     }
 
 static std::string g_createError;
+
+// ---- the shared openings and endings of the optional-field entry points ----
+// "call ps_upload_fields first" under the HOST function's name, also from its _device twin
+static bool notUploaded(ps_context* c, const char* hostName) {
+    if (c->uploaded) return false;
+    c->err = std::string(hostName) + ": call ps_upload_fields first";
+    return true;
+}
+// The refusals of a _device entry point, decided before anything of the context changes and before anything is read through a pointer:
+// not uploaded (hostName; nullptr: the caller has its own rule), then under the _device name the layout and the pointers in list order.
+// true: refused, the reason is in c->err.
+struct DevicePtr { const void* p; int64_t count; const char* label; bool mayBeNull; };
+template <size_t N> static bool refuseDeviceCall(ps_context* c, const char* hostName, const char* deviceName, int layout, const DevicePtr (&ptrs)[N]) {
+    if (hostName && notUploaded(c, hostName)) return true;
+    HIP_CHECK(hipSetDevice(c->device));
+    std::string why;
+    if (const char* m = ps_context::layoutRefusal(layout)) why = m;
+    for (size_t q = 0; q < N && why.empty(); ++q) {
+        if (ptrs[q].p) why = c->checkDeviceField(ptrs[q].p, ptrs[q].count, ptrs[q].label);
+        else if (!ptrs[q].mayBeNull) why = std::string(ptrs[q].label) + ": the pointer is null";
+    }
+    if (!why.empty()) c->err = std::string(deviceName) + ": " + why;
+    return !why.empty();
+}
+// the end of an upload: its value refusal under the host function's name, or success
+static int32_t uploadResult(ps_context* c, const char* prefix, const std::string& why) {
+    if (why.empty()) return PS_SUCCESS;
+    c->err = prefix + why;
+    return PS_INVALID;
+}
 
 // ---- MatrixMarket export (Solver.cpp:533-606; MarketIO.h:310-380) --------------------------------
 static bool writeMarketVector(const std::string& fn, const std::vector<double>& v) {
@@ -773,19 +748,15 @@ int32_t ps_download_fields(ps_context* c, ps_fields_out* out) {
 int32_t ps_upload_density_field(ps_context* c, const float* density) {
     if (!c) return PS_FAILED;
     PS_TRY(c, {
-        if (!c->uploaded) { c->err = "ps_upload_density_field: call ps_upload_fields first"; return PS_INVALID; }
-        const std::string why = c->uploadDensity(density);
-        if (!why.empty()) { c->err = why; return PS_INVALID; }
-        return PS_SUCCESS;
+        if (notUploaded(c, "ps_upload_density_field")) return PS_INVALID;
+        return uploadResult(c, "", c->uploadDensity(density, false, 0, nullptr));   // (its refusals carry the prefix)
     })
 }
 int32_t ps_upload_surface_fields(ps_context* c, const ps_surface_fields* f) {
     if (!c) return PS_FAILED;
     PS_TRY(c, {
-        if (!c->uploaded) { c->err = "ps_upload_surface_fields: call ps_upload_fields first"; return PS_INVALID; }
-        const std::string why = c->uploadSurfaceFields(f, false, 0, nullptr);
-        if (!why.empty()) { c->err = "ps_upload_surface_fields: " + why; return PS_INVALID; }
-        return PS_SUCCESS;
+        if (notUploaded(c, "ps_upload_surface_fields")) return PS_INVALID;
+        return uploadResult(c, "ps_upload_surface_fields: ", c->uploadSurfaceFields(f, false, 0, nullptr));
     })
 }
 int32_t ps_set_surface_tension(ps_context* c, double sigma) {
@@ -808,22 +779,15 @@ int32_t ps_set_contact_angle(ps_context* c, double degrees) {
         }
         c->contactDegSet = degrees < 0. ? -1. : degrees;   // read by the next setup that computes the curvature (applyContactAngle)
         c->contactCosSet = degrees < 0. ? 0. : (degrees == 90. ? 0. : std::cos(degrees * (3.14159265358979323846 / 180.)));
-        if (degrees < 0. && !c->contactCosField && c->wetPhi[0].p) {   // the buffers go with the setting: dropped and, with the stream idle, released here
-            HIP_CHECK(hipSetDevice(c->device));
-            HIP_CHECK(hipStreamSynchronize(c->stream));
-            c->dropWetting();
-            c->drainDeferred(true);
-        }
+        if (degrees < 0. && !c->contactCosField) c->releaseIdle(c->dropWetting());   // the buffers go with the setting: dropped and, with the stream idle, released here
         return PS_SUCCESS;
     })
 }
 int32_t ps_upload_contact_cosine_field(ps_context* c, const float* cosTheta) {
     if (!c) return PS_FAILED;
     PS_TRY(c, {
-        if (!c->uploaded) { c->err = "ps_upload_contact_cosine_field: call ps_upload_fields first"; return PS_INVALID; }
-        const std::string why = c->uploadContactCosine(cosTheta, false, 0, nullptr);
-        if (!why.empty()) { c->err = "ps_upload_contact_cosine_field: " + why; return PS_INVALID; }
-        return PS_SUCCESS;
+        if (notUploaded(c, "ps_upload_contact_cosine_field")) return PS_INVALID;
+        return uploadResult(c, "ps_upload_contact_cosine_field: ", c->uploadContactCosine(cosTheta, false, 0, nullptr));
     })
 }
 int32_t ps_set_solid_boundary(ps_context* c, int32_t mode) {
@@ -845,12 +809,7 @@ int32_t ps_set_solve_precision(ps_context* c, int32_t mode) {
             return PS_INVALID;
         }
         c->solvePrecisionSet = mode;   // read by every later PCG solve (ps_context::solve)
-        if (mode == PS_PRECISION_FP64 && c->d32.p) {   // the fp32 vectors go with the mode: dropped and, with the stream idle, released here
-            HIP_CHECK(hipSetDevice(c->device));
-            HIP_CHECK(hipStreamSynchronize(c->stream));
-            c->dropMixedBuffers();
-            c->drainDeferred(true);
-        }
+        if (mode == PS_PRECISION_FP64) c->releaseIdle(c->dropMixedBuffers());   // the fp32 vectors go with the mode: dropped and, with the stream idle, released here
         return PS_SUCCESS;
     })
 }
@@ -862,13 +821,7 @@ int32_t ps_set_velocity_extrapolation(ps_context* c, int32_t layers) {
             return PS_INVALID;
         }
         c->extrapSet = layers;   // read by every later step that writes the velocity (solveStage)
-        if (layers == 0 && c->extrapCounts.p) {   // the layer buffers go with the setting (and their arrays): dropped and, with the stream idle, released here
-            HIP_CHECK(hipSetDevice(c->device));
-            HIP_CHECK(hipStreamSynchronize(c->stream));
-            for (const char* n : {"extrapolationLayerX", "extrapolationLayerY", "extrapolationLayerZ", "extrapolationCounts"}) c->arrays.erase(n);
-            c->dropExtrapolationBuffers();
-            c->drainDeferred(true);
-        }
+        if (layers == 0) c->releaseIdle(c->dropExtrapolation());   // the layer buffers go with the setting (and their arrays): dropped and, with the stream idle, released here
         return PS_SUCCESS;
     })
 }
@@ -885,22 +838,15 @@ int32_t ps_set_collider_loads(ps_context* c, const ps_collider_loads* l) {
         c->loadsCount = l->count;   // read by every later step that solves and writes the velocity (solveStage)
         if (l->pivots) c->loadsPivots.assign(l->pivots, l->pivots + 3 * l->count); else c->loadsPivots.clear();
         c->forgetLoads();           // what an earlier step computed answered another setting
-        if (l->count == 0 && c->loadsOut.p) {   // the buffers go with the setting: dropped and, with the stream idle, released here
-            HIP_CHECK(hipSetDevice(c->device));
-            HIP_CHECK(hipStreamSynchronize(c->stream));
-            c->dropLoadBuffers();
-            c->drainDeferred(true);
-        }
+        if (l->count == 0) c->releaseIdle(c->dropLoadBuffers());   // the buffers go with the setting: dropped and, with the stream idle, released here
         return PS_SUCCESS;
     })
 }
 int32_t ps_upload_collider_ids(ps_context* c, const int32_t* ids) {
     if (!c) return PS_FAILED;
     PS_TRY(c, {
-        if (!c->uploaded) { c->err = "ps_upload_collider_ids: call ps_upload_fields first"; return PS_INVALID; }
-        const std::string why = c->uploadColliderIds(ids, false, 0, nullptr);
-        if (!why.empty()) { c->err = "ps_upload_collider_ids: " + why; return PS_INVALID; }
-        return PS_SUCCESS;
+        if (notUploaded(c, "ps_upload_collider_ids")) return PS_INVALID;
+        return uploadResult(c, "ps_upload_collider_ids: ", c->uploadColliderIds(ids, false, 0, nullptr));
     })
 }
 int32_t ps_get_collider_loads(ps_context* c, double* out, int64_t out_len) {
@@ -914,7 +860,7 @@ int32_t ps_get_collider_loads(ps_context* c, double* out, int64_t out_len) {
 int32_t ps_label_air_pockets(ps_context* c, int32_t* count) {
     if (!c) return PS_FAILED;
     PS_TRY(c, {
-        if (!c->uploaded) { c->err = "ps_label_air_pockets: call ps_upload_fields first"; return PS_INVALID; }
+        if (notUploaded(c, "ps_label_air_pockets")) return PS_INVALID;
         c->labelAirPockets();
         if (count) *count = c->pocketCount;
         return PS_SUCCESS;
@@ -936,12 +882,8 @@ int32_t ps_download_air_pocket_ids_device(ps_context* c, int32_t* ids, int32_t l
     if (!c) return PS_FAILED;
     PS_TRY(c, {
         if (!c->pocketsHave) throw Error("ps_download_air_pocket_ids: there are no air pocket labels (ps_label_air_pockets after the last upload)");
-        HIP_CHECK(hipSetDevice(c->device));
-        std::string why;
-        if (const char* m = ps_context::layoutRefusal(layout)) why = m;
-        else if (!ids) why = "ids: the pointer is null";
-        else why = c->checkDeviceField(ids, c->g.count(0), "ids");
-        if (!why.empty()) { c->err = "ps_download_air_pocket_ids_device: " + why; return PS_INVALID; }
+        const DevicePtr ptrs[] = {{ids, c->g.count(0), "ids", false}};
+        if (refuseDeviceCall(c, nullptr, "ps_download_air_pocket_ids_device", layout, ptrs)) return PS_INVALID;
         c->copyAirPocketIds(ids, true, layout, (hipStream_t)stream);
         return PS_SUCCESS;
     })
@@ -1045,64 +987,36 @@ int32_t ps_upload_fields_device(ps_context* c, const ps_params* p, const ps_fiel
 int32_t ps_upload_density_field_device(ps_context* c, const float* density, int32_t layout, void* stream) {
     if (!c) return PS_FAILED;
     PS_TRY(c, {
-        if (!c->uploaded) { c->err = "ps_upload_density_field: call ps_upload_fields first"; return PS_INVALID; }
-        HIP_CHECK(hipSetDevice(c->device));
-        std::string why;
-        if (const char* m = ps_context::layoutRefusal(layout)) why = m;
-        else if (density) why = c->checkDeviceField(density, c->g.count(0), "density");
-        if (!why.empty()) { c->err = "ps_upload_density_field_device: " + why; return PS_INVALID; }
-        why = c->uploadDensityDevice(density, layout, (hipStream_t)stream);
-        if (!why.empty()) { c->err = why; return PS_INVALID; }
-        return PS_SUCCESS;
+        const DevicePtr ptrs[] = {{density, c->g.count(0), "density", true}};
+        if (refuseDeviceCall(c, "ps_upload_density_field", "ps_upload_density_field_device", layout, ptrs)) return PS_INVALID;
+        return uploadResult(c, "", c->uploadDensity(density, true, layout, (hipStream_t)stream));   // (its refusals carry the prefix)
     })
 }
 int32_t ps_upload_surface_fields_device(ps_context* c, const ps_surface_fields* f, int32_t layout, void* stream) {
     if (!c) return PS_FAILED;
     PS_TRY(c, {
-        if (!c->uploaded) { c->err = "ps_upload_surface_fields: call ps_upload_fields first"; return PS_INVALID; }
-        HIP_CHECK(hipSetDevice(c->device));
-        std::string why;
-        if (const char* m = ps_context::layoutRefusal(layout)) why = m;
-        if (why.empty() && f && f->sigma) why = c->checkDeviceField(f->sigma, c->g.count(0), "sigma");
-        if (why.empty() && f && f->pressure) why = c->checkDeviceField(f->pressure, c->g.count(0), "pressure");
-        if (!why.empty()) {   // (a refused call drops both fields, like a refused value; nothing was read through a pointer)
-            HIP_CHECK(hipStreamSynchronize(c->stream));
-            c->dropSurfaceFields();
-            c->drainDeferred(true);
-            c->err = "ps_upload_surface_fields_device: " + why;
+        const DevicePtr ptrs[] = {{f ? f->sigma : nullptr, c->g.count(0), "sigma", true}, {f ? f->pressure : nullptr, c->g.count(0), "pressure", true}};
+        if (refuseDeviceCall(c, "ps_upload_surface_fields", "ps_upload_surface_fields_device", layout, ptrs)) {
+            c->releaseIdle(c->dropSurfaceFields());   // (a refused call drops both fields, like a refused value; nothing was read through a pointer)
             return PS_INVALID;
         }
-        why = c->uploadSurfaceFields(f, true, layout, (hipStream_t)stream);
-        if (!why.empty()) { c->err = "ps_upload_surface_fields: " + why; return PS_INVALID; }
-        return PS_SUCCESS;
+        return uploadResult(c, "ps_upload_surface_fields: ", c->uploadSurfaceFields(f, true, layout, (hipStream_t)stream));
     })
 }
 int32_t ps_upload_collider_ids_device(ps_context* c, const int32_t* ids, int32_t layout, void* stream) {
     if (!c) return PS_FAILED;
     PS_TRY(c, {
-        if (!c->uploaded) { c->err = "ps_upload_collider_ids: call ps_upload_fields first"; return PS_INVALID; }
-        HIP_CHECK(hipSetDevice(c->device));
-        std::string why;
-        if (const char* m = ps_context::layoutRefusal(layout)) why = m;
-        else if (ids) why = c->checkDeviceField(ids, c->g.count(0), "ids");
-        if (!why.empty()) { c->err = "ps_upload_collider_ids_device: " + why; return PS_INVALID; }
-        why = c->uploadColliderIds(ids, true, layout, (hipStream_t)stream);
-        if (!why.empty()) { c->err = "ps_upload_collider_ids: " + why; return PS_INVALID; }
-        return PS_SUCCESS;
+        const DevicePtr ptrs[] = {{ids, c->g.count(0), "ids", true}};
+        if (refuseDeviceCall(c, "ps_upload_collider_ids", "ps_upload_collider_ids_device", layout, ptrs)) return PS_INVALID;
+        return uploadResult(c, "ps_upload_collider_ids: ", c->uploadColliderIds(ids, true, layout, (hipStream_t)stream));
     })
 }
 int32_t ps_upload_contact_cosine_field_device(ps_context* c, const float* cosTheta, int32_t layout, void* stream) {
     if (!c) return PS_FAILED;
     PS_TRY(c, {
-        if (!c->uploaded) { c->err = "ps_upload_contact_cosine_field: call ps_upload_fields first"; return PS_INVALID; }
-        HIP_CHECK(hipSetDevice(c->device));
-        std::string why;
-        if (const char* m = ps_context::layoutRefusal(layout)) why = m;
-        else if (cosTheta) why = c->checkDeviceField(cosTheta, c->g.count(0), "cosTheta");
-        if (!why.empty()) { c->err = "ps_upload_contact_cosine_field_device: " + why; return PS_INVALID; }
-        why = c->uploadContactCosine(cosTheta, true, layout, (hipStream_t)stream);
-        if (!why.empty()) { c->err = "ps_upload_contact_cosine_field: " + why; return PS_INVALID; }
-        return PS_SUCCESS;
+        const DevicePtr ptrs[] = {{cosTheta, c->g.count(0), "cosTheta", true}};
+        if (refuseDeviceCall(c, "ps_upload_contact_cosine_field", "ps_upload_contact_cosine_field_device", layout, ptrs)) return PS_INVALID;
+        return uploadResult(c, "ps_upload_contact_cosine_field: ", c->uploadContactCosine(cosTheta, true, layout, (hipStream_t)stream));
     })
 }
 int32_t ps_get_collider_loads_device(ps_context* c, double* dev, int64_t len, void* stream) {
@@ -1123,14 +1037,12 @@ int32_t ps_download_fields_device(ps_context* c, const ps_fields_out* out, int32
     if (!c || !out) return PS_FAILED;
     PS_TRY(c, {
         if (!c->uploaded) throw Error("ps_upload_fields has not been called");
-        HIP_CHECK(hipSetDevice(c->device));
-        std::string why;
-        if (const char* m = ps_context::layoutRefusal(layout)) why = m;
-        for (int a = 0; a < 3 && why.empty(); ++a) {
-            if (out->vel[a]) why = c->checkDeviceField(out->vel[a], c->g.count(1 + a), "out vel");
-            if (why.empty() && out->valid[a]) why = c->checkDeviceField(out->valid[a], c->g.count(1 + a), "out valid");
+        DevicePtr ptrs[6];
+        for (int a = 0; a < 3; ++a) {
+            ptrs[2 * a] = DevicePtr{out->vel[a], c->g.count(1 + a), "out vel", true};
+            ptrs[2 * a + 1] = DevicePtr{out->valid[a], c->g.count(1 + a), "out valid", true};
         }
-        if (!why.empty()) { c->err = "ps_download_fields_device: " + why; return PS_INVALID; }
+        if (refuseDeviceCall(c, nullptr, "ps_download_fields_device", layout, ptrs)) return PS_INVALID;
         c->downloadDevice(out, layout, (hipStream_t)stream);
         return PS_SUCCESS;
     })
@@ -1140,12 +1052,10 @@ int32_t ps_download_solution_fields_device(ps_context* c, const ps_solution_out*
     PS_TRY(c, {
         if (c->slabEnabled) throw Error("ps_download_solution_fields is a single-domain call");
         if (!c->isSetup || !c->isSolved) throw Error("ps_download_solution_fields: no solve since the last setup");
-        HIP_CHECK(hipSetDevice(c->device));
         const float* dst[7] = {out->pressure, out->tauDiag[0], out->tauDiag[1], out->tauDiag[2], out->tauEdge[0], out->tauEdge[1], out->tauEdge[2]};
-        std::string why;
-        if (const char* m = ps_context::layoutRefusal(layout)) why = m;
-        for (int q = 0; q < 7 && why.empty(); ++q) if (dst[q]) why = c->checkDeviceField(dst[q], c->solutionGridCount(q), "solution grid");
-        if (!why.empty()) { c->err = "ps_download_solution_fields_device: " + why; return PS_INVALID; }
+        DevicePtr ptrs[7];
+        for (int q = 0; q < 7; ++q) ptrs[q] = DevicePtr{dst[q], c->solutionGridCount(q), "solution grid", true};
+        if (refuseDeviceCall(c, nullptr, "ps_download_solution_fields_device", layout, ptrs)) return PS_INVALID;
         c->downloadSolutionDevice(out, layout, (hipStream_t)stream);
         return PS_SUCCESS;
     })

@@ -76,6 +76,10 @@ struct ArrayInfo {
     int64_t permOffset = 0;
     bool host = false;               // dptr is host memory of the context (no device copy behind it)
 };
+inline ArrayInfo hostArray(const void* p, int64_t count, int elem) { ArrayInfo a{p, count, elem}; a.host = true; return a; }
+// One entry of a feature's array list (ps_context::setArrays): the feature's register...Arrays() holds the one list of its names, and
+// registers or erases by it
+struct NamedArray { const char* name; ArrayInfo info; };
 
 // The slots of ps_context::counters (int32 each): flags and totals that kernels write and the host reads (readCounter / fetchCounters).
 // Every user clears its own slot before the launch; slots that one fetch reads are adjacent (asserted below).
@@ -129,6 +133,16 @@ void launchFieldsSwapXZ(const FieldTable& T, hipStream_t s);    // ... dst = src
 enum ScanWord { SCAN_BAD = 0, SCAN_DIFFERS = 1, SCAN_FIRST = 2, SCAN_WORDS = 3 };   // k_field_scan: smallest bad index (~0: none), f[i] != f[0] somewhere, bits of f[0]
 enum ScanBad { SCAN_BAD_NONE = 0, SCAN_BAD_NON_FINITE = 1, SCAN_BAD_NON_FINITE_OR_NEGATIVE = 2, SCAN_BAD_OUTSIDE_UNIT = 3 };   // which values count as bad (3: outside [-1, 1], a NaN included)
 void launchFieldScan(const float* f, int64_t n, int bad, uint32_t* out, hipStream_t s);
+// The refusal of a cell field whose smallest bad value (by mode `bad`) sits at x-fastest index `cell`, after the caller's label
+inline std::string scanRefusal(const char* label, int bad, int64_t cell) {
+    const char* what = bad == SCAN_BAD_NON_FINITE ? "non-finite value" : bad == SCAN_BAD_NON_FINITE_OR_NEGATIVE ? "non-finite or negative value" : "value outside [-1, 1]";
+    return std::string(label) + what + " at cell " + std::to_string(cell);
+}
+// What a pass over a cell field found (k_field_scan, or the host loops of ps_upload_density_field): f[0], some f[i] != f[0], the smallest bad index (-1: none)
+struct ScanFacts { float first = 0.f; bool differs = false; int64_t bad = -1; };
+// One cell field of 4-byte words on its way into its x-fastest buffer (ps_context::cellIn allocates it), the values that refuse it
+// (SCAN_BAD_NONE: not scanned) and the label of its refusal
+struct CellIn { const void* src; void* dst; int bad; const char* label; };
 
 struct CellField;     // ps_setup_util.hpp: what the setup kernels sample
 struct FaceDensity;
@@ -173,7 +187,7 @@ struct ps_context {
     bool densField = false;
     int32_t densFieldHost = 0;      // array "densityField": the last setup used a non-constant field
     bool uploaded = false, isSetup = false, isSolved = false;
-    std::string uploadDensity(const float* field);
+    std::string uploadDensity(const float* field, bool device, int layout, hipStream_t caller);   // ps_fields.hip
     // Device-resident fields (ps_*_device, ps_fields.hip): the caller's arrays are GPU memory in layout 0 (x fastest) or 1 (z fastest).
     // An upload is uploadCheck, uploadReset, one of the two ingests, uploadTail; the host path's ingest is the uploadField calls.
     // fieldEv: [0] recorded on the caller's stream and waited for by ours before we touch its arrays, [1] recorded on ours after a download
@@ -197,7 +211,21 @@ struct ps_context {
     void moveFields(const ps::FieldTable& T, int layout) { if (layout == 0) ps::launchFieldsCopy(T, stream); else ps::launchFieldsSwapXZ(T, stream); }
     const uint32_t* scanField(const float* f, int64_t n, int bad);   // k_field_scan (bad: ps::ScanBad) + fetch; synchronises the stream
     void upload(const ps_params* p, const ps_fields_in* in, int layout, hipStream_t caller);   // the device upload
-    std::string uploadDensityDevice(const float* field, int layout, hipStream_t caller);
+    // Optional cell fields (density, sigma / ambient pressure, contact cosine, collider ids; DESIGN.md "optional cell fields"), ps_fields.hip.
+    // moveCellFields: `count` grids of 4-byte words between the caller's arrays (f[q].src towards us, f[q].dst away from us) and our x-fastest
+    // buffers: a host array by hipMemcpyAsync, device arrays by one launch behind the caller's stream (which then waits for a download).
+    // ingestCellFields: moves the fields in, scans them in list order and returns the first refusal, or empty; ends with the stream
+    // synchronised.  The scan words the call allocated go with it unless keepScanWords (the density field keeps them).  facts: of the last scan.
+    // releaseIdle: what an entry point that dropped buffers ends with.
+    template <class T> ps::CellIn cellIn(const T* src, ps::DevBuf<T>& dst, int bad, const char* label) {
+        static_assert(sizeof(T) == 4, "the ingest kernels move 4-byte words whatever they hold");
+        HIP_CHECK(hipSetDevice(device));
+        dst.alloc((size_t)g.count(0));
+        return ps::CellIn{src, dst.p, bad, label};
+    }
+    void moveCellFields(const ps::CellIn* f, int count, bool in, bool device, int layout, hipStream_t caller);
+    std::string ingestCellFields(const ps::CellIn* f, int count, bool device, int layout, hipStream_t caller, bool keepScanWords, ps::ScanFacts* facts = nullptr);
+    void releaseIdle(bool dropped);
     void downloadDevice(const ps_fields_out* out, int layout, hipStream_t caller);
     void downloadSolutionDevice(const ps_solution_out* out, int layout, hipStream_t caller);
     // Surface tension (ps_set_surface_tension): sigmaSet is the context setting, sigmaUsed the value of the last setup (array "surfaceTension").
@@ -215,6 +243,7 @@ struct ps_context {
     bool surfSigmaField = false, surfPressureField = false;
     int32_t surfFieldsUsed = 0;
     bool dropSurfaceFields();                // ps_fields.hip: false when there was nothing to drop
+    void registerSurfaceFieldArrays();       // ps_fields.hip: q_c of the last setup (none once the fields are dropped)
     std::string uploadSurfaceFields(const ps_surface_fields* f, bool device, int layout, hipStream_t caller);   // ps_fields.hip
     // Contact angles (ps_set_contact_angle, ps_upload_contact_cosine_field; ps_wetting.hip): contactDegSet / contactCosSet are the context
     // setting (degrees < 0: off) and its cosine, contactCos the cosine cell field of the last call, for the grid of the last upload (every
@@ -232,6 +261,7 @@ struct ps_context {
     const float* applyContactAngle(bool curvature);   // ps_wetting.hip: the SDF the curvature reads (surface itself when the rule does not run)
     bool dropWetting();                      // ps_wetting.hip: the wet buffers and their arrays; false when there was nothing to drop
     bool dropContactCosine();                // ps_wetting.hip: false when there was nothing to drop
+    void registerWettingArrays();            // ps_wetting.hip: what the last setup's rewrite left (none when it did not run)
     std::string uploadContactCosine(const float* cosTheta, bool device, int layout, hipStream_t caller);   // ps_wetting.hip
     // Solid boundary (ps_set_solid_boundary): solidBoundarySet is the context setting, solidBoundaryUsed the mode of the last setup (array
     // "solidBoundary"; constructMatrixBlocks copies it).  slipEdges: free-slip edges counted by the St count pass (array "solidSlipEdges").
@@ -369,7 +399,7 @@ struct ps_context {
     ps::DevBuf<float> d32, p32, r32, ts32, Ap32;
     std::vector<int32_t> passIters;
     double trueResidualHost = 0;
-    void dropMixedBuffers() { d32.free(); p32.free(); r32.free(); ts32.free(); Ap32.free(); }
+    bool dropMixedBuffers() { const bool had = d32.p != nullptr; d32.free(); p32.free(); r32.free(); ts32.free(); Ap32.free(); return had; }
     // Velocity extrapolation (ps_set_velocity_extrapolation, extension; ps_extrapolate.hip): extrapSet is the context setting, extrapUsedHost the
     // layers the last step ran (array "velocityExtrapolation": 0 when off, on a decomposition, or when the velocity was not written).
     // extrapLayer: the layer of every face, 1 B each (arrays "extrapolationLayerX" / Y / Z); extrapCounts: faces assigned per sweep (array
@@ -378,7 +408,8 @@ struct ps_context {
     ps::DevBuf<int8_t> extrapLayer[3];
     ps::DevBuf<int32_t> extrapCounts;
     void extrapolateVelocity(int layers);               // ps_extrapolate.hip: after the write-back of a step whose velocity is written
-    void dropExtrapolationBuffers() { for (auto& b : extrapLayer) b.free(); extrapCounts.free(); }
+    bool dropExtrapolation();                           // ps_extrapolate.hip: the layer buffers and their arrays; false when there was nothing to drop
+    void registerExtrapolationArrays();                 // ps_extrapolate.hip: the arrays of the last step's layers (none without them)
     // Collider loads (ps_set_collider_loads, extension; ps_loads.hip): loadsCount / loadsPivots are the context setting (pivots empty: the
     // upload's orig), loadsUsedHost the count the last step computed loads for (array "colliderLoads": 0 when off, on a decomposition, or
     // when the step computed none; the getters need it > 0).  colliderIds: the id of every cell (ps_upload_collider_ids), for the grid of
@@ -394,8 +425,13 @@ struct ps_context {
     ps::DevBuf<int32_t> loadsPartialN, loadsTerms;
     ps::DevBuf<unsigned long long> loadsOccurs;
     void computeColliderLoads();                         // ps_loads.hip: after the write-back of a step that solved and whose velocity is written
-    void dropLoadBuffers() { loadsPartial.free(); loadsOut.free(); loadsPivotsDev.free(); loadsPartialN.free(); loadsTerms.free(); loadsOccurs.free(); }
+    bool dropLoadBuffers() {
+        const bool had = loadsOut.p != nullptr;
+        loadsPartial.free(); loadsOut.free(); loadsPivotsDev.free(); loadsPartialN.free(); loadsTerms.free(); loadsOccurs.free();
+        return had;
+    }
     void forgetLoads();                                  // ps_loads.hip: the last step's loads no longer stand (their arrays go)
+    void registerLoadArrays();                           // ps_loads.hip: the arrays of the last step's loads (none without them)
     bool dropColliderIds();                              // ps_loads.hip: false when there was nothing to drop
     std::string uploadColliderIds(const int32_t* ids, bool device, int layout, hipStream_t caller);   // ps_loads.hip
     void copyColliderLoads(double* dst, int64_t len, bool device, hipStream_t caller);                 // ps_loads.hip: throws when there are none
@@ -510,6 +546,10 @@ struct ps_context {
     ps_stats lastStats{};
 
     std::map<std::string, ps::ArrayInfo> arrays;
+    // a feature's arrays, by its one list: registered while the feature has them, erased otherwise
+    template <size_t N> void setArrays(const ps::NamedArray (&list)[N], bool present) {
+        for (const ps::NamedArray& a : list) { if (present) arrays[a.name] = a.info; else arrays.erase(a.name); }
+    }
     std::map<std::string, std::vector<char>> hostArrays;   // materialised-on-demand exports
 
     // ---- stage methods: names follow exec/HDK_PolyStokesSolver.h:96-190 ----

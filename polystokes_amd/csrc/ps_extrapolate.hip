@@ -89,3 +89,19 @@ void ps_context::extrapolateVelocity(int layers) {
     for (int k = 1; k <= layers; ++k) hipLaunchKernelGGL(k_extrap_sweep, grid, dim3(EBS), 0, stream, T, k, extrapCounts.p);
     extrapUsedHost = layers;
 }
+
+void ps_context::registerExtrapolationArrays() {
+    const NamedArray list[] = {{"extrapolationLayerX", ArrayInfo{extrapLayer[0].p, g.count(1), 1}}, {"extrapolationLayerY", ArrayInfo{extrapLayer[1].p, g.count(2), 1}},
+                               {"extrapolationLayerZ", ArrayInfo{extrapLayer[2].p, g.count(3), 1}},
+                               {"extrapolationCounts", ArrayInfo{extrapCounts.p, extrapUsedHost, 4}}};   // faces assigned by each sweep, the three axes together
+    setArrays(list, extrapUsedHost > 0 && extrapCounts.p);
+}
+
+// ps_set_velocity_extrapolation(ctx, 0): the layer buffers go with the setting, and their arrays ("velocityExtrapolation" keeps what the last step ran)
+bool ps_context::dropExtrapolation() {
+    const bool had = extrapCounts.p != nullptr;
+    for (auto& b : extrapLayer) b.free();
+    extrapCounts.free();
+    registerExtrapolationArrays();
+    return had;
+}

@@ -6,6 +6,7 @@
 #include <cstring>
 
 #include "ps_context.hpp"
+#include "ps_setup_util.hpp"
 
 using namespace ps;
 
@@ -226,81 +227,122 @@ void ps_context::upload(const ps_params* p, const ps_fields_in* in, int layout, 
     uploadTail();
 }
 
-// uploadDensity from a device array: the field is ingested first (the scan runs on the x-fastest image, so the index of a non-finite
-// value is the host path's), then kept or dropped by the same rules.
-std::string ps_context::uploadDensityDevice(const float* field, int layout, hipStream_t caller) {
+// ---- optional cell fields: one ingest, one check, one release (DESIGN.md "optional cell fields") ---------------------------------------
+
+// Queued on our stream.  Device arrays: behind whatever the caller's stream holds so far, one launch for all fields (a z-fastest source
+// is transposed on the way in); after a download the caller's stream waits for the copies (no host synchronisation).
+void ps_context::moveCellFields(const CellIn* f, int count, bool in, bool fromDevice, int layout, hipStream_t caller) {
+    HIP_CHECK(hipSetDevice(device));
+    if (!fromDevice) {
+        for (int q = 0; q < count; ++q)
+            HIP_CHECK(hipMemcpyAsync(f[q].dst, f[q].src, (size_t)g.count(0) * 4, in ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost, stream));
+        return;
+    }
+    waitForCaller(caller);
+    FieldTable T;
+    for (int q = 0; q < count; ++q) T.add(static_cast<const float*>(f[q].src), static_cast<float*>(f[q].dst), g.dims(0), in && layout == 1);
+    moveFields(T, layout);
+    if (!in) releaseToCaller(caller);
+}
+
+// Every field reaches its x-fastest buffer first, then k_field_scan checks each image in list order, so the index of a refused value is
+// the x-fastest one in either layout.  Ends with the stream synchronised: the inputs are consumed.
+std::string ps_context::ingestCellFields(const CellIn* f, int count, bool fromDevice, int layout, hipStream_t caller, bool keepScanWords, ScanFacts* facts) {
+    const bool ownScan = !fieldScan.p && !keepScanWords;   // the scan words this call allocates go with it: the fields cost their own buffers and nothing else
+    moveCellFields(f, count, true, fromDevice, layout, caller);
+    std::string why;
+    bool scanned = false;
+    for (int q = 0; q < count && why.empty(); ++q) {
+        if (f[q].bad == SCAN_BAD_NONE) continue;
+        const uint32_t* w = scanField(static_cast<const float*>(f[q].dst), g.count(0), f[q].bad);   // (ends synchronised)
+        scanned = true;
+        ScanFacts k;
+        std::memcpy(&k.first, &w[SCAN_FIRST], sizeof(float));
+        k.differs = w[SCAN_DIFFERS] != 0;
+        k.bad = w[SCAN_BAD] == 0xffffffffu ? -1 : (int64_t)w[SCAN_BAD];
+        if (k.bad >= 0) why = scanRefusal(f[q].label, f[q].bad, k.bad);
+        if (facts) *facts = k;
+    }
+    if (!scanned) HIP_CHECK(hipStreamSynchronize(stream));
+    if (ownScan) fieldScan.free();
+    return why;
+}
+
+// The end of an entry point that dropped buffers.  DevBuf::free only moves memory to the deferred list, so the drops may come before the
+// synchronisation; the drain must come after it (nothing queued still reads the buffers).  Nothing dropped: no synchronisation.
+void ps_context::releaseIdle(bool dropped) {
+    if (!dropped) return;
+    HIP_CHECK(hipSetDevice(device));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    drainDeferred(true);
+}
+
+// ps_upload_density_field / _device.  A constant field (all values equal) runs the scalar path at its clamped value, as a constant
+// viscosity skips the sampling (viscUniform); any other field is sampled per face by the setup kernels (ps_setup_util.hpp: FaceDensity,
+// handed out by densSource).  The host form finds the three facts on the host and uploads nothing for a refused or constant field; the
+// device form ingests first and takes them from k_field_scan on the x-fastest image (and keeps the scan words).  Returns the reason an
+// input is refused (the field is then dropped), or an empty string.
+std::string ps_context::uploadDensity(const float* field, bool fromDevice, int layout, hipStream_t caller) {
+    static const char* const label = "ps_upload_density_field: ";
     densField = false;
     densFieldHost = 0;
     rho = rhoScalar;
     if (!field) return {};
     const double lo = P.mindensity, hi = P.maxdensity;
     if (!std::isfinite(lo) || !std::isfinite(hi) || !(lo > 0.) || hi < lo)
-        return "ps_upload_density_field: mindensity must be positive and maxdensity at least mindensity, both finite";
-    const int64_t nc = g.count(0);
-    HIP_CHECK(hipSetDevice(device));
-    waitForCaller(caller);
-    density.alloc((size_t)nc);
-    FieldTable T;
-    T.add(field, density.p, g.dims(0), layout == 1);
-    moveFields(T, layout);
-    const uint32_t* w = scanField(density.p, nc, SCAN_BAD_NON_FINITE);
-    if (w[SCAN_BAD] != 0xffffffffu) return "ps_upload_density_field: non-finite value at cell " + std::to_string(w[SCAN_BAD]);
+        return std::string(label) + "mindensity must be positive and maxdensity at least mindensity, both finite";
+    ScanFacts k;
+    std::string why;
+    if (fromDevice) {
+        const CellIn in = cellIn(field, density, SCAN_BAD_NON_FINITE, label);
+        why = ingestCellFields(&in, 1, true, layout, caller, true, &k);
+    } else {
+        const int64_t nc = g.count(0);
+        for (int64_t i = 0; i < nc && k.bad < 0; ++i) if (!std::isfinite(field[i])) k.bad = i;
+        k.differs = !fieldIsUniform(field, nc, &k.first);
+        if (k.bad >= 0) why = scanRefusal(label, SCAN_BAD_NON_FINITE, k.bad);
+    }
+    if (!why.empty()) return why;
     densMin = lo; densMax = hi;
-    if (!w[SCAN_DIFFERS]) {
-        float v0;
-        std::memcpy(&v0, &w[SCAN_FIRST], sizeof(float));
-        const double v = (double)v0;
+    if (!k.differs) {
+        const double v = (double)k.first;
         rho = v < lo ? lo : (v > hi ? hi : v);
         return {};
+    }
+    if (!fromDevice) {
+        const CellIn in = cellIn(field, density, SCAN_BAD_NONE, label);
+        ingestCellFields(&in, 1, false, 0, nullptr, true);
     }
     densField = true;
     return {};
 }
 
-// ps_upload_surface_fields / _device.  Both fields of a call reach their x-fastest buffers first (host: two copies; device: one launch of
-// the ingest, which transposes a z-fastest source), then k_field_scan checks each image, sigma first, so the index of a refused value is
-// the x-fastest one in either layout.  A refusal drops both fields.  Ends with the stream idle and everything dropped released.
+// ps_upload_surface_fields / _device: sigma is checked first; a refusal drops both fields.
+void ps_context::registerSurfaceFieldArrays() {
+    const NamedArray list[] = {{"surfaceGhostPressure", ArrayInfo{surfQ.p, g.count(0), 8}}};   // ("surfaceFields" keeps what the last setup used)
+    setArrays(list, surfFieldsUsed != 0 && surfQ.p);
+}
 bool ps_context::dropSurfaceFields() {
     const bool had = surfSigma.p || surfPressure.p || surfQ.p;
     surfSigmaField = surfPressureField = false;
     surfSigma.free(); surfPressure.free(); surfQ.free();
-    arrays.erase("surfaceGhostPressure");   // (its buffer has gone; "surfaceFields" keeps what the last setup used)
+    registerSurfaceFieldArrays();   // (its buffer has gone)
     return had;
 }
 std::string ps_context::uploadSurfaceFields(const ps_surface_fields* f, bool fromDevice, int layout, hipStream_t caller) {
-    HIP_CHECK(hipSetDevice(device));
-    HIP_CHECK(hipStreamSynchronize(stream));
-    dropSurfaceFields();
+    bool dropped = dropSurfaceFields();
     std::string why;
-    if (f && (f->sigma || f->pressure)) {
-        const bool ownScan = !fieldScan.p;   // the scan words this call allocates go with it: the fields cost their own buffers and nothing else
-        const int64_t nc = g.count(0);
-        if (f->sigma) surfSigma.alloc((size_t)nc);
-        if (f->pressure) surfPressure.alloc((size_t)nc);
-        if (fromDevice) {
-            waitForCaller(caller);
-            FieldTable T;
-            if (f->sigma) T.add(f->sigma, surfSigma.p, g.dims(0), layout == 1);
-            if (f->pressure) T.add(f->pressure, surfPressure.p, g.dims(0), layout == 1);
-            moveFields(T, layout);
-        } else {
-            if (f->sigma) HIP_CHECK(hipMemcpyAsync(surfSigma.p, f->sigma, (size_t)nc * sizeof(float), hipMemcpyHostToDevice, stream));
-            if (f->pressure) HIP_CHECK(hipMemcpyAsync(surfPressure.p, f->pressure, (size_t)nc * sizeof(float), hipMemcpyHostToDevice, stream));
-        }
-        if (f->sigma) {
-            const uint32_t* w = scanField(surfSigma.p, nc, SCAN_BAD_NON_FINITE_OR_NEGATIVE);
-            if (w[SCAN_BAD] != 0xffffffffu) why = "sigma: non-finite or negative value at cell " + std::to_string(w[SCAN_BAD]);
-        }
-        if (why.empty() && f->pressure) {
-            const uint32_t* w = scanField(surfPressure.p, nc, SCAN_BAD_NON_FINITE);
-            if (w[SCAN_BAD] != 0xffffffffu) why = "pressure: non-finite value at cell " + std::to_string(w[SCAN_BAD]);
-        }
-        HIP_CHECK(hipStreamSynchronize(stream));   // (the host copies when nothing was scanned after them; the scans end synchronised)
+    CellIn in[2];
+    int n = 0;
+    if (f && f->sigma) in[n++] = cellIn(f->sigma, surfSigma, SCAN_BAD_NON_FINITE_OR_NEGATIVE, "sigma: ");
+    if (f && f->pressure) in[n++] = cellIn(f->pressure, surfPressure, SCAN_BAD_NON_FINITE, "pressure: ");
+    if (n > 0) {
+        why = ingestCellFields(in, n, fromDevice, layout, caller, false);
         if (why.empty()) { surfSigmaField = f->sigma != nullptr; surfPressureField = f->pressure != nullptr; }
         else dropSurfaceFields();
-        if (ownScan) fieldScan.free();
+        dropped = true;   // (the scan words at least)
     }
-    drainDeferred(true);
+    releaseIdle(dropped);
     return why;
 }
 

@@ -299,9 +299,17 @@ void ps_context::computeColliderLoads() {
     loadsUsedHost = count;
 }
 
+void ps_context::registerLoadArrays() {
+    const int64_t nc = loadsUsedHost;
+    const NamedArray list[] = {{"colliderForce", ArrayInfo{loadsOut.p, 3 * nc, 8}}, {"colliderTorque", ArrayInfo{loadsOut.p + 3 * nc, 3 * nc, 8}},
+                               {"colliderLoadScale", ArrayInfo{loadsOut.p + 6 * nc, 6 * nc, 8}},   // A_k, B_k per collider
+                               {"colliderLoadTerms", ArrayInfo{loadsTerms.p, nc + 1, 4}}};          // terms per collider, then the dropped terms
+    setArrays(list, loadsUsedHost > 0);
+}
+
 void ps_context::forgetLoads() {
     loadsUsedHost = 0;
-    for (const char* n : {"colliderForce", "colliderTorque", "colliderLoadScale", "colliderLoadTerms"}) arrays.erase(n);
+    registerLoadArrays();
 }
 
 bool ps_context::dropColliderIds() {
@@ -310,28 +318,15 @@ bool ps_context::dropColliderIds() {
     return had;
 }
 
-// ps_upload_collider_ids / _device: the field reaches its x-fastest buffer (the device form through the ingest kernels of ps_fields.hip,
-// which move 4-byte words whatever they hold).  Ends with the stream idle: the input is consumed and whatever was dropped is released.
+// ps_upload_collider_ids / _device (the ingest of ps_fields.hip; no value is refused).  Ends with the stream idle: the input is consumed
+// and whatever was dropped is released.
 std::string ps_context::uploadColliderIds(const int32_t* ids, bool fromDevice, int layout, hipStream_t caller) {
-    HIP_CHECK(hipSetDevice(device));
-    HIP_CHECK(hipStreamSynchronize(stream));
-    if (!ids) {
-        dropColliderIds();
-        drainDeferred(true);
-        return {};
+    const bool dropped = dropColliderIds();
+    if (ids) {
+        const CellIn in = cellIn(ids, colliderIds, SCAN_BAD_NONE, "");
+        ingestCellFields(&in, 1, fromDevice, layout, caller, false);
     }
-    const int64_t nc = g.count(0);
-    colliderIds.alloc((size_t)nc);
-    if (fromDevice) {
-        waitForCaller(caller);
-        FieldTable T;
-        T.add(reinterpret_cast<const float*>(ids), reinterpret_cast<float*>(colliderIds.p), g.dims(0), layout == 1);
-        moveFields(T, layout);
-    } else {
-        HIP_CHECK(hipMemcpyAsync(colliderIds.p, ids, (size_t)nc * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-    }
-    HIP_CHECK(hipStreamSynchronize(stream));
-    drainDeferred(true);
+    releaseIdle(dropped);
     return {};
 }
 

@@ -195,8 +195,6 @@ __global__ void __launch_bounds__(BS) k_pocket_pressure(const int32_t* __restric
     out[c] = id >= 0 ? (float)table[id] : 0.f;
 }
 
-const char* const kPocketArrays[] = {"airPockets", "airPocketIds", "airPocketUnits", "airPocketCells", "airPocketOpen", "airPocketVolume", "airPocketPasses"};
-
 }  // namespace
 
 bool ps_context::dropAirPockets() {
@@ -204,21 +202,18 @@ bool ps_context::dropAirPockets() {
     pocketsHave = false;
     pocketCount = 0;
     pocketIds.free(); pocketCells.free(); pocketOpen.free(); pocketUnits.free(); pocketVolume.free();
-    for (const char* n : kPocketArrays) arrays.erase(n);
+    registerPocketArrays();
     return had;
 }
 
 void ps_context::registerPocketArrays() {
-    if (!pocketsHave) return;
     const int64_t K = pocketCount;
-    auto reg = [&](const char* n, const void* p, int64_t c, int e, bool host) { ArrayInfo a{p, c, e}; a.host = host; arrays[n] = a; };
-    reg("airPockets", &pocketCount, 1, 4, true);
-    reg("airPocketPasses", &pocketPassesHost, 1, 4, true);    // global propagation passes of the last call (one host round trip each)
-    reg("airPocketIds", pocketIds.p, g.count(0), 4, false);
-    reg("airPocketUnits", pocketUnits.p, K, 8, false);
-    reg("airPocketCells", pocketCells.p, K, 4, false);
-    reg("airPocketOpen", pocketOpen.p, K, 4, false);
-    reg("airPocketVolume", pocketVolume.p, K, 8, false);
+    const NamedArray list[] = {{"airPockets", hostArray(&pocketCount, 1, 4)},
+                               {"airPocketPasses", hostArray(&pocketPassesHost, 1, 4)},    // global propagation passes of the last call (one host round trip each)
+                               {"airPocketIds", ArrayInfo{pocketIds.p, g.count(0), 4}}, {"airPocketUnits", ArrayInfo{pocketUnits.p, K, 8}},
+                               {"airPocketCells", ArrayInfo{pocketCells.p, K, 4}}, {"airPocketOpen", ArrayInfo{pocketOpen.p, K, 4}},
+                               {"airPocketVolume", ArrayInfo{pocketVolume.p, K, 8}}};
+    setArrays(list, pocketsHave);
 }
 
 // After an upload of a single domain.  Runs the weight stage itself (the setup repeats it on the same inputs: the same bits), then labels in
@@ -228,7 +223,7 @@ void ps_context::labelAirPockets() {
     if (slabEnabled || inGroup) throw Error("air pockets need a single domain");
     HIP_CHECK(hipSetDevice(device));
     pocketsHave = false;
-    for (const char* n : kPocketArrays) arrays.erase(n);
+    registerPocketArrays();
     buildIntegrationWeightsAlt();
     Grid gl = g;
     gl.order = PS_ORDER_LINEAR;      // labels are x-fastest cell indices whatever indexOrder is: k_cc_step's pointer jump resolves them through g.order
@@ -289,17 +284,9 @@ void ps_context::copyAirPockets(double* volume, int32_t* open, int64_t len) {
 // waits for it (a download: no host synchronisation); the ingest kernels move 4-byte words whatever they hold.
 void ps_context::copyAirPocketIds(int32_t* dst, bool toDevice, int layout, hipStream_t caller) {
     if (!pocketsHave) throw Error("ps_download_air_pocket_ids: there are no air pocket labels (ps_label_air_pockets after the last upload)");
-    HIP_CHECK(hipSetDevice(device));
-    if (toDevice) {
-        waitForCaller(caller);
-        FieldTable T;
-        T.add(reinterpret_cast<const float*>(pocketIds.p), reinterpret_cast<float*>(dst), g.dims(0), false);
-        moveFields(T, layout);
-        releaseToCaller(caller);
-    } else {
-        HIP_CHECK(hipMemcpyAsync(dst, pocketIds.p, (size_t)g.count(0) * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-        HIP_CHECK(hipStreamSynchronize(stream));
-    }
+    const CellIn out{pocketIds.p, dst, SCAN_BAD_NONE, ""};
+    moveCellFields(&out, 1, false, toDevice, layout, caller);
+    if (!toDevice) HIP_CHECK(hipStreamSynchronize(stream));
 }
 
 // The pressure member of the free-surface fields from a value per pocket: what ps_upload_surface_fields_device installs for the same
@@ -308,27 +295,25 @@ std::string ps_context::setAirPocketPressures(const double* pressure, int64_t le
     if (!pocketsHave) throw Error("ps_set_air_pocket_pressures: there are no air pocket labels (ps_label_air_pockets after the last upload)");
     HIP_CHECK(hipSetDevice(device));
     if (!pressure) {      // the pressure member alone goes; without a sigma field nothing of the fields is left
-        HIP_CHECK(hipStreamSynchronize(stream));
+        bool dropped = surfPressure.p != nullptr;
         surfPressureField = false;
         surfPressure.free();
-        if (!surfSigmaField) dropSurfaceFields();
-        drainDeferred(true);
+        if (!surfSigmaField) dropped |= dropSurfaceFields();
+        releaseIdle(dropped);
         return {};
     }
     const int64_t K = pocketCount;
     if (len != K) return "len must equal the pocket count " + std::to_string(K);
     for (int64_t k = 0; k < K; ++k)      // as the field holds it: a double beyond the range of fp32 would paint an infinity, which the uploads refuse
         if (!std::isfinite((float)pressure[k])) return "pressure of pocket " + std::to_string(k) + " is not finite";
-    HIP_CHECK(hipStreamSynchronize(stream));
     const int64_t n = g.count(0);
     DevBuf<double> table;
     table.alloc((size_t)K);
     if (K > 0) HIP_CHECK(hipMemcpyAsync(table.p, pressure, (size_t)K * sizeof(double), hipMemcpyHostToDevice, stream));
     surfPressure.alloc((size_t)n);
     hipLaunchKernelGGL(k_pocket_pressure, dim3(gridFor(n, BS)), dim3(BS), 0, stream, (const int32_t*)pocketIds.p, (const double*)table.p, surfPressure.p, n);
-    HIP_CHECK(hipStreamSynchronize(stream));
     surfPressureField = true;
-    table.free();      // (deferred, released below)
-    drainDeferred(true);
+    table.free();      // (deferred: released below, once the kernel that reads it has run)
+    releaseIdle(true);
     return {};
 }

@@ -98,11 +98,17 @@ __global__ void __launch_bounds__(WBS) k_wet_sweep(WetArgs A, const float* __res
 
 }  // namespace
 
+void ps_context::registerWettingArrays() {
+    const NamedArray list[] = {{"contactCosine", hostArray(&contactCosUsed, 1, 8)}, {"contactField", hostArray(&contactFieldUsed, 1, 4)},
+                               {"contactCells", ArrayInfo{wetCount.p, 1, 4}}, {"surfaceWetted", ArrayInfo{wetPhi[0].p, g.count(0), 4}}};
+    setArrays(list, contactRan && wetPhi[0].p);
+}
+
 bool ps_context::dropWetting() {
     const bool had = wetPhi[0].p || wetPhi[1].p || wetFlags.p || wetCount.p;
     wetPhi[0].free(); wetPhi[1].free(); wetFlags.free(); wetCount.free();
     contactRan = false;
-    for (const char* n : {"contactCosine", "contactField", "contactCells", "surfaceWetted"}) arrays.erase(n);   // (their buffers have gone)
+    registerWettingArrays();   // (their buffers have gone)
     return had;
 }
 
@@ -146,35 +152,20 @@ const float* ps_context::applyContactAngle(bool curvature) {
     return wetPhi[0].p;
 }
 
-// ps_upload_contact_cosine_field / _device.  The field reaches its x-fastest buffer first (host: a copy; device: the ingest of
-// ps_fields.hip, which transposes a z-fastest source), then k_field_scan checks that image, so the index of a refused value is the
-// x-fastest one in either layout.  A refused value drops the field.  Ends with the stream idle and everything dropped released.
+// ps_upload_contact_cosine_field / _device (the ingest of ps_fields.hip).  A refused value drops the field.  Ends with the stream idle and
+// everything dropped released.
 std::string ps_context::uploadContactCosine(const float* cosTheta, bool fromDevice, int layout, hipStream_t caller) {
-    HIP_CHECK(hipSetDevice(device));
-    HIP_CHECK(hipStreamSynchronize(stream));
     std::string why;
+    bool dropped = true;   // (an ingest: the scan words at least)
     if (!cosTheta) {
-        dropContactCosine();
-        if (contactDegSet < 0.) dropWetting();   // nothing asks for the rule any more
-        drainDeferred(true);
-        return why;
-    }
-    const bool ownScan = !fieldScan.p;   // the scan words this call allocates go with it: the field costs its own buffer and nothing else
-    const int64_t nc = g.count(0);
-    contactCos.alloc((size_t)nc);
-    if (fromDevice) {
-        waitForCaller(caller);
-        FieldTable T;
-        T.add(cosTheta, contactCos.p, g.dims(0), layout == 1);
-        moveFields(T, layout);
+        dropped = dropContactCosine();
+        if (contactDegSet < 0.) dropped |= dropWetting();   // nothing asks for the rule any more
     } else {
-        HIP_CHECK(hipMemcpyAsync(contactCos.p, cosTheta, (size_t)nc * sizeof(float), hipMemcpyHostToDevice, stream));
+        const CellIn in = cellIn(cosTheta, contactCos, SCAN_BAD_OUTSIDE_UNIT, "contact cosine: ");
+        why = ingestCellFields(&in, 1, fromDevice, layout, caller, false);
+        if (why.empty()) contactCosField = true;
+        else dropContactCosine();
     }
-    const uint32_t* w = scanField(contactCos.p, nc, SCAN_BAD_OUTSIDE_UNIT);   // (ends synchronised)
-    if (w[SCAN_BAD] != 0xffffffffu) why = "contact cosine: value outside [-1, 1] at cell " + std::to_string(w[SCAN_BAD]);
-    if (why.empty()) contactCosField = true;
-    else dropContactCosine();
-    if (ownScan) fieldScan.free();
-    drainDeferred(true);
+    releaseIdle(dropped);
     return why;
 }
