@@ -485,6 +485,56 @@ int32_t ps_set_collider_loads(ps_context* ctx, const ps_collider_loads* loads);
 int32_t ps_upload_collider_ids(ps_context* ctx, const int32_t* ids);      /* cell field nx*ny*nz, x-fastest; NULL drops it */
 int32_t ps_get_collider_loads(ps_context* ctx, double* out, int64_t out_len);
 
+/* Collider motions (extension; the input half of rigid-collider coupling, the loads above being the output half): the rigid-body velocity
+ * v + w x (r - o) of the collider a face belongs to, painted on the device into the context's collisionvel grids, from the collision SDF and
+ * the id field the context already holds.  The integration of the bodies stays with the caller: loads out, its few lines of body dynamics,
+ * motions in, with no host synchronisation in the device forms.
+ * Call order and lifetime.  The call follows ps_upload_fields / ps_upload_fields_device, and ps_upload_collider_ids if there is one; it
+ * precedes the setup.  It writes into the context's own collisionvel buffers at once, on the context's stream: what it wrote lives exactly as
+ * long as that upload's collisionvel.  Every field upload replaces it; a setup, solve or step and the Picard passes of ps_set_rheology keep
+ * it.  A second call paints over what is there, and faces it leaves alone keep what they hold.  Ids uploaded after a call do not repaint.
+ * polystokes_step and ps_step_device_fields upload and therefore never see it: a caller uses upload + ids + ps_paint_collider_velocities +
+ * ps_step_device + download.  It is not a context setting and has no "off".  A context that never makes the call launches exactly the
+ * kernels it launched without it.
+ * The rule.  All arithmetic is fp64 from the fp32 / fp64 inputs, unfused, in the order written.  For the face of axis a at indices
+ * (i0, i1, i2) of the a-face grid, n_a the cells along a:
+ *   adjacent cells:  the lower cell L has index i_a - 1 along a and exists iff i_a >= 1; the upper cell U has index i_a and exists iff
+ *                    i_a <= n_a - 1; the other two indices are the face's;
+ *   solid depth:     D_c = -collision[c] with negateCollision = 1, +collision[c] with negateCollision = 0 (the ps_params of that upload;
+ *                    the D of the contact angles);
+ *   chosen cell:     the only existing one; with both existing, U if D_U > D_L, else L — the more solid cell, ties and NaN to the lower;
+ *   id:              k = ids[chosen cell], or 0 without an id field, as the loads do;
+ *   left alone:      k < 0 or k >= count: the face keeps its value and is counted in slot count; the nine values of collider k not all
+ *                    finite (the device form only; the host form refuses such a table): it keeps its value and is counted in slot count + 1;
+ *   painted value:   r_m = orig_m + (double)i_m * dx for m == a and orig_m + ((double)i_m + 0.5) * dx for the other two (the positions the
+ *                    loads use), arm_m = r_m - o_m, a1 = (a + 1) % 3, a2 = (a + 2) % 3:
+ *                    collisionvel[a][face] = (float)( v[a] + (w[a1] * arm[a2] - w[a2] * arm[a1]) );  the face is counted in slot k.
+ *                    (arm[a] does not occur: a rigid motion's component a is constant along a, so one collider's paint is divergence-free.)
+ * The more solid cell decides because a face between a solid cell and a liquid cell is the solid's face: the write-back gives SOLID faces the
+ * collision velocity, and the solid-boundary terms of the right-hand side read it at faces a solid cuts.  The counts are integers: the
+ * result is bitwise reproducible and independent of the traversal (a collider's count wraps beyond 2^31 - 1 faces).
+ * ps_paint_collider_velocities copies the table before it returns.  ps_paint_collider_velocities_device reads 9 * count doubles of device
+ * memory of the context's device (8-byte aligned) behind what `stream` holds, makes `stream` wait until it has read them, and does not
+ * synchronise the host — except a call whose count differs from the previous call's since the same upload, which releases the previous
+ * table and counters first.
+ * Refusals (PS_INVALID, reason in ps_last_error, nothing written): a call before any upload; motions == NULL or motion == NULL;
+ * "count outside 1..64"; host form: "motion of collider N is not finite", N the smallest such collider; device form: the pointer refusals of the other
+ * ps_*_device calls (below) — a pointer that is not 8-byte aligned, memory that is not device memory of the context's device, an allocation
+ * that ends before 9 * count doubles.
+ * Decompositions.  The call is local to a context: a slab or brick rank paints its own grid, from its own upload's orig and local indices;
+ * the caller gives every rank the orig of its block.  No test of this library covers that (its partition helper does not set orig per rank).
+ * Memory: the table and the counters take 72 * count + 4 * (count + 2) bytes from the call to the next upload; nothing else is held, and
+ * ps_memory_stats entry 2 is 0 after the call.
+ * Arrays, registered by a successful call and erased by every upload: "colliderMotions" (int32, 1: the count), "colliderMotionTable" (fp64,
+ * 9 * count: the table the kernel read), "colliderMotionFaces" (int32, count + 2: painted faces per collider over the three axes together,
+ * then the two left-alone counts) and "collisionVelocityX" / Y / Z (fp32 face grids: the buffers the next setup will read). */
+typedef struct ps_collider_motions {
+    int32_t count;          /* 1..PS_COLLIDER_MAX */
+    const double* motion;   /* 9 * count doubles per collider k: v[3] (linear velocity), w[3] (angular velocity, rad per time unit), o[3] (the point v is given at) */
+} ps_collider_motions;
+int32_t ps_paint_collider_velocities(ps_context* ctx, const ps_collider_motions* m);
+int32_t ps_paint_collider_velocities_device(ps_context* ctx, const double* motion, int32_t count, void* stream);
+
 /* Air pockets (extension; the free-surface fields above take the air-side pressure P_c from the caller, and a device-resident caller has
  * nothing that finds trapped air): the connected air regions of the uploaded grid, their volumes and whether they reach the grid's border,
  * and a pressure per pocket painted into the pressure member of the free-surface fields.  The gas law and the tracking of a pocket from

@@ -31,6 +31,7 @@ EXPORTED_SYMBOLS = [
     "ps_step_device_fields", "ps_set_velocity_extrapolation",
     "ps_upload_surface_fields", "ps_upload_surface_fields_device",
     "ps_set_collider_loads", "ps_upload_collider_ids", "ps_upload_collider_ids_device", "ps_get_collider_loads", "ps_get_collider_loads_device",
+    "ps_paint_collider_velocities", "ps_paint_collider_velocities_device",
     "ps_label_air_pockets", "ps_get_air_pockets", "ps_download_air_pocket_ids", "ps_download_air_pocket_ids_device", "ps_set_air_pocket_pressures",
     "ps_set_contact_angle", "ps_upload_contact_cosine_field", "ps_upload_contact_cosine_field_device",
 ]
@@ -161,7 +162,7 @@ def lib():
         L.ps_upload_contact_cosine_field.restype = C.c_int32
         L.ps_upload_contact_cosine_field_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
         L.ps_upload_contact_cosine_field_device.restype = C.c_int32
-        for name, argtypes in _abi.AIR_POCKET_CALLS:
+        for name, argtypes in _abi.COLLIDER_MOTION_CALLS + _abi.AIR_POCKET_CALLS:
             getattr(L, name).argtypes = list(argtypes)
             getattr(L, name).restype = C.c_int32
         _lib = L
@@ -260,7 +261,7 @@ def _kind(name):
                 "surfaceTensionReducedFaces", "surfaceFields", "solidBoundary", "solidSlipEdges", "rheologyModel", "rheologyIterations",
                 "solvePrecisionUsed", "solvePassIterations",
                 "velocityExtrapolation", "extrapolationLayerX", "extrapolationLayerY", "extrapolationLayerZ", "extrapolationCounts",
-                "colliderLoads", "colliderLoadTerms",
+                "colliderLoads", "colliderLoadTerms", "colliderMotions", "colliderMotionFaces",
                 "airPockets", "airPocketIds", "airPocketUnits", "airPocketCells", "airPocketOpen", "airPocketPasses",
                 "contactField", "contactCells"):
         return "i"
@@ -412,6 +413,24 @@ class Solver:
         """ps_get_collider_loads_device into `out` (device memory of `length` doubles).  Returns the ps_result (INVALID: a refused pointer;
         the host is NOT synchronised); raises when the last step computed no loads."""
         return self._check(self.L.ps_get_collider_loads_device(self.h, device_address(out), int(length), stream_handle(stream)), allow=(1, -2))
+
+    def paint_collider_velocities(self, motions):
+        """ps_paint_collider_velocities: `motions` has shape (count, 9) — v[3], w[3], o[3] per collider; the velocity v + w x (r - o) of the
+        collider each face belongs to (the more solid of its two cells, by the collision SDF and the ids of upload_collider_ids) goes into
+        the collisionvel of the last upload, at once.  Returns the ps_result: INVALID before any upload, for a count outside 1..64 or a
+        value that is not finite (nothing written).  Arrays "colliderMotions", "colliderMotionTable", "colliderMotionFaces" and
+        "collisionVelocityX" / Y / Z say what the call left."""
+        m = np.ascontiguousarray(motions, dtype=np.float64)
+        if m.ndim != 2 or m.shape[1] != 9:
+            raise ValueError("motions must hold 9 values per collider")
+        cm = _abi.ColliderMotions(m.shape[0], m.ctypes.data)
+        return self._check(self.L.ps_paint_collider_velocities(self.h, C.byref(cm)), allow=(1, -2))
+
+    def paint_collider_velocities_device(self, ptr, count, stream=None):
+        """ps_paint_collider_velocities_device: the same from 9 * count doubles of device memory, read behind what `stream` holds.  Returns
+        the ps_result (INVALID: a refused pointer or count; the host is NOT synchronised).  A collider whose values are not all finite
+        paints nothing: its faces are counted in the last slot of "colliderMotionFaces"."""
+        return self._check(self.L.ps_paint_collider_velocities_device(self.h, device_address(ptr), int(count), stream_handle(stream)), allow=(1, -2))
 
     def label_air_pockets(self):
         """ps_label_air_pockets: labels the connected air regions of the grid of the last upload (single domain) and returns their number K.

@@ -81,6 +81,18 @@ class ColliderLoads(C.Structure):
     _fields_ = [("count", C.c_int32), ("pivots", C.c_void_p)]
 
 
+class ColliderMotions(C.Structure):
+    """ps_collider_motions (ps_paint_collider_velocities): v[3], w[3], o[3] per collider"""
+    _fields_ = [("count", C.c_int32), ("motion", C.c_void_p)]
+
+
+# the collider motion calls: name -> argument types; every one returns int32
+COLLIDER_MOTION_CALLS = (
+    ("ps_paint_collider_velocities", (C.c_void_p, C.POINTER(ColliderMotions))),
+    ("ps_paint_collider_velocities_device", (C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p)),
+)
+
+
 # the air pocket calls (ps_label_air_pockets ...): name -> argument types; every one returns int32
 AIR_POCKET_CALLS = (
     ("ps_label_air_pockets", (C.c_void_p, C.POINTER(C.c_int32))),

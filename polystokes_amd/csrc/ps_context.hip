@@ -107,7 +107,8 @@ void ps_context::uploadReset(const ps_params* p, const ps_fields_in* in) {
     forgetLoads();                                        // the loads of an earlier step described the previous fields
     dropped |= dropColliderIds();                         // ... and so did the collider ids (ps_upload_collider_ids)
     dropped |= dropAirPockets();                          // ... and the air pocket labels (ps_label_air_pockets)
-    releaseIdle(dropped);                                 // one synchronisation for whatever was present, none when nothing was
+    dropped |= dropMotions();                             // ... and what ps_paint_collider_velocities left: the ingest replaces collisionvel
+    releaseIdle(dropped);                                // one synchronisation for whatever was present, none when nothing was
 }
 
 void ps_context::ingestHost(const ps_fields_in* in) {
@@ -201,6 +202,7 @@ void ps_context::setupPhase(int phase) {
         loadsUsedHost = 0;
         arrays.clear();
         registerPocketArrays();                 // (ps_label_air_pockets: a setup keeps the labels, also one that throws)
+        registerMotionArrays();                 // (ps_paint_collider_velocities: a setup keeps what was painted)
         if (rheoPass == 0) rheoIters.clear();   // (ps_set_rheology: one entry per solve of the step)
         // Picard passes need the halo of the last pass's output velocity: a decomposition refuses them on every rank (ps_dist.hpp: distStep)
         if (slabEnabled && rheoSet.model != PS_RHEOLOGY_NEWTONIAN && rheoSet.passes > 0) throw Error("rheology passes need a single domain");
@@ -457,6 +459,7 @@ void ps_context::registerArrays() {
         if (slabEnabled && isSolved) reg(std::string("owned") + ax[a], ownedFace[a].p, g.count(1 + a), 4);
     }
     registerPocketArrays();   // the labels of ps_label_air_pockets outlive a setup, solve or step
+    registerMotionArrays();   // ... and so does what ps_paint_collider_velocities painted
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -857,6 +860,24 @@ int32_t ps_get_collider_loads(ps_context* c, double* out, int64_t out_len) {
         return PS_SUCCESS;
     })
 }
+// what both forms of ps_paint_collider_velocities refuse before they look at the table: the reason, or empty
+static std::string refuseMotions(const double* motion, int32_t count) {
+    if (!motion) return "motion is null";
+    if (count < 1 || count > PS_COLLIDER_MAX) return "count outside 1.." + std::to_string(PS_COLLIDER_MAX);
+    return {};
+}
+int32_t ps_paint_collider_velocities(ps_context* c, const ps_collider_motions* m) {
+    if (!c) return PS_FAILED;
+    PS_TRY(c, {
+        if (notUploaded(c, "ps_paint_collider_velocities")) return PS_INVALID;
+        std::string why = m ? refuseMotions(m->motion, m->count) : std::string("motions is null");
+        for (int q = 0; why.empty() && q < 9 * m->count; ++q)
+            if (!std::isfinite(m->motion[q])) why = "motion of collider " + std::to_string(q / 9) + " is not finite";
+        if (!why.empty()) { c->err = "ps_paint_collider_velocities: " + why; return PS_INVALID; }
+        c->paintColliderVelocities(m->motion, m->count, false, nullptr);
+        return PS_SUCCESS;
+    })
+}
 int32_t ps_label_air_pockets(ps_context* c, int32_t* count) {
     if (!c) return PS_FAILED;
     PS_TRY(c, {
@@ -1030,6 +1051,19 @@ int32_t ps_get_collider_loads_device(ps_context* c, double* dev, int64_t len, vo
         else why = c->checkDeviceField(dev, 2 * 6 * (int64_t)c->loadsUsedHost, "out");
         if (!why.empty()) { c->err = "ps_get_collider_loads_device: " + why; return PS_INVALID; }
         c->copyColliderLoads(dev, len, true, (hipStream_t)stream);
+        return PS_SUCCESS;
+    })
+}
+int32_t ps_paint_collider_velocities_device(ps_context* c, const double* motion, int32_t count, void* stream) {
+    if (!c) return PS_FAILED;
+    PS_TRY(c, {
+        if (notUploaded(c, "ps_paint_collider_velocities")) return PS_INVALID;
+        std::string why = refuseMotions(motion, count);
+        if (why.empty() && ((uintptr_t)motion & 7)) why = "motion: the pointer is not 8-byte aligned";
+        if (!why.empty()) { c->err = "ps_paint_collider_velocities_device: " + why; return PS_INVALID; }
+        const DevicePtr ptrs[] = {{motion, 2 * 9 * (int64_t)count, "motion", false}};      // (counted in 4-byte words)
+        if (refuseDeviceCall(c, nullptr, "ps_paint_collider_velocities_device", 0, ptrs)) return PS_INVALID;
+        c->paintColliderVelocities(motion, count, true, (hipStream_t)stream);
         return PS_SUCCESS;
     })
 }

@@ -435,6 +435,16 @@ struct ps_context {
     bool dropColliderIds();                              // ps_loads.hip: false when there was nothing to drop
     std::string uploadColliderIds(const int32_t* ids, bool device, int layout, hipStream_t caller);   // ps_loads.hip
     void copyColliderLoads(double* dst, int64_t len, bool device, hipStream_t caller);                 // ps_loads.hip: throws when there are none
+    // Collider motions (ps_paint_collider_velocities, extension; ps_motions.hip): a call writes rigid-body velocities into cvel at once; what it
+    // wrote lives as long as that upload's cvel.  motionsCount: the count of the last call since the last upload (array "colliderMotions"; 0:
+    // none, and none of the arrays); motionTable: the 9 * count doubles the kernel read; motionFaces: count + 2 counters.  Allocated by a
+    // call, as long as its count needs; dropped by every upload.
+    int32_t motionsCount = 0;
+    ps::DevBuf<double> motionTable;
+    ps::DevBuf<int32_t> motionFaces;
+    void paintColliderVelocities(const double* motion, int count, bool device, hipStream_t caller);    // ps_motions.hip: after the ABI's refusals
+    bool dropMotions();                                  // ps_motions.hip: the table, the counters and the arrays; false when there was nothing to drop
+    void registerMotionArrays();                         // ps_motions.hip: the arrays of the last call (none without one since the last upload)
     // Air pockets (ps_label_air_pockets, extension; ps_pockets.hip): the connected air regions of the grid of the last upload (every upload and
     // every ps_set_slab / ps_set_brick drops them; a setup, solve or step keeps them).  pocketsHave: labels exist; pocketCount: K;
     // pocketPassesHost: the global propagation passes the last call ran (array "airPocketPasses").  pocketIds: the pocket of every cell (-1:
