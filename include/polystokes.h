@@ -535,6 +535,77 @@ typedef struct ps_collider_motions {
 int32_t ps_paint_collider_velocities(ps_context* ctx, const ps_collider_motions* m);
 int32_t ps_paint_collider_velocities_device(ps_context* ctx, const double* motion, int32_t count, void* stream);
 
+/* Collider shapes (extension; the piece between "loads out" and "motions in" for colliders that move): each collider's shape is stored
+ * once, as a small SDF volume in the body's own frame; per step a table of rigid poses places all of them into the context's collision
+ * buffer and id field, on the device.  Without it both calls above read the geometry of the last upload, which is stale once a body has
+ * moved, and the caller rasterises every collider into a new collision grid and id grid itself.
+ * ps_set_collider_shapes is a context setting, like the pivots of the loads: it copies every volume to the device before it returns,
+ * persists across uploads, may be called before any upload and touches no field.  count = 0, s == NULL or shape == NULL with count 0 drops
+ * the shapes and releases their memory.  Refusals (PS_INVALID, reason in ps_last_error, the previous shapes kept): "count outside 0..64";
+ * "shape N: extent outside 2..1022"; "shape N: spacing not positive and finite"; "shape N: origin not finite"; "shape N: no samples"
+ * (sdf == NULL); "shape N: non-finite value at sample M" — N the smallest such shape, M its smallest such x-fastest index; shape == NULL with
+ * a count above 0.
+ * ps_place_colliders / _device is a call like the paint, not a setting.  Call order and lifetime: it follows ps_upload_fields /
+ * ps_upload_fields_device, and ps_upload_collider_ids if there is one; it precedes ps_paint_collider_velocities, ps_label_air_pockets and
+ * the setup.  It rewrites the context's own collision buffer and id field at once, on the context's stream: what it wrote lives exactly as
+ * long as that upload's collision.  Every field upload replaces it; a setup, solve or step and the Picard passes of ps_set_rheology keep
+ * it.  A second call unions on top of the first, and the same poses leave the same values.  ps_upload_collider_ids after a call replaces
+ * the whole id field and does not re-place.  A successful placement drops the air-pocket labels, which described the old solids.
+ * polystokes_step and ps_step_device_fields upload and therefore never see a placement: a caller uses upload + ps_place_colliders +
+ * ps_paint_collider_velocities + ps_step_device + download.  With uploaded weights[14] the weights stay the caller's; the placement still
+ * changes what the motions, the loads' attribution and the contact angles read.  A context that never makes the calls launches exactly the
+ * kernels it launched without them.
+ * The pose table holds 12 doubles per collider: R[9], row-major, maps body to world; t[3] is the translation: world = R body + t.  R is
+ * taken as orthonormal and is not checked beyond finiteness (poses are rigid: no scale).
+ * The rule.  All arithmetic is fp64 from the fp32 / fp64 inputs, unfused, in the order written.  For cell c = (i0, i1, i2):
+ *   r_m = orig_m + ((double)i_m + 0.5) * dx;
+ *   D_best = negate ? -(double)collision[c] : (double)collision[c], negate the negateCollision of that upload's ps_params;  k_best = -1.
+ * For k = 0 .. count-1 in order, skipping a collider whose 12 pose values are not all finite (the device form only; each such collider is
+ * counted once in slot count + 1):
+ *   1. d_m = r_m - t_m;  q_a = (R[0][a]*d_0 + R[1][a]*d_1) + R[2][a]*d_2   (R^T d);
+ *   2. s_a = (q_a - o_a) / h - 0.5;  E = (PS_COLLIDER_SHAPE_REACH * dx) / h;  the collider takes part at c iff s_a >= -E and
+ *      s_a <= (double)(n_a - 1) + E for all three a;
+ *   3. c_a = min(max(s_a, 0.0), (double)(n_a - 1));  i_a = min((int)floor(c_a), n_a - 2);  f_a = c_a - (double)i_a;
+ *   4. val = the trilinear value of the eight samples widened to double, interpolated along x, then y, then z, each step lo + (hi - lo) * f;
+ *   5. out_a = (s_a - c_a) * h;  dist = sqrt((out_0*out_0 + out_1*out_1) + out_2*out_2);
+ *   6. D_k = (negate ? -val : val) - dist   (beyond its box a volume continues as its border value minus the distance to the box);
+ *   7. if D_k > D_best then D_best = D_k and k_best = k   (strict: ties go to what the cell holds, then to the lower collider).
+ * With k_best >= 0: collision[c] = (float)(negate ? -D_best : D_best), ids[c] = k_best, and the cell is counted in slot k_best.  Otherwise
+ * the cell keeps both values and is counted in slot count.  If the context holds no id field, the call first creates one filled with -1,
+ * with the lifetime of an uploaded id field, so the loads and the paint see it.  The counters are integers: the result is bitwise
+ * reproducible and independent of the traversal.
+ * ps_place_colliders copies the table before it returns and ends with the stream idle.  ps_place_colliders_device reads 12 * count doubles
+ * of device memory of the context's device (8-byte aligned) behind what `stream` holds, makes `stream` wait until it has read them, and
+ * does not synchronise the host — except a call that has something to release first: a table of another size, or air-pocket labels.
+ * Refusals (PS_INVALID, reason in ps_last_error, nothing written, the context stays usable): a call before any upload; no shapes set;
+ * p == NULL or pose == NULL; "count differs from the shapes' count"; host form: "pose of collider N is not finite", N the smallest such
+ * collider; device form: the pointer refusals of the other ps_*_device calls (below) — a pointer that is not 8-byte aligned, memory that is
+ * not device memory of the context's device, an allocation that ends before 12 * count doubles.
+ * Memory: the shapes cost 4 bytes per sample plus a descriptor table (56 bytes per collider); a placement costs 96 * count + 4 * (count + 2)
+ * bytes until the next upload; a created id field costs one int32 cell grid; ps_memory_stats entry 2 is 0 after each call.
+ * Arrays: "colliderShapes" (int32, 1: the count) stays registered while shapes are set.  A successful placement registers, and every upload
+ * erases: "colliderPlacement" (int32, 1: the count), "colliderPoseTable" (fp64, 12 * count: the table the kernel read),
+ * "colliderPlacedCells" (int32, count + 2: cells per collider, cells left alone, colliders skipped), "collisionField" (fp32 cell grid: the
+ * buffer the next setup reads) and "colliderCellIds" (int32 cell grid).
+ * Out of scope: a device form of ps_set_collider_shapes; scaling or deforming poses; swept volumes for fast bodies; a per-shape contact
+ * cosine; repainting after later id uploads.  Decompositions: a slab or brick rank places on its own grid from its own upload's orig, as
+ * the paint does; no test of this library covers that. */
+#define PS_COLLIDER_SHAPE_REACH 4.0   /* world cells beyond a volume's box that a placement still writes */
+
+typedef struct ps_collider_shape {
+    int32_t n[3];        /* samples along the body's x, y, z; each 2..1022 */
+    int32_t reserved;    /* 0 */
+    double h;            /* sample spacing, > 0; the same length unit as the grid's dx (poses are rigid: no scale) */
+    double orig[3];      /* body-frame low corner of the volume; sample (i,j,k) sits at orig + (i+0.5, j+0.5, k+0.5) * h */
+    const float* sdf;    /* n0*n1*n2 floats, x fastest, host memory; sign convention of the `collision` it is placed into */
+} ps_collider_shape;
+typedef struct ps_collider_shapes { int32_t count; const ps_collider_shape* shape; } ps_collider_shapes;
+int32_t ps_set_collider_shapes(ps_context* ctx, const ps_collider_shapes* s);
+
+typedef struct ps_collider_poses { int32_t count; const double* pose; } ps_collider_poses;
+int32_t ps_place_colliders(ps_context* ctx, const ps_collider_poses* p);
+int32_t ps_place_colliders_device(ps_context* ctx, const double* pose, int32_t count, void* stream);
+
 /* Air pockets (extension; the free-surface fields above take the air-side pressure P_c from the caller, and a device-resident caller has
  * nothing that finds trapped air): the connected air regions of the uploaded grid, their volumes and whether they reach the grid's border,
  * and a pressure per pocket painted into the pressure member of the free-surface fields.  The gas law and the tracking of a pocket from

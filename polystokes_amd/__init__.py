@@ -32,6 +32,7 @@ EXPORTED_SYMBOLS = [
     "ps_upload_surface_fields", "ps_upload_surface_fields_device",
     "ps_set_collider_loads", "ps_upload_collider_ids", "ps_upload_collider_ids_device", "ps_get_collider_loads", "ps_get_collider_loads_device",
     "ps_paint_collider_velocities", "ps_paint_collider_velocities_device",
+    "ps_set_collider_shapes", "ps_place_colliders", "ps_place_colliders_device",
     "ps_label_air_pockets", "ps_get_air_pockets", "ps_download_air_pocket_ids", "ps_download_air_pocket_ids_device", "ps_set_air_pocket_pressures",
     "ps_set_contact_angle", "ps_upload_contact_cosine_field", "ps_upload_contact_cosine_field_device",
 ]
@@ -162,7 +163,7 @@ def lib():
         L.ps_upload_contact_cosine_field.restype = C.c_int32
         L.ps_upload_contact_cosine_field_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
         L.ps_upload_contact_cosine_field_device.restype = C.c_int32
-        for name, argtypes in _abi.COLLIDER_MOTION_CALLS + _abi.AIR_POCKET_CALLS:
+        for name, argtypes in _abi.COLLIDER_MOTION_CALLS + _abi.COLLIDER_SHAPE_CALLS + _abi.AIR_POCKET_CALLS:
             getattr(L, name).argtypes = list(argtypes)
             getattr(L, name).restype = C.c_int32
         _lib = L
@@ -262,6 +263,7 @@ def _kind(name):
                 "solvePrecisionUsed", "solvePassIterations",
                 "velocityExtrapolation", "extrapolationLayerX", "extrapolationLayerY", "extrapolationLayerZ", "extrapolationCounts",
                 "colliderLoads", "colliderLoadTerms", "colliderMotions", "colliderMotionFaces",
+                "colliderShapes", "colliderPlacement", "colliderPlacedCells", "colliderCellIds",
                 "airPockets", "airPocketIds", "airPocketUnits", "airPocketCells", "airPocketOpen", "airPocketPasses",
                 "contactField", "contactCells"):
         return "i"
@@ -431,6 +433,47 @@ class Solver:
         the ps_result (INVALID: a refused pointer or count; the host is NOT synchronised).  A collider whose values are not all finite
         paints nothing: its faces are counted in the last slot of "colliderMotionFaces"."""
         return self._check(self.L.ps_paint_collider_velocities_device(self.h, device_address(ptr), int(count), stream_handle(stream)), allow=(1, -2))
+
+    def set_collider_shapes(self, shapes):
+        """ps_set_collider_shapes: `shapes` is a sequence of (sdf, h, orig) — sdf a float32 array of shape (n2, n1, n0) (x fastest, the body's
+        own frame, the sign convention of the collision field), h the sample spacing, orig the body-frame low corner of the volume; None
+        or an empty sequence drops the shapes.  A context setting: copied at once, kept across uploads.  Returns the ps_result: INVALID
+        for a refused shape (the reason in last_error(), the previous shapes kept).  Array "colliderShapes" holds the count."""
+        shapes = [] if shapes is None else list(shapes)
+        if not shapes:
+            return self._check(self.L.ps_set_collider_shapes(self.h, None), allow=(1, -2))
+        tab = (_abi.ColliderShape * len(shapes))()
+        keep = []
+        for k, (sdf, h, orig) in enumerate(shapes):
+            v = None if sdf is None else np.ascontiguousarray(sdf, dtype=np.float32)
+            if v is not None and v.ndim != 3:
+                raise ValueError("a shape's sdf must be a (n2, n1, n0) array")
+            keep.append(v)
+            n = (0, 0, 0) if v is None else v.shape[::-1]
+            tab[k].n[0], tab[k].n[1], tab[k].n[2] = (int(q) for q in n)
+            tab[k].reserved, tab[k].h = 0, float(h)
+            tab[k].orig[0], tab[k].orig[1], tab[k].orig[2] = (float(q) for q in orig)
+            tab[k].sdf = None if v is None else v.ctypes.data
+        cs = _abi.ColliderShapes(len(shapes), tab)
+        return self._check(self.L.ps_set_collider_shapes(self.h, C.byref(cs)), allow=(1, -2))
+
+    def place_colliders(self, poses):
+        """ps_place_colliders: `poses` has shape (count, 12) — R[9] row-major (body to world), t[3] per collider, count the shapes' count;
+        every shape is placed into the collision field and the id field of the last upload, at once: a cell takes the largest solid
+        depth among what it holds and the colliders that reach it, and the id of the winner.  Returns the ps_result: INVALID before any
+        upload, without shapes, for another count or a value that is not finite (nothing written).  Arrays "colliderPlacement",
+        "colliderPoseTable", "colliderPlacedCells", "collisionField" and "colliderCellIds" say what the call left."""
+        m = np.ascontiguousarray(poses, dtype=np.float64)
+        if m.ndim != 2 or m.shape[1] != 12:
+            raise ValueError("poses must hold 12 values per collider")
+        cp = _abi.ColliderPoses(m.shape[0], m.ctypes.data)
+        return self._check(self.L.ps_place_colliders(self.h, C.byref(cp)), allow=(1, -2))
+
+    def place_colliders_device(self, ptr, count, stream=None):
+        """ps_place_colliders_device: the same from 12 * count doubles of device memory, read behind what `stream` holds.  Returns the
+        ps_result (INVALID: a refused pointer or count; the host is NOT synchronised).  A collider whose pose is not all finite places
+        nothing and is counted in the last slot of "colliderPlacedCells"."""
+        return self._check(self.L.ps_place_colliders_device(self.h, device_address(ptr), int(count), stream_handle(stream)), allow=(1, -2))
 
     def label_air_pockets(self):
         """ps_label_air_pockets: labels the connected air regions of the grid of the last upload (single domain) and returns their number K.

@@ -93,6 +93,32 @@ COLLIDER_MOTION_CALLS = (
 )
 
 
+COLLIDER_SHAPE_REACH = 4.0         # PS_COLLIDER_SHAPE_REACH (ps_place_colliders)
+
+
+class ColliderShape(C.Structure):
+    """ps_collider_shape (ps_set_collider_shapes): one collider's SDF volume in the body's own frame"""
+    _fields_ = [("n", C.c_int32 * 3), ("reserved", C.c_int32), ("h", C.c_double), ("orig", C.c_double * 3), ("sdf", C.c_void_p)]
+
+
+class ColliderShapes(C.Structure):
+    """ps_collider_shapes"""
+    _fields_ = [("count", C.c_int32), ("shape", C.POINTER(ColliderShape))]
+
+
+class ColliderPoses(C.Structure):
+    """ps_collider_poses (ps_place_colliders): R[9] row-major (body to world), t[3] per collider"""
+    _fields_ = [("count", C.c_int32), ("pose", C.c_void_p)]
+
+
+# the collider shape calls: name -> argument types; every one returns int32
+COLLIDER_SHAPE_CALLS = (
+    ("ps_set_collider_shapes", (C.c_void_p, C.POINTER(ColliderShapes))),
+    ("ps_place_colliders", (C.c_void_p, C.POINTER(ColliderPoses))),
+    ("ps_place_colliders_device", (C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p)),
+)
+
+
 # the air pocket calls (ps_label_air_pockets ...): name -> argument types; every one returns int32
 AIR_POCKET_CALLS = (
     ("ps_label_air_pockets", (C.c_void_p, C.POINTER(C.c_int32))),

@@ -108,6 +108,7 @@ void ps_context::uploadReset(const ps_params* p, const ps_fields_in* in) {
     dropped |= dropColliderIds();                         // ... and so did the collider ids (ps_upload_collider_ids)
     dropped |= dropAirPockets();                          // ... and the air pocket labels (ps_label_air_pockets)
     dropped |= dropMotions();                             // ... and what ps_paint_collider_velocities left: the ingest replaces collisionvel
+    dropped |= dropPlacement();                           // ... and what ps_place_colliders left: the ingest replaces collision (the shapes stay)
     releaseIdle(dropped);                                // one synchronisation for whatever was present, none when nothing was
 }
 
@@ -146,6 +147,7 @@ void ps_context::ingestHost(const ps_fields_in* in) {
 void ps_context::uploadTail() {
     uploaded = true; isSetup = false; isSolved = false;
     arrays.clear();          // the registered device pointers may have been re-allocated above
+    registerShapeArrays();   // (ps_set_collider_shapes is a context setting: its array outlives an upload)
     slabEnabled = false;     // a decomposition describes ONE grid: set it again after every upload (ps_set_slab / ps_set_brick)
     deviceShareRows = 0; nXseg[0] = nXseg[1] = 0;
     blockMapOwned = -1;
@@ -203,6 +205,8 @@ void ps_context::setupPhase(int phase) {
         arrays.clear();
         registerPocketArrays();                 // (ps_label_air_pockets: a setup keeps the labels, also one that throws)
         registerMotionArrays();                 // (ps_paint_collider_velocities: a setup keeps what was painted)
+        registerShapeArrays();                  // (ps_set_collider_shapes: a context setting)
+        registerPlacementArrays();              // (ps_place_colliders: a setup keeps what was placed)
         if (rheoPass == 0) rheoIters.clear();   // (ps_set_rheology: one entry per solve of the step)
         // Picard passes need the halo of the last pass's output velocity: a decomposition refuses them on every rank (ps_dist.hpp: distStep)
         if (slabEnabled && rheoSet.model != PS_RHEOLOGY_NEWTONIAN && rheoSet.passes > 0) throw Error("rheology passes need a single domain");
@@ -460,6 +464,8 @@ void ps_context::registerArrays() {
     }
     registerPocketArrays();   // the labels of ps_label_air_pockets outlive a setup, solve or step
     registerMotionArrays();   // ... and so does what ps_paint_collider_velocities painted
+    registerShapeArrays();    // ... the shapes of ps_set_collider_shapes
+    registerPlacementArrays();   // ... and what ps_place_colliders placed
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -878,6 +884,51 @@ int32_t ps_paint_collider_velocities(ps_context* c, const ps_collider_motions* m
         return PS_SUCCESS;
     })
 }
+// what ps_set_collider_shapes refuses: the reason, or empty (the error texts name no macro: the release library holds no PS_* string)
+static std::string refuseShapes(const ps_collider_shapes* s) {
+    if (s->count < 0 || s->count > PS_COLLIDER_MAX) return "count outside 0.." + std::to_string(PS_COLLIDER_MAX);
+    if (!s->shape) return "shape is null";
+    for (int k = 0; k < s->count; ++k) {
+        const ps_collider_shape& S = s->shape[k];
+        const std::string who = "shape " + std::to_string(k) + ": ";
+        for (int a = 0; a < 3; ++a) if (S.n[a] < 2 || S.n[a] > 1022) return who + "extent outside 2..1022";
+        if (!(S.h > 0.) || !std::isfinite(S.h)) return who + "spacing not positive and finite";
+        for (int a = 0; a < 3; ++a) if (!std::isfinite(S.orig[a])) return who + "origin not finite";
+        if (!S.sdf) return who + "no samples";
+        const int64_t n = (int64_t)S.n[0] * S.n[1] * S.n[2];
+        for (int64_t m = 0; m < n; ++m) if (!std::isfinite(S.sdf[m])) return who + "non-finite value at sample " + std::to_string(m);
+    }
+    return {};
+}
+int32_t ps_set_collider_shapes(ps_context* c, const ps_collider_shapes* s) {
+    if (!c) return PS_FAILED;
+    PS_TRY(c, {
+        const bool drop = !s || s->count == 0;
+        const std::string why = drop ? std::string() : refuseShapes(s);
+        if (!why.empty()) { c->err = "ps_set_collider_shapes: " + why; return PS_INVALID; }      // (the previous shapes stay)
+        c->setColliderShapes(drop ? nullptr : s->shape, drop ? 0 : s->count);
+        return PS_SUCCESS;
+    })
+}
+// what both forms of ps_place_colliders refuse before they look at the table: the reason, or empty
+static std::string refusePlacement(const ps_context* c, const double* pose, int32_t count) {
+    if (c->shapesCount <= 0) return "no shapes set: call ps_set_collider_shapes first";
+    if (!pose) return "pose is null";
+    if (count != c->shapesCount) return "count differs from the shapes' count";
+    return {};
+}
+int32_t ps_place_colliders(ps_context* c, const ps_collider_poses* p) {
+    if (!c) return PS_FAILED;
+    PS_TRY(c, {
+        if (notUploaded(c, "ps_place_colliders")) return PS_INVALID;
+        std::string why = c->shapesCount <= 0 ? refusePlacement(c, nullptr, 0) : (p ? refusePlacement(c, p->pose, p->count) : std::string("poses is null"));
+        for (int q = 0; why.empty() && q < 12 * p->count; ++q)
+            if (!std::isfinite(p->pose[q])) why = "pose of collider " + std::to_string(q / 12) + " is not finite";
+        if (!why.empty()) { c->err = "ps_place_colliders: " + why; return PS_INVALID; }
+        c->placeColliders(p->pose, p->count, false, nullptr);
+        return PS_SUCCESS;
+    })
+}
 int32_t ps_label_air_pockets(ps_context* c, int32_t* count) {
     if (!c) return PS_FAILED;
     PS_TRY(c, {
@@ -1064,6 +1115,19 @@ int32_t ps_paint_collider_velocities_device(ps_context* c, const double* motion,
         const DevicePtr ptrs[] = {{motion, 2 * 9 * (int64_t)count, "motion", false}};      // (counted in 4-byte words)
         if (refuseDeviceCall(c, nullptr, "ps_paint_collider_velocities_device", 0, ptrs)) return PS_INVALID;
         c->paintColliderVelocities(motion, count, true, (hipStream_t)stream);
+        return PS_SUCCESS;
+    })
+}
+int32_t ps_place_colliders_device(ps_context* c, const double* pose, int32_t count, void* stream) {
+    if (!c) return PS_FAILED;
+    PS_TRY(c, {
+        if (notUploaded(c, "ps_place_colliders")) return PS_INVALID;
+        std::string why = refusePlacement(c, pose, count);
+        if (why.empty() && ((uintptr_t)pose & 7)) why = "pose: the pointer is not 8-byte aligned";
+        if (!why.empty()) { c->err = "ps_place_colliders_device: " + why; return PS_INVALID; }
+        const DevicePtr ptrs[] = {{pose, 2 * 12 * (int64_t)count, "pose", false}};      // (counted in 4-byte words)
+        if (refuseDeviceCall(c, nullptr, "ps_place_colliders_device", 0, ptrs)) return PS_INVALID;
+        c->placeColliders(pose, count, true, (hipStream_t)stream);
         return PS_SUCCESS;
     })
 }

@@ -144,6 +144,9 @@ struct ScanFacts { float first = 0.f; bool differs = false; int64_t bad = -1; };
 // (SCAN_BAD_NONE: not scanned) and the label of its refusal
 struct CellIn { const void* src; void* dst; int bad; const char* label; };
 
+// One collider's volume in the pool of ps_context::shapePool (ps_set_collider_shapes): extents, first sample, spacing, body-frame low corner
+struct ShapeDesc { int32_t n[3]; int32_t pad; int64_t off; double h; double o[3]; };
+
 struct CellField;     // ps_setup_util.hpp: what the setup kernels sample
 struct FaceDensity;
 
@@ -445,6 +448,23 @@ struct ps_context {
     void paintColliderVelocities(const double* motion, int count, bool device, hipStream_t caller);    // ps_motions.hip: after the ABI's refusals
     bool dropMotions();                                  // ps_motions.hip: the table, the counters and the arrays; false when there was nothing to drop
     void registerMotionArrays();                         // ps_motions.hip: the arrays of the last call (none without one since the last upload)
+    // Collider shapes (ps_set_collider_shapes, ps_place_colliders, extension; ps_shapes.hip).  The shapes are a context setting: shapesCount
+    // (array "colliderShapes"; 0: none), shapePool: every volume's samples back to back, shapeDesc: a descriptor per collider; kept across
+    // uploads, dropped by a call with count 0.  A placement rewrites collision and colliderIds at once (creating the id field where there is
+    // none); what it wrote lives as long as that upload's collision.  placementCount: the count of the last call since the last upload (array
+    // "colliderPlacement"; 0: none, and none of the arrays); placePoses: the 12 * count doubles the kernel read; placeCells: count + 2
+    // counters.  Allocated by a call, as long as its count needs; dropped by every upload.
+    int32_t shapesCount = 0, placementCount = 0;
+    ps::DevBuf<float> shapePool;
+    ps::DevBuf<ps::ShapeDesc> shapeDesc;
+    ps::DevBuf<double> placePoses;
+    ps::DevBuf<int32_t> placeCells;
+    void setColliderShapes(const ps_collider_shape* shape, int count);                                 // ps_shapes.hip: after the ABI's refusals
+    void placeColliders(const double* poses, int count, bool device, hipStream_t caller);              // ps_shapes.hip: after the ABI's refusals
+    bool dropShapes();                                   // ps_shapes.hip: the pool, the descriptors and the array; false when there was nothing to drop
+    bool dropPlacement();                                // ps_shapes.hip: the poses, the counters and the arrays; false when there was nothing to drop
+    void registerShapeArrays();                          // ps_shapes.hip: "colliderShapes" while shapes are set
+    void registerPlacementArrays();                      // ps_shapes.hip: the arrays of the last placement (none without one since the last upload)
     // Air pockets (ps_label_air_pockets, extension; ps_pockets.hip): the connected air regions of the grid of the last upload (every upload and
     // every ps_set_slab / ps_set_brick drops them; a setup, solve or step keeps them).  pocketsHave: labels exist; pocketCount: K;
     // pocketPassesHost: the global propagation passes the last call ran (array "airPocketPasses").  pocketIds: the pocket of every cell (-1:

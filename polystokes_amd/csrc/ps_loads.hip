@@ -326,6 +326,7 @@ std::string ps_context::uploadColliderIds(const int32_t* ids, bool fromDevice, i
         const CellIn in = cellIn(ids, colliderIds, SCAN_BAD_NONE, "");
         ingestCellFields(&in, 1, fromDevice, layout, caller, false);
     }
+    registerPlacementArrays();      // ("colliderCellIds" of ps_place_colliders follows the id field)
     releaseIdle(dropped);
     return {};
 }
