@@ -101,15 +101,62 @@ void ps_context::uploadReset(const ps_params* p, const ps_fields_in* in) {
     dx = in->dx; invDx = 1. / dx; dt = in->dt; invDt = 1. / dt; rho = (double)in->density;
     rhoScalar = rho; densField = false;   // every upload drops a density field (ps_upload_density_field): it described the previous grid
     HIP_CHECK(hipSetDevice(device));
-    bool dropped = dropSurfaceFields();                   // ... and the free-surface fields (ps_upload_surface_fields)
-    dropped |= dropContactCosine();                       // ... and the contact cosine field (ps_upload_contact_cosine_field)
     for (int a = 0; a < 3; ++a) orig[a] = in->orig[a];   // (the default pivot of ps_set_collider_loads)
+    releaseIdle(dropUploadScoped());                     // one synchronisation for whatever was present, none when nothing was
+}
+
+// ---- what lives how long ----
+// Whatever described the fields of the previous upload goes with every upload: a feature with such buffers adds its drop...() here.
+bool ps_context::dropUploadScoped() {
+    bool dropped = dropSurfaceFields();                   // the free-surface fields (ps_upload_surface_fields)
+    dropped |= dropContactCosine();                       // the contact cosine field (ps_upload_contact_cosine_field)
     forgetLoads();                                        // the loads of an earlier step described the previous fields
     dropped |= dropColliderIds();                         // ... and so did the collider ids (ps_upload_collider_ids)
     dropped |= dropAirPockets();                          // ... and the air pocket labels (ps_label_air_pockets)
-    dropped |= dropMotions();                             // ... and what ps_paint_collider_velocities left: the ingest replaces collisionvel
-    dropped |= dropPlacement();                           // ... and what ps_place_colliders left: the ingest replaces collision (the shapes stay)
-    releaseIdle(dropped);                                // one synchronisation for whatever was present, none when nothing was
+    dropped |= dropMotions();                             // what ps_paint_collider_velocities left: the ingest replaces collisionvel
+    dropped |= dropPlacement();                           // what ps_place_colliders left: the ingest replaces collision (the shapes stay)
+    return dropped;
+}
+// The arrays that a setup, solve or step must not lose: everything that clears `arrays` (uploadTail, setupPhase(0), registerArrays) calls
+// this afterwards, and nothing else names these features.  A feature whose arrays outlive a setup adds its register...Arrays() here, and
+// its drop...() above unless it is a context setting like the shapes.  A register...Arrays() erases its names while the feature has
+// nothing, so after an upload only "colliderShapes" is left.  (uploadColliderIds calls registerPlacementArrays as well: "colliderCellIds"
+// follows the id field.)
+void ps_context::registerKeptArrays() {
+    registerPocketArrays();        // ps_label_air_pockets: the labels, also after a setup that throws
+    registerMotionArrays();        // ps_paint_collider_velocities: what was painted
+    registerShapeArrays();         // ps_set_collider_shapes: a context setting
+    registerPlacementArrays();     // ps_place_colliders: what was placed
+}
+
+// ---- collider tables (ps_paint_collider_velocities, ps_place_colliders): the host work the two calls share ----
+bool ps_context::dropColliderTable(ColliderTable& C) {
+    const bool had = C.table.p != nullptr;
+    C.table.free(); C.counters.free();
+    C.count = 0;
+    (this->*C.reg)();
+    return had;
+}
+bool ps_context::ingestColliderTable(ColliderTable& C, const double* src, int count, int stride, bool fromDevice, hipStream_t caller) {
+    const size_t n = (size_t)(stride * count);
+    const bool dropped = C.table.p && C.table.n != n && dropColliderTable(C);
+    C.table.alloc(n);
+    C.counters.alloc((size_t)(count + 2));
+    if (fromDevice) {
+        waitForCaller(caller);
+        HIP_CHECK(hipMemcpyAsync(C.table.p, src, n * sizeof(double), hipMemcpyDeviceToDevice, stream));
+        releaseToCaller(caller);     // the caller's stream may rewrite its table once the copy has run
+    } else {
+        HIP_CHECK(hipMemcpyAsync(C.table.p, src, n * sizeof(double), hipMemcpyHostToDevice, stream));
+    }
+    HIP_CHECK(hipMemsetAsync(C.counters.p, 0, (size_t)(count + 2) * sizeof(int32_t), stream));
+    return dropped;
+}
+void ps_context::finishColliderTable(ColliderTable& C, int count, bool fromDevice, bool dropped) {
+    C.count = count;
+    (this->*C.reg)();
+    if (!fromDevice) HIP_CHECK(hipStreamSynchronize(stream));
+    releaseIdle(dropped);
 }
 
 void ps_context::ingestHost(const ps_fields_in* in) {
@@ -147,7 +194,7 @@ void ps_context::ingestHost(const ps_fields_in* in) {
 void ps_context::uploadTail() {
     uploaded = true; isSetup = false; isSolved = false;
     arrays.clear();          // the registered device pointers may have been re-allocated above
-    registerShapeArrays();   // (ps_set_collider_shapes is a context setting: its array outlives an upload)
+    registerKeptArrays();    // (uploadReset dropped all of them but the shapes, a context setting)
     slabEnabled = false;     // a decomposition describes ONE grid: set it again after every upload (ps_set_slab / ps_set_brick)
     deviceShareRows = 0; nXseg[0] = nXseg[1] = 0;
     blockMapOwned = -1;
@@ -203,10 +250,7 @@ void ps_context::setupPhase(int phase) {
         extrapUsedHost = 0;
         loadsUsedHost = 0;
         arrays.clear();
-        registerPocketArrays();                 // (ps_label_air_pockets: a setup keeps the labels, also one that throws)
-        registerMotionArrays();                 // (ps_paint_collider_velocities: a setup keeps what was painted)
-        registerShapeArrays();                  // (ps_set_collider_shapes: a context setting)
-        registerPlacementArrays();              // (ps_place_colliders: a setup keeps what was placed)
+        registerKeptArrays();                   // (also a setup that throws keeps them)
         if (rheoPass == 0) rheoIters.clear();   // (ps_set_rheology: one entry per solve of the step)
         // Picard passes need the halo of the last pass's output velocity: a decomposition refuses them on every rank (ps_dist.hpp: distStep)
         if (slabEnabled && rheoSet.model != PS_RHEOLOGY_NEWTONIAN && rheoSet.passes > 0) throw Error("rheology passes need a single domain");
@@ -462,10 +506,7 @@ void ps_context::registerArrays() {
         reg(std::string("faceRow") + ax[a], faceRow[a].p, g.count(1 + a), 4);
         if (slabEnabled && isSolved) reg(std::string("owned") + ax[a], ownedFace[a].p, g.count(1 + a), 4);
     }
-    registerPocketArrays();   // the labels of ps_label_air_pockets outlive a setup, solve or step
-    registerMotionArrays();   // ... and so does what ps_paint_collider_velocities painted
-    registerShapeArrays();    // ... the shapes of ps_set_collider_shapes
-    registerPlacementArrays();   // ... and what ps_place_colliders placed
+    registerKeptArrays();
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -866,23 +907,41 @@ int32_t ps_get_collider_loads(ps_context* c, double* out, int64_t out_len) {
         return PS_SUCCESS;
     })
 }
-// what both forms of ps_paint_collider_velocities refuse before they look at the table: the reason, or empty
-static std::string refuseMotions(const double* motion, int32_t count) {
-    if (!motion) return "motion is null";
-    if (count < 1 || count > PS_COLLIDER_MAX) return "count outside 1.." + std::to_string(PS_COLLIDER_MAX);
-    return {};
-}
-int32_t ps_paint_collider_velocities(ps_context* c, const ps_collider_motions* m) {
+// The four collider-table entry points (ps_paint_collider_velocities, ps_place_colliders and their _device forms) are this one call.  Its
+// refusals, in order: not uploaded; no shapes (perShape only); the struct (`given`: the host form's pointer is not null) or the table is
+// null; the count (1..PS_COLLIDER_MAX, or with perShape the shapes' count); then the host form reads the table and refuses a value
+// that is not finite, the device form refuses a misaligned pointer and what refuseDeviceCall refuses.
+struct TableCall {
+    const char* hostName; const char* deviceName; const char* noun; int stride; bool perShape;
+    void (ps_context::*run)(const double*, int, bool, hipStream_t);
+};
+static int32_t colliderTableCall(ps_context* c, const TableCall& K, bool given, const double* table, int32_t count, bool device, void* stream) {
     if (!c) return PS_FAILED;
     PS_TRY(c, {
-        if (notUploaded(c, "ps_paint_collider_velocities")) return PS_INVALID;
-        std::string why = m ? refuseMotions(m->motion, m->count) : std::string("motions is null");
-        for (int q = 0; why.empty() && q < 9 * m->count; ++q)
-            if (!std::isfinite(m->motion[q])) why = "motion of collider " + std::to_string(q / 9) + " is not finite";
-        if (!why.empty()) { c->err = "ps_paint_collider_velocities: " + why; return PS_INVALID; }
-        c->paintColliderVelocities(m->motion, m->count, false, nullptr);
+        if (notUploaded(c, K.hostName)) return PS_INVALID;
+        const std::string noun = K.noun;
+        std::string why;
+        if (K.perShape && c->shapesCount <= 0) why = "no shapes set: call ps_set_collider_shapes first";
+        else if (!given) why = noun + "s is null";
+        else if (!table) why = noun + " is null";
+        else if (!K.perShape && (count < 1 || count > PS_COLLIDER_MAX)) why = "count outside 1.." + std::to_string(PS_COLLIDER_MAX);
+        else if (K.perShape && count != c->shapesCount) why = "count differs from the shapes' count";
+        else if (device && ((uintptr_t)table & 7)) why = noun + ": the pointer is not 8-byte aligned";
+        for (int q = 0; !device && why.empty() && q < K.stride * count; ++q)
+            if (!std::isfinite(table[q])) why = noun + " of collider " + std::to_string(q / K.stride) + " is not finite";
+        if (!why.empty()) { c->err = std::string(device ? K.deviceName : K.hostName) + ": " + why; return PS_INVALID; }
+        if (device) {
+            const DevicePtr ptrs[] = {{table, 2 * K.stride * (int64_t)count, K.noun, false}};      // (counted in 4-byte words)
+            if (refuseDeviceCall(c, nullptr, K.deviceName, 0, ptrs)) return PS_INVALID;
+        }
+        (c->*K.run)(table, count, device, (hipStream_t)stream);
         return PS_SUCCESS;
     })
+}
+static const TableCall kPaintCall = {"ps_paint_collider_velocities", "ps_paint_collider_velocities_device", "motion", 9, false, &ps_context::paintColliderVelocities};
+static const TableCall kPlaceCall = {"ps_place_colliders", "ps_place_colliders_device", "pose", 12, true, &ps_context::placeColliders};
+int32_t ps_paint_collider_velocities(ps_context* c, const ps_collider_motions* m) {
+    return colliderTableCall(c, kPaintCall, m != nullptr, m ? m->motion : nullptr, m ? m->count : 0, false, nullptr);
 }
 // what ps_set_collider_shapes refuses: the reason, or empty (the error texts name no macro: the release library holds no PS_* string)
 static std::string refuseShapes(const ps_collider_shapes* s) {
@@ -910,24 +969,8 @@ int32_t ps_set_collider_shapes(ps_context* c, const ps_collider_shapes* s) {
         return PS_SUCCESS;
     })
 }
-// what both forms of ps_place_colliders refuse before they look at the table: the reason, or empty
-static std::string refusePlacement(const ps_context* c, const double* pose, int32_t count) {
-    if (c->shapesCount <= 0) return "no shapes set: call ps_set_collider_shapes first";
-    if (!pose) return "pose is null";
-    if (count != c->shapesCount) return "count differs from the shapes' count";
-    return {};
-}
 int32_t ps_place_colliders(ps_context* c, const ps_collider_poses* p) {
-    if (!c) return PS_FAILED;
-    PS_TRY(c, {
-        if (notUploaded(c, "ps_place_colliders")) return PS_INVALID;
-        std::string why = c->shapesCount <= 0 ? refusePlacement(c, nullptr, 0) : (p ? refusePlacement(c, p->pose, p->count) : std::string("poses is null"));
-        for (int q = 0; why.empty() && q < 12 * p->count; ++q)
-            if (!std::isfinite(p->pose[q])) why = "pose of collider " + std::to_string(q / 12) + " is not finite";
-        if (!why.empty()) { c->err = "ps_place_colliders: " + why; return PS_INVALID; }
-        c->placeColliders(p->pose, p->count, false, nullptr);
-        return PS_SUCCESS;
-    })
+    return colliderTableCall(c, kPlaceCall, p != nullptr, p ? p->pose : nullptr, p ? p->count : 0, false, nullptr);
 }
 int32_t ps_label_air_pockets(ps_context* c, int32_t* count) {
     if (!c) return PS_FAILED;
@@ -1106,30 +1149,10 @@ int32_t ps_get_collider_loads_device(ps_context* c, double* dev, int64_t len, vo
     })
 }
 int32_t ps_paint_collider_velocities_device(ps_context* c, const double* motion, int32_t count, void* stream) {
-    if (!c) return PS_FAILED;
-    PS_TRY(c, {
-        if (notUploaded(c, "ps_paint_collider_velocities")) return PS_INVALID;
-        std::string why = refuseMotions(motion, count);
-        if (why.empty() && ((uintptr_t)motion & 7)) why = "motion: the pointer is not 8-byte aligned";
-        if (!why.empty()) { c->err = "ps_paint_collider_velocities_device: " + why; return PS_INVALID; }
-        const DevicePtr ptrs[] = {{motion, 2 * 9 * (int64_t)count, "motion", false}};      // (counted in 4-byte words)
-        if (refuseDeviceCall(c, nullptr, "ps_paint_collider_velocities_device", 0, ptrs)) return PS_INVALID;
-        c->paintColliderVelocities(motion, count, true, (hipStream_t)stream);
-        return PS_SUCCESS;
-    })
+    return colliderTableCall(c, kPaintCall, true, motion, count, true, stream);
 }
 int32_t ps_place_colliders_device(ps_context* c, const double* pose, int32_t count, void* stream) {
-    if (!c) return PS_FAILED;
-    PS_TRY(c, {
-        if (notUploaded(c, "ps_place_colliders")) return PS_INVALID;
-        std::string why = refusePlacement(c, pose, count);
-        if (why.empty() && ((uintptr_t)pose & 7)) why = "pose: the pointer is not 8-byte aligned";
-        if (!why.empty()) { c->err = "ps_place_colliders_device: " + why; return PS_INVALID; }
-        const DevicePtr ptrs[] = {{pose, 2 * 12 * (int64_t)count, "pose", false}};      // (counted in 4-byte words)
-        if (refuseDeviceCall(c, nullptr, "ps_place_colliders_device", 0, ptrs)) return PS_INVALID;
-        c->placeColliders(pose, count, true, (hipStream_t)stream);
-        return PS_SUCCESS;
-    })
+    return colliderTableCall(c, kPlaceCall, true, pose, count, true, stream);
 }
 int32_t ps_download_fields_device(ps_context* c, const ps_fields_out* out, int32_t layout, void* stream) {
     if (!c || !out) return PS_FAILED;

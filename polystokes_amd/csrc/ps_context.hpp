@@ -80,6 +80,9 @@ inline ArrayInfo hostArray(const void* p, int64_t count, int elem) { ArrayInfo a
 // One entry of a feature's array list (ps_context::setArrays): the feature's register...Arrays() holds the one list of its names, and
 // registers or erases by it
 struct NamedArray { const char* name; ArrayInfo info; };
+// What a call with a small table of doubles per collider keeps (ps_context::ingestColliderTable): the feature's register...Arrays(), the
+// table the kernel read, count + 2 counters, the count of the last call
+struct ColliderTable { void (::ps_context::*reg)(); DevBuf<double> table; DevBuf<int32_t> counters; int32_t count = 0; };
 
 // The slots of ps_context::counters (int32 each): flags and totals that kernels write and the host reads (readCounter / fetchCounters).
 // Every user clears its own slot before the launch; slots that one fetch reads are adjacent (asserted below).
@@ -438,33 +441,37 @@ struct ps_context {
     bool dropColliderIds();                              // ps_loads.hip: false when there was nothing to drop
     std::string uploadColliderIds(const int32_t* ids, bool device, int layout, hipStream_t caller);   // ps_loads.hip
     void copyColliderLoads(double* dst, int64_t len, bool device, hipStream_t caller);                 // ps_loads.hip: throws when there are none
-    // Collider motions (ps_paint_collider_velocities, extension; ps_motions.hip): a call writes rigid-body velocities into cvel at once; what it
-    // wrote lives as long as that upload's cvel.  motionsCount: the count of the last call since the last upload (array "colliderMotions"; 0:
-    // none, and none of the arrays); motionTable: the 9 * count doubles the kernel read; motionFaces: count + 2 counters.  Allocated by a
-    // call, as long as its count needs; dropped by every upload.
-    int32_t motionsCount = 0;
-    ps::DevBuf<double> motionTable;
-    ps::DevBuf<int32_t> motionFaces;
+    // Collider tables (ps_paint_collider_velocities, ps_place_colliders, extensions): a call brings `stride` doubles per collider, acts on the
+    // grid at once and keeps a ps::ColliderTable for the arrays: the table the kernel read, count + 2 counters, and the count of the last call
+    // since the last upload (0: none, and none of the feature's arrays).  Allocated by a call, as long as its count needs; dropped by every
+    // upload.  ingestColliderTable: drops a pair of another length (true: something was dropped), allocates, copies the table (host
+    // memory, or device memory behind what the caller's stream holds) and clears the counters.  finishColliderTable: the count, the
+    // arrays, a synchronisation in the host form only (its table is pageable memory), releaseIdle(dropped).
+    bool ingestColliderTable(ps::ColliderTable& C, const double* src, int count, int stride, bool device, hipStream_t caller);
+    void finishColliderTable(ps::ColliderTable& C, int count, bool device, bool dropped);
+    bool dropColliderTable(ps::ColliderTable& C);        // the pair and the feature's arrays; false when there was nothing to drop
+    // Collider motions (ps_motions.hip): 9 doubles per collider, painted into cvel; what a call wrote lives as long as that upload's cvel.
+    ps::ColliderTable motions{&ps_context::registerMotionArrays};
     void paintColliderVelocities(const double* motion, int count, bool device, hipStream_t caller);    // ps_motions.hip: after the ABI's refusals
-    bool dropMotions();                                  // ps_motions.hip: the table, the counters and the arrays; false when there was nothing to drop
+    bool dropMotions() { return dropColliderTable(motions); }
     void registerMotionArrays();                         // ps_motions.hip: the arrays of the last call (none without one since the last upload)
-    // Collider shapes (ps_set_collider_shapes, ps_place_colliders, extension; ps_shapes.hip).  The shapes are a context setting: shapesCount
-    // (array "colliderShapes"; 0: none), shapePool: every volume's samples back to back, shapeDesc: a descriptor per collider; kept across
-    // uploads, dropped by a call with count 0.  A placement rewrites collision and colliderIds at once (creating the id field where there is
-    // none); what it wrote lives as long as that upload's collision.  placementCount: the count of the last call since the last upload (array
-    // "colliderPlacement"; 0: none, and none of the arrays); placePoses: the 12 * count doubles the kernel read; placeCells: count + 2
-    // counters.  Allocated by a call, as long as its count needs; dropped by every upload.
-    int32_t shapesCount = 0, placementCount = 0;
+    // Collider shapes (ps_shapes.hip).  The shapes are a context setting: shapesCount (array "colliderShapes"; 0: none), shapePool: every
+    // volume's samples back to back, shapeDesc: a descriptor per collider; kept across uploads, dropped by a call with count 0.  A placement
+    // (12 doubles per collider) rewrites collision and colliderIds at once, creating the id field where there is none; what it wrote lives
+    // as long as that upload's collision.
+    int32_t shapesCount = 0;
     ps::DevBuf<float> shapePool;
     ps::DevBuf<ps::ShapeDesc> shapeDesc;
-    ps::DevBuf<double> placePoses;
-    ps::DevBuf<int32_t> placeCells;
+    ps::ColliderTable placement{&ps_context::registerPlacementArrays};
     void setColliderShapes(const ps_collider_shape* shape, int count);                                 // ps_shapes.hip: after the ABI's refusals
     void placeColliders(const double* poses, int count, bool device, hipStream_t caller);              // ps_shapes.hip: after the ABI's refusals
     bool dropShapes();                                   // ps_shapes.hip: the pool, the descriptors and the array; false when there was nothing to drop
-    bool dropPlacement();                                // ps_shapes.hip: the poses, the counters and the arrays; false when there was nothing to drop
+    bool dropPlacement() { return dropColliderTable(placement); }
     void registerShapeArrays();                          // ps_shapes.hip: "colliderShapes" while shapes are set
     void registerPlacementArrays();                      // ps_shapes.hip: the arrays of the last placement (none without one since the last upload)
+    // The arrays that outlive a setup, solve or step (ps_context.hip states the rule); dropUploadScoped: what every upload drops
+    void registerKeptArrays();
+    bool dropUploadScoped();
     // Air pockets (ps_label_air_pockets, extension; ps_pockets.hip): the connected air regions of the grid of the last upload (every upload and
     // every ps_set_slab / ps_set_brick drops them; a setup, solve or step keeps them).  pocketsHave: labels exist; pocketCount: K;
     // pocketPassesHost: the global propagation passes the last call ran (array "airPocketPasses").  pocketIds: the pocket of every cell (-1:

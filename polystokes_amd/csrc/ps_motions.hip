@@ -7,6 +7,7 @@
 #include <cmath>
 
 #include "ps_context.hpp"
+#include "ps_setup_util.hpp"
 
 using namespace ps;
 
@@ -41,9 +42,8 @@ __device__ __forceinline__ int3 addDigits(int3 p, const int3 s, const int3 fd) {
 
 // A workgroup stages the motions and a finite flag per collider into LDS, then walks tiles of MBS * MU consecutive faces of face grid
 // blockIdx.y, x fastest: tile blockIdx.x, + gridDim.x, ...; a thread takes the faces tid, tid + MBS, ... of a tile.  The walk keeps the
-// face's three indices and adds the stride's three digits with carries: no division per face.  Counting: a wave adds once per distinct
-// slot among its lanes (one LDS add when they share it, which is the rule away from where two colliders meet), and the workgroup adds its
-// bins to the global counters at the end, one atomic per slot that occurred.
+// face's three indices and adds the stride's three digits with carries: no division per face.  Counting: waveBinAdd per face, and the
+// workgroup adds its bins to the global counters at the end, one atomic per slot that occurred.
 __global__ __launch_bounds__(MBS) void k_paint_motions(MotionTable T) {
     __shared__ double mot[PS_COLLIDER_MAX * MV];
     __shared__ int32_t finite[PS_COLLIDER_MAX];
@@ -108,13 +108,7 @@ __global__ __launch_bounds__(MBS) void k_paint_motions(MotionTable T) {
                     T.cvel[a][base + u * MBS + tid] = (float)(m[a] + (m[3 + a1] * arm2 - m[3 + a2] * arm1));
                 }
             }
-            unsigned long long todo = __ballot(live[u]);
-            while (todo) {
-                const int s = __shfl(slot, __ffsll((long long)todo) - 1, 64);
-                const unsigned long long same = __ballot(live[u] && slot == s);
-                if (lane == __ffsll((long long)same) - 1) atomicAdd(&bins[s], __popcll(same));
-                todo &= ~same;
-            }
+            waveBinAdd(bins, live[u], slot, lane);
         }
         p = addDigits(p, sd, fd);
     }
@@ -125,24 +119,12 @@ __global__ __launch_bounds__(MBS) void k_paint_motions(MotionTable T) {
 
 }  // namespace
 
-// ps_paint_collider_velocities / _device, after the ABI's refusals.  One small copy (the table: host memory, or device memory behind what the
-// caller's stream holds), the counters' reset and one launch on the context's stream.  The table and the counters are as long as this
-// call's count needs: a call with another count drops the previous pair and ends with the stream idle; the host form always ends so (its
-// table is pageable memory), the device form otherwise does not synchronise the host.
+// ps_paint_collider_velocities / _device, after the ABI's refusals: the table's ingest (ps_context::ingestColliderTable) and one launch on the
+// context's stream.  The host form ends with the stream idle; the device form synchronises the host only where a table of another size
+// was dropped.
 void ps_context::paintColliderVelocities(const double* motion, int count, bool fromDevice, hipStream_t caller) {
     HIP_CHECK(hipSetDevice(device));
-    const bool dropped = (motionTable.p && motionTable.n != (size_t)(MV * count)) ? dropMotions() : false;
-    motionTable.alloc((size_t)(MV * count));
-    motionFaces.alloc((size_t)(count + 2));
-    const size_t bytes = (size_t)(MV * count) * sizeof(double);
-    if (fromDevice) {
-        waitForCaller(caller);
-        HIP_CHECK(hipMemcpyAsync(motionTable.p, motion, bytes, hipMemcpyDeviceToDevice, stream));
-        releaseToCaller(caller);     // the caller's stream may rewrite its table once the copy has run
-    } else {
-        HIP_CHECK(hipMemcpyAsync(motionTable.p, motion, bytes, hipMemcpyHostToDevice, stream));
-    }
-    HIP_CHECK(hipMemsetAsync(motionFaces.p, 0, (size_t)(count + 2) * sizeof(int32_t), stream));
+    const bool dropped = ingestColliderTable(motions, motion, count, MV, fromDevice, caller);
     MotionTable T{};
     T.d = g.dims(0);
     int64_t most = 1;
@@ -152,33 +134,22 @@ void ps_context::paintColliderVelocities(const double* motion, int count, bool f
     }
     T.collision = collision.p;
     T.ids = colliderIds.p;
-    T.motion = motionTable.p; T.faces = motionFaces.p;
+    T.motion = motions.table.p; T.faces = motions.counters.p;
     T.dx = dx; T.negate = P.negateCollision ? 1 : 0; T.count = count;
     // PS_DEBUG_MOTION_GRID=<n> (lab build, tests): at most n workgroups per face grid, so that a small grid walks several tiles per workgroup
     const int cap = std::max(1, envInt(PS_ENV_LOUD("PS_DEBUG_MOTION_GRID"), MMAXGRID));
     const int perGrid = (int)std::min<int64_t>(cap, gridFor(most, MBS * MU));
     hipLaunchKernelGGL(k_paint_motions, dim3((unsigned)perGrid, 3), dim3(MBS), 0, stream, T);
-    motionsCount = count;
-    registerMotionArrays();
-    if (!fromDevice) HIP_CHECK(hipStreamSynchronize(stream));
-    releaseIdle(dropped);
+    finishColliderTable(motions, count, fromDevice, dropped);
 }
 
 void ps_context::registerMotionArrays() {
-    const int64_t nc = motionsCount;
-    const NamedArray list[] = {{"colliderMotions", hostArray(&motionsCount, 1, 4)},
-                               {"colliderMotionTable", ArrayInfo{motionTable.p, MV * nc, 8}},
-                               {"colliderMotionFaces", ArrayInfo{motionFaces.p, nc + 2, 4}},     // painted faces per collider, then the two left-alone counts
+    const int64_t nc = motions.count;
+    const NamedArray list[] = {{"colliderMotions", hostArray(&motions.count, 1, 4)},
+                               {"colliderMotionTable", ArrayInfo{motions.table.p, MV * nc, 8}},
+                               {"colliderMotionFaces", ArrayInfo{motions.counters.p, nc + 2, 4}},     // painted faces per collider, then the two left-alone counts
                                {"collisionVelocityX", ArrayInfo{cvel[0].p, g.count(1), 4}},        // the buffers the next setup reads
                                {"collisionVelocityY", ArrayInfo{cvel[1].p, g.count(2), 4}},
                                {"collisionVelocityZ", ArrayInfo{cvel[2].p, g.count(3), 4}}};
-    setArrays(list, motionsCount > 0);
-}
-
-bool ps_context::dropMotions() {
-    const bool had = motionTable.p != nullptr;
-    motionTable.free(); motionFaces.free();
-    motionsCount = 0;
-    registerMotionArrays();
-    return had;
+    setArrays(list, motions.count > 0);
 }

@@ -1,6 +1,7 @@
-// Device and host helpers shared by the setup translation units (ps_grid.hip, ps_blocks.hip, ps_tiles.hip, ps_surface.hip, ps_context.hip): the
-// cell-field sampler and the two material-field descriptions built on it, the walk over a region's box (RegionBox), the block scan, the 64-bit
-// mixer and the representative insert of the two hash tables.  Not included by ps_solve.hip: nothing here may reach the solver's device code.
+// Device and host helpers shared by the setup translation units (ps_grid.hip, ps_blocks.hip, ps_tiles.hip, ps_surface.hip, ps_context.hip,
+// ps_pockets.hip, ps_motions.hip, ps_shapes.hip): the cell-field sampler and the two material-field descriptions built on it, the walk over
+// a region's box (RegionBox), the block scan, the 64-bit mixer, the representative insert of the two hash tables and the collider kernels'
+// wave histogram.  Not included by ps_solve.hip: nothing here may reach the solver's device code.
 #pragma once
 #include "ps_common.hpp"
 
@@ -134,6 +135,20 @@ __device__ inline void hashInsertMin(unsigned long long* __restrict__ keys, int3
         unsigned long long cur = keys[slot];
         if (cur == HASH_EMPTY) { cur = atomicCAS(&keys[slot], HASH_EMPTY, h); if (cur == HASH_EMPTY) cur = h; }
         if (cur == h) { atomicMin(&vals[slot], idx); return; }
+    }
+}
+
+// The wave histogram of the collider kernels (ps_motions.hip, ps_shapes.hip): every lane that is `on` counts once into the workgroup's LDS
+// bin `slot`.  The wave adds once per distinct slot among its lanes: the first live lane's slot is broadcast, the lanes that share it are
+// one ballot, the first of them adds their number, and the rest repeat (one round where the lanes agree, which is the rule away from
+// where two colliders meet).  Every lane of the wave calls it; the workgroup adds its bins to the global counters at its end.
+__device__ __forceinline__ void waveBinAdd(int32_t* bins, bool on, int slot, int lane) {
+    unsigned long long todo = __ballot(on);
+    while (todo) {
+        const int s = __shfl(slot, __ffsll((long long)todo) - 1, 64);
+        const unsigned long long same = __ballot(on && slot == s);
+        if (lane == __ffsll((long long)same) - 1) atomicAdd(&bins[s], __popcll(same));
+        todo &= ~same;
     }
 }
 

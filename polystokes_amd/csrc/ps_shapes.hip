@@ -10,6 +10,7 @@
 #include <cmath>
 
 #include "ps_context.hpp"
+#include "ps_setup_util.hpp"
 
 using namespace ps;
 
@@ -140,17 +141,10 @@ __global__ __launch_bounds__(SBS) void k_place_shapes(ShapeTable T) {
         T.collision[c] = (float)(T.negate ? -best : best);
         T.ids[c] = kbest;
     }
-    // counting the won cells: a wave adds once per distinct collider among its lanes, the workgroup adds its bins at the end (as
-    // k_paint_motions does).  The cells left alone are not counted here: one add per workgroup to one address is a queue of its own
-    // (65 536 workgroups at 256^3 took 0.6 ms over it); k_place_finish takes them from the total.
-    const bool won = live && kbest >= 0;
-    unsigned long long todo = __ballot(won);
-    while (todo) {
-        const int s = __shfl(kbest, __ffsll((long long)todo) - 1, 64);
-        const unsigned long long same = __ballot(won && kbest == s);
-        if (lane == __ffsll((long long)same) - 1) atomicAdd(&bins[s], __popcll(same));
-        todo &= ~same;
-    }
+    // counting the won cells: waveBinAdd, and the workgroup adds its bins at the end.  The cells left alone are not counted here: one add
+    // per workgroup to one address is a queue of its own (65 536 workgroups at 256^3 took 0.6 ms over it); k_place_finish takes them
+    // from the total.
+    waveBinAdd(bins, live && kbest >= 0, kbest, lane);
     __syncthreads();
     for (int t = tid; t < count; t += SBS)
         if (bins[t]) atomicAdd(&T.cells[t], bins[t]);
@@ -206,25 +200,13 @@ bool ps_context::dropShapes() {
     return had;
 }
 
-// ps_place_colliders / _device, after the ABI's refusals.  One small copy (the poses: host memory, or device memory behind what the
-// caller's stream holds), the counters' reset, the id field's creation where there is none, and one launch on the context's stream.  The
-// table and the counters are as long as this call's count needs.  The host form ends with the stream idle (its table is pageable
-// memory); the device form synchronises the host only where it has something to release: a table of another size, or air-pocket labels.
+// ps_place_colliders / _device, after the ABI's refusals: the poses' ingest (ps_context::ingestColliderTable), the id field's creation where
+// there is none, and one launch on the context's stream.  The host form ends with the stream idle; the device form synchronises the
+// host only where it has something to release: a table of another size, or air-pocket labels.
 void ps_context::placeColliders(const double* poses, int count, bool fromDevice, hipStream_t caller) {
     HIP_CHECK(hipSetDevice(device));
-    bool dropped = (placePoses.p && placePoses.n != (size_t)(SP * count)) ? dropPlacement() : false;
-    dropped |= dropAirPockets();                      // the labels described the solids this call moves
-    placePoses.alloc((size_t)(SP * count));
-    placeCells.alloc((size_t)(count + 2));
-    const size_t bytes = (size_t)(SP * count) * sizeof(double);
-    if (fromDevice) {
-        waitForCaller(caller);
-        HIP_CHECK(hipMemcpyAsync(placePoses.p, poses, bytes, hipMemcpyDeviceToDevice, stream));
-        releaseToCaller(caller);     // the caller's stream may rewrite its table once the copy has run
-    } else {
-        HIP_CHECK(hipMemcpyAsync(placePoses.p, poses, bytes, hipMemcpyHostToDevice, stream));
-    }
-    HIP_CHECK(hipMemsetAsync(placeCells.p, 0, (size_t)(count + 2) * sizeof(int32_t), stream));
+    bool dropped = dropAirPockets();                  // the labels described the solids this call moves (drops only defer: their order is free)
+    dropped |= ingestColliderTable(placement, poses, count, SP, fromDevice, caller);
     if (!colliderIds.p) {            // no id field: one filled with -1, with the lifetime of an uploaded one (the loads and the paint see it)
         colliderIds.alloc((size_t)g.count(0));
         HIP_CHECK(hipMemsetAsync(colliderIds.p, 0xff, (size_t)g.count(0) * sizeof(int32_t), stream));
@@ -233,35 +215,24 @@ void ps_context::placeColliders(const double* poses, int count, bool fromDevice,
     T.d = g.dims(0);
     T.collision = collision.p; T.ids = colliderIds.p;
     T.desc = shapeDesc.p; T.pool = shapePool.p;
-    T.pose = placePoses.p; T.cells = placeCells.p;
+    T.pose = placement.table.p; T.cells = placement.counters.p;
     for (int a = 0; a < 3; ++a) T.orig[a] = orig[a];
     T.dx = dx; T.negate = P.negateCollision ? 1 : 0; T.count = count;
     // PS_DEBUG_SHAPE_CULL=0 (lab build, tests): no collider is skipped for a whole block, so that a test can show the cull changes nothing
     T.cull = envInt(PS_ENV_LOUD("PS_DEBUG_SHAPE_CULL"), 1) != 0 ? 1 : 0;
     const dim3 grid((unsigned)gridFor(T.d.x, SBX), (unsigned)gridFor(T.d.y, SBY), (unsigned)gridFor(T.d.z, SBZ));
     hipLaunchKernelGGL(k_place_shapes, grid, dim3(SBS), 0, stream, T);
-    hipLaunchKernelGGL(k_place_finish, dim3(1), dim3(1), 0, stream, placeCells.p, count, (int32_t)g.count(0));
-    placementCount = count;
-    registerPlacementArrays();
-    if (!fromDevice) HIP_CHECK(hipStreamSynchronize(stream));
-    releaseIdle(dropped);
+    hipLaunchKernelGGL(k_place_finish, dim3(1), dim3(1), 0, stream, placement.counters.p, count, (int32_t)g.count(0));
+    finishColliderTable(placement, count, fromDevice, dropped);
 }
 
 void ps_context::registerPlacementArrays() {
-    const int64_t nc = placementCount;
-    const NamedArray list[] = {{"colliderPlacement", hostArray(&placementCount, 1, 4)},
-                               {"colliderPoseTable", ArrayInfo{placePoses.p, SP * nc, 8}},
-                               {"colliderPlacedCells", ArrayInfo{placeCells.p, nc + 2, 4}},       // cells per collider, cells left alone, colliders skipped
+    const int64_t nc = placement.count;
+    const NamedArray list[] = {{"colliderPlacement", hostArray(&placement.count, 1, 4)},
+                               {"colliderPoseTable", ArrayInfo{placement.table.p, SP * nc, 8}},
+                               {"colliderPlacedCells", ArrayInfo{placement.counters.p, nc + 2, 4}},   // cells per collider, cells left alone, colliders skipped
                                {"collisionField", ArrayInfo{collision.p, g.count(0), 4}}};         // the buffer the next setup reads
     const NamedArray idList[] = {{"colliderCellIds", ArrayInfo{colliderIds.p, g.count(0), 4}}};   // (ps_upload_collider_ids(NULL) after a call takes it away)
-    setArrays(list, placementCount > 0);
-    setArrays(idList, placementCount > 0 && colliderIds.p);
-}
-
-bool ps_context::dropPlacement() {
-    const bool had = placePoses.p != nullptr;
-    placePoses.free(); placeCells.free();
-    placementCount = 0;
-    registerPlacementArrays();
-    return had;
+    setArrays(list, placement.count > 0);
+    setArrays(idList, placement.count > 0 && colliderIds.p);
 }

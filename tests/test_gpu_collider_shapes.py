@@ -311,6 +311,63 @@ def test_picard_passes_keep_the_placement():
     assert outcomes[0][0] == abi.SUCCESS and outcomes[0] == outcomes[1]
 
 
+KEPT = {    # every array of the four features whose arrays outlive a setup, solve or step (ps_context::registerKeptArrays)
+    "pockets": ("airPockets", "airPocketPasses", "airPocketIds", "airPocketUnits", "airPocketCells", "airPocketOpen", "airPocketVolume"),
+    "motions": ("colliderMotions", "colliderMotionTable", "colliderMotionFaces", "collisionVelocityX", "collisionVelocityY", "collisionVelocityZ"),
+    "shapes": ("colliderShapes",),
+    "placement": ("colliderPlacement", "colliderPoseTable", "colliderPlacedCells", "collisionField", "colliderCellIds"),
+}
+TABLES = ("colliderMotions", "colliderMotionTable", "colliderMotionFaces", "colliderShapes", "colliderPlacement", "colliderPoseTable",
+          "colliderPlacedCells")
+
+
+def test_setup_solve_and_step_keep_the_four_features_arrays_and_an_upload_leaves_the_shapes():
+    """Every name of the four lists answers ps_query_array after a setup, a solve, a step and a step with a Picard pass, the tables and
+    counters byte for byte what the calls left; after the next upload "colliderShapes" alone is left."""
+    sc, p = scenes.spheres(24, tile=8, nspheres=1)
+    p.preconditioner = abi.PRE_DIAGONAL
+    shape = cases.sphere_volume(0.09, 12, 1.0 / 44.0)
+    centre = np.array([0.3, 0.3, 0.7])
+    poses = cases.pose(shape, cases.rotation(np.random.RandomState(2)), centre).reshape(1, 12)
+    motions = np.concatenate([(1.0, 0.0, 0.5), (0.0, 2.0, 0.0), centre]).reshape(1, 9)
+    names = [n for group in KEPT.values() for n in group]
+    assert len(names) == len(set(names)) == 19 and set(TABLES) <= set(names)
+    s = polystokes_amd.Solver(0)
+    try:
+        def present():
+            return {n: int(s.L.ps_query_array(s.h, n.encode(), None)) >= 0 for n in names}
+        assert s.set_collider_shapes([shape]) == abi.SUCCESS
+        s.upload(sc, p)
+        assert s.place_colliders(poses) == abi.SUCCESS, s.last_error()
+        assert s.upload_collider_ids(np.zeros((24, 24, 24), np.int32)) == abi.SUCCESS
+        assert s.paint_collider_velocities(motions) == abi.SUCCESS, s.last_error()
+        s.label_air_pockets()                                                      # (after the placement, which drops the labels)
+        assert int(s.array("colliderPlacedCells")[0]) > 50 and int(s.array("colliderMotionFaces")[0]) > 0
+        assert s.array("colliderPoseTable").tobytes() == poses.tobytes() and s.array("colliderMotionTable").tobytes() == motions.tobytes()
+        before = {n: s.array(n).tobytes() for n in TABLES}
+
+        def kept(stage):
+            got = present()
+            assert all(got.values()), (stage, [n for n in names if not got[n]])
+            assert {n: s.array(n).tobytes() for n in TABLES} == before, stage
+        kept("the calls")
+        assert s.setup() == abi.SUCCESS
+        kept("setup")
+        s.solve()
+        kept("solve")
+        s.step_device()
+        kept("step")
+        assert s.set_rheology(flow_index=0.7, passes=1, min_shear_rate=1e-2, min_viscosity=1e-3, max_viscosity=1e5) == abi.SUCCESS
+        s.step_device()
+        assert len(s.array("rheologyIterations")) == 2                             # the pass ran
+        kept("step with a Picard pass")
+        s.upload(sc, p)
+        got = present()
+        assert [n for n in names if got[n]] == ["colliderShapes"], got
+    finally:
+        s.close()
+
+
 def test_a_placement_drops_air_pocket_labels():
     sc, p, shapes, poses, motions = cases.step_scene()
     s = polystokes_amd.Solver(0)
