@@ -3,19 +3,18 @@ exec/HDK_PolyStokesSolver.cpp:2153-2184).  Both the library and the oracle are b
 (libpolystokes_hip_affine.so, libps_oracle_affine.so); a process can hold one variant, so the checks run in a child."""
 import os
 import subprocess
-import sys
 
 import pytest
 
+import children
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ENV = dict(os.environ, PS_LIB=os.path.join(ROOT, "polystokes_amd", "libpolystokes_hip_affine.so"),
+ENV = dict(PS_LIB=os.path.join(ROOT, "polystokes_amd", "libpolystokes_hip_affine.so"),
            PS_ORACLE_LIB=os.path.join(ROOT, "oracle", "_build", "libps_oracle_affine.so"))
 
 
 def _child(*args):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "affine_child.py"), *args], env=ENV, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
-    return r.stdout
+    return children.run_script("affine_child.py", *args, limit=600, env=ENV).stdout
 
 
 def test_affine_libraries_are_built_and_export_the_abi():

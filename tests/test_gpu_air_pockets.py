@@ -2,7 +2,6 @@
 with the numpy restatement (air_pockets_ref.py) fed those arrays.  Ids, units, cells and open are integers and compared exactly; the
 volume is compared bitwise with the restatement's expression.  No comparison has a tolerance."""
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -15,6 +14,7 @@ from polystokes_amd import scenes
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
+import children  # noqa: E402
 import air_pockets_cases as cases  # noqa: E402
 import air_pockets_ref as ref  # noqa: E402
 
@@ -338,15 +338,9 @@ def test_device_download_in_both_layouts():
     s.close()
 
 
-def _child(name, env_extra):
-    env = dict(os.environ)
-    env.pop("PS_LIB", None)
-    env.update(env_extra)
-    pr = subprocess.run([sys.executable, os.path.join(HERE, "air_pockets_cases.py"), "label", name],
-                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600, env=env)
-    assert pr.returncode == 0, pr.stdout[-3000:]
-    line = [l for l in pr.stdout.splitlines() if l.startswith("DIGEST")][-1]
-    return line, pr.stdout
+def _child(name, env_extra, expect=()):
+    pr = children.run_script("air_pockets_cases.py", "label", name, limit=600, env=env_extra, drop=("PS_LIB",), expect=expect)
+    return " ".join(("DIGEST",) + pr.digests()[-1]), pr.output
 
 
 def _digest(name):
@@ -357,8 +351,7 @@ def _digest(name):
 @pytest.mark.parametrize("name", ["bubbles", "serpentine"])
 def test_poisoned_buffers_change_nothing(name):
     """PS_DEBUG_POISON=1 fills whatever a buffer allocation hands out with 0xff: a label, a flag or a sum nobody wrote would show"""
-    line, out = _child(name, {"PS_DEBUG_POISON": "1"})
-    assert "PS_DEBUG_POISON" in out                                            # the switch was active in the child
+    line, _ = _child(name, {"PS_DEBUG_POISON": "1"}, expect=("PS_DEBUG_POISON=1 is active",))     # the child read the switch
     assert line == _digest(name)
 
 

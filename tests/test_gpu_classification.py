@@ -5,22 +5,18 @@ two regions in one tile with overlapping boxes, regions that do not fill their b
 limit.  The library and the CPU oracle are given the same weights; the integer state is compared bit for bit, what the regions feed with the
 tolerances of test_gpu_parity.py (helpers.check_*).  test_classification_cases_cpu.py asserts that the cases reach all this.  Single domain only.
 """
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 from polystokes_amd import _abi as abi
 from polystokes_amd import scenes
 
+import children
 import classification_cases as cc
 from helpers import check_rhs_and_operator, check_solve, check_stencil_blocks, check_tile_blocks
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INTEGER_KINDS = ("LiquidWeights", "FluidWeights", "Labels", "ActiveIndices", "ReducedIndices")
 LABEL_KINDS = ("Labels", "ActiveIndices", "ReducedIndices")
 
@@ -128,10 +124,7 @@ def test_fed_solve_matches(fed):
 
 # ---- switches read once per process: a child runs the cases and stores their state ------------------------------------------------------------
 _CHILD = r'''
-import sys, numpy as np
-root, out, names = sys.argv[1], sys.argv[2], sys.argv[3:]
-sys.path.insert(0, root); sys.path.insert(0, root + "/tests")
-import polystokes_amd
+out, names = sys.argv[1], sys.argv[2:]
 import classification_cases as cc
 import test_gpu_classification as t
 s = polystokes_amd.Solver(0)
@@ -155,12 +148,8 @@ s.close()
 
 def run_child(tmp_path, env, names):
     out = str(tmp_path / "child.npz")
-    pr = subprocess.run([sys.executable, "-c", _CHILD, ROOT, out] + list(names), env=dict(os.environ, **env), stdout=subprocess.PIPE,
-                        stderr=subprocess.STDOUT, text=True, timeout=300)
-    assert pr.returncode == 0, pr.stdout[-3000:]
-    for k, v in env.items():                      # (the lab build names a test-only switch that changes results when it finds it set)
-        if k == "PS_DEBUG_POISON":
-            assert f"{k}={v} is active" in pr.stdout, pr.stdout[-1000:]
+    # (the lab build names a test-only switch that changes results when it finds it set)
+    children.run_python(_CHILD, out, *names, limit=300, env=env, expect=[f"{k}={v} is active" for k, v in env.items() if k == "PS_DEBUG_POISON"])
     return np.load(out)
 
 

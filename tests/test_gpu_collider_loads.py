@@ -3,7 +3,6 @@ in numpy (collider_loads_ref.py): every comparison feeds the restatement what th
 asks for  |F - F_ref| <= (terms_k + 8) 2^-53 A_k  per axis, the same with B_k for the torque and for the scales themselves, and equal
 counts.  test_collider_loads_ref_cpu.py shows that these scenes tell the rule from its near misses and fixes sign and scale."""
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -15,12 +14,12 @@ from polystokes_amd import _hip
 from polystokes_amd import scenes
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import children  # noqa: E402
 import collider_loads_cases as cases  # noqa: E402
 import collider_loads_ref as ref  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 # scene, id field, count, pivots
 CASES = {
     "blob_no_ids": ("blob", None, 1, None),
@@ -120,15 +119,9 @@ def test_bitwise_equal_across_runs_and_contexts(case):
 
 def test_poisoned_buffers_change_nothing():
     """PS_DEBUG_POISON=1 fills whatever a buffer allocation hands out with 0xff: a sum that read a partial nobody wrote would show"""
-    env = dict(os.environ)
-    env.pop("PS_LIB", None)
-    env["PS_DEBUG_POISON"] = "1"
-    pr = subprocess.run([sys.executable, os.path.join(HERE, "collider_loads_cases.py"), "step", "spheres32", "spheres", "8"],
-                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600, env=env)
-    assert pr.returncode == 0, pr.stdout[-4000:]
-    assert "PS_DEBUG_POISON" in pr.stdout                                          # the switch was active in the child
-    lines = [tuple(ln.split()[1:]) for ln in pr.stdout.splitlines() if ln.startswith("DIGEST ")]
-    assert lines == [_digest_of("spheres_nearest")], pr.stdout[-2000:]
+    pr = children.run_script("collider_loads_cases.py", "step", "spheres32", "spheres", 8, limit=600, env={"PS_DEBUG_POISON": "1"}, drop=("PS_LIB",),
+                             expect=("PS_DEBUG_POISON=1 is active",))              # the child read the switch
+    assert pr.digests() == [_digest_of("spheres_nearest")], pr.output[-2000:]
 
 
 def test_device_id_upload_equals_the_host_upload_in_both_layouts():

@@ -4,7 +4,6 @@ step after a paint with a step of a fresh context uploaded with the restatement'
 shared cases tell the rule from its near misses."""
 import ctypes
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -16,13 +15,12 @@ from polystokes_amd import _hip
 from polystokes_amd import scenes
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import children  # noqa: E402
 import collider_loads_ref as loads_ref  # noqa: E402
 import collider_motions_cases as cases  # noqa: E402
 import collider_motions_ref as ref  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-
-HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 def bits(g):
@@ -255,15 +253,9 @@ def test_poisoned_buffers_change_nothing():
     """PS_DEBUG_POISON=1 fills whatever a buffer allocation hands out with 0xff: a kernel that read a word nobody wrote would show"""
     case = "spheres_nearest"
     sc, p, ids, tab, grids, counters = cases.build(case)
-    env = dict(os.environ)
-    env.pop("PS_LIB", None)
-    env["PS_DEBUG_POISON"] = "1"
-    pr = subprocess.run([sys.executable, os.path.join(HERE, "collider_motions_cases.py"), "paint", case],
-                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600, env=env)
-    assert pr.returncode == 0, pr.stdout[-4000:]
-    assert "PS_DEBUG_POISON" in pr.stdout                                          # the switch was active in the child
-    lines = [tuple(ln.split()[1:]) for ln in pr.stdout.splitlines() if ln.startswith("DIGEST ")]
-    assert lines == [(cases.digest(grids + [counters]), cases.outcome_digest(fresh_outcome(case)))], pr.stdout[-2000:]
+    pr = children.run_script("collider_motions_cases.py", "paint", case, limit=600, env={"PS_DEBUG_POISON": "1"}, drop=("PS_LIB",),
+                             expect=("PS_DEBUG_POISON=1 is active",))              # the child read the switch
+    assert pr.digests() == [(cases.digest(grids + [counters]), cases.outcome_digest(fresh_outcome(case)))], pr.output[-2000:]
 
 
 # ---- 8. memory -----------------------------------------------------------------------------------------------------------------------------

@@ -5,7 +5,6 @@ context uploaded with the restatement's field.  test_collider_shapes_ref_cpu.py 
 misses."""
 import ctypes
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -17,13 +16,12 @@ from polystokes_amd import _hip
 from polystokes_amd import scenes
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import children  # noqa: E402
 import collider_motions_ref as motions_ref  # noqa: E402
 import collider_shapes_cases as cases  # noqa: E402
 import collider_shapes_ref as ref  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-
-HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 def assert_placed(s, col, idf, counters, what=""):
@@ -71,17 +69,10 @@ def test_placement_equals_the_restatement(case):
 
 
 def _child(env_extra, names):
-    env = dict(os.environ)
-    env.pop("PS_LIB", None)
-    env.update(env_extra)
-    pr = subprocess.run([sys.executable, os.path.join(HERE, "collider_shapes_cases.py"), "place"] + list(names),
-                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600, env=env)
-    assert pr.returncode == 0, pr.stdout[-4000:]
-    for k in env_extra:
-        assert k in pr.stdout, k                                                   # the switch was active in the child
-    got = {ln.split()[1]: ln.split()[2] for ln in pr.stdout.splitlines() if ln.startswith("DIGEST ")}
+    pr = children.run_script("collider_shapes_cases.py", "place", *names, limit=600, env=env_extra, drop=("PS_LIB",),
+                             expect=["%s=%s is active" % kv for kv in env_extra.items()])  # the child read the switch
     want = {c: cases.digest(cases.build(c)[5:8]) for c in names}
-    assert got == want, pr.stdout[-2000:]
+    assert dict(pr.digests()) == want, pr.output[-2000:]
 
 
 def test_without_the_cull_the_outputs_are_identical():

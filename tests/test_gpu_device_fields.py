@@ -2,7 +2,6 @@
 the outputs exactly as the host entry points do.  Every comparison is on the bytes: the device path fills the same buffers with the same
 values, and the step is deterministic (the first test is that control)."""
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -12,6 +11,7 @@ import polystokes_amd
 from polystokes_amd import _abi as abi, scenes
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import children  # noqa: E402
 import device_fields_cases as cases  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -303,13 +303,7 @@ def test_group_ranks_take_the_device_upload():
 
 # ---- 10. torch, and the release library ----------------------------------------------------------------------------------------
 def _child(mode, env_extra):
-    env = dict(os.environ)
-    env.pop("PS_LIB", None)
-    env.update(env_extra)
-    pr = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "device_fields_cases.py"), mode], stdout=subprocess.PIPE,
-                        stderr=subprocess.STDOUT, text=True, timeout=600, env=env)
-    assert pr.returncode == 0, pr.stdout[-4000:]
-    return pr.stdout
+    return children.run_script("device_fields_cases.py", mode, limit=600, env=env_extra, drop=("PS_LIB",)).output
 
 
 def test_torch_tensors_on_the_current_stream():

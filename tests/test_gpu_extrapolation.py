@@ -3,8 +3,6 @@ exactly in numpy (extrapolation_ref.py), so every comparison is on the bytes: th
 context WITHOUT the setting returns for the same scene (the step is deterministic: test_gpu_device_fields.py holds that control).
 test_extrapolation_ref_cpu.py shows that these scenes tell the rule from its near misses."""
 import os
-import socket
-import subprocess
 import sys
 
 import numpy as np
@@ -15,6 +13,7 @@ from polystokes_amd import _abi as abi
 from polystokes_amd import scenes
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import children  # noqa: E402
 import device_fields_cases as dcases  # noqa: E402
 import extrapolation_cases as cases  # noqa: E402
 import extrapolation_ref as ref  # noqa: E402
@@ -22,7 +21,6 @@ import extrapolation_ref as ref  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HERE = os.path.dirname(os.path.abspath(__file__))
 MESSAGE = "layers outside 0..64"
 _mode0, _want = {}, {}
 
@@ -263,42 +261,11 @@ def test_in_process_groups_ignore_the_setting(dims):
     assert runs[0][0] == abi.SUCCESS and runs[0] == runs[1]
 
 
-def _free_port_base(n):
-    for base in range(30100 + (os.getpid() % 500) * 8, 40000, 64):
-        socks = []
-        try:
-            for q in range(n):
-                sk = socket.socket(socket.AF_INET, socket.SOCK_STREAM)
-                sk.bind(("127.0.0.1", base + q))
-                socks.append(sk)
-            return base
-        except OSError:
-            continue
-        finally:
-            for sk in socks:
-                sk.close()
-    raise RuntimeError("no free port range")
-
-
 def _slab_pair(layers, tmp_path):
     """two processes, one slab rank each, over the host-staged TCP transport (ps_step_device -> the distributed step)"""
-    base = _free_port_base(2)
+    base = children.free_port_base(2)
     outs = [str(tmp_path / ("slab%d.r%d.npz" % (layers, r))) for r in range(2)]
-    env = dict(os.environ)
-    env.pop("PS_LIB", None)
-    procs = [subprocess.Popen([sys.executable, os.path.join(HERE, "extrapolation_cases.py"), "slab", str(layers), str(r), str(base), outs[r]],
-                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=env) for r in range(2)]
-    logs = []
-    for pr in procs:
-        try:
-            o, _ = pr.communicate(timeout=240)
-        except subprocess.TimeoutExpired:
-            for q in procs:
-                q.kill()
-            raise
-        logs.append(o)
-    for r, pr in enumerate(procs):
-        assert pr.returncode == 0, (r, logs[r][-2000:])
+    children.run_group([children.script_argv("extrapolation_cases.py", "slab", layers, r, base, outs[r]) for r in range(2)], limit=240, drop=("PS_LIB",))
     return [np.load(o) for o in outs]
 
 
@@ -313,16 +280,11 @@ def test_a_slab_pair_of_processes_ignores_the_setting(tmp_path):
 
 
 # ---- 9. child processes ------------------------------------------------------------------------------------------------------------------
-def _child_digest(name, layers, env_extra):
-    env = dict(os.environ)
-    env.pop("PS_LIB", None)
-    env.update(env_extra)
-    pr = subprocess.run([sys.executable, os.path.join(HERE, "extrapolation_cases.py"), "step", name, str(layers)], stdout=subprocess.PIPE,
-                        stderr=subprocess.STDOUT, text=True, timeout=600, env=env)
-    assert pr.returncode == 0, pr.stdout[-4000:]
-    lines = [ln.split()[1] for ln in pr.stdout.splitlines() if ln.startswith("DIGEST ")]
-    assert len(lines) == 1, pr.stdout[-2000:]
-    return lines[0], pr.stdout
+def _child_digest(name, layers, env_extra, expect=()):
+    pr = children.run_script("extrapolation_cases.py", "step", name, layers, limit=600, env=env_extra, drop=("PS_LIB",), expect=expect)
+    lines = pr.digests()
+    assert len(lines) == 1, pr.output[-2000:]
+    return lines[0][0], pr.output
 
 
 def _want_digest(name, layers):
@@ -332,8 +294,7 @@ def _want_digest(name, layers):
 
 def test_poisoned_buffers_change_nothing():
     """PS_DEBUG_POISON=1 fills whatever a buffer allocation hands out with 0xff: a sweep that read layer bytes nobody wrote would show"""
-    got, out = _child_digest("blob0", 3, {"PS_DEBUG_POISON": "1"})
-    assert "PS_DEBUG_POISON" in out                                    # the switch was active in the child
+    got, _ = _child_digest("blob0", 3, {"PS_DEBUG_POISON": "1"}, expect=("PS_DEBUG_POISON=1 is active",))   # the child read the switch
     assert got == _want_digest("blob0", 3)
 
 

@@ -8,9 +8,6 @@ iterations.  x_50 crosses one batch boundary, where the parity of the double-buf
 Bounds: ITERATE_BOUND (fp64 steps) and ITERATE_BOUND_F32 (the fp32 Chebyshev polynomial, its M taken from the device) in helpers.py, measured on
 an MI355X and checked against two perturbations of the reference itself by test_iterate_tolerances_cpu.py."""
 import json
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -18,11 +15,10 @@ import pytest
 from polystokes_amd import _abi as abi
 from polystokes_amd import scenes
 
+import children
 from helpers import CG_BATCH, ITERATE_BOUND, ITERATE_BOUND_F32, ITERATE_DROPPED, ITERATE_SHORT, iterate_after, numpy_pcg, relerr, trajectory_params
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 SCENES = {
@@ -125,8 +121,6 @@ def test_iterates_match_the_reference(scene, pre):
 
 # ---- 2. forced forms, one child process per switch set --------------------------------------------------------------------------------
 _CHILD = (
-    "import sys, json\n"
-    f"sys.path.insert(0, {ROOT!r}); sys.path.insert(0, {os.path.join(ROOT, 'tests')!r})\n"
     "import test_gpu_iterates as t\n"
     "out = []\n"
     "for case in json.loads(sys.argv[1]):\n"
@@ -138,10 +132,7 @@ _CHILD = (
 
 
 def run_child(env, cases, timeout=900):
-    pr = subprocess.run([sys.executable, "-c", _CHILD, json.dumps(cases)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
-                        env=dict(os.environ, **env), timeout=timeout)
-    assert pr.returncode == 0, pr.stderr[-3000:]
-    return json.loads([line for line in pr.stdout.splitlines() if line.startswith("RESULT ")][-1][7:])
+    return children.run_python(_CHILD, json.dumps(cases), limit=timeout, env=env).result()
 
 
 _PAIR = [["coil32", "jacobi"], ["spheres32", "cheb4"]]

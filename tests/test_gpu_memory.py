@@ -6,8 +6,6 @@ stream has just been synchronised — at the end of every setup / solve / step, 
   * with several asynchronous ranks in ONE process (the test arrangement of tests/mp_rank.py "r0,r1") running out of memory FAILS the ranks through
     ps_last_error instead of releasing inside the step (which could hang two ranks)."""
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -15,9 +13,10 @@ import pytest
 from polystokes_amd import _abi as abi
 from polystokes_amd import scenes
 
+import children
+
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
@@ -46,9 +45,6 @@ def test_setup_loops_and_scene_changes_do_not_grow_device_memory():
 
 
 _CHILD = (
-    "import sys, json, numpy as np\n"
-    f"sys.path.insert(0, {ROOT!r})\n"
-    "import polystokes_amd\nfrom polystokes_amd import scenes, _abi as abi\n"
     "s = polystokes_amd.Solver(0)\n"
     "out = {}\n"
     "sc, p = scenes.cavity(64, precond=abi.PRE_DIAGONAL)\n"
@@ -68,12 +64,7 @@ _CHILD = (
 
 
 def _child(env_extra):
-    import json
-    env = dict(os.environ, **env_extra)
-    pr = subprocess.run([sys.executable, "-c", _CHILD], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env, timeout=300)
-    assert pr.returncode == 0, pr.stderr[-3000:]
-    line = [l for l in pr.stdout.splitlines() if l.startswith("RESULT ")][-1]
-    return json.loads(line[7:])
+    return children.run_python(_CHILD, limit=300, env=env_extra).result()
 
 
 def test_forced_out_of_memory_fails_the_step_and_the_context_recovers():
@@ -97,13 +88,11 @@ def test_threaded_ranks_fail_instead_of_releasing_inside_a_step(tmp_path):
     outs = [str(tmp_path / ("r%d.npz" % r)) for r in range(2)]
 
     def run(extra, port):
-        env = dict(os.environ, PS_TEST_TRANSPORT="stub", PS_RCCL_LIB=stub, **extra)
-        pr = subprocess.run([sys.executable, os.path.join(HERE, "mp_rank.py"), "cavity_w2", "2", "0,1", str(port), ",".join(outs)],
-                            stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=env, timeout=300)
-        return pr, [np.load(o) for o in outs]
+        children.run_script("mp_rank.py", "cavity_w2", 2, "0,1", port, ",".join(outs), limit=300,
+                            env=dict(extra, PS_TEST_TRANSPORT="stub", PS_RCCL_LIB=stub))
+        return [np.load(o) for o in outs]
 
-    pr, res = run({}, 29710)
-    assert pr.returncode == 0, pr.stdout[-3000:]
+    res = run({}, 29710)
     assert all(int(r["rc"]) == abi.SUCCESS for r in res)
     after_upload = max(int(r["mem_after_upload"]) for r in res)
     peak = max(int(r["mem_peak"]) for r in res)
@@ -111,8 +100,7 @@ def test_threaded_ranks_fail_instead_of_releasing_inside_a_step(tmp_path):
     limit = after_upload + (peak - after_upload) // 3
     for o in outs:
         os.remove(o)
-    pr, res = run({"PS_DEBUG_ALLOC_LIMIT": str(limit)}, 29720)
-    assert pr.returncode == 0, pr.stdout[-3000:]
+    res = run({"PS_DEBUG_ALLOC_LIMIT": str(limit)}, 29720)
     errs = [str(r["err"]) for r in res]
     assert all(int(r["rc"]) == -1 for r in res), errs
     assert any("out of device memory" in e for e in errs), errs

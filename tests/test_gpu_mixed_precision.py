@@ -5,11 +5,8 @@ operator by test_mixed_precision_ref_cpu.py).
 The reference of every case is the fp64 mode of the same library: iterations against mode 0 on the same context, the error against a mode-0
 solve at tol 1e-12.  Two valid solves stop at different iterates, so x is never compared with x64 directly.
 Every case prints its figures before it asserts (run with -s); profiles/mixed_precision.md says which of them have been measured."""
-import json
 import math
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -17,6 +14,7 @@ import pytest
 from polystokes_amd import _abi as abi
 from polystokes_amd import scenes
 
+import children
 from helpers import fdot
 from mixed_precision_ref import ERROR_CAP, ITERATION_CAP, PASS_CAP
 
@@ -127,9 +125,7 @@ def mixed_solve_meets_the_rule_and_the_caps(gpu, scene, pre, tol, make=None):
 
 # ---- 2. both step forms and the release library, in child processes (the switches are read once per process) ----------------------------
 _CHILD = (
-    "import sys, json, math, numpy as np\n"
-    f"sys.path.insert(0, {ROOT!r}); sys.path.insert(0, {os.path.join(ROOT, 'tests')!r})\n"
-    "import polystokes_amd\nfrom polystokes_amd import scenes, _abi as abi\nfrom helpers import fdot\n"
+    "from helpers import fdot\n"
     "n, precond, tol = int(sys.argv[1]), int(sys.argv[2]), float(sys.argv[3])\n"
     "tile = int(sys.argv[4]) if len(sys.argv) > 4 else 16\n"
     "sc, p = scenes.cavity(n, tile=tile, precond=precond)\n"
@@ -154,10 +150,7 @@ _CHILD = (
 
 
 def _child(n, precond, tol, env, tile=16):
-    pr = subprocess.run([sys.executable, "-c", _CHILD, str(n), str(int(precond)), repr(tol), str(tile)], stdout=subprocess.PIPE, stderr=subprocess.PIPE,
-                        text=True, env=dict(os.environ, **env), timeout=600)
-    assert pr.returncode == 0, pr.stderr[-3000:]
-    return json.loads([line for line in pr.stdout.splitlines() if line.startswith("RESULT ")][-1][7:])
+    return children.run_python(_CHILD, n, int(precond), repr(tol), tile, limit=600, env=env).result()
 
 
 @pytest.mark.parametrize("n,env,fused", [

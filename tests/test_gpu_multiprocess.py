@@ -2,9 +2,8 @@
 slab, ps_step_device -> ps_dist_step_single, halos and scalars exchanged through the host-staged TCP transport
 (ps_comm_init_tcp; RCCL refuses several ranks on one device).  Same Dist code as the RCCL path except transport()/
 allreduce().  Compared with the single-domain solve of the whole scene."""
+import json
 import os
-import socket
-import subprocess
 import sys
 
 import numpy as np
@@ -13,48 +12,20 @@ import pytest
 from polystokes_amd import _abi as abi
 from polystokes_amd import partition
 
+import children
 import mp_cases
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
-def _free_port_base(n):
-    """a base port with n consecutive free ports (checked by binding them once)"""
-    for base in range(29600 + (os.getpid() % 500) * 8, 40000, 64):
-        socks = []
-        try:
-            for q in range(n):
-                s = socket.socket(socket.AF_INET, socket.SOCK_STREAM)
-                s.bind(("127.0.0.1", base + q))
-                socks.append(s)
-            return base
-        except OSError:
-            continue
-        finally:
-            for s in socks:
-                s.close()
-    raise RuntimeError("no free port range")
-
-
 def _run_ranks(case, world, tmp_path, env=None, per_process=1):
     """per_process > 1: every process holds that many ranks, one thread each (mp_rank.py) — the box admits six GPU processes"""
-    base = _free_port_base(world)
+    base = children.free_port_base(world)
     outs = [str(tmp_path / f"{case}.r{r}.npz") for r in range(world)]
     groups = [list(range(q, min(q + per_process, world))) for q in range(0, world, per_process)]
-    procs = [subprocess.Popen([sys.executable, os.path.join(HERE, "mp_rank.py"), case, str(world), ",".join(str(r) for r in g), str(base), ",".join(outs[r] for r in g)],
-                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=dict(os.environ, **(env or {}))) for g in groups]
-    logs = []
-    for pr in procs:
-        try:
-            o, _ = pr.communicate(timeout=240)
-        except subprocess.TimeoutExpired:
-            for q in procs:
-                q.kill()
-            raise
-        logs.append(o)
-    for q, pr in enumerate(procs):
-        assert pr.returncode == 0, (groups[q], logs[q][-2000:])
+    children.run_group([children.script_argv("mp_rank.py", case, world, ",".join(str(r) for r in g), base, ",".join(outs[r] for r in g)) for g in groups],
+                       limit=240, env=env)
     return [np.load(o) for o in outs]
 
 
@@ -218,24 +189,26 @@ def test_multiprocess_tile_size_mismatch_fails_every_rank(tmp_path):
     assert any("configured differently" in e for e in errs), errs
 
 
+def _bench_line(*args, limit, env=None):
+    """bench.py in a child: its stdout must be ONE line of JSON"""
+    pr = children.run([sys.executable, os.path.join(os.path.dirname(HERE), "bench.py")] + list(args), limit=limit, env=env)
+    lines = [l for l in pr.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, pr.stdout[-2000:]
+    return json.loads(lines[0])
+
+
 def test_bench_two_ranks_produces_one_line_whatever_the_transport(tmp_path):
     """`python bench.py --gpus 2 --full` without a launcher: spawns one process per rank, rendezvous over gloo, and prints ONE JSON
     line.  With two GPUs the ranks talk over RCCL; on a one-GPU box RCCL refuses the duplicate device, every rank agrees on that
     (gloo) before any further collective, and all of them switch to the host-staged transport — the line says which."""
-    import json
     import polystokes_amd
     try:                                   # a second device?  (probed through the library: no torch import in this process)
         polystokes_amd.Solver(1).close()
         two_gpus = True
     except polystokes_amd.PolyStokesError:
         two_gpus = False
-    env = dict(os.environ, MASTER_PORT=str(_free_port_base(1)))
-    pr = subprocess.run([sys.executable, os.path.join(os.path.dirname(HERE), "bench.py"), "--gpus", "2", "--res", "32", "--steps", "1", "--warmup", "1",
-                         "--full", "--no-cpu-baseline", "--strong-res", "96"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=420, env=env)
-    assert pr.returncode == 0, pr.stderr[-3000:]
-    lines = [l for l in pr.stdout.splitlines() if l.strip()]
-    assert len(lines) == 1, pr.stdout[-2000:]
-    d = json.loads(lines[0])
+    d = _bench_line("--gpus", "2", "--res", "32", "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline", "--strong-res", "96",
+                    limit=420, env={"MASTER_PORT": str(children.free_port_base(1))})
     assert d["n_gpus"] == 2 and d["unit"] == "ms/step" and d["value"] > 0 and d["cg_iterations"] > 0
     assert d["config"]["grid"] == [32, 32, 64] and d["scaling"] == "weak"
     if two_gpus:
@@ -257,14 +230,8 @@ def test_bench_two_ranks_produces_one_line_whatever_the_transport(tmp_path):
 def test_bench_four_ranks_as_bricks(tmp_path):
     """`bench.py --gpus 4 --bricks 2x2x1`: the decomposition along x and y (ps_set_brick), weak scaling = 32^3 owned cells per rank of the
     64 x 64 x 32 cavity; on a one-GPU box over the host-staged transport."""
-    import json
-    env = dict(os.environ, MASTER_PORT=str(_free_port_base(1)))
-    pr = subprocess.run([sys.executable, os.path.join(os.path.dirname(HERE), "bench.py"), "--gpus", "4", "--bricks", "2x2x1", "--res", "32", "--steps", "1",
-                         "--warmup", "1", "--no-cpu-baseline", "--no-strong-512", "--transport", "tcp"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=420, env=env)
-    assert pr.returncode == 0, pr.stderr[-3000:]
-    lines = [l for l in pr.stdout.splitlines() if l.strip()]
-    assert len(lines) == 1, pr.stdout[-2000:]
-    d = json.loads(lines[0])
+    d = _bench_line("--gpus", "4", "--bricks", "2x2x1", "--res", "32", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-strong-512",
+                    "--transport", "tcp", limit=420, env={"MASTER_PORT": str(children.free_port_base(1))})
     assert d["n_gpus"] == 4 and d["value"] > 0 and d["cg_iterations"] > 0
     assert d["config"]["grid"] == [64, 64, 32] and "2x2x1 bricks" in d["config"]["parallelism"]
     # the same system as one rank solves it: the iteration count of the 64 x 64 x 32 cavity
@@ -282,26 +249,19 @@ def test_rccl_communicator_next_to_a_live_torch_context():
     """bench.py's situation for N > 1: torch imported and its GPU context live, then the library's RCCL communicator.  The library
     must pick up the librccl torch has already mapped (RTLD_NOLOAD) — two copies in one process abort at exit — and a slab step over
     the communicator (world 1: the exchange lists are empty, the all-reduces real) must run and exit cleanly."""
-    pr = subprocess.run([sys.executable, os.path.join(os.path.dirname(HERE), "scripts", "rccl_with_torch.py")], stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
-                        text=True, timeout=300)
-    assert pr.returncode == 0, pr.stdout[-3000:]
-    after = [l for l in pr.stdout.splitlines() if l.startswith("rccl mapped after:")]
-    assert after and after[0].count("librccl") == 1, pr.stdout[-2000:]
-    assert " rc 1 " in after[0] and "closed" in pr.stdout
+    pr = children.run([sys.executable, os.path.join(os.path.dirname(HERE), "scripts", "rccl_with_torch.py")], limit=300)
+    after = [l for l in pr.output.splitlines() if l.startswith("rccl mapped after:")]
+    assert after and after[0].count("librccl") == 1, pr.output[-2000:]
+    assert " rc 1 " in after[0] and "closed" in pr.output
 
 
 def test_bench_single_gpu_line_keeps_the_contract(tmp_path):
     """`python bench.py --full` (N = 1) on a small stand-in (64^3 cavity, 64^3 coil for the strong block, a 32^3 CPU sample): ONE JSON line with the
     driver's keys, the roofline and cpu_baseline objects, and r05's additions — the identity / Chebyshev lines beside the Jacobi headline
      and the box calibration; --dump-outputs writes the last timed step's fields whole (they fit the budget at 64^3)."""
-    import json
     dump = tmp_path / "out"
-    pr = subprocess.run([sys.executable, os.path.join(os.path.dirname(HERE), "bench.py"), "--res", "64", "--steps", "2", "--warmup", "1", "--full", "--strong-res", "64",
-                         "--cpu-sample-res", "32", "--dump-outputs", str(dump)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
-    assert pr.returncode == 0, pr.stderr[-3000:]
-    lines = [l for l in pr.stdout.splitlines() if l.strip()]
-    assert len(lines) == 1, pr.stdout[-2000:]
-    d = json.loads(lines[0])
+    d = _bench_line("--res", "64", "--steps", "2", "--warmup", "1", "--full", "--strong-res", "64", "--cpu-sample-res", "32", "--dump-outputs", str(dump),
+                    limit=600)
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config"):
         assert k in d, k
     assert d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1 and d["higher_is_better"] is False and d["vs_baseline"] is None
@@ -335,14 +295,8 @@ def test_bench_single_gpu_line_keeps_the_contract(tmp_path):
 
 def test_bench_plain_line_is_the_headline_alone(tmp_path):
     """`python bench.py` without --full: the headline keys and the timed step's outputs, none of the blocks that take runs of their own."""
-    import json
     dump = tmp_path / "out"
-    pr = subprocess.run([sys.executable, os.path.join(os.path.dirname(HERE), "bench.py"), "--res", "64", "--steps", "2", "--warmup", "1",
-                         "--dump-outputs", str(dump)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
-    assert pr.returncode == 0, pr.stderr[-3000:]
-    lines = [l for l in pr.stdout.splitlines() if l.strip()]
-    assert len(lines) == 1, pr.stdout[-2000:]
-    d = json.loads(lines[0])
+    d = _bench_line("--res", "64", "--steps", "2", "--warmup", "1", "--dump-outputs", str(dump), limit=300)
     assert d["metric"] == "Stokes-solve wall ms/step (assembly+PCG) on 256^3 grid; CG iters/sec"
     assert d["unit"] == "ms/step" and d["higher_is_better"] is False and d["dtype"] == "f64" and d["value"] == d["ms_per_step"] > 0
     assert d["steps"] == 2 and d["warmup"] == 1 and d["result"] == 1 and d["cg_iterations"] > 0

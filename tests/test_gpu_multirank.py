@@ -6,6 +6,8 @@ import pytest
 from polystokes_amd import _abi as abi
 from polystokes_amd import scenes
 
+import children
+
 pytestmark = pytest.mark.gpu
 
 
@@ -123,7 +125,7 @@ def test_bricks_match_single_domain(case):
     single.close()
 
 
-@pytest.mark.skipif(__import__("os").environ.get("PS_TEST_CHILD") == "1", reason="this IS the child run")
+@pytest.mark.skipif(children.IS_CHILD_RUN, reason="this IS the child run")
 @pytest.mark.parametrize("split", ["", "1"])
 def test_bricks_and_slabs_with_the_four_kernel_step_forced(split):
     """The four-kernel PCG step across the cuts (the St kernel corrects r on owned rows, the halo rows' A p travels back axis after axis,
@@ -131,33 +133,21 @@ def test_bricks_and_slabs_with_the_four_kernel_step_forced(split):
     r06: the ranks of an in-process group share one stream, so their S and St run as ONE launch each (two units per wave, halo rows included:
     k_spmv_St_ell2<.., HALO>) and an exchange is one kernel for all ranks (k_xchg_direct) — split "": that path; split "1" (PS_DIST_OVERLAP=1):
     the launches split into the chunks next to a cut and the rest, pack / transport / unpack, as one process per GPU runs them."""
-    import os
-    import subprocess
-    import sys
-    env = dict(os.environ, PS_FUSED_R="1", PS_TEST_CHILD="1")
+    env = {"PS_FUSED_R": "1"}
     if split:
         env["PS_DIST_OVERLAP"] = split
-    pr = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-m", "gpu", "-x", "-q", "-p", "no:cacheprovider",
-                         "-k", "test_bricks_match_single_domain or test_group_matches_single_domain"],
-                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900, env=env)
-    assert pr.returncode == 0, pr.stdout[-3000:]
+    children.run_pytest(__file__, "test_bricks_match_single_domain or test_group_matches_single_domain", limit=900, env=env)
 
 
-@pytest.mark.skipif(__import__("os").environ.get("PS_TEST_CHILD") == "1", reason="this IS the child run")
+@pytest.mark.skipif(children.IS_CHILD_RUN, reason="this IS the child run")
 @pytest.mark.parametrize("fused", ["0", "1"])
 def test_bricks_with_the_forwarding_rounds_forced(fused):
     """r05: the exchanges of the solve run as ONE round (every list holds the sender's own samples; Dist::decideExchangeMode checks on the
     matrices that no row reaches a diagonal neighbour's sample) and fall back to the three forwarding rounds x -> y -> z of r03 / r04 only
     when one does (tilePadding 1: the seeds of test_bricks_classification_that_reaches_beyond_the_halo).  The brick cases once more in a child
     with the forwarding rounds forced (PS_DIST_FORWARD=1), with the five- and the four-kernel step: both modes must reproduce the single domain."""
-    import os
-    import subprocess
-    import sys
-    env = dict(os.environ, PS_DIST_FORWARD="1", PS_FUSED_R=fused, PS_TEST_CHILD="1")
-    pr = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-m", "gpu", "-x", "-q", "-p", "no:cacheprovider",
-                         "-k", "test_bricks_match_single_domain or test_bricks_without_reduced_regions"],
-                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900, env=env)
-    assert pr.returncode == 0, pr.stdout[-3000:]
+    children.run_pytest(__file__, "test_bricks_match_single_domain or test_bricks_without_reduced_regions", limit=900,
+                        env={"PS_DIST_FORWARD": "1", "PS_FUSED_R": fused})
 
 
 def test_rccl_entry_points_world1():
@@ -256,20 +246,15 @@ def test_reused_group_child(dims):
     single.close()
 
 
-@pytest.mark.skipif(__import__("os").environ.get("PS_TEST_CHILD") == "1", reason="this IS the child run")
+@pytest.mark.skipif(children.IS_CHILD_RUN, reason="this IS the child run")
 @pytest.mark.parametrize("poison", ["0", "1"])
 def test_group_reused_across_scenes_with_the_four_kernel_step(poison):
     """ADVICE r03 (high / medium / low): contexts reused across uploads with another numbering, the overlapped four-kernel step forced;
     with PS_DEBUG_POISON=1 every buffer alloc() hands out is filled with NaN / -1 first, so a word nobody wrote this step shows."""
-    import os
-    import subprocess
-    import sys
-    env = dict(os.environ, PS_FUSED_R="1", PS_TEST_CHILD="1", PS_TEST_REUSE_CHILD="1", PS_DEBUG_POISON=poison)
+    env = {"PS_FUSED_R": "1", "PS_TEST_REUSE_CHILD": "1", "PS_DEBUG_POISON": poison}
     if poison == "1":
         env["PS_DIST_OVERLAP"] = "1"      # (r06: an in-process group runs unsplit launches by default; the poisoned run walks the split ones)
-    pr = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-m", "gpu", "-x", "-q", "-p", "no:cacheprovider",
-                         "-k", "test_reused_group_child"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900, env=env)
-    assert pr.returncode == 0, pr.stdout[-3000:]
+    children.run_pytest(__file__, "test_reused_group_child", limit=900, env=env)
 
 
 @pytest.mark.parametrize("mode", ["dosolve_off_keep", "dosolve_off_drop", "noconverge_keep", "noconverge_drop"])

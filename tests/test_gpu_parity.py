@@ -2,14 +2,13 @@
 
 Bit-exact for every integer / index / label / weight array; stated fp64 tolerances elsewhere.
 """
-import os
-
 import numpy as np
 import pytest
 
 from polystokes_amd import _abi as abi
 from polystokes_amd import scenes
 
+import children
 from helpers import check_rhs_and_operator, check_solve, check_stencil_blocks, check_tile_blocks, relerr
 
 pytestmark = pytest.mark.gpu
@@ -662,9 +661,6 @@ def test_fallback_kernel_paths_agree(gpu, tmp_path, env):
     and the cache-policy level, which default by system size: this grid runs five kernels at level 0).  Run the
     alternatives in a child process: same iteration count, same velocities to rounding (the formats reproduce the same
     fp64 products; only summation orders of the dot products differ)."""
-    import os
-    import subprocess
-    import sys
     sc, p = scenes.blob(20, 18, 22, seed=9, tile=8)
     p.tolerance = 1e-8
     p.maxSolverIterations = 20000
@@ -672,14 +668,11 @@ def test_fallback_kernel_paths_agree(gpu, tmp_path, env):
     assert int(gpu.array("fusedStep")[0]) == 0    # small system: five-kernel PCG step (the four-kernel one runs from 1.2 M rows, or PS_FUSED_R=1)
     out = str(tmp_path / "alt.npz")
     code = (
-        "import sys, numpy as np\n"
-        f"sys.path.insert(0, {os.path.dirname(os.path.dirname(os.path.abspath(__file__)))!r})\n"
-        "import polystokes_amd\nfrom polystokes_amd import scenes\n"
         "sc, p = scenes.blob(20, 18, 22, seed=9, tile=8)\np.tolerance = 1e-8\np.maxSolverIterations = 20000\n"
         "s = polystokes_amd.Solver(0)\nrc = s.step(sc, p)\n"
         f"np.savez({out!r}, rc=rc, it=s.stats.solveData[1], vx=s.vel[0], vy=s.vel[1], vz=s.vel[2], c16=s.array('columns16'), coded=s.array('valuesCoded'), dc=s.array('diagonalsCoded'), fused=s.array('fusedStep'), rpl=s.array('rowPerLane'))\n"
     )
-    subprocess.run([sys.executable, "-c", code], check=True, env=dict(os.environ, **env), timeout=300)
+    children.run_python(code, limit=300, env=env)
     alt = np.load(out)
     assert int(alt["rc"]) == abi.SUCCESS
     assert int(alt["dc"][0]) == (0 if "PS_NO_DIAG_CODES" in env else 2)   # blob: variable viscosity -> uInv stays fp64, McInv is coded
@@ -703,9 +696,6 @@ def test_chebyshev_f32_needs_the_pair_walk_grid(gpu, tmp_path):
     """The fp32 inner applies run on the pair-walking two-unit kernels only, whose grid must be a multiple of 8 with the XCD walk on.
     PS_PIPE_GRID_ST2=4 caps the Chebyshev term's St launch below that: PS_PRE_CHEBYSHEV_F32 then runs the fp64 polynomial (array
     chebInner32 reads 0) and solves as the fp64 Chebyshev form does (run in a child process: the switch is read once per process)."""
-    import os
-    import subprocess
-    import sys
     sc, p = scenes.cavity(32)
     p.tolerance = 1e-8
     p.preconditioner = abi.PRE_CHEBYSHEV
@@ -713,14 +703,11 @@ def test_chebyshev_f32_needs_the_pair_walk_grid(gpu, tmp_path):
     assert int(gpu.array("chebInner32")[0]) == 0
     out = str(tmp_path / "alt.npz")
     code = (
-        "import sys, numpy as np\n"
-        f"sys.path.insert(0, {os.path.dirname(os.path.dirname(os.path.abspath(__file__)))!r})\n"
-        "import polystokes_amd\nfrom polystokes_amd import _abi as abi, scenes\n"
         "sc, p = scenes.cavity(32)\np.tolerance = 1e-8\np.preconditioner = abi.PRE_CHEBYSHEV_F32\n"
         "s = polystokes_amd.Solver(0)\nrc = s.step(sc, p)\n"
         f"np.savez({out!r}, rc=rc, it=s.stats.solveData[1], c32=s.array('chebInner32'), vx=s.vel[0], vy=s.vel[1], vz=s.vel[2])\n"
     )
-    subprocess.run([sys.executable, "-c", code], check=True, env=dict(os.environ, PS_PIPE_GRID_ST2="4"), timeout=300)
+    children.run_python(code, limit=300, env={"PS_PIPE_GRID_ST2": "4"})
     alt = np.load(out)
     assert int(alt["rc"]) == abi.SUCCESS
     assert int(alt["c32"][0]) == 0
@@ -754,9 +741,6 @@ def test_four_kernel_step_matches_and_is_reproducible(gpu, tmp_path, precond, de
     forced on a small grid in a child process: same iteration count as the five-kernel step to +-1, same x to rounding,
     and 100 solves give one outcome bit for bit.  With the Chebyshev preconditioner the same St kernel also forms the
     polynomial's first term on the rows it updates (degree 1: that term is the whole preconditioner)."""
-    import os
-    import subprocess
-    import sys
     sc, p = scenes.cavity(32, precond=precond)
     p.tolerance = 1e-8
     p.preconditionerDegree = degree
@@ -765,9 +749,6 @@ def test_four_kernel_step_matches_and_is_reproducible(gpu, tmp_path, precond, de
     x_ref = gpu.array("solutionVector").copy()
     out = str(tmp_path / "fused.npz")
     code = (
-        "import sys, numpy as np\n"
-        f"sys.path.insert(0, {os.path.dirname(os.path.dirname(os.path.abspath(__file__)))!r})\n"
-        "import polystokes_amd\nfrom polystokes_amd import scenes\n"
         f"sc, p = scenes.cavity(32, precond={int(precond)})\np.tolerance = 1e-8\np.preconditionerDegree = {int(degree)}\n"
         "s = polystokes_amd.Solver(0)\ns.upload(sc, p)\nseen = set()\n"
         "for _ in range(100):\n"
@@ -775,7 +756,7 @@ def test_four_kernel_step_matches_and_is_reproducible(gpu, tmp_path, precond, de
         "    seen.add((rc, int(s.stats.solveData[1]), float(s.stats.solveData[0]).hex(), s.array('solutionVector').tobytes()))\n"
         f"np.savez({out!r}, outcomes=len(seen), rc=rc, it=s.stats.solveData[1], x=s.array('solutionVector'), fused=s.array('fusedStep'))\n"
     )
-    subprocess.run([sys.executable, "-c", code], check=True, env=dict(os.environ, PS_FUSED_R="1"), timeout=300)
+    children.run_python(code, limit=300, env={"PS_FUSED_R": "1"})
     alt = np.load(out)
     assert int(alt["fused"][0]) == 1 and int(alt["rc"]) == abi.SUCCESS
     assert int(alt["outcomes"]) == 1
@@ -783,19 +764,13 @@ def test_four_kernel_step_matches_and_is_reproducible(gpu, tmp_path, precond, de
     assert np.linalg.norm(alt["x"] - x_ref) <= 1e-6 * np.linalg.norm(x_ref)
 
 
-@pytest.mark.skipif(os.environ.get("PS_TEST_CHILD") == "1", reason="this IS the child run")
+@pytest.mark.skipif(children.IS_CHILD_RUN, reason="this IS the child run")
 def test_oracle_parity_with_the_large_system_switches_forced(tmp_path):
     """The four-kernel PCG step and the non-temporal cache policies switch on by system size (2 M / 4 M / 10 M rows), above
     what the oracle can check.  Run the oracle-parity tests of the solve (all fixed scenes: free surfaces, no tiles, ragged grids,
     layer variants; Jacobi; BiCGStab fallback; Chebyshev) once more in a child pytest with both forced on."""
-    import subprocess
-    import sys
-    env = dict(os.environ, PS_FUSED_R="1", PS_NT_LEVEL="2", PS_TEST_CHILD="1")
-    pr = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-m", "gpu", "-x", "-q", "-p", "no:cacheprovider",
-                         "-k", "solve_matches or jacobi_pcg or bicgstab or chebyshev or rhs_and_operator or zero_rhs"],
-                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900, env=env)
-    assert pr.returncode == 0, pr.stdout[-4000:]
-    assert " passed" in pr.stdout and "failed" not in pr.stdout, pr.stdout[-2000:]
+    children.run_pytest(__file__, "solve_matches or jacobi_pcg or bicgstab or chebyshev or rhs_and_operator or zero_rhs", limit=900,
+                        env={"PS_FUSED_R": "1", "PS_NT_LEVEL": "2"})
 
 
 def test_shared_runs_on_a_periodic_scene(gpu, oracle_mod):
@@ -878,10 +853,6 @@ def test_noconverge_with_and_without_keeping_the_results(gpu, oracle_mod, keep):
 
 
 _TILE_CLASS_CHILD = r'''
-import sys, numpy as np
-sys.path.insert(0, sys.argv[1])
-import polystokes_amd
-from polystokes_amd import scenes
 from polystokes_amd._abi import Scene, default_params
 n = 64
 dx = 1.0 / n
@@ -893,27 +864,22 @@ p = default_params(tileSize=16, tilePadding=2)
 s = polystokes_amd.Solver(0)
 s.upload(sc, p)
 s.setup()
-np.savez(sys.argv[2], K=s.array("reducedViscosityMatrices"), Binv=s.array("Inv_Mr_plus_2JDtuDJ"), Mr=s.array("reducedMassMatrices"), R=np.int64(s.nRegions))
+np.savez(sys.argv[1], K=s.array("reducedViscosityMatrices"), Binv=s.array("Inv_Mr_plus_2JDtuDJ"), Mr=s.array("reducedMassMatrices"), R=np.int64(s.nRegions))
 s.close()
 '''
 
 
-@pytest.mark.skipif(os.environ.get("PS_TEST_CHILD") == "1", reason="child run")
+@pytest.mark.skipif(children.IS_CHILD_RUN, reason="child run")
 def test_shared_tile_blocks_equal_the_tiles_own_sums(tmp_path):
     """ADVICE r04: K is shared between tiles of one class (same labels, regions, viscosity samples; ps_tiles.hip:buildTileClasses) — on by
     default.  On a free-surface scene whose viscosity varies INSIDE every tile (and repeats from tile to tile, so that classes exist) the
     shared blocks must equal the blocks every tile sums for itself (PS_NO_TILE_CLASSES=1) to rounding: K and BInv <= 1e-12 relative per
     block; Mr is never shared: bit-identical."""
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = {}
     for tag, env in (("shared", {}), ("own", {"PS_NO_TILE_CLASSES": "1"})):
         f = str(tmp_path / (tag + ".npz"))
-        pr = subprocess.run([sys.executable, "-c", _TILE_CLASS_CHILD, root, f], env=dict(os.environ, PS_VERBOSE="1", **env), stdout=subprocess.PIPE,
-                            stderr=subprocess.STDOUT, text=True, timeout=600)
-        assert pr.returncode == 0, pr.stdout[-3000:]
-        out[tag] = (np.load(f), pr.stdout)
+        pr = children.run_python(_TILE_CLASS_CHILD, f, limit=600, env=dict(env, PS_VERBOSE="1"))
+        out[tag] = (np.load(f), pr.output)
     a, b = out["shared"][0], out["own"][0]
     R = int(a["R"])
     assert R == int(b["R"]) and R >= 32

@@ -15,8 +15,6 @@ Every test prints a line "RECOVERY <case> ..." with the largest |d| / bound, the
 reference and the largest cancellation factor (profiles/velocity_recovery.md)."""
 import json
 import os
-import subprocess
-import sys
 import time
 
 import numpy as np
@@ -25,6 +23,7 @@ import pytest
 from polystokes_amd import _abi as abi
 from polystokes_amd import partition, scenes
 
+import children
 import recovery_ref as rr
 
 pytestmark = pytest.mark.gpu
@@ -208,21 +207,13 @@ def run_form_cases(cases):
 
 
 _CHILD = (
-    "import sys, json\n"
-    f"sys.path.insert(0, {ROOT!r}); sys.path.insert(0, {os.path.join(ROOT, 'tests')!r})\n"
     "import test_gpu_recovery as t\n"
     "print('RESULT ' + json.dumps(t.run_form_cases(json.loads(sys.argv[1]))))\n"
 )
 
 
 def run_child(env, cases, timeout=600):
-    pr = subprocess.run(["timeout", "-k", "10", str(timeout), sys.executable, "-c", _CHILD, json.dumps(cases)], stdout=subprocess.PIPE,
-                        stderr=subprocess.PIPE, text=True, env=dict(os.environ, **env))
-    if pr.returncode < 0 or pr.returncode in (124, 134, 137, 139):
-        # a fault, an abort or the time limit in the child: nothing more is started on the GPU by this run
-        pytest.exit("child %r ended with %d: %s" % (env, pr.returncode, pr.stderr[-2000:]), returncode=3)
-    assert pr.returncode == 0, (pr.returncode, pr.stderr[-3000:])
-    return json.loads([line for line in pr.stdout.splitlines() if line.startswith("RESULT ")][-1][7:])
+    return children.run_python(_CHILD, json.dumps(cases), limit=timeout, env=env).result()
 
 
 @pytest.mark.parametrize("form", list(FORMS))

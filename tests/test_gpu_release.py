@@ -4,11 +4,11 @@ the CPU box).  A wrong default would be invisible in the lab build; here the rel
   * reproduce the committed small goldens (tests/test_golden.py::test_hip_path_reproduces_golden, in a child pytest with PS_LIB set), and
   * give a bit-identical solution vector to the lab build on a Jacobi, a Chebyshev and an identity solve (and the same iteration count)."""
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
+
+import children
 
 pytestmark = pytest.mark.gpu
 
@@ -16,9 +16,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RELEASE = os.path.join(ROOT, "polystokes_amd", "libpolystokes_hip_release.so")
 
 _SOLVES = (
-    "import sys, numpy as np\n"
-    f"sys.path.insert(0, {ROOT!r})\n"
-    "import polystokes_amd\nfrom polystokes_amd import scenes, _abi as abi\n"
     "assert polystokes_amd.LIB_PATH.endswith(sys.argv[2]), polystokes_amd.LIB_PATH\n"
     "cases = {'cavity32_jacobi': scenes.cavity(32, precond=abi.PRE_DIAGONAL), 'coil48_chebyshev': scenes.coil(48), 'blob6_identity': scenes.blob(seed=6),\n"
     "         'cavity96_jacobi_4k': scenes.cavity(96, precond=abi.PRE_DIAGONAL)}   # 2.6 M rows: the four-kernel step engages by size\n"
@@ -37,14 +34,9 @@ _SOLVES = (
 
 
 def _run(path, lib_env, suffix):
-    env = dict(os.environ)
-    env.pop("PS_LIB", None)
-    env.update(lib_env)
     # switches of the lab build that would change results must not leak into the comparison (the release build would ignore them anyway)
-    for k in list(env):
-        if k.startswith("PS_") and k not in ("PS_LIB", "PS_VERBOSE"):
-            env.pop(k)
-    subprocess.run([sys.executable, "-c", _SOLVES, path, suffix], check=True, env=env, timeout=600)
+    inherited = [k for k in os.environ if k.startswith("PS_") and k != "PS_VERBOSE"]
+    children.run_python(_SOLVES, path, suffix, limit=600, env=lib_env, drop=inherited)
     return np.load(path)
 
 
@@ -60,9 +52,4 @@ def test_release_library_is_bit_identical_to_the_lab_build(tmp_path):
 
 
 def test_release_library_reproduces_the_small_goldens():
-    env = dict(os.environ, PS_LIB=RELEASE, PS_TEST_CHILD="1")
-    pr = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_golden.py"), "-m", "gpu", "-x", "-q", "-p", "no:cacheprovider",
-                         "-k", "test_hip_path_reproduces_golden"],
-                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900, env=env)
-    assert pr.returncode == 0, pr.stdout[-4000:]
-    assert " passed" in pr.stdout and "failed" not in pr.stdout, pr.stdout[-2000:]
+    children.run_pytest(os.path.join(ROOT, "tests", "test_golden.py"), "test_hip_path_reproduces_golden", limit=900, env={"PS_LIB": RELEASE})

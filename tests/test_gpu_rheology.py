@@ -3,10 +3,7 @@
 The strain rate and the viscosity are checked against the numpy restatement (rheology_ref.py) computed from the uploaded velocity and the
 step's `valid` flags; the solve is checked against the uploaded-field path, which the oracle covers elsewhere: a second context given the
 computed viscosity as its field solves the same system."""
-import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -14,6 +11,7 @@ import pytest
 from polystokes_amd import _abi as abi
 from polystokes_amd import scenes
 
+import children
 import rheology_ref as ref
 
 pytestmark = pytest.mark.gpu
@@ -351,9 +349,7 @@ def test_passes_on_a_group_fail_on_every_rank():
 
 # ---- 7. robustness ------------------------------------------------------------------------------------------------------------
 _CHILD = (
-    "import sys, json, hashlib, numpy as np\n"
-    f"sys.path.insert(0, {ROOT!r})\n"
-    "import polystokes_amd\nfrom polystokes_amd import scenes\n"
+    "import hashlib\n"
     "sc, p = scenes.blob()\n"
     "s = polystokes_amd.Solver(0)\n"
     "s.set_rheology(flow_index=0.6, yield_stress=0.3, passes=2, min_shear_rate=1e-2, min_viscosity=1e-3, max_viscosity=1e5)\n"
@@ -365,10 +361,7 @@ _CHILD = (
 
 
 def _child(env):
-    pr = subprocess.run([sys.executable, "-c", _CHILD], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
-                        env=dict(os.environ, **env), timeout=600)
-    assert pr.returncode == 0, pr.stderr[-3000:]
-    return json.loads([line for line in pr.stdout.splitlines() if line.startswith("RESULT ")][-1][7:])
+    return children.run_python(_CHILD, limit=600, env=env).result()
 
 
 def test_poison_and_release_library_give_the_same_velocities():

@@ -2,19 +2,15 @@
 
 The oracle has no-slip walls only, so the checks here are physical (rigid sliding, a moving floor that does not drag), structural
 against the no-slip path (which is checked against the oracle elsewhere), and the usual agreement of every solve route."""
-import json
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 from polystokes_amd import _abi as abi
 from polystokes_amd import scenes
 
+import children
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FREE, NO = abi.SOLID_FREE_SLIP, abi.SOLID_NO_SLIP
 
 
@@ -230,23 +226,17 @@ def test_well_posed_and_preconditioners_agree():
         assert err[FREE][pre] <= _bound(p.tolerance, err[NO][pre]), (pre, err)
 
 
-_CHILD = ("import sys, json, numpy as np\n"
-          "sys.path.insert(0, {root!r})\n"
-          "import polystokes_amd\nfrom polystokes_amd import scenes, _abi as abi\n"
-          "sc, p = scenes.spheres(32, tile=8)\n"
+_CHILD = ("sc, p = scenes.spheres(32, tile=8)\n"
           "p.preconditioner = {pre}\np.tolerance = 1e-8\np.maxSolverIterations = 20000\n"
           "s = polystokes_amd.Solver(0)\ns.set_solid_boundary(abi.SOLID_FREE_SLIP)\nrc = s.step(sc, p)\n"
           "np.save({out!r}, s.array('solutionVector'))\n"
-          "print(json.dumps(dict(rc=rc, coded=int(s.array('valuesCoded')[0]), c16=int(s.array('columns16')[0]),"
+          "print('RESULT ' + json.dumps(dict(rc=rc, coded=int(s.array('valuesCoded')[0]), c16=int(s.array('columns16')[0]),"
           " slip=int(s.array('solidSlipEdges')[0]))))\n")
 
 
 def _child(tmp_path, tag, env, pre):
     out = str(tmp_path / (tag + ".npy"))
-    pr = subprocess.run(["timeout", "-k", "10", "300", sys.executable, "-c", _CHILD.format(root=ROOT, pre=pre, out=out)],
-                        capture_output=True, text=True, env=dict(os.environ, **env))
-    assert pr.returncode == 0, (tag, pr.stdout[-2000:], pr.stderr[-3000:])
-    info = json.loads(pr.stdout.strip().splitlines()[-1])
+    info = children.run_python(_CHILD.format(pre=pre, out=out), limit=300, env=env).result()
     assert info["rc"] == abi.SUCCESS, (tag, info)
     return info, np.load(out)
 

@@ -3,11 +3,6 @@
 The oracle knows one scalar density, so the density-dependent assembly is checked against numpy restatements: the face mass
 (McInv, Mc, the active rhs) face by face, the tile mass Mr = sum_f rho_f C_f^T C_f region by region, and then the operator and
 solve against the literal path of the exported component matrices.  A constant field is the scalar path bit for bit."""
-import json
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
@@ -15,9 +10,9 @@ from polystokes_amd import _abi as abi
 from polystokes_amd import scenes
 from helpers import basis_rows, per_row, rigid_rotation_scene
 
-pytestmark = pytest.mark.gpu
+import children
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
@@ -239,15 +234,12 @@ def test_tile_mass_against_numpy(gpu, name, kind):
 
 def test_tile_mass_valu_form(tmp_path):
     """the VALU form of the tile sums (PS_TILE_VALU=1, read once per process): a child runs the same checks"""
-    code = ("import sys\n"
-            f"sys.path.insert(0, {ROOT!r}); sys.path.insert(0, {os.path.join(ROOT, 'tests')!r})\n"
-            "import polystokes_amd, test_gpu_variable_density as t\n"
+    code = ("import test_gpu_variable_density as t\n"
             "s = polystokes_amd.Solver(0)\n"
             "t._check_tile_mass(s, 'blob', 'smooth'); t._check_tile_mass(s, 'cavity32', 'layers')\n"
             "s.close(); print('VALU_OK')\n")
-    pr = subprocess.run(["timeout", "-k", "10", "300", sys.executable, "-c", code], capture_output=True, text=True,
-                        env=dict(os.environ, PS_TILE_VALU="1"))
-    assert pr.returncode == 0 and "VALU_OK" in pr.stdout, (pr.stdout[-2000:], pr.stderr[-3000:])
+    pr = children.run_python(code, limit=300, env={"PS_TILE_VALU": "1"})
+    assert "VALU_OK" in pr.stdout, pr.describe()
 
 
 # ---- 5. operator and solve against the literal path ---------------------------------------------------------------------
@@ -284,23 +276,17 @@ def test_eigen_solver_on_a_field_scene(gpu):
 
 
 # ---- 6. the fast path: two-unit S kernel with the fp64 face mass ----------------------------------------------------------
-_CHILD = ("import sys, json, numpy as np\n"
-          "sys.path.insert(0, {root!r})\n"
-          "import polystokes_amd\nfrom polystokes_amd import scenes, _abi as abi\n"
-          "sc, p = scenes.cavity(80)\nscenes.with_density_field(sc, 'smooth', rho0=4.0)\n"
+_CHILD = ("sc, p = scenes.cavity(80)\nscenes.with_density_field(sc, 'smooth', rho0=4.0)\n"
           "p.preconditioner = {pre}\np.tolerance = 1e-6\n"
           "s = polystokes_amd.Solver(0)\nrc = s.step(sc, p)\n"
           "np.save({out!r}, s.array('solutionVector'))\n"
-          "print(json.dumps(dict(rc=rc, it=s.stats.solveData[1], dc=int(s.array('diagonalsCoded')[0]), c32=int(s.array('chebInner32')[0]),"
+          "print('RESULT ' + json.dumps(dict(rc=rc, it=s.stats.solveData[1], dc=int(s.array('diagonalsCoded')[0]), c32=int(s.array('chebInner32')[0]),"
           " fused=int(s.array('fusedStep')[0]))))\n")
 
 
 def _child(tmp_path, tag, env, pre=abi.PRE_CHEBYSHEV_F32):
     out = str(tmp_path / (tag + ".npy"))
-    pr = subprocess.run(["timeout", "-k", "10", "300", sys.executable, "-c", _CHILD.format(root=ROOT, pre=pre, out=out)],
-                        capture_output=True, text=True, env=dict(os.environ, **env))
-    assert pr.returncode == 0, (tag, pr.stdout[-2000:], pr.stderr[-3000:])
-    info = json.loads(pr.stdout.strip().splitlines()[-1])
+    info = children.run_python(_CHILD.format(pre=pre, out=out), limit=300, env=env).result()
     assert info["rc"] == abi.SUCCESS, (tag, info)
     return info, np.load(out)
 

@@ -7,23 +7,17 @@ NOT covered: the third region, the all-scalar form a kernel takes when a base po
 pointer today: the vectors are device allocations, and a rank's kernels run on x + ownLo with ownLo = 0 — the owned lattice blocks come first
 in every rank's numbering ("ownedRange", asserted in the rank test below).  An odd owned count on a rank changes n, not the base: the
 rank test walks the one-element tail through Dist's launch sites, no more."""
-import json
-import os
-import subprocess
-import sys
-
 import pytest
 
 from polystokes_amd import _abi as abi
 from polystokes_amd import scenes
 
+import children
 import test_gpu_iterates as iterates
 import test_gpu_mixed_precision as mixed
 from test_gpu_mixed_precision import gpu  # noqa: F401  (the module's solver fixture)
 
 on_gpu = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # scene (test_gpu_iterates.SCENES) -> (nSystem, nSystem % 4).  tail1-3: scenes.blob(20, 18, 22, seed = 4, 1, 2, tile=8), a viscosity field (the
 # fp64 stress diagonal); tail1c: scenes.coil(30, tile=8), the coded one
@@ -134,8 +128,6 @@ def ranks_child():
 
 
 _CHILD = (
-    "import sys, json\n"
-    f"sys.path.insert(0, {ROOT!r}); sys.path.insert(0, {os.path.join(ROOT, 'tests')!r})\n"
     "import test_gpu_vector_tails as t\n"
     "print('RESULT ' + json.dumps(t.ranks_child()))\n"
 )
@@ -146,9 +138,6 @@ def test_two_ranks_with_an_odd_and_an_even_cut():
     """Measured on an MI355X: blob36_0's lower rank owns 2552 DOFs (even), blob36_1's 2501 (odd) — the walk ends after two candidates.
     Both ranks' ownedRange starts at 0: the odd count is an odd n (a one-element scalar tail in k_cg_update_r / _xp / _xp_u / _xp_z on a rank),
     not an unaligned base."""
-    pr = subprocess.run([sys.executable, "-c", _CHILD], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
-                        env=dict(os.environ, PS_FUSED_R="1"), timeout=600)
-    assert pr.returncode == 0, (pr.stdout[-2000:], pr.stderr[-3000:])
-    out = json.loads([line for line in pr.stdout.splitlines() if line.startswith("RESULT ")][-1][7:])
+    out = children.run_python(_CHILD, limit=600, env={"PS_FUSED_R": "1"}).result()
     print(out)
     assert out["odd"] is not None and out["even"] is not None, out

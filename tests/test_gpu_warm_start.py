@@ -2,10 +2,7 @@
 
 Mode PS_WARM_PREVIOUS_STEP: a kept single-domain PCG step leaves its [p; tau] on the device as fp32 grids; the next PCG solve on the same grid
 starts from them, gathered through the new step's index maps (r0 = b - A x0, pcg.h:284), and runs the unchanged PCG from there."""
-import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -13,6 +10,7 @@ import pytest
 from polystokes_amd import _abi as abi
 from polystokes_amd import scenes
 
+import children
 from helpers import numpy_pcg
 
 pytestmark = pytest.mark.gpu
@@ -283,9 +281,6 @@ def test_carried_state_is_flat_across_steps_and_released_when_dropped():
 
 # ---- 6. both step forms, fallback formats, the release library -------------------------------------------------------------------------
 _CHILD = (
-    "import sys, json, numpy as np\n"
-    f"sys.path.insert(0, {ROOT!r})\n"
-    "import polystokes_amd\nfrom polystokes_amd import scenes, _abi as abi\n"
     "n, precond = int(sys.argv[1]), int(sys.argv[2])\n"
     "sc, p = scenes.cavity(n, precond=precond)\n"
     "s = polystokes_amd.Solver(0)\n"
@@ -311,10 +306,7 @@ _CHILD = (
     (32, abi.PRE_IDENTITY, {"PS_LIB": os.path.join(ROOT, "polystokes_amd", "libpolystokes_hip_release.so")}),
 ])
 def test_step_forms_fallbacks_and_release_library(n, precond, env):
-    pr = subprocess.run([sys.executable, "-c", _CHILD, str(n), str(int(precond))], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
-                        env=dict(os.environ, **env), timeout=600)
-    assert pr.returncode == 0, pr.stderr[-3000:]
-    r = json.loads([line for line in pr.stdout.splitlines() if line.startswith("RESULT ")][-1][7:])
+    r = children.run_python(_CHILD, n, int(precond), limit=600, env=env).result()
     assert r["rc"] == [abi.SUCCESS, abi.SUCCESS]
     assert r["used"] == 1 and r["x0_exact"]
     assert r["it"][1] <= 1 < r["it"][0], r["it"]
