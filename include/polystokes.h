@@ -706,6 +706,64 @@ int32_t ps_download_solution_fields_device(ps_context* ctx, const ps_solution_ou
 int32_t ps_step_device_fields(ps_context* ctx, const ps_params* p, const ps_fields_in* in, const ps_fields_out* out,
                               ps_stats* stats, int32_t layout, void* stream);
 
+/* Advection (extension; the one grid-sized pass of a time step that a device-resident caller still had to write itself): up to
+ * PS_ADVECT_MAX_CELL_FIELDS cell fields — the liquid SDF, the viscosity, the density, a surfactant field — and the MAC velocity itself,
+ * moved semi-Lagrangian by a face velocity, the carrier: the context's written velocity or the caller's own three face grids.  The call
+ * reads the context and writes only the caller's arrays.
+ * Call order and lifetime.  It follows ps_upload_fields / ps_upload_fields_device of a single domain; nx, ny, nz and dx are that upload's.
+ * It is not a setting: it changes nothing a setup, solve, step, download or any other call reads, and a context that never makes the call
+ * launches exactly what it launched without it.  With carrier all NULL it needs a step or solve since that upload and since any later setup; the carrier is then the
+ * velocity ps_download_fields would return, as it stands: after the write-back and, where set, ps_set_velocity_extrapolation.  With the
+ * caller's carrier no step is needed.
+ * ps_advect_fields_device follows ps_download_fields_device: it waits for what `stream` holds, runs on the context's stream, makes `stream`
+ * wait for the result and does not synchronise the host; layout applies to every array of the call; the pointer refusals of the other
+ * ps_*_device calls (above) apply.  ps_advect_fields takes host arrays, x fastest, and stages them through device temporaries that it
+ * releases before it returns: ps_memory_stats entry 2 is 0 afterwards and the stream is idle.
+ * The rule.  All arithmetic is fp64 from the fp32 inputs, unfused, in the order written.
+ *   Index space.  Grid kind g (0 cell, 1 faceX, 2 faceY, 3 faceZ) has the extents d_m of the table at the top of this file and the offsets
+ *   o_m = 0.5, except o_a = 0 on face grid a.  Sample (i_0, i_1, i_2) sits at p0_m = (double)i_m + o_m.
+ *   Sampler Smp(F, g, p) for a finite p.  Per axis m: s_m = p_m - o_m;  c_m = min(max(s_m, 0.0), (double)(d_m - 1));  l_m = (int)floor(c_m);
+ *   h_m = min(l_m + 1, d_m - 1);  f_m = c_m - (double)l_m.  The eight samples F[l or h], widened to double, are interpolated along x, then
+ *   y, then z, each step lo + (hi - lo) * f.  (h is clamped, not l: the last layer has f = 0, so dt = 0 returns every finite field bit for
+ *   bit — but for a -0, which returns as +0.)
+ *   Carrier velocity.  U(p) = (Smp(C_0, 1, p), Smp(C_1, 2, p), Smp(C_2, 3, p)).
+ *   Step factor.  r = dt / dx, one division on the host (array "advectionStep").
+ *   Departure point.  order 1: p1_m = p0_m - r * U_m(p0).  order 2: pm_m = p0_m - (0.5 * r) * U_m(p0), then p1_m = p0_m - r * U_m(pm).
+ *   Left alone.  If any pm_m (order 2) or any p1_m is not finite, nothing further is sampled: the sample takes the bits of its own source
+ *   sample (cellIn[q] at the cell, C_a at the face) and is counted in slot 4.
+ *   Value.  A cell output gets (float)Smp(cellIn[q], 0, p1), a velocity output on face grid a gets (float)Smp(C_a, 1 + a, p1); a value that
+ *   is a NaN is stored as the quiet NaN 0x7fc00000 (the bits of a NaN that arithmetic produced are not the same on every processor).  The
+ *   sample is counted in slot g when, for the sampled grid, some s_m < 0 or s_m > d_m - 1: the departure point left the grid and was
+ *   clamped.  A cell's departure point is computed once and serves every cell field; a sample is counted once, whatever the number of
+ *   fields.  The counts are int32 and wrap; they are integers: the result is bitwise reproducible and independent of the traversal.
+ * Refusals (PS_INVALID, reason in ps_last_error, nothing written, the context stays usable): a call before any upload; a == NULL; "order
+ * outside 1..2"; "cellFields outside 0..8"; "dt not finite"; "cellIn[N] is null" / "cellOut[N] is null" among the first cellFields;
+ * "carrier partly null"; "velOut partly null"; "nothing to do" (cellFields == 0 and no velOut); the device form's layout and pointer
+ * refusals; "output N overlaps input M" / "output N overlaps output M" for any output range that overlaps an input or another output — the
+ * gather reads neighbours, so no array may be advected in place.  Outputs are numbered cellOut[q] = q, velOut[a] = 8 + a; inputs
+ * carrier[a] = a, cellIn[q] = 3 + q.  PS_FAILED: "advection needs a single domain" on a slab or brick rank or a context of a ps_group;
+ * "no written velocity since the upload" when the carrier is NULL and nothing has stepped.
+ * Memory: a call holds 20 bytes of counters from the first call to the next upload and nothing else; ps_memory_stats entry 2 is 0 after
+ * each call.
+ * Arrays, registered by a successful call and erased by every upload: "advection" (int32, 1: the order), "advectionStep" (fp64, 1: r),
+ * "advectionCounts" (int32, 5: clamped samples of the cell grid and of the faceX / faceY / faceZ grids, samples left alone).
+ * Out of scope: MacCormack / BFECC correction and higher-order interpolation; redistancing of the SDF; body forces; CFL sub-stepping (the
+ * caller chooses dt); advection across the cuts of a decomposition; in-place operation. */
+#define PS_ADVECT_MAX_CELL_FIELDS 8
+typedef struct ps_advection {
+    double dt;                 /* finite, any sign (negative traces forward); 0 copies */
+    int32_t order;             /* 1: Euler back-trace, 2: midpoint back-trace */
+    int32_t cellFields;        /* 0..PS_ADVECT_MAX_CELL_FIELDS */
+    const float* carrier[3];   /* faceX / faceY / faceZ grids.  All NULL: the velocity ps_download_fields would return.
+                                  All non-NULL: the caller's own arrays.  A mix of NULL and non-NULL is refused. */
+    const float* cellIn[PS_ADVECT_MAX_CELL_FIELDS];    /* cell grids nx*ny*nz */
+    float* cellOut[PS_ADVECT_MAX_CELL_FIELDS];
+    float* velOut[3];          /* all NULL: the velocity is not advected.  All non-NULL: the carrier advected by itself.
+                                  A mix of NULL and non-NULL is refused. */
+} ps_advection;
+int32_t ps_advect_fields(ps_context* ctx, const ps_advection* a);                                        /* host arrays, x fastest */
+int32_t ps_advect_fields_device(ps_context* ctx, const ps_advection* a, int32_t layout, void* stream);   /* device arrays */
+
 /* y = A x for host vectors of length nPressures+nStresses:
  * ApplyPressureStressMatrix::apply (lib/include/ApplyPressureStressMatrix.h:102-184). */
 int32_t ps_apply_operator(ps_context* ctx, const double* x, double* y);

@@ -35,6 +35,7 @@ EXPORTED_SYMBOLS = [
     "ps_set_collider_shapes", "ps_place_colliders", "ps_place_colliders_device",
     "ps_label_air_pockets", "ps_get_air_pockets", "ps_download_air_pocket_ids", "ps_download_air_pocket_ids_device", "ps_set_air_pocket_pressures",
     "ps_set_contact_angle", "ps_upload_contact_cosine_field", "ps_upload_contact_cosine_field_device",
+    "ps_advect_fields", "ps_advect_fields_device",
 ]
 
 
@@ -163,7 +164,7 @@ def lib():
         L.ps_upload_contact_cosine_field.restype = C.c_int32
         L.ps_upload_contact_cosine_field_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
         L.ps_upload_contact_cosine_field_device.restype = C.c_int32
-        for name, argtypes in _abi.COLLIDER_MOTION_CALLS + _abi.COLLIDER_SHAPE_CALLS + _abi.AIR_POCKET_CALLS:
+        for name, argtypes in _abi.COLLIDER_MOTION_CALLS + _abi.COLLIDER_SHAPE_CALLS + _abi.AIR_POCKET_CALLS + _abi.ADVECTION_CALLS:
             getattr(L, name).argtypes = list(argtypes)
             getattr(L, name).restype = C.c_int32
         _lib = L
@@ -265,7 +266,7 @@ def _kind(name):
                 "colliderLoads", "colliderLoadTerms", "colliderMotions", "colliderMotionFaces",
                 "colliderShapes", "colliderPlacement", "colliderPlacedCells", "colliderCellIds",
                 "airPockets", "airPocketIds", "airPocketUnits", "airPocketCells", "airPocketOpen", "airPocketPasses",
-                "contactField", "contactCells"):
+                "contactField", "contactCells", "advection", "advectionCounts"):
         return "i"
     if name in ("ownedX", "ownedY", "ownedZ"):
         return "f"
@@ -474,6 +475,42 @@ class Solver:
         ps_result (INVALID: a refused pointer or count; the host is NOT synchronised).  A collider whose pose is not all finite places
         nothing and is counted in the last slot of "colliderPlacedCells"."""
         return self._check(self.L.ps_place_colliders_device(self.h, device_address(ptr), int(count), stream_handle(stream)), allow=(1, -2))
+
+    def advection(self, dt, order=2, cell_in=(), cell_out=(), carrier=None, vel_out=None):
+        """The ps_advection of a call from addresses or arrays (numpy arrays by their data pointer, device arrays through device_address);
+        carrier / vel_out: None or three arrays."""
+        def addr(a):
+            return a.ctypes.data if isinstance(a, np.ndarray) else device_address(a)
+        A = _abi.Advection()
+        A.dt, A.order, A.cellFields = float(dt), int(order), len(cell_in)
+        if len(cell_in) != len(cell_out) or len(cell_in) > _abi.ADVECT_MAX_CELL_FIELDS:
+            raise ValueError("as many outputs as inputs, at most %d" % _abi.ADVECT_MAX_CELL_FIELDS)
+        for q, (i, o) in enumerate(zip(cell_in, cell_out)):
+            A.cellIn[q], A.cellOut[q] = addr(i), addr(o)
+        for a in range(3):
+            A.carrier[a] = None if carrier is None else addr(carrier[a])
+            A.velOut[a] = None if vel_out is None else addr(vel_out[a])
+        return A
+
+    def advect(self, dt, cell_fields=(), order=2, carrier=None, velocity=False):
+        """ps_advect_fields on host arrays: every array of `cell_fields` (float32, shape (nz, ny, nx)) and, with `velocity`, the carrier
+        itself moved semi-Lagrangian over `dt` by the carrier — three face grids, or None for the velocity the last step wrote.  order 1
+        is the Euler back-trace, 2 the midpoint one.  Returns (rc, cell outputs, velocity outputs or None); INVALID for a refused call
+        (the reason in last_error(), nothing written).  Arrays "advection", "advectionStep", "advectionCounts" say what the call did."""
+        sh = _abi.grid_shapes(self.scene.nx, self.scene.ny, self.scene.nz)
+        cin = [np.ascontiguousarray(f, dtype=np.float32).reshape(sh["center"]) for f in cell_fields]
+        car = None if carrier is None else [np.ascontiguousarray(carrier[a], dtype=np.float32).reshape(sh["face" + "XYZ"[a]]) for a in range(3)]
+        cout = [np.empty(sh["center"], np.float32) for _ in cin]
+        vout = [np.empty(sh["face" + a], np.float32) for a in "XYZ"] if velocity else None
+        A = self.advection(dt, order, cin, cout, car, vout)
+        rc = self._check(self.L.ps_advect_fields(self.h, C.byref(A)), allow=(1, -2))
+        return rc, cout, vout
+
+    def advect_device(self, dt, cell_in=(), cell_out=(), order=2, carrier=None, vel_out=None, layout=0, stream=None):
+        """ps_advect_fields_device: the same on device arrays in `layout`, behind what `stream` holds; `stream` then waits for the outputs
+        and the host is NOT synchronised.  No output may overlap an input or another output.  Returns the ps_result (INVALID: refused)."""
+        A = self.advection(dt, order, cell_in, cell_out, carrier, vel_out)
+        return self._check(self.L.ps_advect_fields_device(self.h, C.byref(A), int(layout), stream_handle(stream)), allow=(1, -2))
 
     def label_air_pockets(self):
         """ps_label_air_pockets: labels the connected air regions of the grid of the last upload (single domain) and returns their number K.

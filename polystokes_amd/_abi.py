@@ -119,6 +119,23 @@ COLLIDER_SHAPE_CALLS = (
 )
 
 
+ADVECT_MAX_CELL_FIELDS = 8         # PS_ADVECT_MAX_CELL_FIELDS (ps_advect_fields)
+
+
+class Advection(C.Structure):
+    """ps_advection (ps_advect_fields): dt, the order, the carrier's face grids (all None: the context's written velocity), the cell fields in
+    and out, the velocity out (all None: not advected)"""
+    _fields_ = [("dt", C.c_double), ("order", C.c_int32), ("cellFields", C.c_int32), ("carrier", C.c_void_p * 3),
+                ("cellIn", C.c_void_p * ADVECT_MAX_CELL_FIELDS), ("cellOut", C.c_void_p * ADVECT_MAX_CELL_FIELDS), ("velOut", C.c_void_p * 3)]
+
+
+# the advection calls: name -> argument types; every one returns int32
+ADVECTION_CALLS = (
+    ("ps_advect_fields", (C.c_void_p, C.POINTER(Advection))),
+    ("ps_advect_fields_device", (C.c_void_p, C.POINTER(Advection), C.c_int32, C.c_void_p)),
+)
+
+
 # the air pocket calls (ps_label_air_pockets ...): name -> argument types; every one returns int32
 AIR_POCKET_CALLS = (
     ("ps_label_air_pockets", (C.c_void_p, C.POINTER(C.c_int32))),

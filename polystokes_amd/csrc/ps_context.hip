@@ -115,6 +115,7 @@ bool ps_context::dropUploadScoped() {
     dropped |= dropAirPockets();                          // ... and the air pocket labels (ps_label_air_pockets)
     dropped |= dropMotions();                             // what ps_paint_collider_velocities left: the ingest replaces collisionvel
     dropped |= dropPlacement();                           // what ps_place_colliders left: the ingest replaces collision (the shapes stay)
+    dropped |= dropAdvection();                           // the counters of ps_advect_fields: they counted on the previous grid
     return dropped;
 }
 // The arrays that a setup, solve or step must not lose: everything that clears `arrays` (uploadTail, setupPhase(0), registerArrays) calls
@@ -127,6 +128,7 @@ void ps_context::registerKeptArrays() {
     registerMotionArrays();        // ps_paint_collider_velocities: what was painted
     registerShapeArrays();         // ps_set_collider_shapes: a context setting
     registerPlacementArrays();     // ps_place_colliders: what was placed
+    registerAdvectionArrays();     // ps_advect_fields: what the last call counted
 }
 
 // ---- collider tables (ps_paint_collider_velocities, ps_place_colliders): the host work the two calls share ----
@@ -1181,6 +1183,61 @@ int32_t ps_download_solution_fields_device(ps_context* c, const ps_solution_out*
         return PS_SUCCESS;
     })
 }
+// ps_advect_fields / _device are this one call.  Its refusals, in order: not uploaded; the struct; the order, the field count and dt; a
+// null field among the first cellFields; a partly null carrier or velOut; nothing to do; the device form's layout and pointers; an output
+// range that overlaps an input or another output.  Then the two PS_FAILED cases: a decomposition, and no written velocity for a null carrier.
+static int32_t advectCall(ps_context* c, const ps_advection* a, bool device, int32_t layout, void* stream) {
+    if (!c) return PS_FAILED;
+    PS_TRY(c, {
+        if (notUploaded(c, "ps_advect_fields")) return PS_INVALID;
+        const char* name = device ? "ps_advect_fields_device" : "ps_advect_fields";
+        std::string why;
+        int nCar = 0, nVel = 0;
+        if (a) for (int m = 0; m < 3; ++m) { nCar += a->carrier[m] ? 1 : 0; nVel += a->velOut[m] ? 1 : 0; }
+        if (!a) why = "a is null";
+        else if (a->order < 1 || a->order > 2) why = "order outside 1..2";
+        else if (a->cellFields < 0 || a->cellFields > PS_ADVECT_MAX_CELL_FIELDS) why = "cellFields outside 0.." + std::to_string(PS_ADVECT_MAX_CELL_FIELDS);
+        else if (!std::isfinite(a->dt)) why = "dt not finite";
+        for (int q = 0; why.empty() && q < a->cellFields; ++q) {
+            if (!a->cellIn[q]) why = "cellIn[" + std::to_string(q) + "] is null";
+            else if (!a->cellOut[q]) why = "cellOut[" + std::to_string(q) + "] is null";
+        }
+        if (why.empty() && nCar != 0 && nCar != 3) why = "carrier partly null";
+        if (why.empty() && nVel != 0 && nVel != 3) why = "velOut partly null";
+        if (why.empty() && a->cellFields == 0 && nVel == 0) why = "nothing to do";
+        if (!why.empty()) { c->err = std::string(name) + ": " + why; return PS_INVALID; }
+        // inputs 0..2 the carrier, 3.. the cell fields; outputs 0..7 the cell fields, 8..10 the velocity (include/polystokes.h)
+        constexpr int NF = PS_ADVECT_MAX_CELL_FIELDS;
+        DevicePtr in[3 + NF], out[NF + 3];
+        for (int m = 0; m < 3; ++m) {
+            in[m] = DevicePtr{a->carrier[m], c->g.count(1 + m), "carrier", true};
+            out[NF + m] = DevicePtr{a->velOut[m], c->g.count(1 + m), "velOut", true};
+        }
+        for (int q = 0; q < NF; ++q) {
+            const bool used = q < a->cellFields;
+            in[3 + q] = DevicePtr{used ? a->cellIn[q] : nullptr, c->g.count(0), "cellIn", true};
+            out[q] = DevicePtr{used ? a->cellOut[q] : nullptr, c->g.count(0), "cellOut", true};
+        }
+        if (device && (refuseDeviceCall(c, nullptr, name, layout, in) || refuseDeviceCall(c, nullptr, name, layout, out))) return PS_INVALID;
+        auto meet = [](const DevicePtr& x, const DevicePtr& y) {
+            const uintptr_t x0 = (uintptr_t)x.p, y0 = (uintptr_t)y.p;
+            return x.p && y.p && x0 < y0 + (uintptr_t)y.count * sizeof(float) && y0 < x0 + (uintptr_t)x.count * sizeof(float);
+        };
+        for (int n = 0; why.empty() && n < NF + 3; ++n) {
+            for (int m = 0; why.empty() && m < 3 + NF; ++m)
+                if (meet(out[n], in[m])) why = "output " + std::to_string(n) + " overlaps input " + std::to_string(m);
+            for (int m = 0; why.empty() && m < n; ++m)
+                if (meet(out[n], out[m])) why = "output " + std::to_string(n) + " overlaps output " + std::to_string(m);
+        }
+        if (!why.empty()) { c->err = std::string(name) + ": " + why; return PS_INVALID; }
+        if (c->slabEnabled || c->inGroup) throw Error("ps_advect_fields: advection needs a single domain");
+        if (nCar == 0 && !c->isSolved) throw Error("ps_advect_fields: no written velocity since the upload");
+        c->advectFields(*a, device, layout, (hipStream_t)stream);
+        return PS_SUCCESS;
+    })
+}
+int32_t ps_advect_fields(ps_context* c, const ps_advection* a) { return advectCall(c, a, false, 0, nullptr); }
+int32_t ps_advect_fields_device(ps_context* c, const ps_advection* a, int32_t layout, void* stream) { return advectCall(c, a, true, layout, stream); }
 // polystokes_step on device arrays: upload, step, download, the three export flags
 int32_t ps_step_device_fields(ps_context* c, const ps_params* p, const ps_fields_in* in, const ps_fields_out* out, ps_stats* st, int32_t layout,
                               void* stream) {

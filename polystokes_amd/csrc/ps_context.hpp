@@ -469,6 +469,16 @@ struct ps_context {
     bool dropPlacement() { return dropColliderTable(placement); }
     void registerShapeArrays();                          // ps_shapes.hip: "colliderShapes" while shapes are set
     void registerPlacementArrays();                      // ps_shapes.hip: the arrays of the last placement (none without one since the last upload)
+    // Advection (ps_advect_fields, extension; ps_advect.hip): a call, not a setting.  It reads velOut (or the caller's carrier) and writes only
+    // the caller's arrays; the context keeps the five counters (array "advectionCounts"), the order and the step factor r = dt / dx of the
+    // last call since the last upload (arrays "advection", "advectionStep").  The counters are allocated by the first call and dropped
+    // by every upload.
+    int32_t advectOrderHost = 0;
+    double advectStepHost = 0.;
+    ps::DevBuf<int32_t> advectCounts;
+    void advectFields(const ps_advection& a, bool device, int layout, hipStream_t caller);           // ps_advect.hip: after the ABI's refusals
+    bool dropAdvection();                                // ps_advect.hip: the counters and the arrays; false when there was nothing to drop
+    void registerAdvectionArrays();                      // ps_advect.hip: the arrays of the last call (none without one since the last upload)
     // The arrays that outlive a setup, solve or step (ps_context.hip states the rule); dropUploadScoped: what every upload drops
     void registerKeptArrays();
     bool dropUploadScoped();
