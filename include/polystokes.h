@@ -747,7 +747,7 @@ int32_t ps_step_device_fields(ps_context* ctx, const ps_params* p, const ps_fiel
  * each call.
  * Arrays, registered by a successful call and erased by every upload: "advection" (int32, 1: the order), "advectionStep" (fp64, 1: r),
  * "advectionCounts" (int32, 5: clamped samples of the cell grid and of the faceX / faceY / faceZ grids, samples left alone).
- * Out of scope: MacCormack / BFECC correction and higher-order interpolation; redistancing of the SDF; body forces; CFL sub-stepping (the
+ * Out of scope: BFECC correction and higher-order interpolation (the MacCormack correction is ps_advect_fields_scheme, below); redistancing of the SDF; body forces; CFL sub-stepping (the
  * caller chooses dt); advection across the cuts of a decomposition; in-place operation. */
 #define PS_ADVECT_MAX_CELL_FIELDS 8
 typedef struct ps_advection {
@@ -763,6 +763,54 @@ typedef struct ps_advection {
 } ps_advection;
 int32_t ps_advect_fields(ps_context* ctx, const ps_advection* a);                                        /* host arrays, x fastest */
 int32_t ps_advect_fields_device(ps_context* ctx, const ps_advection* a, int32_t layout, void* stream);   /* device arrays */
+
+/* Advection schemes (extension): ps_advect_fields / _device with a scheme — the semi-Lagrangian gather above, or the modified MacCormack
+ * scheme of Selle et al. (a forward pass, a reverse pass, half the difference added back) with a limiter.  The limiter needs the eight
+ * samples the forward sampler read at the departure point, which only the kernel knows; a caller composing two ps_advect_fields_device
+ * calls cannot apply it, and writes the intermediate grid twice.
+ * Everything ps_advect_fields / _device say about call order, the carrier, the layouts, stream ordering, the single-domain rule and every
+ * refusal and its text holds for these calls.  Added refusals (PS_INVALID, nothing written, nothing launched), checked after "a is null":
+ * "s is null"; "scheme outside 0..1"; "limiter outside 0..2".  With scheme == PS_ADVECT_SEMI_LAGRANGIAN the limiter is still validated and
+ * otherwise the call IS ps_advect_fields / _device: the same bytes, the same single launch, the same three arrays, 20 bytes held, no new
+ * array registered.
+ * The rule for scheme == PS_ADVECT_MACCORMACK.  All arithmetic is fp64, unfused, in the order written.  For the sample x at p0 of grid g with
+ * the source F (cellIn[q] on the cell grid, C_a on face grid a; the carrier is C throughout and is never replaced):
+ *   Forward pass.  The rule of ps_advect_fields unchanged: it gives p1, whether the sample is left alone, whether the sampler clamped, and
+ *   hat[x], the fp32 value ps_advect_fields would store (the quiet-NaN rule included).  hat is an fp32 grid of its own.
+ *   Reverse trace.  The departure rule with -r in place of r (negation is exact: this equals dt -> -dt), started at p0, not at p1.
+ *   order 1: q1_m = p0_m - (-r) * U_m(p0).  order 2: qm_m = p0_m - (0.5 * (-r)) * U_m(p0), then q1_m = p0_m - (-r) * U_m(qm).
+ *   bar = Smp(hat, g, q1), kept in fp64.
+ *   Corrected value.  v = (double)hat[x] + 0.5 * ((double)F[x] - bar).
+ *   Limits.  The eight samples F[l or h] of the forward sampler at p1, widened to double, in the order x fastest, then y, then z:
+ *   lo = hi = the first; for each t of the next seven: if (t < lo) lo = t; if (t > hi) hi = t (a NaN sample fails both comparisons).
+ *   outside = v < lo || v > hi.  PS_ADVECT_LIMIT_CLAMP: v = v < lo ? lo : (v > hi ? hi : v).  PS_ADVECT_LIMIT_REVERT: v = outside ?
+ *   (double)hat[x] : v.  PS_ADVECT_LIMIT_NONE: v is unchanged and nothing is counted.  With a limiter, the value is counted as changed
+ *   when outside holds.
+ *   Fallback.  The sample takes the bits of hat[x], and the limiter is neither applied nor counted, if the forward pass left the sample
+ *   alone; or the forward sampler clamped (the departure point left the grid); or any qm_m or q1_m is not finite; or the reverse sampler of
+ *   hat clamped.
+ *   Store.  Otherwise (float)v, a NaN as 0x7fc00000.  A cell's two traces are computed once for all its fields.
+ * Arrays.  "advection", "advectionStep" and "advectionCounts" are as after the forward pass.  A successful scheme 1 call registers, and
+ * every upload erases with the others: "advectionScheme" (int32, 2: the scheme and the limiter) and "advectionCorrection" (int32, 8: slots
+ * 0..3 the values the limiter changed on the cell, faceX, faceY, faceZ grids — a cell counts once per field changed; slots 4..7 the
+ * fallback samples of those grids — a cell counts once).  They describe the last scheme 1 call since the upload; a later scheme 0 call
+ * leaves them.  The counts are int32 and wrap; they are integers: bitwise reproducible and independent of the traversal.
+ * Memory.  A scheme 1 device call holds, from that call until the next upload, 32 more bytes of counters and an fp32 scratch for hat of
+ * 4 * (cellFields * nx*ny*nz + (velOut ? the three face grids : 0)) bytes, sized to the largest such call since the upload; a call that
+ * needs no more than what is held allocates nothing, and ps_memory_stats entry 2 is 0 after it (a call that has to grow the scratch leaves
+ * the smaller one there until the context next synchronises).  The host form puts hat into its staging temporary and releases it before it
+ * returns: only the 32 + 20 bytes of counters stay.  The overlap refusals are unchanged: the scratch is the library's own and overlaps
+ * nothing.
+ * Out of scope: BFECC; cubic interpolation; redistancing; CFL sub-stepping; advection across the cuts of a decomposition; in-place
+ * operation; a caller-supplied scratch. */
+#define PS_ADVECT_SEMI_LAGRANGIAN 0
+#define PS_ADVECT_MACCORMACK      1
+#define PS_ADVECT_LIMIT_NONE   0
+#define PS_ADVECT_LIMIT_CLAMP  1
+#define PS_ADVECT_LIMIT_REVERT 2
+typedef struct ps_advection_scheme { int32_t scheme; int32_t limiter; } ps_advection_scheme;
+int32_t ps_advect_fields_scheme(ps_context* ctx, const ps_advection* a, const ps_advection_scheme* s);
+int32_t ps_advect_fields_scheme_device(ps_context* ctx, const ps_advection* a, const ps_advection_scheme* s, int32_t layout, void* stream);
 
 /* y = A x for host vectors of length nPressures+nStresses:
  * ApplyPressureStressMatrix::apply (lib/include/ApplyPressureStressMatrix.h:102-184). */

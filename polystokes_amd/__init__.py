@@ -35,7 +35,7 @@ EXPORTED_SYMBOLS = [
     "ps_set_collider_shapes", "ps_place_colliders", "ps_place_colliders_device",
     "ps_label_air_pockets", "ps_get_air_pockets", "ps_download_air_pocket_ids", "ps_download_air_pocket_ids_device", "ps_set_air_pocket_pressures",
     "ps_set_contact_angle", "ps_upload_contact_cosine_field", "ps_upload_contact_cosine_field_device",
-    "ps_advect_fields", "ps_advect_fields_device",
+    "ps_advect_fields", "ps_advect_fields_device", "ps_advect_fields_scheme", "ps_advect_fields_scheme_device",
 ]
 
 
@@ -164,7 +164,7 @@ def lib():
         L.ps_upload_contact_cosine_field.restype = C.c_int32
         L.ps_upload_contact_cosine_field_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
         L.ps_upload_contact_cosine_field_device.restype = C.c_int32
-        for name, argtypes in _abi.COLLIDER_MOTION_CALLS + _abi.COLLIDER_SHAPE_CALLS + _abi.AIR_POCKET_CALLS + _abi.ADVECTION_CALLS:
+        for name, argtypes in _abi.COLLIDER_MOTION_CALLS + _abi.COLLIDER_SHAPE_CALLS + _abi.AIR_POCKET_CALLS + _abi.ADVECTION_CALLS + _abi.ADVECTION_SCHEME_CALLS:
             getattr(L, name).argtypes = list(argtypes)
             getattr(L, name).restype = C.c_int32
         _lib = L
@@ -266,7 +266,7 @@ def _kind(name):
                 "colliderLoads", "colliderLoadTerms", "colliderMotions", "colliderMotionFaces",
                 "colliderShapes", "colliderPlacement", "colliderPlacedCells", "colliderCellIds",
                 "airPockets", "airPocketIds", "airPocketUnits", "airPocketCells", "airPocketOpen", "airPocketPasses",
-                "contactField", "contactCells", "advection", "advectionCounts"):
+                "contactField", "contactCells", "advection", "advectionCounts", "advectionScheme", "advectionCorrection"):
         return "i"
     if name in ("ownedX", "ownedY", "ownedZ"):
         return "f"
@@ -492,25 +492,36 @@ class Solver:
             A.velOut[a] = None if vel_out is None else addr(vel_out[a])
         return A
 
-    def advect(self, dt, cell_fields=(), order=2, carrier=None, velocity=False):
+    def advect(self, dt, cell_fields=(), order=2, carrier=None, velocity=False, scheme=None, limiter=_abi.ADVECT_LIMIT_CLAMP):
         """ps_advect_fields on host arrays: every array of `cell_fields` (float32, shape (nz, ny, nx)) and, with `velocity`, the carrier
         itself moved semi-Lagrangian over `dt` by the carrier — three face grids, or None for the velocity the last step wrote.  order 1
         is the Euler back-trace, 2 the midpoint one.  Returns (rc, cell outputs, velocity outputs or None); INVALID for a refused call
-        (the reason in last_error(), nothing written).  Arrays "advection", "advectionStep", "advectionCounts" say what the call did."""
+        (the reason in last_error(), nothing written).  Arrays "advection", "advectionStep", "advectionCounts" say what the call did.
+        With `scheme` (ADVECT_SEMI_LAGRANGIAN or ADVECT_MACCORMACK) the call is ps_advect_fields_scheme with that scheme and `limiter`
+        (ADVECT_LIMIT_NONE / _CLAMP / _REVERT); the MacCormack correction also leaves "advectionScheme" and "advectionCorrection"."""
         sh = _abi.grid_shapes(self.scene.nx, self.scene.ny, self.scene.nz)
         cin = [np.ascontiguousarray(f, dtype=np.float32).reshape(sh["center"]) for f in cell_fields]
         car = None if carrier is None else [np.ascontiguousarray(carrier[a], dtype=np.float32).reshape(sh["face" + "XYZ"[a]]) for a in range(3)]
         cout = [np.empty(sh["center"], np.float32) for _ in cin]
         vout = [np.empty(sh["face" + a], np.float32) for a in "XYZ"] if velocity else None
         A = self.advection(dt, order, cin, cout, car, vout)
-        rc = self._check(self.L.ps_advect_fields(self.h, C.byref(A)), allow=(1, -2))
+        if scheme is None:
+            rc = self._check(self.L.ps_advect_fields(self.h, C.byref(A)), allow=(1, -2))
+        else:
+            S = _abi.AdvectionScheme(int(scheme), int(limiter))
+            rc = self._check(self.L.ps_advect_fields_scheme(self.h, C.byref(A), C.byref(S)), allow=(1, -2))
         return rc, cout, vout
 
-    def advect_device(self, dt, cell_in=(), cell_out=(), order=2, carrier=None, vel_out=None, layout=0, stream=None):
+    def advect_device(self, dt, cell_in=(), cell_out=(), order=2, carrier=None, vel_out=None, layout=0, stream=None, scheme=None,
+                      limiter=_abi.ADVECT_LIMIT_CLAMP):
         """ps_advect_fields_device: the same on device arrays in `layout`, behind what `stream` holds; `stream` then waits for the outputs
-        and the host is NOT synchronised.  No output may overlap an input or another output.  Returns the ps_result (INVALID: refused)."""
+        and the host is NOT synchronised.  No output may overlap an input or another output.  Returns the ps_result (INVALID: refused).
+        With `scheme` the call is ps_advect_fields_scheme_device."""
         A = self.advection(dt, order, cell_in, cell_out, carrier, vel_out)
-        return self._check(self.L.ps_advect_fields_device(self.h, C.byref(A), int(layout), stream_handle(stream)), allow=(1, -2))
+        if scheme is None:
+            return self._check(self.L.ps_advect_fields_device(self.h, C.byref(A), int(layout), stream_handle(stream)), allow=(1, -2))
+        S = _abi.AdvectionScheme(int(scheme), int(limiter))
+        return self._check(self.L.ps_advect_fields_scheme_device(self.h, C.byref(A), C.byref(S), int(layout), stream_handle(stream)), allow=(1, -2))
 
     def label_air_pockets(self):
         """ps_label_air_pockets: labels the connected air regions of the grid of the last upload (single domain) and returns their number K.

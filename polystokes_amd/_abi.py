@@ -136,6 +136,22 @@ ADVECTION_CALLS = (
 )
 
 
+ADVECT_SEMI_LAGRANGIAN, ADVECT_MACCORMACK = 0, 1                  # PS_ADVECT_* (ps_advection_scheme.scheme)
+ADVECT_LIMIT_NONE, ADVECT_LIMIT_CLAMP, ADVECT_LIMIT_REVERT = 0, 1, 2   # PS_ADVECT_LIMIT_* (ps_advection_scheme.limiter)
+
+
+class AdvectionScheme(C.Structure):
+    """ps_advection_scheme (ps_advect_fields_scheme): the scheme and, for the MacCormack correction, its limiter"""
+    _fields_ = [("scheme", C.c_int32), ("limiter", C.c_int32)]
+
+
+# the advection calls that take a scheme: name -> argument types; every one returns int32
+ADVECTION_SCHEME_CALLS = (
+    ("ps_advect_fields_scheme", (C.c_void_p, C.POINTER(Advection), C.POINTER(AdvectionScheme))),
+    ("ps_advect_fields_scheme_device", (C.c_void_p, C.POINTER(Advection), C.POINTER(AdvectionScheme), C.c_int32, C.c_void_p)),
+)
+
+
 # the air pocket calls (ps_label_air_pockets ...): name -> argument types; every one returns int32
 AIR_POCKET_CALLS = (
     ("ps_label_air_pockets", (C.c_void_p, C.POINTER(C.c_int32))),

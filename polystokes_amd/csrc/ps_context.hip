@@ -1186,15 +1186,21 @@ int32_t ps_download_solution_fields_device(ps_context* c, const ps_solution_out*
 // ps_advect_fields / _device are this one call.  Its refusals, in order: not uploaded; the struct; the order, the field count and dt; a
 // null field among the first cellFields; a partly null carrier or velOut; nothing to do; the device form's layout and pointers; an output
 // range that overlaps an input or another output.  Then the two PS_FAILED cases: a decomposition, and no written velocity for a null carrier.
-static int32_t advectCall(ps_context* c, const ps_advection* a, bool device, int32_t layout, void* stream) {
+// ps_advect_fields_scheme / _device (schemed) are the same call with a scheme: after "a is null" they refuse a null s, a scheme outside
+// 0..1 and a limiter outside 0..2; scheme 0 then is ps_advect_fields, scheme 1 passes the limiter on.
+static int32_t advectCall(ps_context* c, const ps_advection* a, bool device, int32_t layout, void* stream, bool schemed = false,
+                          const ps_advection_scheme* s = nullptr) {
     if (!c) return PS_FAILED;
     PS_TRY(c, {
         if (notUploaded(c, "ps_advect_fields")) return PS_INVALID;
-        const char* name = device ? "ps_advect_fields_device" : "ps_advect_fields";
+        const char* name = schemed ? (device ? "ps_advect_fields_scheme_device" : "ps_advect_fields_scheme") : device ? "ps_advect_fields_device" : "ps_advect_fields";
         std::string why;
         int nCar = 0, nVel = 0;
         if (a) for (int m = 0; m < 3; ++m) { nCar += a->carrier[m] ? 1 : 0; nVel += a->velOut[m] ? 1 : 0; }
         if (!a) why = "a is null";
+        else if (schemed && !s) why = "s is null";
+        else if (schemed && (s->scheme < PS_ADVECT_SEMI_LAGRANGIAN || s->scheme > PS_ADVECT_MACCORMACK)) why = "scheme outside 0..1";
+        else if (schemed && (s->limiter < PS_ADVECT_LIMIT_NONE || s->limiter > PS_ADVECT_LIMIT_REVERT)) why = "limiter outside 0..2";
         else if (a->order < 1 || a->order > 2) why = "order outside 1..2";
         else if (a->cellFields < 0 || a->cellFields > PS_ADVECT_MAX_CELL_FIELDS) why = "cellFields outside 0.." + std::to_string(PS_ADVECT_MAX_CELL_FIELDS);
         else if (!std::isfinite(a->dt)) why = "dt not finite";
@@ -1232,12 +1238,16 @@ static int32_t advectCall(ps_context* c, const ps_advection* a, bool device, int
         if (!why.empty()) { c->err = std::string(name) + ": " + why; return PS_INVALID; }
         if (c->slabEnabled || c->inGroup) throw Error("ps_advect_fields: advection needs a single domain");
         if (nCar == 0 && !c->isSolved) throw Error("ps_advect_fields: no written velocity since the upload");
-        c->advectFields(*a, device, layout, (hipStream_t)stream);
+        c->advectFields(*a, device, layout, (hipStream_t)stream, schemed && s->scheme == PS_ADVECT_MACCORMACK ? s->limiter : -1);
         return PS_SUCCESS;
     })
 }
 int32_t ps_advect_fields(ps_context* c, const ps_advection* a) { return advectCall(c, a, false, 0, nullptr); }
 int32_t ps_advect_fields_device(ps_context* c, const ps_advection* a, int32_t layout, void* stream) { return advectCall(c, a, true, layout, stream); }
+int32_t ps_advect_fields_scheme(ps_context* c, const ps_advection* a, const ps_advection_scheme* s) { return advectCall(c, a, false, 0, nullptr, true, s); }
+int32_t ps_advect_fields_scheme_device(ps_context* c, const ps_advection* a, const ps_advection_scheme* s, int32_t layout, void* stream) {
+    return advectCall(c, a, true, layout, stream, true, s);
+}
 // polystokes_step on device arrays: upload, step, download, the three export flags
 int32_t ps_step_device_fields(ps_context* c, const ps_params* p, const ps_fields_in* in, const ps_fields_out* out, ps_stats* st, int32_t layout,
                               void* stream) {

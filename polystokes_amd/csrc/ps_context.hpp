@@ -80,6 +80,7 @@ inline ArrayInfo hostArray(const void* p, int64_t count, int elem) { ArrayInfo a
 // One entry of a feature's array list (ps_context::setArrays): the feature's register...Arrays() holds the one list of its names, and
 // registers or erases by it
 struct NamedArray { const char* name; ArrayInfo info; };
+struct AdvectTable;                  // ps_kernels_advect.hpp: the by-value table of the advection kernels
 // What a call with a small table of doubles per collider keeps (ps_context::ingestColliderTable): the feature's register...Arrays(), the
 // table the kernel read, count + 2 counters, the count of the last call
 struct ColliderTable { void (::ps_context::*reg)(); DevBuf<double> table; DevBuf<int32_t> counters; int32_t count = 0; };
@@ -476,7 +477,15 @@ struct ps_context {
     int32_t advectOrderHost = 0;
     double advectStepHost = 0.;
     ps::DevBuf<int32_t> advectCounts;
-    void advectFields(const ps_advection& a, bool device, int layout, hipStream_t caller);           // ps_advect.hip: after the ABI's refusals
+    // The MacCormack correction (ps_advect_fields_scheme, scheme 1; ps_advect_correct.hip) adds eight counters (array "advectionCorrection"),
+    // the scheme and the limiter of the last such call (array "advectionScheme") and, for the device form, the fp32 scratch of the forward
+    // result, which only grows; every upload drops all three with the rest.
+    int32_t advectSchemeHost[2] = {0, 0};
+    ps::DevBuf<int32_t> advectCorrection;
+    ps::DevBuf<float> advectScratch;
+    void advectFields(const ps_advection& a, bool device, int layout, hipStream_t caller, int limiter = -1);   // ps_advect.hip: after the ABI's refusals; limiter >= 0: the correction
+    void launchAdvect(const ps::AdvectTable& T, int total);                                          // ps_advect.hip: the forward pass, into the arrays T names
+    void correctAdvected(const ps::AdvectTable& T, const ps::AdvectTable& H, int total, int limiter);   // ps_advect_correct.hip: the caller's arrays from the forward result in H's
     bool dropAdvection();                                // ps_advect.hip: the counters and the arrays; false when there was nothing to drop
     void registerAdvectionArrays();                      // ps_advect.hip: the arrays of the last call (none without one since the last upload)
     // The arrays that outlive a setup, solve or step (ps_context.hip states the rule); dropUploadScoped: what every upload drops
