@@ -902,45 +902,41 @@ class Group:
             r.stats = self.stats
         return rc
 
-    def solve_scene(self, scene, params):
-        """Partition `scene` into slabs, run the distributed step, merge the owned faces into global arrays."""
+    def set_scene(self, scene, params):
+        """Partition `scene` into slabs or bricks, upload every rank's part and set its slab or brick; returns the parts (self.slabs)."""
         from . import partition
+        if self.dims is None:
+            parts = [partition.make_slab(scene.nz, self.world, r, params.tileSize) for r in range(self.world)]
+        else:
+            parts = [partition.make_brick((scene.nx, scene.ny, scene.nz), self.dims, r, params.tileSize) for r in range(self.world)]
+        for r, part in enumerate(parts):
+            if self.dims is None:
+                self.ranks[r].upload(partition.local_scene(scene, part), params)   # (with the scene's density field cut to the slab)
+                self.ranks[r].set_slab(part)
+            else:
+                self.ranks[r].upload(partition.local_scene_brick(scene, part), params)
+                self.ranks[r].set_brick(part)
+        self.slabs = parts
         if self.dims is not None:
-            return self._solve_scene_bricks(scene, params)
-        slabs = [partition.make_slab(scene.nz, self.world, r, params.tileSize) for r in range(self.world)]
-        for r, sl in enumerate(slabs):
-            self.ranks[r].upload(partition.local_scene(scene, sl), params)   # (with the scene's density field cut to the slab)
-            self.ranks[r].set_slab(sl)
-        rc = self.step()
-        sh = _abi.grid_shapes(scene.nx, scene.ny, scene.nz)
-        vel = [np.array(scene.vel[a], copy=True) for a in range(3)]
-        valid = [np.zeros(sh["face" + "XYZ"[a]], np.float32) for a in range(3)]
-        for r, sl in enumerate(slabs):
-            lv, lval = self.ranks[r].download()
-            for a in range(3):
-                owned = self.ranks[r].array("owned" + "XYZ"[a])
-                partition.merge_faces(vel[a], lv[a], owned, sl, a)
-                partition.merge_faces(valid[a], lval[a], owned, sl, a)
-        self.vel, self.valid, self.slabs = vel, valid, slabs
-        return rc
+            self.bricks = parts
+        return parts
 
-    def _solve_scene_bricks(self, scene, params):
+    def solve_scene(self, scene, params):
+        """Partition `scene` into slabs or bricks, run the distributed step, merge the owned faces into global arrays."""
         from . import partition
-        bricks = [partition.make_brick((scene.nx, scene.ny, scene.nz), self.dims, r, params.tileSize) for r in range(self.world)]
-        for r, b in enumerate(bricks):
-            self.ranks[r].upload(partition.local_scene_brick(scene, b), params)
-            self.ranks[r].set_brick(b)
+        parts = self.set_scene(scene, params)
         rc = self.step()
+        merge = partition.merge_faces if self.dims is None else partition.merge_faces_brick
         sh = _abi.grid_shapes(scene.nx, scene.ny, scene.nz)
         vel = [np.array(scene.vel[a], copy=True) for a in range(3)]
         valid = [np.zeros(sh["face" + "XYZ"[a]], np.float32) for a in range(3)]
-        for r, b in enumerate(bricks):
+        for r, part in enumerate(parts):
             lv, lval = self.ranks[r].download()
             for a in range(3):
                 owned = self.ranks[r].array("owned" + "XYZ"[a])
-                partition.merge_faces_brick(vel[a], lv[a], owned, b, a)
-                partition.merge_faces_brick(valid[a], lval[a], owned, b, a)
-        self.vel, self.valid, self.slabs, self.bricks = vel, valid, bricks, bricks
+                merge(vel[a], lv[a], owned, part, a)
+                merge(valid[a], lval[a], owned, part, a)
+        self.vel, self.valid = vel, valid
         return rc
 
     def close(self):

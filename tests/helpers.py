@@ -136,6 +136,59 @@ def merge_dof_field_brick(global_out, local, b, kind, global_n):
     glo[tuple(sl_g)] = loc[tuple(sl_l)]
 
 
+def dof_numbering(solver):
+    """(where, n) of a single domain: the DOF number at every sample of every kind, NaN where there is none.  solver: a Solver after its
+    setup, or an Oracle after its run"""
+    n = solver.nP + solver.nT
+    where = {k: dof_field(solver, k, np.arange(n, dtype=np.float64), np.float64) for k in DOF_KINDS}
+    assert sum(int((~np.isnan(w)).sum()) for w in where.values()) == n
+    return where, n
+
+
+def merged_x(where, n, grp, sc):
+    """the owned DOFs of every rank's solutionVector as one x in the single domain's numbering (where: the DOF number at every sample).
+    grp: a Group after set_scene, or anything with its `ranks` (each with .array(name)), `slabs` (the parts) and `dims`"""
+    x = np.full(n, np.nan)
+    for kind in DOF_KINDS:
+        merged = np.full(where[kind].shape, np.nan)
+        for r, part in enumerate(grp.slabs):
+            loc = dof_field(grp.ranks[r], kind, grp.ranks[r].array("solutionVector"), np.float64)
+            if grp.dims is None:
+                merge_dof_field(merged, loc, part, kind)
+            else:
+                merge_dof_field_brick(merged, loc, part, kind, (sc.nx, sc.ny, sc.nz))
+        assert np.array_equal(np.isnan(merged), np.isnan(where[kind])), kind            # the same DOFs exist
+        m = ~np.isnan(merged)
+        x[where[kind][m].astype(np.int64)] = merged[m]
+    assert not np.isnan(x).any()
+    return x
+
+
+RANK_ARRAYS = ("solutionVector",) + tuple(s + "ActiveIndices" for s in ("center", "faceX", "faceY", "faceZ", "edgeYZ", "edgeXZ", "edgeXY"))
+
+
+class SavedRanks:
+    """what merged_x reads of a group, over arrays the ranks saved: saved[r] maps the names of RANK_ARRAYS to rank r's arrays (an npz does)"""
+
+    class _Rank:
+        def __init__(self, data):
+            self.data = data
+
+        def array(self, name):
+            return self.data[name]
+
+    def __init__(self, saved, parts, dims):
+        self.ranks = [SavedRanks._Rank(d) for d in saved]
+        self.slabs, self.dims = parts, (tuple(dims) if dims is not None else None)
+
+
+def make_parts(sc, tile, world, dims):
+    """the slabs (dims None) or bricks of every rank, as Group.set_scene cuts them"""
+    from polystokes_amd import partition
+    if dims is None:
+        return [partition.make_slab(sc.nz, world, r, tile) for r in range(world)]
+    return [partition.make_brick((sc.nx, sc.ny, sc.nz), dims, r, tile) for r in range(world)]
+
 
 # ---- the random brick cases of scripts/fuzz_bricks.py (seed -> scene, parameters, decomposition) ---------------------------------
 FUZZ_BRICK_DIMS = [(2, 2, 1), (2, 1, 2), (1, 2, 2), (2, 2, 2), (3, 1, 2), (1, 3, 2), (2, 2, 3)]
@@ -180,7 +233,8 @@ def rigid_rotation_scene(n=24, w=(0.3, -0.2, 0.5)):
 # ---- the PCG restated in fp64, and the library's iterate after a whole number of batches -------------------------------------------
 # Bounds on max |x_device - x_reference| / max |x_reference| after 25 and 50 iterations (tests/test_gpu_iterates.py): fp64 steps, and the
 # Chebyshev polynomial with fp32 inner vectors (its M taken from the device).  About 100x the largest drift measured on an MI355X: 1.3e-13
-# (fp64), 1.4e-8 (fp32: the solve's fused first term rounds its fp32 terms differently from the stand-alone apply).
+# (fp64), 1.4e-8 (fp32: the solve's fused first term rounds its fp32 terms differently from the stand-alone apply).  The decomposed solves
+# (slabs, bricks, one process per rank: per-rank partial sums and an all-reduce are one more summation order) stay inside that: 5.2e-14 at most.
 ITERATE_BOUND = 1e-11
 ITERATE_BOUND_F32 = 2e-6
 # Cases whose x_50 has converged so far that a 1e-6 error of beta at iteration 24 moves it by less than ITERATE_BOUND (the self-checks,
@@ -255,6 +309,32 @@ def iterate_after(target, m, scene=None, params=None):
     assert rc == abi.INCOMPLETE and len(calls) == m, (rc, len(calls))
     assert int(target.stats.solveData[1]) == CG_BATCH * m, target.stats.solveData[1]
     return target.array("solutionVector").copy()
+
+
+def group_interrupted_step(grp, m, scene, params):
+    """Every rank of a Group uploads its part of the scene with the trajectory tolerance; an interrupt on ONE rank, the last, fires at its
+    m-th call; the step must return PS_INCOMPLETE after exactly CG_BATCH * m iterations on every rank (Dist::batchEnd carries the request
+    to all of them).  The ranks then hold x after that many updates on their owned DOFs (halo entries may be stale: no merge reads them)."""
+    calls = []
+    stop = lambda: calls.append(1) or len(calls) >= m
+    grp.set_scene(scene, trajectory_params(params))
+    last = grp.ranks[-1]
+    last.set_interrupt(stop)
+    try:
+        rc = grp.step()
+    finally:
+        last.set_interrupt(None)
+    assert rc == abi.INCOMPLETE and len(calls) == m, (rc, len(calls))
+    for r in grp.ranks:                                   # (an in-process group's ranks leave Dist::solve together and share its record)
+        assert int(r.stats.result) == abi.INCOMPLETE and int(r.stats.solveData[1]) == CG_BATCH * m, (r.stats.result, r.stats.solveData[1])
+
+
+def group_iterate_after(grp, m, scene, params, *, numbering):
+    """x (the single domain's reference numbering, fp64) after exactly CG_BATCH * m PCG iterations of a decomposed solve on a Group of
+    slabs or bricks.  numbering: dof_numbering() of the whole scene"""
+    group_interrupted_step(grp, m, scene, params)
+    where, n = numbering
+    return merged_x(where, n, grp, scene)
 
 
 # ---- the library's setup and solve against the oracle's, given both (test_gpu_parity.py on the SDF scenes, test_gpu_classification.py on the

@@ -26,7 +26,17 @@ def tall_coil(n, nz):
 
 def base_case(case):
     """the scene of a case without its variant suffix"""
-    return case.replace("_interrupt", "").replace("_failrank", "").replace("_f32first", "").replace("_tilemismatch", "")
+    for suffix in ("_interrupt", "_failrank", "_f32first", "_tilemismatch", "_iterate1", "_iterate2"):
+        case = case.replace(suffix, "")
+    return case
+
+
+def iterate_batches(case):
+    """m of a case "<base>_iterate<m>": the rank stops at the m-th batch boundary and saves its x (0: any other case)"""
+    for m in (1, 2):
+        if case.endswith("_iterate%d" % m):
+            return m
+    return 0
 
 
 def make(case):

@@ -56,6 +56,9 @@ def run_rank(case, world, rank, port, out, device, done):
     import mp_cases
     sc, p = mp_cases.make(case)
     dims = mp_cases.DIMS.get(mp_cases.base_case(case))
+    batches = mp_cases.iterate_batches(case)      # "_iterate<m>": stop at the m-th batch boundary and save x (tests/test_gpu_multiprocess.py)
+    if batches:
+        from helpers import RANK_ARRAYS, trajectory_params
     s = polystokes_amd.Solver(device)
     if dims is not None:
         sl = partition.make_brick((sc.nx, sc.ny, sc.nz), dims, rank, p.tileSize)
@@ -81,7 +84,7 @@ def run_rank(case, world, rank, port, out, device, done):
         res["single_rc"] = s.step_device()
         res["single_c32"] = int(s.array("chebInner32")[0])
     else:
-        s.upload(loc, p)
+        s.upload(loc, trajectory_params(p) if batches else p)
     if dims is not None:
         s.set_brick(sl)
     else:
@@ -107,6 +110,9 @@ def run_rank(case, world, rank, port, out, device, done):
     mem_after_upload = s.memory_stats()["live_bytes"]      # (process-wide: all ranks of this process)
     if case.endswith("_interrupt") and rank == world - 1:
         s.set_interrupt(lambda: True)     # ONE rank asks to stop: every rank must return PS_INCOMPLETE at the same batch
+    calls = []
+    if batches and rank == world - 1:     # the same, at the last rank's m-th call
+        s.set_interrupt(lambda: calls.append(1) or len(calls) >= batches)
     try:
         rc = s.step_device()
         err = ""
@@ -114,6 +120,9 @@ def run_rank(case, world, rank, port, out, device, done):
         rc, err = -1, str(e)
     res.update(rc=rc, err=err, iters=int(s.stats.solveData[1]), used_bicgstab=int(s.stats.usedBiCGStab), mem_after_upload=mem_after_upload,
                mem_peak=s.memory_stats()["peak_bytes"], mem_deferred=s.memory_stats()["deferred_bytes"])
+    if batches and rc != -1:
+        res.update({nm: s.array(nm) for nm in RANK_ARRAYS}, calls=len(calls), fused=int(s.array("fusedStep")[0]),
+                   overlap=int(bool(s.dist_stats()["overlap"])))
     if rc in (0, 1):
         lv, lval = s.download()
         for a in range(3):

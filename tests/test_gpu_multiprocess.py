@@ -19,13 +19,13 @@ pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
-def _run_ranks(case, world, tmp_path, env=None, per_process=1):
+def _run_ranks(case, world, tmp_path, env=None, per_process=1, limit=240):
     """per_process > 1: every process holds that many ranks, one thread each (mp_rank.py) — the box admits six GPU processes"""
     base = children.free_port_base(world)
     outs = [str(tmp_path / f"{case}.r{r}.npz") for r in range(world)]
     groups = [list(range(q, min(q + per_process, world))) for q in range(0, world, per_process)]
     children.run_group([children.script_argv("mp_rank.py", case, world, ",".join(str(r) for r in g), base, ",".join(outs[r] for r in g)) for g in groups],
-                       limit=240, env=env)
+                       limit=limit, env=env)
     return [np.load(o) for o in outs]
 
 
@@ -154,6 +154,40 @@ def test_multiprocess_interrupt_stops_every_rank(tmp_path):
     res = _run_ranks("cavity_w2_interrupt", 2, tmp_path)
     assert [int(r["rc"]) for r in res] == [abi.INCOMPLETE, abi.INCOMPLETE]
     assert int(res[0]["iters"]) == int(res[1]["iters"]) == 25
+
+
+@pytest.mark.parametrize("case,transport", [("cavity_w2", "tcp"), ("cavity_w2", "stub"), ("cavity_w2+fused", "stub"), ("cavity_b2x1x2", "stub")])
+def test_multiprocess_iterates_match_the_reference(case, transport, tmp_path):
+    """x_25 and x_50 of the production path — one process per rank, a comm stream, events, asynchronous sends (the in-process groups of
+    test_gpu_iterates.py share one stream) — against the same fp64 reference of the whole scene, to the same bound: two slabs over TCP, over
+    the stand-in RCCL library with the five-kernel step and with the overlapped four-kernel step, and 2 x 1 x 2 bricks (four processes) over
+    the stand-in.  Only the last rank asks to stop, at its m-th batch; every rank must report PS_INCOMPLETE after 25 m iterations.  The ranks
+    save their solutionVector and index arrays (mp_rank.py, "_iterate<m>"); the merge is helpers.merged_x.
+    Measured max |dx| / max |x| on an MI355X (x_25 / x_50): cavity_w2 over TCP 1.4e-14 / 4.5e-14, over the stand-in the same figures (same
+    kernels, same reduction order), with the four-kernel step 7.0e-15 / 2.3e-14; cavity_b2x1x2 over the stand-in 9.1e-15 / 2.8e-14."""
+    import test_gpu_iterates as ti
+    from helpers import CG_BATCH, SavedRanks, make_parts, merged_x
+    if transport == "stub" and not os.path.exists(STUB_LIB):
+        pytest.fail("tests/stub_rccl/libps_stub_rccl.so is missing: __graft_entry__.build() compiles it")
+    fused = case.endswith("+fused")
+    case = case.replace("+fused", "")
+    world, dims = mp_cases.WORLD[case], mp_cases.DIMS.get(case)
+    env = {"PS_TEST_TRANSPORT": "stub", "PS_RCCL_LIB": STUB_LIB} if transport == "stub" else {}
+    if fused:
+        env["PS_FUSED_R"] = "1"
+    scene, pre = ti.MP_CASES[case]
+    sc, p = mp_cases.make(case)
+    got = {}
+    for m in ti.batches_of(scene, pre):       # children first: the parent opens no GPU context here at all
+        (tmp_path / str(m)).mkdir()
+        res = _run_ranks("%s_iterate%d" % (case, m), world, tmp_path / str(m), env, limit=120)
+        assert [int(r["rc"]) for r in res] == [abi.INCOMPLETE] * world, [(int(r["rc"]), str(r["err"])) for r in res]
+        assert [int(r["iters"]) for r in res] == [CG_BATCH * m] * world
+        assert [int(r["calls"]) for r in res] == [0] * (world - 1) + [m]
+        assert [int(r["fused"]) for r in res] == [int(fused)] * world and [int(r["overlap"]) for r in res] == [int(fused)] * world
+        where, n = ti.reference(scene, pre)[1]
+        got[CG_BATCH * m] = merged_x(where, n, SavedRanks(res, make_parts(sc, p.tileSize, world, dims), dims), sc)
+    ti.check_group("%s/%s%s" % (case, transport, "+fused" if fused else ""), scene, pre, got)
 
 
 def test_decomposed_step_does_not_report_an_earlier_fp32_polynomial(tmp_path):

@@ -25,6 +25,7 @@ from polystokes_amd import partition, scenes
 
 import children
 import recovery_ref as rr
+from helpers import merged_x
 
 pytestmark = pytest.mark.gpu
 
@@ -390,25 +391,6 @@ def _single_blocks(name, sc, p):
     return _blocks[name]
 
 
-def _merged_x(where, n, grp, sc):
-    """the owned DOFs of every rank's solutionVector as one x in the single domain's numbering (where: the DOF number at every sample)"""
-    from helpers import DOF_KINDS, dof_field, merge_dof_field, merge_dof_field_brick
-    x = np.full(n, np.nan)
-    for kind in DOF_KINDS:
-        merged = np.full(where[kind].shape, np.nan)
-        for r, part in enumerate(grp.slabs):
-            loc = dof_field(grp.ranks[r], kind, grp.ranks[r].array("solutionVector"), np.float64)
-            if grp.dims is None:
-                merge_dof_field(merged, loc, part, kind)
-            else:
-                merge_dof_field_brick(merged, loc, part, kind, (sc.nx, sc.ny, sc.nz))
-        assert np.array_equal(np.isnan(merged), np.isnan(where[kind])), kind            # the same DOFs exist
-        m = ~np.isnan(merged)
-        x[where[kind][m].astype(np.int64)] = merged[m]
-    assert not np.isnan(x).any()
-    return x
-
-
 @pytest.mark.parametrize("name,world", DECOMP, ids=lambda v: "x".join(map(str, v)) if isinstance(v, tuple) else str(v))
 def test_decompositions(name, world):
     """grp.vel (every rank's owned faces) against the reference on the merged x and the single domain's blocks; and every rank's own output
@@ -423,7 +405,7 @@ def test_decompositions(name, world):
     grp = polystokes_amd.Group(world if dims is None else dims[0] * dims[1] * dims[2], dims=dims)
     try:
         assert grp.solve_scene(sc, p) == abi.SUCCESS
-        x = _merged_x(where, n, grp, sc)
+        x = merged_x(where, n, grp, sc)
         assert np.any(x)
         res = rr.check(b, x, grp.vel, need=DECOMP_NEED[name])
         report("%s/%s" % (name, "x".join(map(str, dims)) if dims else "slabs%d" % world), res)
