@@ -522,7 +522,13 @@ int32_t ps_get_collider_loads(ps_context* ctx, double* out, int64_t out_len);
  * ps_*_device calls (below) — a pointer that is not 8-byte aligned, memory that is not device memory of the context's device, an allocation
  * that ends before 9 * count doubles.
  * Decompositions.  The call is local to a context: a slab or brick rank paints its own grid, from its own upload's orig and local indices;
- * the caller gives every rank the orig of its block.  No test of this library covers that (its partition helper does not set orig per rank).
+ * the caller gives every rank the orig of its block: orig_m + origin_m * dx, origin the global index of the rank's local cell 0 (the
+ * partition helper does).  A rank's result is the rule on its own grid.  It equals the result on the whole grid at every face, given equal
+ * positions (exact where dx and orig are dyadic), with one exception the rule itself makes: a face of axis a on the outermost plane of a
+ * halo side (local i_a = 0 on a side with a lower neighbour, local i_a = n_a on a side with an upper one, where that plane lies inside the
+ * whole grid) has one cell on the rank and two in the whole grid, and may take the other collider's value.  That plane is the far edge
+ * of the halo block and the solve does not read it: a step after the ranks' own paint equals, byte for byte, a step of ranks that were
+ * uploaded the whole grid's paint (tested on slabs and bricks).
  * Memory: the table and the counters take 72 * count + 4 * (count + 2) bytes from the call to the next upload; nothing else is held, and
  * ps_memory_stats entry 2 is 0 after the call.
  * Arrays, registered by a successful call and erased by every upload: "colliderMotions" (int32, 1: the count), "colliderMotionTable" (fp64,
@@ -589,7 +595,10 @@ int32_t ps_paint_collider_velocities_device(ps_context* ctx, const double* motio
  * buffer the next setup reads) and "colliderCellIds" (int32 cell grid).
  * Out of scope: a device form of ps_set_collider_shapes; scaling or deforming poses; swept volumes for fast bodies; a per-shape contact
  * cosine; repainting after later id uploads.  Decompositions: a slab or brick rank places on its own grid from its own upload's orig, as
- * the paint does; no test of this library covers that. */
+ * the paint does.  A rank's result is the rule on its own grid, halo blocks included (a collider that reaches only a halo block is placed
+ * there), and its counters are those of its own grid.  A cell reads and writes only itself, so given equal positions the result equals
+ * the whole grid's at every cell, and the two ranks that share a cut hold the same values on both sides of it (tested on slabs and
+ * bricks, with the placement before and after ps_set_slab / ps_set_brick). */
 #define PS_COLLIDER_SHAPE_REACH 4.0   /* world cells beyond a volume's box that a placement still writes */
 
 typedef struct ps_collider_shape {

@@ -902,29 +902,39 @@ class Group:
             r.stats = self.stats
         return rc
 
-    def set_scene(self, scene, params):
-        """Partition `scene` into slabs or bricks, upload every rank's part and set its slab or brick; returns the parts (self.slabs)."""
+    def set_scene(self, scene, params, per_rank=None, when="after_cut"):
+        """Partition `scene` into slabs or bricks, upload every rank's part and set its slab or brick; returns the parts (self.slabs).
+        per_rank(solver, part, local_scene), if given, is called once on every rank between its upload and the step — before its
+        ps_set_slab / ps_set_brick with when = "before_cut", after it with "after_cut": the place for the calls that follow an upload
+        (ps_upload_collider_ids, ps_place_colliders, ps_paint_collider_velocities).  The local scene carries the rank's own orig."""
         from . import partition
+        if when not in ("before_cut", "after_cut"):
+            raise ValueError('when must be "before_cut" or "after_cut"')
         if self.dims is None:
             parts = [partition.make_slab(scene.nz, self.world, r, params.tileSize) for r in range(self.world)]
         else:
             parts = [partition.make_brick((scene.nx, scene.ny, scene.nz), self.dims, r, params.tileSize) for r in range(self.world)]
         for r, part in enumerate(parts):
+            local = partition.local_scene(scene, part) if self.dims is None else partition.local_scene_brick(scene, part)
+            self.ranks[r].upload(local, params)                                    # (with the scene's optional cell fields cut to the part)
+            if per_rank is not None and when == "before_cut":
+                per_rank(self.ranks[r], part, local)
             if self.dims is None:
-                self.ranks[r].upload(partition.local_scene(scene, part), params)   # (with the scene's density field cut to the slab)
                 self.ranks[r].set_slab(part)
             else:
-                self.ranks[r].upload(partition.local_scene_brick(scene, part), params)
                 self.ranks[r].set_brick(part)
+            if per_rank is not None and when == "after_cut":
+                per_rank(self.ranks[r], part, local)
         self.slabs = parts
         if self.dims is not None:
             self.bricks = parts
         return parts
 
-    def solve_scene(self, scene, params):
-        """Partition `scene` into slabs or bricks, run the distributed step, merge the owned faces into global arrays."""
+    def solve_scene(self, scene, params, per_rank=None, when="after_cut"):
+        """Partition `scene` into slabs or bricks, run the distributed step, merge the owned faces into global arrays.  per_rank, when:
+        see set_scene."""
         from . import partition
-        parts = self.set_scene(scene, params)
+        parts = self.set_scene(scene, params, per_rank, when)
         rc = self.step()
         merge = partition.merge_faces if self.dims is None else partition.merge_faces_brick
         sh = _abi.grid_shapes(scene.nx, scene.ny, scene.nz)

@@ -24,7 +24,10 @@ class Slab:
 
 
 def slab_ranges(nz, world, align):
-    """Contiguous owned ranges, multiples of `align`, as even as possible; the last one takes the remainder."""
+    """Contiguous owned ranges, multiples of `align`, as even as possible; the last one takes the remainder.  An axis that is not cut
+    (world 1) is one range of any length, below `align` too."""
+    if world == 1:
+        return [(0, nz)]
     blocks = nz // align
     if blocks < world:
         raise ValueError(f"{nz} layers cannot be cut into {world} slabs of multiples of {align}")
@@ -56,8 +59,17 @@ def _cut_opt(scene, name, cut):
     return None if f is None else cut(f)
 
 
+def local_orig(scene, origin):
+    """The world position of the low corner of the local grid whose cell 0 has the global index `origin` (x, y, z):
+    orig[m] = scene.orig[m] + origin[m] * scene.dx in fp64, one multiply and one add per axis (scene.orig defaults to zeros).  An axis
+    with origin 0 keeps the value the scene was given (it adds 0.0).  ps_place_colliders and ps_paint_collider_velocities read it on a
+    rank."""
+    base = getattr(scene, "orig", (0.0, 0.0, 0.0))
+    return tuple(float(base[m]) + float(origin[m]) * float(scene.dx) for m in range(3))
+
+
 def local_scene(scene, slab):
-    """The slab (+halo) of `scene` as an ordinary Scene."""
+    """The slab (+halo) of `scene` as an ordinary Scene; its orig is local_orig of (0, 0, slab.g0)."""
     a, b = slab.g0, slab.g0 + slab.nz_local
     cut = lambda arr, extra=0: np.ascontiguousarray(arr[a:b + extra])
     sc = Scene(scene.nx, scene.ny, slab.nz_local, scene.dx, scene.dt, scene.density,
@@ -71,6 +83,7 @@ def local_scene(scene, slab):
                surface_pressure_field=_cut_opt(scene, "surface_pressure_field", cut),
                contact_angle=getattr(scene, "contact_angle", None),
                contact_cosine_field=_cut_opt(scene, "contact_cosine_field", cut))
+    sc.orig = local_orig(scene, (0, 0, slab.g0))
     return sc
 
 
@@ -113,7 +126,7 @@ def make_brick(n, dims, rank, tile_size=16):
 
 
 def local_scene_brick(scene, b):
-    """The brick (+halo) of `scene` as an ordinary Scene (arrays are (z, y, x), x fastest)."""
+    """The brick (+halo) of `scene` as an ordinary Scene (arrays are (z, y, x), x fastest); its orig is local_orig of b.origin."""
     ox, oy, oz = b.origin
     nx, ny, nz = b.n_local
 
@@ -121,7 +134,7 @@ def local_scene_brick(scene, b):
         return np.ascontiguousarray(arr[oz:oz + nz + ez, oy:oy + ny + ey, ox:ox + nx + ex])
 
     faces = lambda v: [cut(v[0], ex=1), cut(v[1], ey=1), cut(v[2], ez=1)]
-    return Scene(nx, ny, nz, scene.dx, scene.dt, scene.density, faces(scene.vel), cut(scene.surface), cut(scene.collision), cut(scene.viscosity),
+    sc = Scene(nx, ny, nz, scene.dx, scene.dt, scene.density, faces(scene.vel), cut(scene.surface), cut(scene.collision), cut(scene.viscosity),
                  collisionvel=faces(scene.collisionvel), name=f"{scene.name}.b{b.rank}",
                  density_field=_cut_opt(scene, "density_field", cut),
                  surface_tension=getattr(scene, "surface_tension", None),
@@ -129,6 +142,8 @@ def local_scene_brick(scene, b):
                  surface_pressure_field=_cut_opt(scene, "surface_pressure_field", cut),
                  contact_angle=getattr(scene, "contact_angle", None),
                  contact_cosine_field=_cut_opt(scene, "contact_cosine_field", cut))
+    sc.orig = local_orig(scene, b.origin)
+    return sc
 
 
 def merge_faces_brick(global_out, local_out, owned_mask, b, axis):

@@ -62,8 +62,30 @@ def make(case):
         return sc, p
     if base == "cavity_b2x1x2":
         return tall_cavity(32, 64)
+    if base == "spheres64_w2_colliders":   # the stepping scene of the collider decomposition tests: every rank places and paints (colliders())
+        import collider_decomposition_cases as cdc
+        return cdc.step_scene()[:2]
     raise KeyError(case)
 
 
+def colliders(case):
+    """(shapes, poses, motions) that every rank of the case places and paints between its upload and the step; None: the case has none"""
+    if base_case(case) != "spheres64_w2_colliders":
+        return None
+    import collider_decomposition_cases as cdc
+    return cdc.step_scene()[2:]
+
+
+def place_and_paint(s, case):
+    """on a context that has uploaded: an id field that names no collider, the case's placement and its paint (shapes set here: a context
+    setting, it may follow the upload)"""
+    shapes, poses, motions = colliders(case)
+    assert s.set_collider_shapes(shapes) == abi.SUCCESS, s.last_error()
+    assert s.upload_collider_ids(np.full((s.scene.nz, s.scene.ny, s.scene.nx), -1, np.int32)) == abi.SUCCESS, s.last_error()
+    assert s.place_colliders(poses) == abi.SUCCESS, s.last_error()
+    assert s.paint_collider_velocities(motions) == abi.SUCCESS, s.last_error()
+
+
 DIMS = {"cavity64_b2x2x1": (2, 2, 1), "cavity_b2x1x2": (2, 1, 2), "cavity64_b2x2x2": (2, 2, 2), "cavity32_b2x2x2": (2, 2, 2)}      # brick cases: ranks per axis
-WORLD = {"cavity64_b2x2x2": 8, "cavity32_b2x2x2": 8, "cavity64_b2x2x1": 4, "cavity_b2x1x2": 4, "cavity_w2": 2, "cavity_w3_jacobi": 3, "coil_w2": 2, "cavity_w2_bicgstab": 2, "cavity_w2_chebyshev": 2}
+WORLD = {"cavity64_b2x2x2": 8, "cavity32_b2x2x2": 8, "cavity64_b2x2x1": 4, "cavity_b2x1x2": 4, "cavity_w2": 2, "cavity_w3_jacobi": 3, "coil_w2": 2, "cavity_w2_bicgstab": 2, "cavity_w2_chebyshev": 2,
+         "spheres64_w2_colliders": 2}

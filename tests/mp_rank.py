@@ -85,6 +85,8 @@ def run_rank(case, world, rank, port, out, device, done):
         res["single_c32"] = int(s.array("chebInner32")[0])
     else:
         s.upload(loc, trajectory_params(p) if batches else p)
+    if mp_cases.colliders(case) is not None:      # after the upload, from the rank's own orig (partition.local_orig), before the cut is set
+        mp_cases.place_and_paint(s, case)
     if dims is not None:
         s.set_brick(sl)
     else:

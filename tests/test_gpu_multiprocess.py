@@ -115,7 +115,13 @@ def _compare_with_single_domain(case, world, res):
     import polystokes_amd
     sc, p = mp_cases.make(case)
     single = polystokes_amd.Solver(0)
-    rc1 = single.step(sc, p)
+    if mp_cases.colliders(case) is None:
+        rc1 = single.step(sc, p)
+    else:                                   # upload, place, paint, step, download: polystokes_step would upload over the placement
+        single.upload(sc, p)
+        mp_cases.place_and_paint(single, case)
+        rc1 = single.step_device()
+        single.download()
     assert all(int(r["rc"]) == rc1 for r in res), [(int(r["rc"]), str(r["err"])) for r in res]
     it1 = single.stats.solveData[1]
     assert all(abs(int(r["iters"]) - it1) <= max(2, 0.02 * it1) for r in res), (it1, [int(r["iters"]) for r in res])
@@ -188,6 +194,51 @@ def test_multiprocess_iterates_match_the_reference(case, transport, tmp_path):
         where, n = ti.reference(scene, pre)[1]
         got[CG_BATCH * m] = merged_x(where, n, SavedRanks(res, make_parts(sc, p.tileSize, world, dims), dims), sc)
     ti.check_group("%s/%s%s" % (case, transport, "+fused" if fused else ""), scene, pre, got)
+
+
+def test_multiprocess_ranks_place_and_paint_colliders(tmp_path):
+    """spheres64_w2_colliders: two rank processes over TCP, each placing three sphere volumes (one across the cut) and painting their
+    motions on its own slab from its own orig before the step.  The merged velocities and valid flags against the single domain that
+    places and paints the whole grid; and x_25 of every rank (the "_iterate1" form: the last rank stops the solve at the first batch)
+    against the in-process group of the same case that does the same calls through Group.set_scene's hook, rank by rank, to ITERATE_BOUND:
+    the two differ by the order of the all-reduce alone."""
+    import polystokes_amd
+    from helpers import CG_BATCH, DOF_KINDS, ITERATE_BOUND, SavedRanks, dof_field, merge_dof_field, relerr, trajectory_params
+    case, world = "spheres64_w2_colliders", 2
+    res = _run_ranks(case, world, tmp_path)            # children first: the parent's own GPU context comes after
+    _compare_with_single_domain(case, world, res)
+    (tmp_path / "it").mkdir()
+    it = _run_ranks(case + "_iterate1", world, tmp_path / "it", limit=120)
+    assert [int(r["rc"]) for r in it] == [abi.INCOMPLETE] * world, [(int(r["rc"]), str(r["err"])) for r in it]
+    assert [int(r["iters"]) for r in it] == [CG_BATCH] * world
+    sc, p = mp_cases.make(case)
+    grp = polystokes_amd.Group(world)
+    try:
+        calls = []
+        grp.set_scene(sc, trajectory_params(p), per_rank=lambda s, part, local: mp_cases.place_and_paint(s, case), when="before_cut")
+        grp.ranks[-1].set_interrupt(lambda: calls.append(1) or len(calls) >= 1)
+        try:
+            rc = grp.step()
+        finally:
+            grp.ranks[-1].set_interrupt(None)
+        assert rc == abi.INCOMPLETE and int(grp.stats.solveData[1]) == CG_BATCH
+        saved = SavedRanks(it, grp.slabs, None).ranks
+        for r, slab in enumerate(grp.slabs):               # the DOFs the rank owns (a halo entry may be stale on either side: nothing reads it)
+            assert it[r]["solutionVector"].shape == grp.ranks[r].array("solutionVector").shape
+            for kind in DOF_KINDS:
+                got, want = (dof_field(q, kind, q.array("solutionVector"), np.float64) for q in (saved[r], grp.ranks[r]))
+                own_got, own_want = np.full_like(got, np.nan), np.full_like(want, np.nan)
+                one = type(slab)(slab.rank, slab.world, slab.z0, slab.z1, slab.lo_halo, slab.hi_halo)
+                one.g0 = 0                                     # merge into an array of the rank's own layers
+                merge_dof_field(own_got, got, one, kind)
+                merge_dof_field(own_want, want, one, kind)
+                assert np.array_equal(np.isnan(own_got), np.isnan(own_want)), (r, kind)
+                m = ~np.isnan(own_want)
+                d = relerr(own_got[m], own_want[m])
+                print("rank", r, kind, "x_25 process against in-process group: %.2e over %d owned DOFs" % (d, int(m.sum())))
+                assert m.any() and d <= ITERATE_BOUND, (r, kind, d)
+    finally:
+        grp.close()
 
 
 def test_decomposed_step_does_not_report_an_earlier_fp32_polynomial(tmp_path):
